@@ -8,13 +8,23 @@ A "step" is one outer power iteration (fission source, ng group solves, k update
 Inputs are uploaded and the line systems factored before the timed region; the timed region is K outer
 iterations bracketed by barrier + device synchronize; value = K / max-over-ranks time.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if given and prints the JSON line.  The
+extras below take runs of their own and come with --full only (--no-converge / --no-parity / --no-small / --no-c5 /
+--cpu-sample-iters 0 switch single ones off again):
   roofline      dominant kernel of the hot path (slowest Schur-apply direction pass): algorithmic bytes per
                 launch / mean launch duration measured with HIP events on the solver's stream inside the timed
                 region (DESIGN.md "Algorithmic bytes"); peak 8.0 TB/s.
   cpu_baseline  the CPU oracle (oracle/nf_oracle.c, 1 core, kind "port") timed on a bounded sample of the same
                 workload: a fixed number of CG iterations on the same n^3 operator, extrapolated with the CG
                 counts of the timed GPU steps.  Rank 0, N=1 only.
+  converged     untimed converged solve with the drivers' settings (k-eff, pcm); other_configs, higher_order, parity,
+                parity_at_bench_size, c5_single_gpu: the small BASELINE configs, an RT1-P1 throughput figure, parity probes
+                against the oracle and BASELINE config 4 on this one GPU.
+
+--dump-outputs DIR writes what the timed path computed in its last step, for two builds to be compared output by output:
+  keff.npy      (1,) float64, k-eff after the timed steps
+  phi.npy       (ng, M) float64, the scalar flux of every group at M cells: all cells (z-major, then y, then x) when they fit
+                in DUMP_BYTES, else a sorted sample drawn with the fixed seed DUMP_SEED, the same on every run with the same --n
 """
 import argparse
 import json
@@ -28,6 +38,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BYTES = 16 << 20            # --dump-outputs: size cap of phi.npy
+DUMP_SEED = 20261016             # --dump-outputs: seed of the cell sample
 
 
 def parse():
@@ -47,6 +59,9 @@ def parse():
     ap.add_argument("--cg-tol", type=float, default=1e-4, help="relative CG tolerance of the timed steps (the drivers' 1e-4 is the headline; tighter values are a "
                     "diagnostic: at 1e-4 one more or fewer CG iteration of a solve at the stopping threshold moves k by ~1e-9)")
     ap.add_argument("--loopback-slabs", type=int, default=1, help="z-slabs per process (>1: exercise the slab path on one GPU)")
+    ap.add_argument("--full", action="store_true", help="also measure the extras (roofline, converged solve, small configs, higher orders, CPU baseline, "
+                    "parity probes, C5); off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write k-eff and the flux (a fixed sample of it on big meshes) after the timed steps as DIR/<name>.npy")
     ap.add_argument("--watchdog-s", type=float, default=float(os.environ.get("NEUTFEM_WATCHDOG_S", "300")),
                     help="multi-rank runs: exit non-zero when no outer iteration completes within this many seconds (a peer is gone or stuck)")
     return ap.parse_args()
@@ -80,6 +95,25 @@ class Watchdog:
             elif time.monotonic() - self.t0 > self.limit:
                 print(f"[bench watchdog] rank {self.rank}: no outer iteration completed for {self.limit:.0f} s (stuck at {n}): exiting", file=sys.stderr, flush=True)
                 os._exit(3)
+
+
+def dump_outputs(d, s, k, N, nxy, k0, ng, dist):
+    """--dump-outputs: keff.npy and phi.npy (see the module docstring).  Every rank takes its own planes' share of the cell sample, the
+    shares meet in a sum over ranks (each entry has one owner, the others add zero) and rank 0 writes."""
+    per_group = DUMP_BYTES // (8 * ng)
+    idx = np.arange(N) if N <= per_group else np.sort(np.random.default_rng(DUMP_SEED).choice(N, per_group, replace=False))
+    phi = (s.get_phi_local() if hasattr(s, "get_phi_local") else s.get_phi()).reshape(ng, -1)
+    off = k0 * nxy                                              # global index of this rank's first cell
+    mine = (idx >= off) & (idx < off + phi.shape[1])
+    part = np.zeros((ng, idx.size))
+    part[:, mine] = phi[:, idx[mine] - off]
+    if dist is not None:
+        import torch
+        t = torch.from_numpy(part); dist.all_reduce(t, op=dist.ReduceOp.SUM); part = t.numpy()
+    if int(os.environ.get("RANK", "0")) == 0:
+        os.makedirs(d, exist_ok=True)
+        np.save(os.path.join(d, "keff.npy"), np.array([k], dtype=np.float64))
+        np.save(os.path.join(d, "phi.npy"), part)
 
 
 def make_solver(case, device):
@@ -228,6 +262,8 @@ def main():
     # well-formed line for the wrong N
     if a.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         raise SystemExit(launch_ranks(a))
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -279,6 +315,7 @@ def main():
         head = s.head
         N_local = sum(x.ne for x in s.slabs); ng, dim = head.ng, head.dim
         N = a.n * a.n * nz
+        nxy = head.nx * head.ny
     else:
         note(f"building case {a.case} n={a.n}")
         case = cases.iaea3d_resampled(a.n) if a.case == "iaea3d" else cases.synthetic_checkerboard(a.n, a.groups)
@@ -288,6 +325,7 @@ def main():
         head = s
         comm_ranks, transport = 0, ""
         N, ng, dim = s.ne, s.ng, s.dim
+        k0, nxy = 0, s.nx * s.ny
     TOL_FLUX, MAX_INNER = a.cg_tol, (1000 if a.cg_tol >= 1e-4 else 20000)   # drivers: set_tol(1e-5,1e-4,1e-4,200,1000)
     if a.case == "checker":                                     # fixed work, exactly 50 CG iterations per group solve
         TOL_FLUX, MAX_INNER = 0.0, 50
@@ -308,6 +346,7 @@ def main():
     s.set_tol(0.0, TOL_FLUX, 1e-4, a.steps, MAX_INNER)          # tol_keff = 0 -> exactly K outers
     s.profile_reset()
     note("timed steps")
+    # profiled on every run, not only --full's: the event timing of every 8th apply is part of the timed path the headline has always measured
     barrier(); t0 = time.perf_counter()
     k_timed, n_out = s.solve_keff(profile=True)
     barrier(); dt = time.perf_counter() - t0
@@ -317,93 +356,98 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64); dist.all_reduce(t, op=dist.ReduceOp.MAX); dt = float(t.item())
     hist = s.history()
     cg_per_outer = float(hist["cg"].sum()) / a.steps
+    if a.dump_outputs:
+        note(f"writing outputs to {a.dump_outputs}")
+        dump_outputs(a.dump_outputs, s, k_timed, N, nxy, k0, ng, dist)
 
-    # roofline of the dominant kernel (slowest direction pass of the Schur apply)
-    # per-launch figures refer to what ONE rank's launches process (its own planes)
-    if slabs_total > 1:
-        nzl = max(x.nz for x in s.slabs); nxl, nyl = head.nx, head.ny
-        Nl = nxl * nyl * nzl
-    else:
-        nzl, nxl, nyl, Nl = s.nz, s.nx, s.ny, N
-    nJd = {0: (nxl + 1) * nyl * nzl, 1: nxl * (nyl + 1) * nzl, 2: nxl * nyl * (nzl + 1)}
-    kern = {0: "k_schur_x<2,NCH,VEC>", 1: "k_schur_s<SEG,1> / k_schur_c<1> (y lines)", 2: "k_schur_s<SEG,2> / k_schur_c<2> (z lines)"}
-    passes = []
-    # fused CG (undivided RT0-P0 mesh): the x pass also carries x_sol += alpha p and p = r + beta p of the previous
-    # iteration (read r, x_sol; write p, x_sol = 32 B/cell on top of the apply; p itself is read once for both jobs) on every
-    # CG iteration but the first of a group solve
-    n_solves = hist["cg"].size
-    fused_bytes = 32.0 * Nl * (1.0 - n_solves / max(float(hist["cg"].sum()), 1.0)) if slabs_total == 1 else 0.0
-    for d, nm in enumerate(["schur_x", "schur_y", "schur_z"][:dim]):
-        c, ms = s.profile(nm)
-        if c:
-            per = a.loopback_slabs                                  # launches per timed pass (one per local slab)
-            passes.append(dict(name=nm, kernel=kern[d], launches=c * per, avg_ms=ms / c / per,
-                               alg_bytes=algorithmic_bytes(dim, Nl, nJd[d]) + (fused_bytes if d == 0 else 0.0)))
-    if not passes:
-        # small / medium meshes run the three passes of an apply as ONE launch (k_apply3): no per-direction timing exists; the
-        # dominant kernel is that launch, charged with the whole apply (+ the fused CG vector updates)
-        c, ms = s.profile("schur_apply")
-        passes.append(dict(name="schur_apply", kernel="k_apply3 (x, y, z passes of one Schur apply in one launch)", launches=max(c, 1), avg_ms=ms / max(c, 1),
-                           alg_bytes=24.0 * Nl + 40.0 * sum(nJd[d] for d in range(dim)) + fused_bytes))
-    dom = max(passes, key=lambda p: p["avg_ms"])
-    # HBM traffic of that kernel from the PMC counters.  Counters cannot be read inside this process: the figure comes from separate
-    # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command (profiles/collect.sh; gfx950 x2 read correction), stored per
-    # cell in a committed profile; `traffic_source` says which one, so a stale profile is visible.  null when no profile matches the run.
-    traffic, traffic_source = None, None
-    try:
-        import re
-        def _tag(fn):                                               # r02_a_... -> (2, 1, "a"); r03_zz_... -> (3, 2, "zz"); r01_... -> (1, 0, "")
-            m = re.match(r"r(\d+)_(?:([a-z]+)_)?", fn)
-            return (int(m.group(1)), len(m.group(2) or ""), m.group(2) or "") if m else (0, 0, "")
-        sys.path.insert(0, os.path.join(ROOT, "profiles"))
-        from summarize import kernel_source_hash
-        cur = kernel_source_hash()
-        cands = sorted((f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_pmc_traffic_256cube.json")), key=_tag)
-        def _load(fn):
-            with open(os.path.join(ROOT, "profiles", fn)) as f:
-                return json.load(f)
-        fresh_ones = [f for f in cands if _load(f).get("kernel_source_sha256") == cur]     # the profile of THESE kernels if there is one, else the latest
-        prof = fresh_ones[-1] if fresh_ones else cands[-1]
-        pj = _load(prof)
-        pmc = pj["kernels"]
-        pat = {"schur_x": r"k_schur_x<", "schur_y": r"k_schur_[sc]<(\d+, )?1,", "schur_z": r"k_schur_[sc]<(\d+, )?2,", "schur_apply": r"k_apply3<"}[dom["name"]]
-        hits = [k for k in pmc if re.match(pat, k)]
-        key = max(hits, key=lambda k: pmc[k].get("dispatches", 0)) if hits else None
-        fresh = pj.get("kernel_source_sha256") == cur
-        if os.environ.get("NEUTFEM_OPTS"):
-            traffic_source = dict(file="profiles/" + prof, stale=True, why="NEUTFEM_OPTS overrides launch parameters: this is not the run that was profiled: traffic = null")
-        elif a.n == 256 and a.case == "iaea3d" and slabs_total == 1 and key in pmc and not fresh:
-            # the newest committed profile was taken with other kernel sources: no figure rather than a stale one
-            traffic_source = dict(file="profiles/" + prof, stale=True, why="the kernels or their launch logic changed since this profile was collected (sha256 of nf_kernels.h + nf_assembly.h + neutfem_hip.hip differs): traffic = null")
-        elif a.n == 256 and a.case == "iaea3d" and slabs_total == 1 and key in pmc:
-            traffic = round(pmc[key]["hbm_bytes_per_cell"] * N)
-            traffic_source = dict(file="profiles/" + prof, kernel=key, measured_in_this_run=False, kernel_sources_match=True,
-                                  how="separate rocprofv3 --pmc passes (FETCH_SIZE x2 gfx950 correction, WRITE_SIZE) of `python bench.py`; bytes per cell x cells of this run",
-                                  tag=pj.get("tag"), commit=pj.get("commit"))
-    except Exception:
+    roofline = None
+    if a.full:
+        # roofline of the dominant kernel (slowest direction pass of the Schur apply)
+        # per-launch figures refer to what ONE rank's launches process (its own planes)
+        if slabs_total > 1:
+            nzl = max(x.nz for x in s.slabs); nxl, nyl = head.nx, head.ny
+            Nl = nxl * nyl * nzl
+        else:
+            nzl, nxl, nyl, Nl = s.nz, s.nx, s.ny, N
+        nJd = {0: (nxl + 1) * nyl * nzl, 1: nxl * (nyl + 1) * nzl, 2: nxl * nyl * (nzl + 1)}
+        kern = {0: "k_schur_x<2,NCH,VEC>", 1: "k_schur_s<SEG,1> / k_schur_c<1> (y lines)", 2: "k_schur_s<SEG,2> / k_schur_c<2> (z lines)"}
+        passes = []
+        # fused CG (undivided RT0-P0 mesh): the x pass also carries x_sol += alpha p and p = r + beta p of the previous
+        # iteration (read r, x_sol; write p, x_sol = 32 B/cell on top of the apply; p itself is read once for both jobs) on every
+        # CG iteration but the first of a group solve
+        n_solves = hist["cg"].size
+        fused_bytes = 32.0 * Nl * (1.0 - n_solves / max(float(hist["cg"].sum()), 1.0)) if slabs_total == 1 else 0.0
+        for d, nm in enumerate(["schur_x", "schur_y", "schur_z"][:dim]):
+            c, ms = s.profile(nm)
+            if c:
+                per = a.loopback_slabs                                  # launches per timed pass (one per local slab)
+                passes.append(dict(name=nm, kernel=kern[d], launches=c * per, avg_ms=ms / c / per,
+                                   alg_bytes=algorithmic_bytes(dim, Nl, nJd[d]) + (fused_bytes if d == 0 else 0.0)))
+        if not passes:
+            # small / medium meshes run the three passes of an apply as ONE launch (k_apply3): no per-direction timing exists; the
+            # dominant kernel is that launch, charged with the whole apply (+ the fused CG vector updates)
+            c, ms = s.profile("schur_apply")
+            passes.append(dict(name="schur_apply", kernel="k_apply3 (x, y, z passes of one Schur apply in one launch)", launches=max(c, 1), avg_ms=ms / max(c, 1),
+                               alg_bytes=24.0 * Nl + 40.0 * sum(nJd[d] for d in range(dim)) + fused_bytes))
+        dom = max(passes, key=lambda p: p["avg_ms"])
+        # HBM traffic of that kernel from the PMC counters.  Counters cannot be read inside this process: the figure comes from separate
+        # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command (profiles/collect.sh; gfx950 x2 read correction), stored per
+        # cell in a committed profile; `traffic_source` says which one, so a stale profile is visible.  null when no profile matches the run.
         traffic, traffic_source = None, None
-    ach = dom["alg_bytes"] / (dom["avg_ms"] * 1e-3) / 1e9
-    ca, cms = s.profile("schur_apply")
-    apply_bytes = (24.0 * Nl + 40.0 * sum(nJd[d] for d in range(dim))) * a.loopback_slabs + fused_bytes
-    roofline = dict(bound="hbm", kernel=dom["kernel"], achieved=round(ach, 1), peak=HBM_PEAK_GBS, unit="GB/s",
-                    frac=round(ach / HBM_PEAK_GBS, 4), traffic=traffic, traffic_source=traffic_source, launches=dom["launches"], avg_ms=round(dom["avg_ms"], 4),
-                    event_sampling="HIP events bracket every 8th Schur apply of the timed steps (nf_set_option prof_every): an event record keeps "
-                                   "neighbouring launches from going out back to back, 8 records per apply cost 6 % of a CG iteration at 256^3",
-                    alg_bytes_per_launch=dom["alg_bytes"], fused_cg_vector_bytes_in_x_pass=fused_bytes,
-                    schur_apply=dict(avg_ms=round(cms / max(ca, 1), 4), alg_bytes=apply_bytes,
-                                     achieved=round(apply_bytes / (cms / max(ca, 1) * 1e-3) / 1e9, 1),
-                                     frac=round(apply_bytes / (cms / max(ca, 1) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)),
-                    passes=[dict(name=p["name"], avg_ms=round(p["avg_ms"], 4),
-                                 achieved=round(p["alg_bytes"] / (p["avg_ms"] * 1e-3) / 1e9, 1)) for p in passes])
-    # the same fraction against what a plain streaming copy reaches on this very GPU ("of spec" and "of measured copy")
-    copy_gbs = head.time_device_copy(1 << 30, 20)
-    roofline["measured_copy"] = dict(GBps=round(copy_gbs, 1), frac_of_copy=round(ach / copy_gbs, 4),
-                                     schur_apply_frac_of_copy=round(roofline["schur_apply"]["achieved"] / copy_gbs, 4),
-                                     note="best of plain / nontemporal copy kernels and hipMemcpyDtoD, 1 GiB, read + write counted; "
-                                          "fractions use ALGORITHMIC bytes, which exceed the HBM traffic (PMC) of these kernels")
-    if traffic:
-        tg = traffic / (dom["avg_ms"] * 1e-3) / 1e9
-        roofline["measured_copy"].update(hbm_traffic_GBps=round(tg, 1), hbm_traffic_frac_of_copy=round(tg / copy_gbs, 4))
+        try:
+            import re
+            def _tag(fn):                                               # r02_a_... -> (2, 1, "a"); r03_zz_... -> (3, 2, "zz"); r01_... -> (1, 0, "")
+                m = re.match(r"r(\d+)_(?:([a-z]+)_)?", fn)
+                return (int(m.group(1)), len(m.group(2) or ""), m.group(2) or "") if m else (0, 0, "")
+            sys.path.insert(0, os.path.join(ROOT, "profiles"))
+            from summarize import kernel_source_hash
+            cur = kernel_source_hash()
+            cands = sorted((f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_pmc_traffic_256cube.json")), key=_tag)
+            def _load(fn):
+                with open(os.path.join(ROOT, "profiles", fn)) as f:
+                    return json.load(f)
+            fresh_ones = [f for f in cands if _load(f).get("kernel_source_sha256") == cur]     # the profile of THESE kernels if there is one, else the latest
+            prof = fresh_ones[-1] if fresh_ones else cands[-1]
+            pj = _load(prof)
+            pmc = pj["kernels"]
+            pat = {"schur_x": r"k_schur_x<", "schur_y": r"k_schur_[sc]<(\d+, )?1,", "schur_z": r"k_schur_[sc]<(\d+, )?2,", "schur_apply": r"k_apply3<"}[dom["name"]]
+            hits = [k for k in pmc if re.match(pat, k)]
+            key = max(hits, key=lambda k: pmc[k].get("dispatches", 0)) if hits else None
+            fresh = pj.get("kernel_source_sha256") == cur
+            if os.environ.get("NEUTFEM_OPTS"):
+                traffic_source = dict(file="profiles/" + prof, stale=True, why="NEUTFEM_OPTS overrides launch parameters: this is not the run that was profiled: traffic = null")
+            elif a.n == 256 and a.case == "iaea3d" and slabs_total == 1 and key in pmc and not fresh:
+                # the newest committed profile was taken with other kernel sources: no figure rather than a stale one
+                traffic_source = dict(file="profiles/" + prof, stale=True, why="the kernels or their launch logic changed since this profile was collected (sha256 of nf_kernels.h + nf_assembly.h + neutfem_hip.hip differs): traffic = null")
+            elif a.n == 256 and a.case == "iaea3d" and slabs_total == 1 and key in pmc:
+                traffic = round(pmc[key]["hbm_bytes_per_cell"] * N)
+                traffic_source = dict(file="profiles/" + prof, kernel=key, measured_in_this_run=False, kernel_sources_match=True,
+                                      how="separate rocprofv3 --pmc passes (FETCH_SIZE x2 gfx950 correction, WRITE_SIZE) of `python bench.py`; bytes per cell x cells of this run",
+                                      tag=pj.get("tag"), commit=pj.get("commit"))
+        except Exception:
+            traffic, traffic_source = None, None
+        ach = dom["alg_bytes"] / (dom["avg_ms"] * 1e-3) / 1e9
+        ca, cms = s.profile("schur_apply")
+        apply_bytes = (24.0 * Nl + 40.0 * sum(nJd[d] for d in range(dim))) * a.loopback_slabs + fused_bytes
+        roofline = dict(bound="hbm", kernel=dom["kernel"], achieved=round(ach, 1), peak=HBM_PEAK_GBS, unit="GB/s",
+                        frac=round(ach / HBM_PEAK_GBS, 4), traffic=traffic, traffic_source=traffic_source, launches=dom["launches"], avg_ms=round(dom["avg_ms"], 4),
+                        event_sampling="HIP events bracket every 8th Schur apply of the timed steps (nf_set_option prof_every): an event record keeps "
+                                       "neighbouring launches from going out back to back, 8 records per apply cost 6 % of a CG iteration at 256^3",
+                        alg_bytes_per_launch=dom["alg_bytes"], fused_cg_vector_bytes_in_x_pass=fused_bytes,
+                        schur_apply=dict(avg_ms=round(cms / max(ca, 1), 4), alg_bytes=apply_bytes,
+                                         achieved=round(apply_bytes / (cms / max(ca, 1) * 1e-3) / 1e9, 1),
+                                         frac=round(apply_bytes / (cms / max(ca, 1) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)),
+                        passes=[dict(name=p["name"], avg_ms=round(p["avg_ms"], 4),
+                                     achieved=round(p["alg_bytes"] / (p["avg_ms"] * 1e-3) / 1e9, 1)) for p in passes])
+        # the same fraction against what a plain streaming copy reaches on this very GPU ("of spec" and "of measured copy")
+        copy_gbs = head.time_device_copy(1 << 30, 20)
+        roofline["measured_copy"] = dict(GBps=round(copy_gbs, 1), frac_of_copy=round(ach / copy_gbs, 4),
+                                         schur_apply_frac_of_copy=round(roofline["schur_apply"]["achieved"] / copy_gbs, 4),
+                                         note="best of plain / nontemporal copy kernels and hipMemcpyDtoD, 1 GiB, read + write counted; "
+                                              "fractions use ALGORITHMIC bytes, which exceed the HBM traffic (PMC) of these kernels")
+        if traffic:
+            tg = traffic / (dom["avg_ms"] * 1e-3) / 1e9
+            roofline["measured_copy"].update(hbm_traffic_GBps=round(tg, 1), hbm_traffic_frac_of_copy=round(tg / copy_gbs, 4))
 
     out = dict(metric="outer power-iters/sec (IAEA-3D RT0-P0 k-eigenvalue solve)" if a.case == "iaea3d" else "outer power-iters/sec (synthetic checkerboard RT0-P0 k-eigenvalue solve, fixed work)", value=round(a.steps / dt, 4), unit="outer-iters/s",
                n_gpus=world, rccl_ranks=(comm_ranks if world > 1 else 1), transport=(transport if world > 1 else "none (one rank: no collective on the data path)"),
@@ -414,11 +458,13 @@ def main():
                            cells=int(N), groups=int(ng),
                            cg_iters_per_outer=round(cg_per_outer, 1),
                            parallelism=f"{world} process(es) x {a.loopback_slabs} z-slab(s) each; RCCL: interface planes + scalar all-reduces"),
-               roofline=roofline, keff_after_timed_steps=k_timed)
+               keff_after_timed_steps=k_timed)
+    if roofline is not None:
+        out["roofline"] = roofline
 
     # ---- untimed: converged k-eff at full size with the drivers' settings (coarse-mesh start included), on every N: the
     # pcm half of BASELINE's metric.  Collective on a decomposed run (all ranks solve, rank 0 reports).
-    if not a.no_converge and a.case == "iaea3d":
+    if a.full and not a.no_converge and a.case == "iaea3d":
         note("converged solve (untimed)")
         s.reset_flux()
         s.set_tol(1e-5, 1e-4, 1e-4, 200, 1000)
@@ -461,16 +507,16 @@ def main():
                 out["converged"].update(keff_one_gpu=ref[0], keff_one_gpu_source=ref[1], pcm_vs_one_gpu=round(1e5 * abs(kc - ref[0]) / ref[0], 4))
     # ---- the other BASELINE configs (small, latency bound): timed with the reference drivers' own settings; before the big CPU
     # baseline, whose 10 GB of host arrays leave the allocator in a state that distorts millisecond-scale CPU timings
-    if rank == 0 and slabs_total == 1 and not a.no_small:
+    if a.full and rank == 0 and slabs_total == 1 and not a.no_small:
         note("small BASELINE configs")
         out["other_configs"] = small_configs(local)
-    if rank == 0 and slabs_total == 1 and not a.no_small and a.case == "iaea3d":
+    if a.full and rank == 0 and slabs_total == 1 and not a.no_small and a.case == "iaea3d":
         note("higher-order throughput (RT1-P1 Schur apply at 128^3)")
         try:
             out["higher_order"] = higher_order_throughput(local)
         except Exception as e:                                       # an extra must never cost the headline line
             out["higher_order"] = dict(error=str(e)[:300])
-    if rank == 0 and slabs_total == 1:
+    if a.full and rank == 0 and slabs_total == 1:
         # ---- CPU baseline: bounded sample of the same workload on the host (1 core) -------------------------------
         if a.cpu_sample_iters > 0:
             note("CPU baseline (oracle, 1 core)")
@@ -525,7 +571,7 @@ def main():
     # ---- BASELINE configs[4] (synthetic 512^3, 8 groups, fixed work of 50 CG iterations per group solve) on this ONE GPU,
     # so that the driver's run times it too.  Needs ~165 GB of HBM and ~75 GB of host memory for the case arrays: skipped when the
     # box has less.  The headline (`value`, `config.workload`) stays the IAEA-3D 256^3 case above.
-    if rank == 0 and world == 1 and slabs_total == 1 and a.case == "iaea3d" and a.n == 256 and not a.no_c5:
+    if a.full and rank == 0 and world == 1 and slabs_total == 1 and a.case == "iaea3d" and a.n == 256 and not a.no_c5:
         try:
             free_b, _tot = capi.mem_info(local)
             with open("/proc/meminfo") as f:

@@ -104,3 +104,38 @@ def test_split_planes():
     assert split_planes(256, 8) == [(32 * i, 32 * i + 32) for i in range(8)]
     p = split_planes(19, 3)
     assert p[0][0] == 0 and p[-1][1] == 19 and all(a[1] == b[0] for a, b in zip(p, p[1:]))
+
+
+class _FakeFlux:
+    """what bench.dump_outputs reads of a solver: the flux (ng, cells) of an undivided mesh, or a team's (ng, planes, ny, nx)"""
+
+    def __init__(self, phi, team):
+        self.phi, self.team = phi, team
+        if team:
+            self.get_phi_local = lambda: self.phi
+
+    def get_phi(self):
+        return self.phi.reshape(self.phi.shape[0], -1)
+
+
+@pytest.mark.parametrize("nz", [6, 200])
+def test_bench_dump_outputs_of_slabs_match_the_undivided_mesh(tmp_path, monkeypatch, nz):
+    """--dump-outputs: what the ranks of a z-split run contribute adds up to what one rank writes for the whole mesh, whether phi.npy
+    holds every cell (small mesh) or the fixed sample (a cap forced below the cell count)"""
+    import bench
+    monkeypatch.delenv("RANK", raising=False)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 8 * 1000)
+    ng, ny, nx = 2, 7, 9
+    phi = np.random.default_rng(3).random((ng, nz, ny, nx)) + 0.5
+    N = nz * ny * nx
+    bench.dump_outputs(str(tmp_path / "whole"), _FakeFlux(phi, False), 1.25, N, nx * ny, 0, ng, None)
+    parts = []
+    for r, (k0, k1) in enumerate(bench.split_planes(nz, 3)):
+        bench.dump_outputs(str(tmp_path / f"r{r}"), _FakeFlux(phi[:, k0:k1].copy(), True), 1.25, N, nx * ny, k0, ng, None)
+        parts.append(np.load(str(tmp_path / f"r{r}" / "phi.npy")))
+    whole = np.load(str(tmp_path / "whole" / "phi.npy"))
+    assert whole.dtype == np.float64 and whole.shape == (ng, min(N, 1000))
+    assert np.array_equal(sum(parts), whole) and np.all(whole > 0)
+    if N <= 1000:
+        assert np.array_equal(whole, phi.reshape(ng, -1))
+    assert np.load(str(tmp_path / "whole" / "keff.npy")).tolist() == [1.25]

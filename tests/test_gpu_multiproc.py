@@ -249,7 +249,7 @@ def test_bench_two_ranks_on_one_gpu():
     counts and which library carried the data (--gpus used to be ignored)"""
     e = _env(); e["NEUTFEM_FORCE_DEVICE"] = "0"; e["NEUTFEM_BENCH_N"] = "64"
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"): e.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"],
                        env=e, capture_output=True, text=True, timeout=400, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "starting 2 ranks" in r.stderr
@@ -273,9 +273,9 @@ def test_bench_two_ranks_on_one_gpu():
 
 
 def test_bench_json_contract_single_rank():
-    """the one-line JSON of `python bench.py` (driver contract + the tier's roofline / cpu_baseline objects), on a small mesh"""
+    """the one-line JSON of `python bench.py --full` (driver contract + the tier's roofline / cpu_baseline objects), on a small mesh"""
     e = dict(os.environ); e["NEUTFEM_BENCH_N"] = "48"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-sample-iters", "3"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-sample-iters", "3", "--full"],
                        env=e, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -294,6 +294,29 @@ def test_bench_json_contract_single_rank():
     assert cb["cores"] == 1 and cb["kind"] == "port" and cb["value"] > 0 and isinstance(cb["sample"], str)
     assert d["parity"]["pcm"] < 1.0 and d["parity"]["flux_rel_l2"] < 1e-8
     assert len(d["other_configs"]) == 4 and all(c["pcm_vs_oracle"] < 1.0 for c in d["other_configs"])
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """a plain `python bench.py` (no --full) prints the headline and nothing it has to measure apart; --steps sets the timed outers;
+    --dump-outputs writes k and the flux of the last timed step, the same on two runs with the same arguments"""
+    e = dict(os.environ); e["NEUTFEM_BENCH_N"] = "48"
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / run)],
+                           env=e, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+    d = lines[0]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) / d["value"] < 1e-3
+    assert not set(d) & {"roofline", "converged", "other_configs", "higher_order", "cpu_baseline", "parity", "parity_at_bench_size", "c5_single_gpu"}
+    k = [np.load(str(tmp_path / run / "keff.npy")) for run in ("a", "b")]
+    phi = [np.load(str(tmp_path / run / "phi.npy")) for run in ("a", "b")]
+    assert k[0].dtype == np.float64 and k[0].shape == (1,) and k[0][0] == d["keff_after_timed_steps"]
+    assert phi[0].dtype == np.float64 and phi[0].shape == (2, 48 ** 3) and np.all(np.isfinite(phi[0])) and phi[0].max() > 0
+    assert abs(k[1][0] - k[0][0]) < 1e-12 * k[0][0] and rel_l2(phi[1].ravel(), phi[0].ravel()) < 1e-12
 
 
 def test_two_ranks_over_the_real_rccl(tmp_path):
