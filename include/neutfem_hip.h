@@ -125,6 +125,36 @@ typedef struct nf_keff_opts {
  * current flux (nf_set_phi/nf_get_phi) and has_valid_keff_/last_keff_direct_. */
 int nf_solve_keff(nf_handle h, const nf_keff_opts *opts, double *keff, int *n_outer);
 
+/* External source SRC_data_ (include/NeutFEM.hpp:365-388, get_SRC() at src/wrapper.cpp:829; SolveSubcritical reads it,
+ * src/wrapper.cpp:699-715) -> device, host layout [g*N + e] like the cross sections; on a slab, the slab's own cells (as nf_upload_xs).
+ * SRC is piecewise constant per cell: it loads DOF 0 only, q_g[e, 0] = Q_g(e) |e|.  Needs no nf_build and survives one; a new upload
+ * replaces the source.  Non-finite values are refused (NF_ERR_ARG). */
+int nf_upload_source(nf_handle h, const double *src_host);
+
+typedef struct nf_subcrit_result {
+    double M;                   /* amplification: phi_int / phi_int_nofission (include/NeutFEM.hpp:275-279, src/wrapper.cpp:699-715) */
+    double k_source;            /* production / (production + source) */
+    double ratio;               /* contraction dP_n / dP_{n-1} of the fission phase (last value with |dP_n| >= 1e-6 P_n; with downscatter only
+                                 * it tends to the k-eff of the same core) */
+    double phi_int, phi_int_nofission;   /* sum over g, e of |e| phibar_g(e) (phibar = DOF 0, the cell mean) with and without fission */
+    double production;          /* sum over g, e of nuSigf_g(e) |e| phibar_g(e) */
+    double source;              /* sum over g, e of Q_g(e) |e| */
+    int n_outer, n_outer_nofission, cg_total, converged;   /* outers of the fission / no-fission phase, group-solve iterations of both */
+} nf_subcrit_result;
+
+/* NeutFEM::SolveSubcritical (declared include/NeutFEM.hpp:275-279 with the contract of src/wrapper.cpp:699-715, never defined there):
+ * -div(D grad phi) + Sigma_r phi = F phi + Q, i.e. per group S_g phi_g = chi_g tf(phi) + sum_{g'!=g} Ms[g<-g'] phi_g' + q_g with the fission
+ * source not divided by an eigenvalue.  Source iteration in two phases from phi = 0: without fission (phi0), then with it from phi0; each
+ * stops when |P_n - P_{n-1}| / P_n < tol_keff (phase 0: phi_int in place of P) and ||phi_n - phi_{n-1}|| / ||phi_n|| < tol_flux, or after
+ * max_outer outers (NF_OK, converged = 0).  Reads from opts: tol_keff, tol_flux, max_outer, max_inner, use_diagonal_solver (RT0-P0),
+ * solver_type, solver_type_pushed -- the group solver is the one nf_solve_keff picks; use_coarse_init / use_cmfd must be 0 (NF_ERR_ARG).
+ * Needs nf_build and nf_upload_source on every slab.  Errors: a zero source -> NF_ERR_ARG; a system that is not subcritical (the fission
+ * phase's contraction >= 1 in 5 consecutive outers from its 5th on, or non-finite sums) -> NF_ERR_NUMERIC, current flux reset to 1.
+ * Afterwards the converged flux (absolute units per unit source) is the current flux (nf_get_phi, nf_get_J); the warm state
+ * (has_valid_keff / last_keff), nf_get_history and nf_info "last_outer" keep what the last nf_solve_keff left; nf_progress counts the
+ * outers of both phases; nf_info "last_path" is 0.  Undivided meshes and linked slabs of one process; multi-rank teams: NF_ERR_UNSUPPORTED. */
+int nf_solve_subcritical(nf_handle h, const nf_keff_opts *opts, nf_subcrit_result *res);
+
 /* No reference counterpart (the reference is one process): outer iterations the running or last nf_solve_keff has completed
  * (the `it` of the loop at src/NeutFEM.cpp:1694).  May be called from another thread while nf_solve_keff runs -- the watchdog
  * of a multi-rank job tells a slow solve from one whose peers are gone.  On a multi-rank team a rank that fails inside a solve

@@ -14,7 +14,7 @@ SYMBOLS = [
     "nf_last_error", "nf_device_count", "nf_create", "nf_destroy", "nf_create_slab", "nf_link_slabs", "nf_comm_unique_id",
     "nf_comm_init", "nf_comm_info", "nf_comm_selftest", "nf_team_schur_apply", "nf_info", "nf_set_bc", "nf_upload_xs", "nf_build",
     "nf_schur_apply", "nf_solve_group", "nf_build_diagonal_cache", "nf_get_diagonal_cache", "nf_solve_keff",
-    "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
+    "nf_upload_source", "nf_solve_subcritical", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
     "nf_get_warm_state", "nf_get_history", "nf_profile_get", "nf_profile_reset", "nf_time_schur_apply", "nf_time_device_copy", "nf_progress", "nf_set_progress_callback", "nf_local_matrices",
     "nf_set_option", "nf_mem_info", "nf_dev_alloc", "nf_dev_free", "nf_memcpy_h2d", "nf_memcpy_d2h", "nf_synchronize", "nf_stream",
 ]
@@ -25,6 +25,14 @@ class KeffOpts(C.Structure):
                 ("use_coarse_init", C.c_int), ("coarse_factors", C.c_int * 3), ("n_coarse_factors", C.c_int),
                 ("use_diagonal_solver", C.c_int), ("solver_type", C.c_int), ("solver_type_pushed", C.c_int),
                 ("profile", C.c_int), ("use_cmfd", C.c_int)]
+
+
+class SubcritResult(C.Structure):
+    _fields_ = [("M", C.c_double), ("k_source", C.c_double), ("ratio", C.c_double), ("phi_int", C.c_double),
+                ("phi_int_nofission", C.c_double), ("production", C.c_double), ("source", C.c_double),
+                ("n_outer", C.c_int), ("n_outer_nofission", C.c_int), ("cg_total", C.c_int), ("converged", C.c_int)]
+
+    def as_dict(self): return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 _LIB = None
@@ -60,6 +68,8 @@ def load():
     L.nf_build_diagonal_cache.argtypes = [vp]
     L.nf_get_diagonal_cache.argtypes = [vp, C.c_int, dp]
     L.nf_solve_keff.argtypes = [vp, C.POINTER(KeffOpts), dp, ip]
+    L.nf_upload_source.argtypes = [vp, dp]
+    L.nf_solve_subcritical.argtypes = [vp, C.POINTER(KeffOpts), C.POINTER(SubcritResult)]
     L.nf_solve_coarse.argtypes = [vp, C.POINTER(KeffOpts), dp, dp]
     L.nf_solve_adjoint.argtypes = [vp, C.POINTER(KeffOpts), C.c_int, C.c_int, dp, ip]
     L.nf_get_phi_adj.argtypes = [vp, dp]
@@ -208,6 +218,18 @@ class HipSolver:
         k, n = C.c_double(), C.c_int()
         self._chk(self.L.nf_solve_keff(self.h, C.byref(o), C.byref(k), C.byref(n)))
         return k.value, n.value
+
+    def upload_source(self, src):
+        """external source SRC (ng, cells) in the reference layout [g*N + e]: piecewise constant per cell"""
+        a = np.ascontiguousarray(src, dtype=np.float64).ravel(); assert a.size == self.ng * self.ne
+        self._chk(self.L.nf_upload_source(self.h, _dp(a)))
+
+    def solve_subcritical(self, use_diag=False):
+        """fixed-source solve (nf_solve_subcritical) with the tolerances / linear solver of this object: the result struct as a dict"""
+        o = self.opts(use_diag=use_diag)
+        r = SubcritResult()
+        self._chk(self.L.nf_solve_subcritical(self.h, C.byref(o), C.byref(r)))
+        return r.as_dict()
 
     def coarsen(self, rx, ry=1, rz=1):
         """built coarse twin (HipSolver over the merged mesh, block-mean XS); close() it when done"""
@@ -390,6 +412,13 @@ class HipTeam:
 
     def build(self):
         for s in self.slabs: s.build()
+
+    def upload_source(self, src, k_offset=0):
+        """global (ng, nz, ny, nx) source split over the local slabs as upload_xs_global splits the cross sections"""
+        for s, (k0, k1) in zip(self.slabs, self.planes):
+            s.upload_source(np.asarray(src)[:, k0 - k_offset:k1 - k_offset])
+
+    def solve_subcritical(self, use_diag=False): return self.head.solve_subcritical(use_diag)
 
     def solve_keff(self, use_coarse=False, factors=(), profile=False, use_diag=False, use_cmfd=False):
         return self.head.solve_keff(use_coarse, factors, use_diag, profile, use_cmfd)

@@ -3,7 +3,7 @@
 //
 // The class keeps what the reference keeps on the host -- cross-section arrays, flux, tolerances,
 // BC map, warm-start flags -- and hands the hot path (BuildMatrices, SolveKeff, SolveCoarse,
-// build_diagonal_cache) to the HIP library.  There is NO CPU fallback: without a HIP device those
+// build_diagonal_cache, SolveSubcritical) to the HIP library.  There is NO CPU fallback: without a HIP device those
 // methods raise RuntimeError.  Methods the reference binds but that lie outside the accelerated
 // path (never-defined projections, reflectors) raise RuntimeError with that explanation.
 #include <pybind11/numpy.h>
@@ -170,6 +170,37 @@ public:
         has_valid_keff_ = true; last_keff_ = k;
         return k;
     }
+    // SolveSubcritical (include/NeutFEM.hpp:275-279, src/wrapper.cpp:699-715; declared, never defined there): fixed-source solve with the
+    // source of get_SRC(), uploaded on every call (a source set after BuildMatrices counts); returns M = flux with / without fission
+    double SolveSubcritical()
+    {
+        need_built("SolveSubcritical");
+        Log(VerbosityLevel::NORMAL, "\n=== CALCUL SOUS-CRITIQUE (SOURCE EXTERNE) ===");
+        chk(nf_upload_source(h_, SRC_.data()));
+        nf_keff_opts o = make_opts(false, {}, false);
+        nf_subcrit_result r{};
+        chk(nf_solve_subcritical(h_, &o, &r));
+        chk(nf_get_phi(h_, Phi_.data()));
+        subcrit_ = r; has_subcrit_ = true;
+        if (verb_ >= VerbosityLevel::NORMAL) {
+            std::cout << "  Sans fission : " << r.n_outer_nofission << " iterations, avec fission : " << r.n_outer << " iterations"
+                      << (r.converged ? "" : " (non converge)") << std::endl;
+            std::cout << "  Rapport de convergence = " << std::fixed << std::setprecision(6) << r.ratio << "  k-source = " << r.k_source
+                      << std::defaultfloat << std::endl;
+            std::cout << "  Facteur d'amplification M = " << std::fixed << std::setprecision(8) << r.M << std::defaultfloat << std::endl;
+        }
+        return r.M;
+    }
+    py::dict GetSubcriticalInfo() const
+    {
+        if (!has_subcrit_) throw std::runtime_error("get_subcritical_info: call SolveSubcritical() first");
+        const nf_subcrit_result &r = subcrit_;
+        py::dict d;
+        d["M"] = r.M; d["k_source"] = r.k_source; d["ratio"] = r.ratio; d["phi_int"] = r.phi_int; d["phi_int_nofission"] = r.phi_int_nofission;
+        d["production"] = r.production; d["source"] = r.source; d["n_outer"] = r.n_outer; d["n_outer_nofission"] = r.n_outer_nofission;
+        d["cg_total"] = r.cg_total; d["converged"] = r.converged;
+        return d;
+    }
     std::pair<double, py::array_t<double>> SolveCoarse(const std::vector<int> &refine)
     {
         need_built("SolveCoarse");
@@ -306,6 +337,7 @@ private:
     double tol_keff_ = 1e-5, tol_flux_ = 1e-5, tol_L2_ = 1e-5; int max_outer_ = 200, max_inner_ = 1000;
     VerbosityLevel verb_ = VerbosityLevel::NORMAL; double cmfd_omega_ = 1.0;
     bool has_valid_keff_ = false, has_valid_adjoint_ = false;
+    nf_subcrit_result subcrit_{}; bool has_subcrit_ = false;     // the last SolveSubcritical (get_subcritical_info)
 };
 
 PYBIND11_MODULE(_neutfem_eigen, m)
@@ -352,7 +384,7 @@ PYBIND11_MODULE(_neutfem_eigen, m)
         .def("SolveKeff", &NeutFEM::SolveKeff, py::arg("use_coarse_init") = false, py::arg("coarse_factors") = std::vector<int>{},
              py::arg("use_diagonal_solver") = false, py::arg("use_cmfd") = false)
         .def("SolveAdjoint", &NeutFEM::SolveAdjoint, py::arg("normalize_to_direct") = true, py::arg("use_direct_keff") = true)
-        .def("SolveSubcritical", [](NeutFEM &s) { s.oos("SolveSubcritical", "declared at include/NeutFEM.hpp:279, never defined"); })
+        .def("SolveSubcritical", &NeutFEM::SolveSubcritical)
         .def("SolveCoarse", &NeutFEM::SolveCoarse, py::arg("refine"))
         .def("build_diagonal_cache", &NeutFEM::BuildDiagonalCache)
         .def("initialize_cmfd", &NeutFEM::InitializeCMFD)
@@ -371,6 +403,8 @@ PYBIND11_MODULE(_neutfem_eigen, m)
         .def("get_flux_adj", [](NeutFEM &s) { return s.flux(s.PhiAdj_, s.fluxAdjP0_); })
         .def("get_current", &NeutFEM::GetCurrent, "extension: Sol_J_ as a flat (ng*n_J) array in the reference DOF order")
         .def("get_bc_map", &NeutFEM::GetBCMap, "extension: {attr: BCType value} as set through set_bc")
+        .def("get_subcritical_info", &NeutFEM::GetSubcriticalInfo,
+             "extension: the last SolveSubcritical's nf_subcrit_result as a dict (M, k_source, ratio, integrals, outer counts, converged)")
         .def("reset_flux", &NeutFEM::ResetFlux)
         .def("GetNumElements", [](const NeutFEM &s) { return s.ne_; })
         .def("GetNumGroups", [](const NeutFEM &s) { return s.nphi_ / s.ne_; })      // reference bug kept, src/wrapper.cpp:953-955

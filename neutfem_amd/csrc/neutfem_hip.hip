@@ -241,6 +241,8 @@ struct nf_solver {
     bool zw_dot = false;                                // this apply: the y / z passes emit T_a sum z_f w_f as their share of x.y (team_schur_apply, split)
     hipStream_t pass_stream = nullptr;                  // this launch goes to another stream than the team's (x || y on small slabs)
     bool pass_noacc = false; const double *pass_yadd = nullptr;   // SlabArgs::noacc / yadd of this launch
+    double *d_qsrc = nullptr;                           // external source as a load vector, ng * nphi (nf_upload_source, k_source_q)
+    double src_total = 0.0; bool src_any = false;       // sum of Q |e| over the slab's cells, some Q != 0
     double *d_Jz = nullptr; bool jz_valid = false;      // slabs: z currents of the last solve, ng * nJz face DOFs (nf_get_J)
     double *d_Jzb = nullptr;                            // slabs, RT1+: z bubbles of the local cells, ng * N * ni
     // CMFD (include/NeutFEM.hpp:119-143): D~ / D^ per direction (ng * faces), PCG work vectors, scalars
@@ -553,6 +555,7 @@ int nf_destroy(nf_handle S)
     dfree(S->d_Jz); dfree(S->d_Jzb); dfree(S->d_ctlo); dfree(S->d_cthi); dfree(S->d_elo); dfree(S->d_ehi); dfree(S->d_relo); dfree(S->d_rehi);
     dfree(S->d_phi); dfree(S->d_raw); dfree(S->d_p0); dfree(S->d_p1);
     dfree(S->d_tf); dfree(S->d_rhs); dfree(S->d_r); dfree(S->d_p); dfree(S->d_q); dfree(S->d_p2); dfree(S->d_qy); dfree(S->d_qz);
+    dfree(S->d_qsrc);
     if (T) {
         T->slabs.erase(std::remove(T->slabs.begin(), T->slabs.end(), S), T->slabs.end());
         for (size_t i = 0; i < T->slabs.size(); ++i) T->slabs[i]->slab_index = (int)i;
@@ -2859,6 +2862,24 @@ static int solve_keff_xcd(nf_team *T, const nf_keff_opts *o, const Fuse3Plan &P,
 }
 
 // ---- SolveKeff (src/NeutFEM.cpp:1627-1815) -----------------------------------------------------
+// The group solver of the host-driven outer loops (SolveKeff, SolveSubcritical).
+// SchurSolver type: DIRECT_* or n_phi < 200 -> "exact" solve (CG to 1e-14 stands in)
+// SchurSolver::NeedsExplicitSchur (src/solvers.cpp:114-124): direct types, a type that was never pushed (quirk 11), n_phi < 200.
+// Undivided meshes up to direct_max_dofs get the real thing (dense S^-1, dense_prepare); beyond that and on slab teams CG to
+// 1e-14 stands in, bounded so that an ill-conditioned S (IAEA-3D: cond ~1e17) cannot run away; such solves are counted.
+struct InnerPlan { bool direct, dense; double cg_tol; int cg_max; };
+static InnerPlan inner_plan(const nf_team *T, const nf_keff_opts *o)
+{
+    const bool single = team_is_single(T);
+    long Ntot = 0; for (auto *S : T->slabs) Ntot += S->nphi;
+    InnerPlan p;
+    p.direct = !o->solver_type_pushed || o->solver_type <= 2 || (single && Ntot < 200);
+    p.dense = p.direct && single && !T->rccl_reduce && Ntot <= T->direct_max_dofs;
+    p.cg_tol = p.direct ? 1e-14 : o->tol_flux;                    // SetTolerance forwards tol_flux (:334)
+    p.cg_max = p.direct ? (int)std::min<long>(20 * Ntot + 50, 200000L) : o->max_inner;   // CG ends in <= n steps in exact arithmetic
+    return p;
+}
+
 static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, int *n_outer)
 {
     const int ns = (int)T->slabs.size();
@@ -2878,15 +2899,10 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
         NFCHK(coarse_init(T, o, &kc, dsts, &done));
         keff = done ? kc : 1.0;
     }
-    long Ntot = 0; for (auto *S : T->slabs) Ntot += S->nphi;
-    // SchurSolver type: DIRECT_* or n_phi < 200 -> "exact" solve (CG to 1e-14 stands in)
-    // SchurSolver::NeedsExplicitSchur (src/solvers.cpp:114-124): direct types, a type that was never pushed (quirk 11), n_phi < 200.
-    // Undivided meshes up to direct_max_dofs get the real thing (dense S^-1, dense_prepare); beyond that and on slab teams CG to
-    // 1e-14 stands in, bounded so that an ill-conditioned S (IAEA-3D: cond ~1e17) cannot run away; such solves are counted.
-    const bool direct = !o->solver_type_pushed || o->solver_type <= 2 || (single && Ntot < 200);
-    const bool dense = direct && single && !T->rccl_reduce && Ntot <= T->direct_max_dofs;
-    const double cg_tol = direct ? 1e-14 : o->tol_flux;           // SetTolerance forwards tol_flux (:334)
-    const int cg_max = direct ? (int)std::min<long>(20 * Ntot + 50, 200000L) : o->max_inner;   // CG ends in <= n steps in exact arithmetic
+    const InnerPlan ip = inner_plan(T, o);
+    const bool direct = ip.direct, dense = ip.dense;
+    const double cg_tol = ip.cg_tol;
+    const int cg_max = ip.cg_max;
     T->last_direct = dense ? 1 : direct ? 2 : 0;
     if (dense) NFCHK(dense_prepare(T));
     // ChebyshevAccel(15, 0.98), src/solvers.cpp:664-700
@@ -2970,7 +2986,7 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
                 double *dst = use_diag ? S->d_raw + g * NP : S->d_rhs;
                 // CG path: the start of the solve (x = 0, r = p = rhs, |rhs|^2 partials) rides in the same launch (cg_solve(..., inited))
                 const bool cgi = !use_diag && !dense;
-                hipLaunchKernelGGL(k_group_rhs, dim3(gN[i]), dim3(256), 0, T->stream, sa, g, S->d_Chi + g * N, S->d_tf, 1.0 / keff, S->d_raw, S->d_phi,
+                hipLaunchKernelGGL(k_group_rhs<false>, dim3(gN[i]), dim3(256), 0, T->stream, sa, g, S->d_Chi + g * N, S->d_tf, 1.0 / keff, S->d_raw, S->d_phi,
                                    use_diag ? S->d_Sinv + g * N : (const double *)nullptr, dst, NP, N,
                                    cgi ? S->d_raw + g * NP : (double *)nullptr, cgi ? S->d_r : (double *)nullptr, cgi ? S->d_p : (double *)nullptr,
                                    cgi ? T->d_partials + i * T->slab_cap : (double *)nullptr);
@@ -3072,6 +3088,170 @@ int nf_progress(nf_handle S, long *outers_done)
     return NF_OK;
 }
 
+// ---- SolveSubcritical (declared include/NeutFEM.hpp:275-279, src/wrapper.cpp:699-715; never defined there) ----------------------
+// -div(D grad phi) + Sigma_r phi = F phi + Q: per group S_g phi_g = chi_g tf(phi) + scatter_g(phi) + q_g, solved by source iteration
+// (DESIGN.md 11).  SRC is piecewise constant per cell: q_g[e, dof 0] = Q_g(e) |e|, higher moments 0.
+int nf_upload_source(nf_handle S, const double *src)
+{
+    if (!S || !src) return fail(NF_ERR_ARG, "nf_upload_source: bad arguments");
+    HIPCHK(hipSetDevice(S->device));
+    hipStream_t st = S->team->stream;
+    const long N = S->N, NT = S->nphi * S->ng;
+    double tot = 0.0; bool any = false;
+    for (int g = 0; g < S->ng; ++g)
+        for (long e = 0; e < N; ++e) {
+            const double v = src[g * N + e];
+            if (!std::isfinite(v)) return fail(NF_ERR_ARG, "nf_upload_source: non-finite source in group %d, cell %ld", g, e);
+            const long r = e / S->nx;
+            tot += v * (S->hx[e % S->nx] * S->hy[r % S->ny] * S->hz[r / S->ny]);
+            any |= v != 0.0;
+        }
+    if (!S->d_qsrc) NFCHK(dalloc(&S->d_qsrc, (size_t)NT));
+    DevTmp<double> d_src; NFCHK(dalloc(&d_src.p, (size_t)N * S->ng));
+    HIPCHK(hipMemcpyAsync(d_src.p, src, (size_t)N * S->ng * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_source_q, dim3(grid_for(NT)), dim3(256), 0, st, (const double *)d_src.p, S->d_qsrc, S->d_hx, S->d_hy, S->d_hz,
+                       S->nx, S->ny, N, S->nphi, NT);
+    HIPCHK(hipStreamSynchronize(st));                             // d_src is freed on return
+    HIPCHK(hipGetLastError());
+    S->src_total = tot; S->src_any = any;
+    return NF_OK;
+}
+
+// Two phases of the host-driven loop of solve_keff_impl: phase 0 with the fission term off (the flux without fission, phi0), phase 1
+// from phi0 with fission at scale 1 (no eigenvalue).  Each outer: tf from the previous outer's flux, Gauss-Seidel group sweep with the
+// same group solver SolveKeff picks (inner_plan / diagonal S^-1), then one streaming pass (k_subcrit_reduce) for Phi, P, the norms and
+// the copy raw -> phi.  No normalisation, no acceleration.  Phase 0 starts from phi = 0, so the result does not depend on the flux the
+// handle held before.
+static int solve_subcritical_impl(nf_team *T, const nf_keff_opts *o, nf_subcrit_result *res)
+{
+    if (T->nproc > 1) return fail(NF_ERR_UNSUPPORTED, "nf_solve_subcritical: multi-rank teams are not supported (one process, undivided mesh or linked slabs)");
+    if (o->use_coarse_init || o->use_cmfd) return fail(NF_ERR_ARG, "nf_solve_subcritical: coarse start and CMFD do not apply to the fixed-source iteration");
+    if (o->max_outer < 1) return fail(NF_ERR_ARG, "nf_solve_subcritical: max_outer must be at least 1");
+    const int ns = (int)T->slabs.size();
+    nf_solver *S0 = T->slabs[0];
+    const int ng = S0->ng;
+    double src_total = 0.0; bool src_any = false;
+    for (auto *S : T->slabs) {
+        if (!S->d_qsrc) return fail(NF_ERR_STATE, "nf_solve_subcritical: call nf_upload_source first (every slab)");
+        src_total += S->src_total; src_any |= S->src_any;
+    }
+    if (!src_any) return fail(NF_ERR_ARG, "nf_solve_subcritical: the external source is zero on every cell");
+    NFCHK(team_prepare(T));
+    const int use_diag = (o->use_diagonal_solver && S0->k == 0 && S0->m == 0) ? 1 : 0;
+    if (use_diag) NFCHK(nf_build_diagonal_cache(S0));
+    const InnerPlan ip = inner_plan(T, o);
+    T->last_direct = ip.dense ? 1 : ip.direct ? 2 : 0;
+    if (ip.dense) NFCHK(dense_prepare(T));
+    T->last_path = 0; T->profile = false;
+    ScatterArgs sa; sa.ng = ng;
+    std::vector<int> gN(ns), gT(ns);
+    std::vector<const double *> rhs(ns); std::vector<double *> sol(ns);
+    for (int i = 0; i < ns; ++i) { gN[i] = grid_for(T->slabs[i]->nphi); gT[i] = grid_for(T->slabs[i]->nphi * ng); }
+    nf_subcrit_result r; memset(&r, 0, sizeof r);
+    r.source = src_total; r.ratio = 0.0;
+    double hout[4] = { 0, 0, 0, 0 };
+    long outers = 0;
+    for (auto *S : T->slabs) HIPCHK(hipMemsetAsync(S->d_phi, 0, (size_t)S->nphi * ng * sizeof(double), T->stream));   // phase 0 starts from phi = 0
+    int rc = NF_OK;
+    bool conv[2] = { false, false };
+    for (int phase = 0; phase < 2 && rc == NF_OK; ++phase) {
+        const double fscale = phase;                              // 0: flux without fission, 1: with fission
+        double q_old = 0.0, dq_old = 0.0;                         // Phi (phase 0) / P (phase 1) and its change at the previous outer
+        int streak = 0, n = 0;
+        if (phase == 1) q_old = r.production;                     // P of phi0
+        for (int it = 0; it < o->max_outer; ++it) {
+            for (int i = 0; i < ns; ++i) {                        // tf = sum_g Mf_g phi_g of the previous outer (finite, also when scaled by 0)
+                nf_solver *S = T->slabs[i];
+                hipLaunchKernelGGL(k_fission, dim3(gN[i]), dim3(256), 0, T->stream, S->d_Mf, S->d_phi, ng, S->nphi, S->d_tf, T->d_partials + i * T->slab_cap, (const double *)nullptr, 0L);
+            }
+            for (int g = 0; g < ng && rc == NF_OK; ++g) {
+                for (int i = 0; i < ns; ++i) {
+                    nf_solver *S = T->slabs[i]; const long N = S->N, NP = S->nphi;
+                    for (int gp = 0; gp < 64; ++gp) sa.M[gp] = gp < ng ? S->d_Ms[g * ng + gp] : nullptr;
+                    double *dst = use_diag ? S->d_raw + g * NP : S->d_rhs;
+                    const bool cgi = !use_diag && !ip.dense;      // CG start rides in the same launch (cg_solve(..., inited))
+                    hipLaunchKernelGGL(k_group_rhs<true>, dim3(gN[i]), dim3(256), 0, T->stream, sa, g, S->d_Chi + g * N, S->d_tf, fscale, S->d_raw, S->d_phi,
+                                       use_diag ? S->d_Sinv + g * N : (const double *)nullptr, dst, NP, N,
+                                       cgi ? S->d_raw + g * NP : (double *)nullptr, cgi ? S->d_r : (double *)nullptr, cgi ? S->d_p : (double *)nullptr,
+                                       cgi ? T->d_partials + i * T->slab_cap : (double *)nullptr, (const double *)(S->d_qsrc + g * NP));
+                    rhs[i] = S->d_rhs; sol[i] = S->d_raw + g * NP;
+                }
+                int its = 0; double cres = 0.0;
+                if (use_diag) { }
+                else if (ip.dense) { dense_solve(T, g, rhs[0], sol[0]); its = 1; }
+                else {
+                    rc = cg_solve(T, g, rhs, sol, ip.cg_tol, ip.cg_max, &its, &cres, true);
+                    if (rc == NF_OK && ip.direct && !(cres <= 1e-14)) ++T->standin_unconverged;
+                }
+                r.cg_total += its;
+            }
+            if (rc != NF_OK) break;
+            for (int i = 0; i < ns; ++i) {
+                nf_solver *S = T->slabs[i];
+                hipLaunchKernelGGL(k_subcrit_reduce, dim3(gT[i]), dim3(256), 0, T->stream, S->d_Mf, (const double *)S->d_raw, S->d_phi, S->d_hx, S->d_hy, S->d_hz,
+                                   S->nx, S->ny, S->N, S->nphi, S->nphi * ng, T->d_partials + i * T->slab_cap, T->partial_stride);
+            }
+            if ((rc = team_finalize(T, FIN_SUM, gT, 4, T->d_out, 0.0, 0)) != NF_OK) break;
+            if ((rc = readback(T, nullptr, nullptr, T->d_out, hout, 4)) != NF_OK) break;
+            const double Phi = hout[0], P = hout[1], nsq = hout[2], dsq = hout[3];
+            const double qn = phase ? P : Phi;
+            const double dq = qn - q_old, dphi = std::sqrt(dsq / nsq);
+            const double rel = dq == 0.0 ? 0.0 : std::fabs(dq) / std::fabs(qn);
+            n = it + 1; ++outers;
+            __atomic_store_n(&T->outers_done, outers, __ATOMIC_RELEASE);
+            if (!std::isfinite(Phi) || !std::isfinite(P) || !std::isfinite(dphi)) {
+                rc = fail(NF_ERR_NUMERIC, "nf_solve_subcritical: the system is not subcritical: the source iteration diverged (phase %d, outer %d: Phi=%g P=%g; contraction estimate %g)",
+                          phase, it, Phi, P, r.ratio);
+                break;
+            }
+            if (phase == 1) {
+                // contraction of the iteration dP_n / dP_{n-1}; below 1e-6 P the differences are inner-solve noise
+                const bool meaningful = dq != 0.0 && std::fabs(dq) >= 1e-6 * std::fabs(qn) && dq_old != 0.0;
+                if (meaningful) r.ratio = dq / dq_old;
+                streak = (it >= 4 && meaningful && dq / dq_old >= 1.0) ? streak + 1 : 0;
+                if (streak >= 5) {
+                    rc = fail(NF_ERR_NUMERIC, "nf_solve_subcritical: the system is not subcritical: the source iteration does not contract "
+                              "(estimate %.6f >= 1 over 5 consecutive outers, outer %d; k-eff of the core is about that value or above)", r.ratio, it);
+                    break;
+                }
+            }
+            r.phi_int = Phi; r.production = P;
+            dq_old = dq; q_old = qn;
+            if (rel < o->tol_keff && dphi < o->tol_flux) { conv[phase] = true; break; }
+        }
+        if (rc != NF_OK) break;
+        if (phase == 0) { r.n_outer_nofission = n; r.phi_int_nofission = r.phi_int; }
+        else r.n_outer = n;
+    }
+    HIPCHK(hipStreamSynchronize(T->stream));
+    HIPCHK(hipGetLastError());
+    if (rc != NF_OK) {                                            // the handle stays usable: current flux back to ResetFlux's 1, warm state untouched
+        for (int i = 0; i < ns; ++i) {
+            nf_solver *S = T->slabs[i];
+            hipLaunchKernelGGL(k_fill_const, dim3(gT[i]), dim3(256), 0, T->stream, S->d_phi, S->nphi * ng, 1.0);
+            S->raw_valid = false; S->jz_valid = false;
+        }
+        (void)hipStreamSynchronize(T->stream);
+        return rc;
+    }
+    for (auto *S : T->slabs) { S->raw_valid = true; S->raw_is_diag = use_diag != 0; S->jz_valid = false; }
+    r.M = r.phi_int / r.phi_int_nofission;
+    r.k_source = r.production / (r.production + r.source);
+    r.converged = conv[0] && conv[1] ? 1 : 0;
+    if (res) *res = r;
+    return NF_OK;
+}
+
+int nf_solve_subcritical(nf_handle S, const nf_keff_opts *o, nf_subcrit_result *res)
+{
+    if (!S || !o) return fail(NF_ERR_ARG, "nf_solve_subcritical: bad arguments");
+    if (S->team->dead) return fail(NF_ERR_COMM, "this team lost a collective (NF_ERR_COMM) and is unusable: destroy the handles and end the process with a non-zero code (never re-exec)");
+    for (auto *X : S->team->slabs) if (!X->built) return fail(NF_ERR_STATE, "nf_solve_subcritical: call nf_build first");
+    HIPCHK(hipSetDevice(S->device));
+    __atomic_store_n(&S->team->outers_done, 0L, __ATOMIC_RELEASE);
+    return solve_subcritical_impl(S->team, o, res);
+}
+
 // ---- SolveAdjoint (src/NeutFEM.cpp:1877-2082) -----------------------------------------------------
 // Literal control flow of the reference, including what makes it fragile (forward-ordered sweep on the transposed scatter,
 // Chebyshev from outer 5 when k is free).  Works on slab teams (collective).
@@ -3139,7 +3319,7 @@ int nf_solve_adjoint(nf_handle S, const nf_keff_opts *o, int normalize_to_direct
             for (int i = 0; i < ns; ++i) {
                 nf_solver *X = T->slabs[i];
                 for (int gp = 0; gp < 64; ++gp) sa.M[gp] = gp < ng ? X->d_Ms[gp * ng + g] : nullptr;       // transposed blocks (:1944-1950)
-                hipLaunchKernelGGL(k_group_rhs, dim3(gN[i]), dim3(256), 0, st, sa, g, X->d_NSF + g * X->N, X->d_tf, 1.0 / keff, X->d_raw, X->d_phi_adj,
+                hipLaunchKernelGGL(k_group_rhs<false>, dim3(gN[i]), dim3(256), 0, st, sa, g, X->d_NSF + g * X->N, X->d_tf, 1.0 / keff, X->d_raw, X->d_phi_adj,
                                    (const double *)nullptr, X->d_rhs, X->nphi, X->N);
                 rhs[i] = X->d_rhs; sol[i] = X->d_raw + g * X->nphi;
             }

@@ -2239,12 +2239,15 @@ struct ScatterArgs { const double *M[64]; int ng; };
 // n = DOFs per group (SoA [p][e]), ncell = cells: chi is per cell; for P>=1 elements with |chi/k| < 1e-14 are skipped (:1551).
 // With r0 != nullptr the CG start of src/solvers.cpp:583-592 rides along (x = 0, r = p = rhs, block partials of |rhs|^2: what k_cg_init
 // does), one launch less per group solve.
+// SRC (fixed-source solve, nf_solve_subcritical): the external source q (this group's n DOFs, k_source_q) is added last; inv_k is then
+// the fission scale (1: fission on, 0: the no-fission phase).  SRC = false is the eigenvalue instantiation, unchanged.
+template <bool SRC>
 __global__ __launch_bounds__(256) void k_group_rhs(ScatterArgs sa, int g, const double *__restrict__ chi,
                                                    const double *__restrict__ tf, double inv_k,
                                                    const double *__restrict__ phi_new, const double *__restrict__ phi_old,
                                                    const double *__restrict__ sinv, double *__restrict__ out, long n, long ncell,
                                                    double *__restrict__ x0 = nullptr, double *__restrict__ r0 = nullptr, double *__restrict__ p0 = nullptr,
-                                                   double *__restrict__ partials = nullptr)
+                                                   double *__restrict__ partials = nullptr, const double *__restrict__ q = nullptr)
 {
     __shared__ double sred[4];
     double s2 = 0.0;
@@ -2257,6 +2260,7 @@ __global__ __launch_bounds__(256) void k_group_rhs(ScatterArgs sa, int g, const 
             const double *ph = gp < g ? phi_new : phi_old;
             v += sa.M[gp][i] * ph[gp * n + i];
         }
+        if constexpr (SRC) v += q[i];
         out[i] = sinv ? sinv[i] * v : v;
         if (r0) { x0[i] = 0.0; r0[i] = v; p0[i] = v; s2 += v * v; }
     }
@@ -2278,6 +2282,47 @@ __global__ __launch_bounds__(256) void k_outer_reduce(const double *__restrict__
     }
     sp = block_sum(sp, sred); sn = block_sum(sn, sred); sd = block_sum(sd, sred);
     if (threadIdx.x == 0) { partials[blockIdx.x] = sp; partials[stride + blockIdx.x] = sn; partials[2 * stride + blockIdx.x] = sd; }
+}
+
+// ---- fixed-source (subcritical) solve, nf_solve_subcritical ------------------------------------------------------------------------
+// |e| of cell e: hx hy hz (inactive axes have width 1), the measure the fission matrix uses (k_cell_coef: C-hat_00 detJ = |e|)
+__device__ __forceinline__ double cell_measure(const double *__restrict__ hx, const double *__restrict__ hy, const double *__restrict__ hz,
+                                               int nx, int ny, long e)
+{
+    const int ix = (int)(e % nx); const long r = e / nx; const int iy = (int)(r % ny); const int iz = (int)(r / ny);
+    return hx[ix] * hy[iy] * hz[iz];
+}
+// q = the per-cell source SRC [g*N + e] as a load vector: DOF 0 of cell e gets Q_g(e) |e|, the higher moments 0.  Output over all groups,
+// SoA [g*n + p*N + e] (n = DOFs per group).  No 1e-14 drop.
+__global__ __launch_bounds__(256) void k_source_q(const double *__restrict__ src, double *__restrict__ q, const double *__restrict__ hx,
+                                                  const double *__restrict__ hy, const double *__restrict__ hz, int nx, int ny, long N,
+                                                  long n, long ntot)
+{
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < ntot; i += gridDim.x * 256L) {
+        const long g = i / n, j = i - g * n;
+        q[i] = j < N ? src[g * N + j] * cell_measure(hx, hy, hz, nx, ny, j) : 0.0;
+    }
+}
+// one streaming pass over all groups after the group sweep: block partials of Phi = sum |e| phi_0, P = sum Mf_0 phi_0 (DOF 0 of every
+// cell: Mf_0 = nuSigf |e|), ||phi||^2 and ||phi - old||^2 into rows 0..3 of the team partials layout; old <- phi in the same sweep
+__global__ __launch_bounds__(256) void k_subcrit_reduce(const double *__restrict__ Mf, const double *__restrict__ phi, double *__restrict__ old,
+                                                        const double *__restrict__ hx, const double *__restrict__ hy, const double *__restrict__ hz,
+                                                        int nx, int ny, long N, long n, long ntot, double *__restrict__ partials, long stride)
+{
+    __shared__ double sred[4];
+    double sf = 0.0, sp = 0.0, sn = 0.0, sd = 0.0;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < ntot; i += gridDim.x * 256L) {
+        const double v = phi[i], d = v - old[i];
+        sn += v * v; sd += d * d;
+        old[i] = v;
+        const long j = i - (i / n) * n;
+        if (j < N) { sf += cell_measure(hx, hy, hz, nx, ny, j) * v; sp += Mf[i] * v; }
+    }
+    sf = block_sum(sf, sred); sp = block_sum(sp, sred); sn = block_sum(sn, sred); sd = block_sum(sd, sred);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = sf; partials[stride + blockIdx.x] = sp;
+        partials[2 * stride + blockIdx.x] = sn; partials[3 * stride + blockIdx.x] = sd;
+    }
 }
 // phi /= norm, then ChebyshevAccel::operator() (src/solvers.cpp:720-756).  mode 0: no acceleration,
 // 1: store phi0, 2: phi1 = phi0 + a1 (phi - phi0), 3: three-term.  cur <- result.
