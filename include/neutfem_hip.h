@@ -183,6 +183,21 @@ int nf_get_cmfd_coefficients(nf_handle h, int g, int dir, double *dtilde_host, d
 int nf_solve_adjoint(nf_handle h, const nf_keff_opts *opts, int normalize_to_direct, int use_direct_keff, double *keff_adj, int *n_outer);
 int nf_get_phi_adj(nf_handle h, double *phi_adj_host);
 
+/* Sub-cell projection: every cell e is cut into rx x ry x rz equal sub-cells and each gets the exact mean of the cell's flux polynomial
+ * sum_p c_p P_i(xi) P_j(eta) P_k(zeta) over it (the Legendre means of every sub-interval in closed form).  Output on the
+ * device (out_dev, e.g. from nf_dev_alloc) in the reference's cell order of the refined mesh, x fastest: fine cell
+ * (X, Y, Z) = (ix rx + a, iy ry + b, iz rz + c) at (Z NY + Y) NX + X, NX = nx rx, NY = ny ry.  The factors are taken literally: < 1, or > 1
+ * on an axis the mesh does not have (ry in 1D, rz in 1D / 2D) -> NF_ERR_ARG.  adjoint = 1 projects the adjoint flux (all ones before
+ * any adjoint solve, as nf_get_phi_adj).  Needs nf_build (NF_ERR_STATE); changes no state of the handle.  On a slab: the slab's own
+ * planes in slab-local fine numbering (nz_slab rz planes); not collective.
+ * NeutFEM::ProjectFluxRefined (include/NeutFEM.hpp:303, src/wrapper.cpp:1003-1022; declared, never defined there):
+ * g >= 0 -> N rx ry rz doubles of group g; g = -1 -> all groups, ng N rx ry rz doubles (group-major); other g -> NF_ERR_ARG. */
+int nf_project_flux(nf_handle h, int rx, int ry, int rz, int adjoint, int g, double *out_dev);
+/* NeutFEM::ProjectPowerRefined (include/NeutFEM.hpp:307, src/wrapper.cpp:1024-1043): P(E) = sum_g ksf_g(e) phibar_g(E), N rx ry rz
+ * doubles, no normalisation.  ksf_host: kappa Sigma_f, ng N values in the host layout [g*N + e] (get_KSF()), uploaded for this call only;
+ * non-finite values -> NF_ERR_ARG. */
+int nf_project_power(nf_handle h, int rx, int ry, int rz, int adjoint, const double *ksf_host, double *out_dev);
+
 /* NeutFEM::SolveCoarse (src/NeutFEM.cpp:2380-2611): returns k_coarse and the prolonged flux
  * (ng*n_phi doubles, host) without touching the fine solution. */
 int nf_solve_coarse(nf_handle h, const nf_keff_opts *opts, double *k_coarse, double *phi_host);

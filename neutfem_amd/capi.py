@@ -14,7 +14,7 @@ SYMBOLS = [
     "nf_last_error", "nf_device_count", "nf_create", "nf_destroy", "nf_create_slab", "nf_link_slabs", "nf_comm_unique_id",
     "nf_comm_init", "nf_comm_info", "nf_comm_selftest", "nf_team_schur_apply", "nf_info", "nf_set_bc", "nf_upload_xs", "nf_build",
     "nf_schur_apply", "nf_solve_group", "nf_build_diagonal_cache", "nf_get_diagonal_cache", "nf_solve_keff",
-    "nf_upload_source", "nf_solve_subcritical", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
+    "nf_upload_source", "nf_solve_subcritical", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_project_flux", "nf_project_power", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
     "nf_get_warm_state", "nf_get_history", "nf_profile_get", "nf_profile_reset", "nf_time_schur_apply", "nf_time_device_copy", "nf_progress", "nf_set_progress_callback", "nf_local_matrices",
     "nf_set_option", "nf_mem_info", "nf_dev_alloc", "nf_dev_free", "nf_memcpy_h2d", "nf_memcpy_d2h", "nf_synchronize", "nf_stream",
 ]
@@ -73,6 +73,8 @@ def load():
     L.nf_solve_coarse.argtypes = [vp, C.POINTER(KeffOpts), dp, dp]
     L.nf_solve_adjoint.argtypes = [vp, C.POINTER(KeffOpts), C.c_int, C.c_int, dp, ip]
     L.nf_get_phi_adj.argtypes = [vp, dp]
+    L.nf_project_flux.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.nf_project_power.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, vp]
     L.nf_set_phi.argtypes = [vp, dp]
     L.nf_get_phi.argtypes = [vp, dp]
     L.nf_get_J.argtypes = [vp, dp]
@@ -276,6 +278,39 @@ class HipSolver:
 
     def get_phi_adj(self):
         out = np.empty(self.ng * self.n_phi); self._chk(self.L.nf_get_phi_adj(self.h, _dp(out))); return out.reshape(self.ng, self.n_phi)
+
+    def refined_shape(self, refine):
+        """(NZ, NY, NX) of the mesh refined by `refine` = (rx[, ry[, rz]]), trimmed by dimension like get_flux()"""
+        r = tuple(refine) + (1,) * (3 - len(refine))
+        full = (self.nz * r[2], self.ny * r[1], self.nx * r[0])
+        return full[3 - self.dim:]
+
+    def project_flux(self, refine, adjoint=False, group=None):
+        """nf_project_flux: the mean flux of every sub-cell, refine = (rx[, ry[, rz]]) taken literally (missing factors are 1).
+        (ng, [NZ,] [NY,] NX), or ([NZ,] [NY,] NX) of one group"""
+        r = tuple(int(f) for f in refine) + (1,) * (3 - len(refine))
+        shape = self.refined_shape(r)
+        n = int(np.prod(shape)) * (self.ng if group is None else 1)
+        v = DeviceVector(self, n)
+        try:
+            self._chk(self.L.nf_project_flux(self.h, r[0], r[1], r[2], int(adjoint), -1 if group is None else int(group), v.ptr))
+            out = v.download()
+        finally:
+            v.free()
+        return out.reshape(shape if group is not None else (self.ng,) + shape)
+
+    def project_power(self, ksf, refine, adjoint=False):
+        """nf_project_power: sum_g ksf_g (ng, cells) times the projected flux of group g, ([NZ,] [NY,] NX)"""
+        a = np.ascontiguousarray(ksf, dtype=np.float64).ravel(); assert a.size == self.ng * self.ne
+        r = tuple(int(f) for f in refine) + (1,) * (3 - len(refine))
+        shape = self.refined_shape(r)
+        v = DeviceVector(self, int(np.prod(shape)))
+        try:
+            self._chk(self.L.nf_project_power(self.h, r[0], r[1], r[2], int(adjoint), _dp(a), v.ptr))
+            out = v.download()
+        finally:
+            v.free()
+        return out.reshape(shape)
 
     def diagonal_cache(self, g):
         out = np.empty(self.ne)

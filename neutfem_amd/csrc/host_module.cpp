@@ -3,9 +3,9 @@
 //
 // The class keeps what the reference keeps on the host -- cross-section arrays, flux, tolerances,
 // BC map, warm-start flags -- and hands the hot path (BuildMatrices, SolveKeff, SolveCoarse,
-// build_diagonal_cache, SolveSubcritical) to the HIP library.  There is NO CPU fallback: without a HIP device those
-// methods raise RuntimeError.  Methods the reference binds but that lie outside the accelerated
-// path (never-defined projections, reflectors) raise RuntimeError with that explanation.
+// build_diagonal_cache, SolveSubcritical, project_flux, project_power) to the HIP library.  There is NO CPU fallback: without a
+// HIP device those methods raise RuntimeError.  Methods the reference binds but that lie outside the accelerated
+// path (zoom_resolved, never defined; reflectors) raise RuntimeError with that explanation.
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -226,6 +226,12 @@ public:
         return k;
     }
     void BuildDiagonalCache() { need_built("build_diagonal_cache"); chk(nf_build_diagonal_cache(h_)); }
+    // ProjectFluxRefined / ProjectPowerRefined (include/NeutFEM.hpp:303-313, src/wrapper.cpp:1003-1043; declared, never defined there):
+    // the exact mean of the flux polynomial over every sub-cell of the mesh refined by `refine` (read like SolveCoarse reads it,
+    // src/NeutFEM.cpp:2396-2398).  The field is the host mirror (get_flux() / get_flux_adj()), pushed through the device flux, which
+    // then gets Phi_ back as SolveKeff / SolveAdjoint / SolveCoarse push it.  One group at a time: the device holds N rx ry rz doubles.
+    py::array_t<double> ProjectFlux(const std::vector<int> &refine, bool adjoint) { return project("project_flux", refine, adjoint, false); }
+    py::array_t<double> ProjectPower(const std::vector<int> &refine, bool adjoint) { return project("project_power", refine, adjoint, true); }
     py::array_t<double> GetCurrent()
     {
         need_built("get_current");
@@ -330,6 +336,37 @@ private:
         chk(nf_create(rt_, p_, ng_, (int)xb_.size(), xb_.data(), (int)yb_.size(), yb_.data(), (int)zb_.size(), zb_.data(), dev, &h_));
     }
     void need_built(const char *who) const { if (!h_) throw std::runtime_error(std::string(who) + ": call BuildMatrices() first"); }
+    py::array_t<double> project(const char *who, const std::vector<int> &refine, bool adjoint, bool power)
+    {
+        need_built(who);
+        const int rx = refine.size() > 0 ? std::max(refine[0], 1) : 1;
+        const int ry = refine.size() > 1 && dim_ >= 2 ? std::max(refine[1], 1) : 1;
+        const int rz = refine.size() > 2 && dim_ >= 3 ? std::max(refine[2], 1) : 1;
+        const long NX = (long)nx_ * rx, NY = (long)ny_ * ry, NZ = (long)nz_ * rz, NE = NX * NY * NZ;
+        std::vector<py::ssize_t> shape; if (!power) shape.push_back(ng_);
+        if (dim_ >= 3) shape.push_back(NZ);
+        if (dim_ >= 2) shape.push_back(NY);
+        shape.push_back(NX);
+        py::array_t<double> out(shape);
+        struct DevBuf { nf_handle h; void *p = nullptr; ~DevBuf() { if (p) nf_dev_free(h, p); } } buf{h_};
+        chk(nf_dev_alloc(h_, (size_t)NE * sizeof(double), &buf.p));
+        double *d = static_cast<double *>(buf.p), *o = out.mutable_data();
+        chk(nf_set_phi(h_, adjoint ? PhiAdj_.data() : Phi_.data()));
+        int rc = NF_OK;
+        if (power) rc = nf_project_power(h_, rx, ry, rz, 0, KSF_.data(), d);
+        for (int g = 0; !power && g < ng_ && rc == NF_OK; ++g) {
+            rc = nf_project_flux(h_, rx, ry, rz, 0, g, d);
+            if (rc == NF_OK) rc = nf_memcpy_d2h(h_, o + (size_t)g * NE, d, (size_t)NE * sizeof(double));
+        }
+        if (power && rc == NF_OK) rc = nf_memcpy_d2h(h_, o, d, (size_t)NE * sizeof(double));
+        if (adjoint) {                                            // the device flux gets the direct mirror back, after an error too
+            const std::string err = rc == NF_OK ? std::string() : nf_last_error();
+            chk(nf_set_phi(h_, Phi_.data()));
+            if (rc != NF_OK) throw std::runtime_error("neutfem_amd: " + err);
+        }
+        chk(rc);
+        return out;
+    }
 
     nf_handle h_ = nullptr;
     std::map<int, BCType> bc_types_; std::map<int, double> bc_values_; std::map<int, std::pair<double, double>> robin_;
@@ -412,7 +449,9 @@ PYBIND11_MODULE(_neutfem_eigen, m)
         .def("GetLastKeff", [](const NeutFEM &s) { return s.last_keff_; })
         .def("GetLastKeffAdjoint", [](const NeutFEM &s) { return s.last_keff_adj_; })
         .def("GetSolverName", &NeutFEM::GetSolverName)
-        .def("project_flux", [](NeutFEM &s, const std::vector<int> &, bool) { s.oos("project_flux", "bound at src/wrapper.cpp:1003, never defined"); }, py::arg("refine"), py::arg("adjoint") = false)
-        .def("project_power", [](NeutFEM &s, const std::vector<int> &, bool) { s.oos("project_power", "bound at src/wrapper.cpp:1024, never defined"); }, py::arg("refine"), py::arg("adjoint") = false)
+        .def("project_flux", &NeutFEM::ProjectFlux, py::arg("refine"), py::arg("adjoint") = false,
+             "mean flux of every sub-cell of the mesh refined by [rx, ry, rz]: (ng, [NZ,] [NY,] NX) like get_flux()")
+        .def("project_power", &NeutFEM::ProjectPower, py::arg("refine"), py::arg("adjoint") = false,
+             "sum over groups of get_KSF() times project_flux: ([NZ,] [NY,] NX), no normalisation")
         .def("zoom_resolved", [](NeutFEM &s, const std::vector<int> &, bool) { s.oos("zoom_resolved", "bound at src/wrapper.cpp:1045, never defined"); }, py::arg("refine"), py::arg("adjoint") = false);
 }

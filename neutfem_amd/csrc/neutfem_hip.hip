@@ -19,8 +19,10 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -3401,6 +3403,91 @@ int nf_get_phi_adj(nf_handle S, double *phi_host)
     if (!S || !phi_host) return fail(NF_ERR_ARG, "nf_get_phi_adj: bad arguments");
     if (!S->d_phi_adj) { for (long i = 0; i < S->nphi * S->ng; ++i) phi_host[i] = 1.0; return NF_OK; }   // Sol_Phi_adj_ = 1 (:226-235)
     return phi_transfer(S, phi_host, false, S->d_phi_adj);
+}
+
+// ---- ProjectFluxRefined / ProjectPowerRefined (declared include/NeutFEM.hpp:303-313, bound src/wrapper.cpp:1003-1043; never defined
+// there): the mean of every cell's flux polynomial over rx x ry x rz equal sub-cells, k_project_refined
+template <int DIM, int M>
+static void launch_project_dm(bool power, int grid, hipStream_t st, const double *phi, const double *ksf, double *out, const nf_solver *S,
+                              int rx, int ry, int rz, int NX, int NY, int crows, int npairs, int vec, int step_rows, int step_pairs)
+{
+    if (power)
+        hipLaunchKernelGGL((k_project_refined<DIM, M, true>), dim3(grid), dim3(256), 0, st, phi, ksf, out, S->nx, S->ny, S->N, S->nphi, S->ng,
+                           rx, ry, rz, NX, NY, crows, npairs, vec, step_rows, step_pairs);
+    else
+        hipLaunchKernelGGL((k_project_refined<DIM, M, false>), dim3(grid), dim3(256), 0, st, phi, ksf, out, S->nx, S->ny, S->N, S->nphi, S->ng,
+                           rx, ry, rz, NX, NY, crows, npairs, vec, step_rows, step_pairs);
+}
+template <int DIM>
+static void launch_project_d(int m, bool power, int grid, hipStream_t st, const double *phi, const double *ksf, double *out, const nf_solver *S,
+                             int rx, int ry, int rz, int NX, int NY, int crows, int npairs, int vec, int step_rows, int step_pairs)
+{
+    if (m == 0) launch_project_dm<DIM, 0>(power, grid, st, phi, ksf, out, S, rx, ry, rz, NX, NY, crows, npairs, vec, step_rows, step_pairs);
+    else if (m == 1) launch_project_dm<DIM, 1>(power, grid, st, phi, ksf, out, S, rx, ry, rz, NX, NY, crows, npairs, vec, step_rows, step_pairs);
+    else launch_project_dm<DIM, 2>(power, grid, st, phi, ksf, out, S, rx, ry, rz, NX, NY, crows, npairs, vec, step_rows, step_pairs);
+}
+
+// flux (ksf == nullptr): group g >= 0, or every group (g = -1) into consecutive N R blocks; power: sum over the groups weighted by ksf
+static int project_impl(nf_solver *S, int rx, int ry, int rz, int adjoint, int g, const double *ksf_host, double *out, const char *who)
+{
+    const bool power = ksf_host != nullptr;
+    if (!S || !out) return fail(NF_ERR_ARG, "%s: bad arguments", who);
+    if (!power && (g < -1 || g >= S->ng)) return fail(NF_ERR_ARG, "%s: group %d outside -1 .. %d", who, g, S->ng - 1);
+    if (rx < 1 || ry < 1 || rz < 1) return fail(NF_ERR_ARG, "%s: refine factors must be >= 1 (got %d, %d, %d)", who, rx, ry, rz);
+    if ((S->dim < 2 && ry > 1) || (S->dim < 3 && rz > 1))
+        return fail(NF_ERR_ARG, "%s: refine factor > 1 on an axis the %dD mesh does not have (%d, %d, %d)", who, S->dim, rx, ry, rz);
+    if (!S->built) return fail(NF_ERR_STATE, "%s: call nf_build first", who);
+    const long NXl = (long)S->nx * rx, rowsl = (long)S->ny * ry * S->nz * rz;
+    if (NXl >= INT_MAX || rowsl > INT_MAX / 2) return fail(NF_ERR_ARG, "%s: refined mesh of %ld x %ld cells is too large", who, NXl, rowsl);
+    const int NX = (int)NXl, NY = S->ny * ry, crows = S->ny * S->nz, npairs = (NX + 1) / 2;
+    const long NE = (long)S->N * rx * ry * rz;
+    const long N = S->N;
+    if (power)
+        for (int gg = 0; gg < S->ng; ++gg)
+            for (long e = 0; e < N; ++e)
+                if (!std::isfinite(ksf_host[gg * N + e])) return fail(NF_ERR_ARG, "%s: non-finite kappa Sigma_f in group %d, cell %ld", who, gg, e);
+    HIPCHK(hipSetDevice(S->device));
+    hipStream_t st = S->team->stream;
+    (void)hipGetLastError();                                      // a failed allocation of an earlier call must not be reported here
+    DevTmp<double> ones, ksf;
+    const double *src = adjoint ? S->d_phi_adj : S->d_phi;
+    if (!src) {                                                   // no adjoint solve yet: Sol_Phi_adj_ = 1 on every DOF (nf_get_phi_adj)
+        const long n = power ? S->nphi * S->ng : S->nphi;
+        NFCHK(dalloc(&ones.p, (size_t)n));
+        hipLaunchKernelGGL(k_fill_const, dim3(grid_for(n)), dim3(256), 0, st, ones.p, n, 1.0);
+        src = ones.p;
+    }
+    if (power) {
+        NFCHK(dalloc(&ksf.p, (size_t)N * S->ng));
+        HIPCHK(hipMemcpyAsync(ksf.p, ksf_host, (size_t)N * S->ng * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    int ncu = 256; (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, S->device);
+    const long items = (long)crows * npairs;                     // a thread: one x pair of one coarse row, all its ry rz fine rows
+    const int grid = (int)std::max<long>(1, std::min<long>((items + 255) / 256, 8L * ncu));   // 32 waves per CU, then grid-stride
+    const long stride = (long)grid * 256;
+    const int step_rows = (int)(stride / npairs), step_pairs = (int)(stride % npairs);
+    const int vec = (NX % 2 == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
+    const int g0 = power ? 0 : (g < 0 ? 0 : g), g1 = power ? 1 : (g < 0 ? S->ng : g + 1);
+    for (int gg = g0; gg < g1; ++gg) {
+        const double *phi = src == ones.p || power ? src : src + (size_t)gg * S->nphi;
+        double *o = out + (g < 0 && !power ? (size_t)gg * NE : 0);
+        const int v = vec && ((uintptr_t)o & 15) == 0;
+        if (S->dim == 1) launch_project_d<1>(S->m, power, grid, st, phi, ksf.p, o, S, rx, ry, rz, NX, NY, crows, npairs, v, step_rows, step_pairs);
+        else if (S->dim == 2) launch_project_d<2>(S->m, power, grid, st, phi, ksf.p, o, S, rx, ry, rz, NX, NY, crows, npairs, v, step_rows, step_pairs);
+        else launch_project_d<3>(S->m, power, grid, st, phi, ksf.p, o, S, rx, ry, rz, NX, NY, crows, npairs, v, step_rows, step_pairs);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));                             // the temporaries are freed on return
+    return NF_OK;
+}
+int nf_project_flux(nf_handle S, int rx, int ry, int rz, int adjoint, int g, double *out_dev)
+{
+    return project_impl(S, rx, ry, rz, adjoint, g, nullptr, out_dev, "nf_project_flux");
+}
+int nf_project_power(nf_handle S, int rx, int ry, int rz, int adjoint, const double *ksf_host, double *out_dev)
+{
+    if (!ksf_host) return fail(NF_ERR_ARG, "nf_project_power: bad arguments");
+    return project_impl(S, rx, ry, rz, adjoint, 0, ksf_host, out_dev, "nf_project_power");
 }
 
 int nf_get_history(nf_handle S, double *k, double *dk, double *dphi, int *cg, int cap)

@@ -3664,6 +3664,103 @@ __global__ void k_check_xs(const double *__restrict__ v, long n, int need_nonzer
     if (bad) atomicOr(flags, 1 << bit);
 }
 
+// ---- sub-cell projection (nf_project_flux / nf_project_power) ------------------------------------------------------------
+// mean of P_0..P_M over sub-interval s of r equal parts of [-1, 1], [al, be] = [(2s - r) / r, (2s + 2 - r) / r]:
+// 1, (al + be) / 2, (al^2 + al be + be^2 - 1) / 2.  r = 1 gives exactly 1, 0, 0; the last sub-interval ends exactly at 1.
+template <int M>
+__device__ __forceinline__ void sub_means(int s, int r, double *A)
+{
+    A[0] = 1.0;
+    if (M >= 1) {
+        const double rr = (double)r, al = (double)(2 * s - r) / rr, be = (double)(2 * s + 2 - r) / rr;
+        A[1] = 0.5 * (al + be);
+        if (M >= 2) A[2] = 0.5 * (al * al + al * be + be * be - 1.0);
+    }
+}
+// x contraction of one cell for two x sub-intervals: s[q] = sum_i c_ijk A_i, q = j + nj k (nj = M+1 from 2D on), one load per coefficient.
+// c = one group's coefficients in the device layout [p*N + e], p = i + (M+1) j + (M+1)^2 k = i + (M+1) q.  A_0 = 1: the i = 0 term is c itself
+template <int DIM, int M>
+__device__ __forceinline__ void x_contract2(const double *__restrict__ c, long N, long e, const double *A0, const double *A1, double *s0, double *s1)
+{
+    constexpr int n1 = M + 1, nq = (DIM >= 2 ? n1 : 1) * (DIM == 3 ? n1 : 1);
+#pragma unroll
+    for (int q = 0; q < nq; ++q) {
+        const double c0 = c[(long)(n1 * q) * N + e];
+        double v0 = c0, v1 = c0;
+#pragma unroll
+        for (int i = 1; i <= M; ++i) { const double ci = c[(long)(i + n1 * q) * N + e]; v0 += ci * A0[i]; v1 += ci * A1[i]; }
+        s0[q] = v0; s1[q] = v1;
+    }
+}
+// the y / z means of sub-row (B, Cz): sum_{j,k} B_j C_k s[j + nj k], the (0, 0) term (weight 1) first
+template <int DIM, int M>
+__device__ __forceinline__ double yz_contract(const double *s, const double *B, const double *Cz)
+{
+    constexpr int nj = DIM >= 2 ? M + 1 : 1, nk = DIM == 3 ? M + 1 : 1;
+    double v = s[0];                                             // refine 1 and P0 give DOF 0 exactly
+#pragma unroll
+    for (int kk = 0; kk < nk; ++kk)
+#pragma unroll
+        for (int j = 0; j < nj; ++j)
+            if (j || kk) v += s[j + nj * kk] * ((DIM >= 2 ? B[j] : 1.0) * (DIM == 3 ? Cz[kk] : 1.0));
+    return v;
+}
+// One thread per pair of fine columns (X, X+1) of one coarse row (iy, iz): it contracts the (one or two) cells' coefficients over xi once,
+// then writes the pair in each of the ry rz fine rows the coarse row covers -- every coefficient is loaded once per pair, not once per
+// fine row (across XCDs the fine rows of one coarse row do not share an L2).  Consecutive lanes write consecutive 16-byte pairs of a fine
+// row (one non-temporal 16-byte store when `vec`: NX even and `out` 16-byte aligned; else one or two 8-byte stores).  The fine cell
+// (X, Y, Z) = (ix rx + a, iy ry + b, iz rz + c) lies at (Z NY + Y) NX + X.  Flux: `phi` = one group's coefficients, out = that group's
+// field.  POWER: phi = all ng groups (stride nphi); kappa Sigma_f is constant on the cell, so the groups' x contractions are summed with
+// ksf[g*N + e] as weights before the y / z means.  Pairs are walked grid-stride with the (coarse row, pair) position advanced
+// incrementally (no 64-bit division per pair).
+template <int DIM, int M, bool POWER>
+__global__ __launch_bounds__(256) void k_project_refined(const double *__restrict__ phi, const double *__restrict__ ksf, double *__restrict__ out,
+                                                         int nx, int ny, long N, long nphi, int ng, int rx, int ry, int rz, int NX, int NY,
+                                                         int crows, int npairs, int vec, int step_rows, int step_pairs)
+{
+    constexpr int nq = (DIM >= 2 ? M + 1 : 1) * (DIM == 3 ? M + 1 : 1);
+    const long i0 = (long)blockIdx.x * 256 + threadIdx.x;
+    int row = (int)(i0 / npairs), pr = (int)(i0 - (long)row * npairs);
+    while (row < crows) {
+        const int iz = row / ny, iy = row - iz * ny;
+        const int X0 = 2 * pr;
+        const bool two = X0 + 1 < NX;
+        const int ix0 = X0 / rx, ix1 = (X0 + 1) / rx;
+        double A0[M + 1], A1[M + 1];
+        sub_means<M>(X0 - ix0 * rx, rx, A0);
+        sub_means<M>(X0 + 1 - ix1 * rx, rx, A1);
+        const long e0 = (long)row * nx + ix0, e1 = (long)row * nx + (two ? ix1 : ix0);
+        double s0[nq], s1[nq];
+        for (int g = 0; g < (POWER ? ng : 1); ++g) {
+            const double *c = phi + (long)g * nphi;
+            double t0[nq], t1[nq], u[nq];
+            x_contract2<DIM, M>(c, N, e0, A0, A1, t0, t1);
+            if (e1 != e0) x_contract2<DIM, M>(c, N, e1, A1, A1, t1, u);
+            const double k0 = POWER ? ksf[(long)g * N + e0] : 1.0, k1 = POWER ? ksf[(long)g * N + e1] : 1.0;
+#pragma unroll
+            for (int q = 0; q < nq; ++q) {
+                if (!POWER) { s0[q] = t0[q]; s1[q] = t1[q]; }
+                else if (g == 0) { s0[q] = k0 * t0[q]; s1[q] = k1 * t1[q]; }
+                else { s0[q] += k0 * t0[q]; s1[q] += k1 * t1[q]; }
+            }
+        }
+        for (int cz = 0; cz < rz; ++cz) {
+            double Cz[M + 1];
+            sub_means<M>(cz, rz, Cz);
+            for (int b = 0; b < ry; ++b) {
+                double B[M + 1];
+                sub_means<M>(b, ry, B);
+                const double v0 = yz_contract<DIM, M>(s0, B, Cz), v1 = yz_contract<DIM, M>(s1, B, Cz);
+                const long o = ((long)(iz * rz + cz) * NY + (iy * ry + b)) * NX + X0;
+                if (vec) { nf_d2 v = { v0, v1 }; __builtin_nontemporal_store(v, reinterpret_cast<nf_d2 *>(out + o)); }
+                else { __builtin_nontemporal_store(v0, out + o); if (two) __builtin_nontemporal_store(v1, out + o + 1); }
+            }
+        }
+        pr += step_pairs; row += step_rows;                       // advance by the grid's stride: step_rows rows + step_pairs pairs
+        if (pr >= npairs) { pr -= npairs; ++row; }
+    }
+}
+
 // fill with a deterministic pseudo-random pattern (profiling helper)
 __global__ void k_fill_pattern(double *__restrict__ v, long n)
 {
