@@ -145,7 +145,6 @@ struct nf_team {
     double *d_vec = nullptr; long vec_stride = 0;          // 2 rows: all-reduced p.q partials, all-reduced |r|^2 partials (+ flag slot each)
     int vec_cnt_pq = 0, vec_cnt_rr = 0; bool vec_ok = false; int opt_vec_reduce = 1, last_vec_reduce = 0;
     bool dead = false;              // a collective timed out (NF_ERR_COMM): the streams may hold operations that never complete -- no further solve, no stream waits at teardown
-    bool dry = false;               // launch functions only report their partial counts
     bool poisoned = false; int poison_rc = 0; char poison_msg[256] = { 0 };
     int xchg_in_apply = 0;          // interface exchanges issued since the current Schur apply began
     long cg_iter_total = 0;         // CG iterations launched since the team was created (NEUTFEM_INJECT_FAIL=<rank>:<iteration>)
@@ -229,20 +228,13 @@ struct nf_solver {
     double *d_sinv_lo = nullptr, *d_sinv_hi = nullptr;  // ng * nlines[2]
     double *d_clo = nullptr, *d_chi = nullptr, *d_rlo = nullptr, *d_rhi = nullptr, *d_ulo = nullptr, *d_uhi = nullptr;
     double *d_ctlo = nullptr, *d_cthi = nullptr, *d_elo = nullptr, *d_ehi = nullptr, *d_relo = nullptr, *d_rehi = nullptr;   // separator sweeps (thin slabs)
-    double *d_Wlo = nullptr, *d_Whi = nullptr; bool w_valid = false; int sr_cnt3 = 0;   // endpoint functionals of the z lines (k_endpoint_w), ng * N each; |r|^2 partials of its last launch
+    double *d_Wlo = nullptr, *d_Whi = nullptr; bool w_valid = false;   // endpoint functionals of the z lines (k_endpoint_w), ng * N each
     // state
     double *d_phi = nullptr, *d_raw = nullptr;          // current iterate / raw group solutions, ng*N
     double *d_p0 = nullptr, *d_p1 = nullptr;            // Chebyshev history
     double *d_tf = nullptr, *d_rhs = nullptr, *d_r = nullptr, *d_p = nullptr, *d_q = nullptr;
     double *d_p2 = nullptr, *d_qy = nullptr, *d_qz = nullptr;   // fused-direction CG (k_apply3): second buffer of the p pair, y / z outputs
     bool raw_valid = false, raw_is_diag = false;
-    CgFuse fuse = { nullptr, nullptr, nullptr };        // set by cg_solve around the applies of a fused CG (k_schur_x / k_schur_s mode 1)
-    CgLean lean = { nullptr, nullptr, 0, 0, 0 };        // set by cg_solve per iteration of a lean CG (k_schur_x consumes the |r|^2 partials)
-    CgLean lean_z1 = { nullptr, nullptr, 0, 0, 0 };     // slab teams: the endpoint pass of the z lines consumes the all-reduced |r|^2
-    Cg1 cg1 = { nullptr, nullptr, 0 };                  // slab teams, single-reduction CG (set by cg_solve per iteration): the z passes take their SR instantiations
-    bool zw_dot = false;                                // this apply: the y / z passes emit T_a sum z_f w_f as their share of x.y (team_schur_apply, split)
-    hipStream_t pass_stream = nullptr;                  // this launch goes to another stream than the team's (x || y on small slabs)
-    bool pass_noacc = false; const double *pass_yadd = nullptr;   // SlabArgs::noacc / yadd of this launch
     double *d_qsrc = nullptr;                           // external source as a load vector, ng * nphi (nf_upload_source, k_source_q)
     double src_total = 0.0; bool src_any = false;       // sum of Q |e| over the slab's cells, some Q != 0
     double *d_Jz = nullptr; bool jz_valid = false;      // slabs: z currents of the last solve, ng * nJz face DOFs (nf_get_J)
@@ -950,7 +942,26 @@ static int exchange_planes(nf_team *T, int which, int g, hipStream_t st)
     return NF_OK;
 }
 
-static int launch_s(nf_solver *S, int d, int g, const ModeArgs &ma, const Geom &G, int last, double *partials, const CgScalars *cg, int *nparts, int zmode);
+// What a CG iteration hands to the kernels of a Schur apply.  The launch functions are pure in their arguments: these two values are the
+// only way the state of a solve reaches a kernel, and a default-constructed one means "a plain apply outside CG".
+struct ApplyCg {                                        // per apply: cg_solve -> team_schur_apply / team_endpoint_phase
+    const CgScalars *cg = nullptr;
+    bool fused = false; const std::vector<double *> *xsol = nullptr;   // fused CG: CgFuse of slab i = { d_p, d_r, (*xsol)[i] } (k_schur_x / k_schur_s mode 1)
+    CgLean lean = {};                                   // lean CG, undivided mesh: the x pass consumes the |r|^2 partials
+    CgLean lean_z1 = {};                                // lean CG, slab teams: the endpoint pass of the z lines consumes the all-reduced |r|^2
+    Cg1 cg1 = {};                                       // slab teams, single-reduction CG: the z passes take their SR instantiations
+};
+struct PassCg {                                         // per launch: team_schur_apply / team_endpoint_phase -> launch_x / launch_s
+    const CgScalars *cg = nullptr; CgFuse fuse = {}; CgLean lean = {}, lean_z1 = {}; Cg1 cg1 = {};   // of the apply, for this slab
+    bool zw_dot = false;                                // the y / z passes emit T_a sum z_f w_f as their share of x.y (team_schur_apply, split)
+    hipStream_t stream = nullptr;                       // another stream than the team's (x || y on small slabs)
+    bool noacc = false; const double *yadd = nullptr;   // SlabArgs::noacc / yadd
+};
+static PassCg pass_cg(const ApplyCg &A, const nf_solver *S, int i) { return { A.cg, A.fused ? CgFuse{ S->d_p, S->d_r, (*A.xsol)[i] } : CgFuse{}, A.lean, A.lean_z1, A.cg1 }; }   // slab i
+// launch shape of the one-chunk line kernel (k_schur_s); rc != NF_OK: the line length is refused
+struct SegPlan { int rc = NF_OK, SEG = 0, NSEG = 0, TX = 0, nparts = 0; dim3 grid, block; size_t lds = 0; };
+static SegPlan seg_plan(const nf_solver *S, int d, int zmode);
+static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const Geom &G, int last, double *partials, const PassCg &P, int *nparts, int zmode);
 // build-time: S_red = own half + neighbour's half for every separator; checks that separators decouple
 static int team_prepare(nf_team *T)
 {
@@ -1030,10 +1041,8 @@ static int team_prepare(nf_team *T)
         const bool eligible = T->slabs.size() == 1 && S->nloc == 1 && S->dim == 3 && (S->if_lo || S->if_hi);
         int np = 0;
         if (eligible) {
-            T->dry = true;
-            const int rc = launch_s(S, 2, 0, mode_args(S, 0, 2, 0, S->d_p, S->d_q), make_geom(S), 1, T->d_partials, nullptr, &np, 2);
-            T->dry = false;
-            if (rc != NF_OK) np = 0;                              // not an error here: the scalar route serves
+            const SegPlan sp = seg_plan(S, 2, 2);
+            np = sp.rc == NF_OK ? sp.nparts : 0;                  // a refused plan is not an error here: the scalar route serves
         }
         const int nr = eligible ? grid_for(S->nphi) : 0;
         double v[5] = { (double)np, -(double)np, (double)nr, -(double)nr, (double)T->team_max_cells };
@@ -1063,7 +1072,7 @@ static int team_prepare(nf_team *T)
                 for (int k = 0; k < S->nz; ++k) {
                     double *plane = S->d_p + (size_t)k * nxy;
                     hipLaunchKernelGGL(k_fill_const, dim3(gf), dim3(256), 0, T->stream, plane, nxy, 1.0);
-                    NFCHK(launch_s(S, 2, g, mode_args(S, g, 2, 0, S->d_p, S->d_q), G, 0, nullptr, nullptr, nullptr, 1));
+                    NFCHK(launch_s(S, 2, g, mode_args(S, g, 2, 0, S->d_p, S->d_q), G, 0, nullptr, PassCg(), nullptr, 1));
                     if (S->if_lo) HIPCHK(hipMemcpyAsync(S->d_Wlo + (size_t)g * S->N + (size_t)k * nxy, S->d_clo, (size_t)nxy * sizeof(double), hipMemcpyDeviceToDevice, T->stream));
                     if (S->if_hi) HIPCHK(hipMemcpyAsync(S->d_Whi + (size_t)g * S->N + (size_t)k * nxy, S->d_chi, (size_t)nxy * sizeof(double), hipMemcpyDeviceToDevice, T->stream));
                     hipLaunchKernelGGL(k_fill_const, dim3(gf), dim3(256), 0, T->stream, plane, nxy, 0.0);
@@ -1150,11 +1159,11 @@ static int team_reduce(nf_team *T, const std::vector<int> &counts, double *red)
 
 // single-reduction CG: the four rows of block partials (p.q, q.q, r.q from the accumulation pass, |r|^2 from the endpoint pass; the same
 // count per slab in every row) -> red[0..3], this rank's error flag -> red[4], one all-reduce of five doubles
-static int team_reduce_sr(nf_team *T, const std::vector<int> &counts)
+static int team_reduce_sr(nf_team *T, const std::vector<int> &counts, const std::vector<int> &cnt3)
 {
     PartSegs ps = segs_for(T, counts);
     std::vector<int> c3(counts);                                 // row 3: the endpoint pass's own block count where k_endpoint_w ran (0 on a poisoned rank)
-    for (size_t i = 0; i < c3.size(); ++i) if (T->slabs[i]->sr_cnt3 > 0 && counts[i] > 0) c3[i] = T->slabs[i]->sr_cnt3;
+    for (size_t i = 0; i < c3.size(); ++i) if (cnt3[i] > 0 && counts[i] > 0) c3[i] = cnt3[i];
     PartSegs ps3 = segs_for(T, c3);
     hipLaunchKernelGGL(k_reduce_rows, dim3(1), dim3(256), 0, T->stream, (const double *)T->d_partials, ps, ps3, T->partial_stride, T->d_red, (const double *)T->d_errsrc);
     if (T->rccl_reduce) { TRACE_COMM("rank %d allreduce single-reduction count=5 poisoned=%d", T->rank, (int)T->poisoned); NCCLCHK(g_rccl.AllReduce(T->d_red, T->d_red, 5, NCCL_DOUBLE, NCCL_SUM, T->comm, T->stream)); }
@@ -1180,14 +1189,14 @@ static bool lds_opt_in(const void *fn, size_t lds)
 }
 // ---- Schur apply -----------------------------------------------------------------------------
 template <int NCH, int NB>
-static void launch_x_t(nf_solver *S, int g, const ModeArgs &ma, const Geom &G, int lpl_log2, int first, int last,
-                       double *partials, const CgScalars *cg, unsigned grid)
+static void launch_x_t(const nf_solver *S, int g, const ModeArgs &ma, const Geom &G, int lpl_log2, int first, int last,
+                       double *partials, const PassCg &P, unsigned grid)
 {
     const long N = S->N;
     const bool vec = (S->nx % 2 == 0);
     hipStream_t st = S->team->stream;
     const double *L = S->d_L[0] + g * N, *DR = S->d_DR[0] + g * N, *D0 = S->d_D0[0] + g * S->nlines[0];
-    const CgFuse fz = (S->if_lo || S->if_hi) ? CgFuse{ nullptr, nullptr, nullptr } : S->fuse;   // slabs fuse in their endpoint pass instead
+    const CgFuse fz = (S->if_lo || S->if_hi) ? CgFuse{ nullptr, nullptr, nullptr } : P.fuse;   // slabs fuse in their endpoint pass instead
     const ModeTab mt = mode_tab(S, 0);
     const dim3 gr(grid, (unsigned)mt.n);                          // all transverse modes in one launch
     const bool nt = NB == 0 && vec && S->team->opt_nt_loads && N > S->team->nt_min_cells;   // streaming loads beyond the caches (per slab on teams)
@@ -1195,14 +1204,14 @@ static void launch_x_t(nf_solver *S, int g, const ModeArgs &ma, const Geom &G, i
     // three -- and no faster (512^3: 1548 vs 1529 us, 256^3: 185.9 vs 186.3; profiles/r03_e_ab_cg.txt).  Kept as an option, off.
     const bool p2 = NB == 0 && NCH >= 2 && fz.p && S->team->opt_x_p2 == 1;
     if (nt && p2) hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB, NB == 0, NB == 0 && (NCH >= 2)>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2,
-                               first | ((S->team->opt_xcd >= 0 && (S->team->opt_xcd & 4)) ? 2 : 0), last, partials, cg, fz, S->lean);
+                               first | ((S->team->opt_xcd >= 0 && (S->team->opt_xcd & 4)) ? 2 : 0), last, partials, P.cg, fz, P.lean);
     else if (nt) hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB, NB == 0>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2,
-                               first | ((S->team->opt_xcd >= 0 && (S->team->opt_xcd & 4)) ? 2 : 0), last, partials, cg, fz, S->lean);
-    else if (vec) hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2, first, last, partials, cg, fz, S->lean);
-    else hipLaunchKernelGGL((k_schur_x<2, NCH, false, NB>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2, first, last, partials, cg, fz, S->lean);
+                               first | ((S->team->opt_xcd >= 0 && (S->team->opt_xcd & 4)) ? 2 : 0), last, partials, P.cg, fz, P.lean);
+    else if (vec) hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2, first, last, partials, P.cg, fz, P.lean);
+    else hipLaunchKernelGGL((k_schur_x<2, NCH, false, NB>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2, first, last, partials, P.cg, fz, P.lean);
 }
 template <int NB>
-static int launch_x_nb(nf_solver *S, int g, const ModeArgs &ma, const Geom &G, int last, double *partials, const CgScalars *cg, int *nparts)
+static int launch_x_nb(const nf_solver *S, int g, const ModeArgs &ma, const Geom &G, int last, double *partials, const PassCg &P, int *nparts)
 {
     const int K = 2;
     int lanes = (S->nx + K - 1) / K, lpl_log2 = 0;
@@ -1211,20 +1220,20 @@ static int launch_x_nb(nf_solver *S, int g, const ModeArgs &ma, const Geom &G, i
     const int nch = (S->nx + LPL * K - 1) / (LPL * K);
     const unsigned grid = (unsigned)((S->nlines[0] + 4 * LPW - 1) / (4 * LPW));
     if (nparts) *nparts = (int)grid * n_modes(S);
-    if (nch <= 1) launch_x_t<1, NB>(S, g, ma, G, lpl_log2, 1, last, partials, cg, grid);
-    else if (nch <= 2) launch_x_t<2, NB>(S, g, ma, G, lpl_log2, 1, last, partials, cg, grid);
-    else if (nch <= 4) launch_x_t<4, NB>(S, g, ma, G, lpl_log2, 1, last, partials, cg, grid);
-    else if (nch <= 8) launch_x_t<8, NB>(S, g, ma, G, lpl_log2, 1, last, partials, cg, grid);
-    else if (nch <= 16 && NB == 0) launch_x_t<16, 0>(S, g, ma, G, lpl_log2, 1, last, partials, cg, grid);   // long lines: more registers per lane, lower occupancy
-    else if (nch <= 32 && NB == 0) launch_x_t<32, 0>(S, g, ma, G, lpl_log2, 1, last, partials, cg, grid);
+    if (nch <= 1) launch_x_t<1, NB>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
+    else if (nch <= 2) launch_x_t<2, NB>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
+    else if (nch <= 4) launch_x_t<4, NB>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
+    else if (nch <= 8) launch_x_t<8, NB>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
+    else if (nch <= 16 && NB == 0) launch_x_t<16, 0>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);   // long lines: more registers per lane, lower occupancy
+    else if (nch <= 32 && NB == 0) launch_x_t<32, 0>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
     else return fail(NF_ERR_UNSUPPORTED, "nx = %d exceeds the x-line kernel limit (%d cells)", S->nx, NB == 0 ? 4096 : 1024);
     return NF_OK;
 }
-static int launch_x(nf_solver *S, int g, const ModeArgs &ma, const Geom &G, int last, double *partials, const CgScalars *cg, int *nparts)
+static int launch_x(const nf_solver *S, int g, const ModeArgs &ma, const Geom &G, int last, double *partials, const PassCg &P, int *nparts)
 {
-    if (S->nb == 0) return launch_x_nb<0>(S, g, ma, G, last, partials, cg, nparts);
-    if (S->nb == 1) return launch_x_nb<1>(S, g, ma, G, last, partials, cg, nparts);
-    return launch_x_nb<2>(S, g, ma, G, last, partials, cg, nparts);
+    if (S->nb == 0) return launch_x_nb<0>(S, g, ma, G, last, partials, P, nparts);
+    if (S->nb == 1) return launch_x_nb<1>(S, g, ma, G, last, partials, P, nparts);
+    return launch_x_nb<2>(S, g, ma, G, last, partials, P, nparts);
 }
 
 // Does direction d (1 = y, 2 = z) of this mesh take the chunked long-line kernel (k_schur_c)?  Plain lines of RT0-P0 meshes beyond
@@ -1259,10 +1268,41 @@ static ChunkPlan chunk_plan(const nf_solver *S, int d)
     return P;
 }
 
-// zmode: 0 = plain line kernel (y lines, or z lines of an undivided mesh); 1 / 2 = slab chain passes (z lines)
-static int launch_s(nf_solver *S, int d, int g, const ModeArgs &ma, const Geom &G, int last, double *partials, const CgScalars *cg, int *nparts, int zmode)
+// 8-cell segments up to 1024 cells per line (16 / 32 cells spill to scratch: 1.4x slower even though TX drops to 8 at 1024)
+// higher orders: 4-cell segments up to 256 cells per line; beyond, RT1 keeps 8 (148 B / lane of scratch and still faster: y 97 vs 122 us on
+// 48 x 512 x 48), RT2 takes 4 up to 512 cells (8 columns per block, no scratch: y 352 vs 383 us, z 412 vs 431; profiles/r04_g_higher_orders.txt)
+static SegPlan seg_plan(const nf_solver *S, int d, int zmode)     // direction d (1 = y, 2 = z); zmode as in launch_s
 {
-    nf_team *T = S->team;
+    SegPlan P; const nf_team *T = S->team;
+    const int n = d == 1 ? S->ny : S->nz, nouter = d == 1 ? S->nz : S->ny;
+    P.SEG = T->opt_s_seg ? T->opt_s_seg : (S->nb > 0 ? ((n <= 256 || (S->nb == 2 && n <= 512)) ? 4 : 8) : (n <= 1024 ? 8 : (n <= 2048 ? 16 : 32)));
+    P.NSEG = (n + P.SEG - 1) / P.SEG;
+    if (P.NSEG > 128) { P.rc = fail(NF_ERR_UNSUPPORTED, "line length %d exceeds the segmented kernel limit", n); return P; }
+    P.TX = T->opt_s_tx ? T->opt_s_tx : 64;
+    const int tmax = zmode != 0 ? 512 : 1024;                     // slab variants: 512 threads (register budget, see k_schur_s)
+    while (P.TX > 8 && P.TX * P.NSEG > tmax) P.TX >>= 1;
+    if (P.TX * P.NSEG > tmax) { P.rc = fail(NF_ERR_UNSUPPORTED, "line length %d needs more than %d threads per block", n, tmax); return P; }
+    while (P.TX > 8 && P.TX / 2 >= S->nx) P.TX >>= 1;             // narrow meshes
+    // whole wavefronts: the reductions use data-parallel-primitive moves and read lane 63 (threads beyond TX * NSEG only keep the barriers company)
+    P.grid = dim3((unsigned)((S->nx + P.TX - 1) / P.TX), (unsigned)nouter, (unsigned)n_modes(S)); P.block = dim3((unsigned)((P.TX * P.NSEG + 63) / 64 * 64));
+    P.nparts = (int)(P.grid.x * P.grid.y * P.grid.z);
+    P.lds = (size_t)(4 * P.TX * (P.NSEG + 1) + P.TX + 32) * sizeof(double);   // + reduction scratch (block_sum: 8, block_sum3: 24 doubles at 512 threads)
+    return P;
+}
+struct SchurSLaunch {                                             // every argument of a k_schur_s launch
+    const SegPlan &sp; hipStream_t st; const ModeArgs &ma; const ModeTab &mt; const Geom &G; const double *L, *DR, *D0; int n; long sl, ostride; int nx, last;
+    double *partials; const CgScalars *cg; const SlabArgs &sa; const CgFuse &fz; const CgLean &lz;
+};
+template <int SEG, int DIR, bool SLAB, int NB, bool SF = false, bool NTS = false, bool ZW = false, bool SR = false>
+static void launch_s_t(const SchurSLaunch &a)
+{
+    hipLaunchKernelGGL((k_schur_s<SEG, DIR, SLAB, NB, SF, NTS, ZW, SR>), a.sp.grid, a.sp.block, a.sp.lds, a.st, a.ma, a.mt, a.G, a.L, a.DR, a.D0, a.n, a.sl, a.ostride, a.nx,
+                       a.sp.TX, a.sp.NSEG, a.last, a.partials, a.cg, a.sa, a.fz, a.lz);
+}
+// zmode: 0 = plain line kernel (y lines, or z lines of an undivided mesh); 1 / 2 = slab chain passes (z lines)
+static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const Geom &G, int last, double *partials, const PassCg &P, int *nparts, int zmode)
+{
+    const nf_team *T = S->team; const CgScalars *cg = P.cg;
     const long N = S->N;
     const int n = d == 1 ? S->ny : S->nz;
     const long nxy = (long)S->nx * S->ny;
@@ -1271,7 +1311,7 @@ static int launch_s(nf_solver *S, int d, int g, const ModeArgs &ma, const Geom &
     // long plain lines of RT0-P0 meshes: two chunks per block, twice the tile width (k_schur_c).  Its share of x.y comes in the z.w
     // form only: inside CG it needs the split dot product of team_schur_apply
     const ChunkPlan cp = zmode == 0 ? chunk_plan(S, d) : ChunkPlan();
-    if (cp.ok && (!(last && partials) || S->zw_dot)) {
+    if (cp.ok && (!(last && partials) || P.zw_dot)) {
         const int NS = cp.NS, TXc = cp.TX; const size_t ldsc = cp.lds;
         {
             dim3 grid((unsigned)((S->nx + TXc - 1) / TXc), (unsigned)nouter), block((unsigned)((TXc * NS + 63) / 64 * 64));
@@ -1287,26 +1327,15 @@ static int launch_s(nf_solver *S, int d, int g, const ModeArgs &ma, const Geom &
             if (launched) { if (nparts) *nparts = (int)(grid.x * grid.y); return NF_OK; }
         }
     }
-    // 8-cell segments up to 1024 cells per line (16 / 32 cells spill to scratch: 1.4x slower even though TX drops to 8 at 1024)
-    // higher orders: 4-cell segments up to 256 cells per line; beyond, RT1 keeps 8 (148 B / lane of scratch and still faster: y 97 vs 122 us on
-    // 48 x 512 x 48), RT2 takes 4 up to 512 cells (8 columns per block, no scratch: y 352 vs 383 us, z 412 vs 431; profiles/r04_g_higher_orders.txt)
-    int SEG = T->opt_s_seg ? T->opt_s_seg : (S->nb > 0 ? ((n <= 256 || (S->nb == 2 && n <= 512)) ? 4 : 8) : (n <= 1024 ? 8 : (n <= 2048 ? 16 : 32)));
-    int NSEG = (n + SEG - 1) / SEG;
-    if (NSEG > 128) return fail(NF_ERR_UNSUPPORTED, "line length %d exceeds the segmented kernel limit", n);
-    int TX = T->opt_s_tx ? T->opt_s_tx : 64;
-    const int tmax = zmode != 0 ? 512 : 1024;                     // slab variants: 512 threads (register budget, see k_schur_s)
-    while (TX > 8 && TX * NSEG > tmax) TX >>= 1;
-    if (TX * NSEG > tmax) return fail(NF_ERR_UNSUPPORTED, "line length %d needs more than %d threads per block", n, tmax);
-    while (TX > 8 && TX / 2 >= S->nx) TX >>= 1;                   // narrow meshes
+    const SegPlan sp = seg_plan(S, d, zmode);
+    if (sp.rc != NF_OK) return sp.rc;
+    const int SEG = sp.SEG;
     const ModeTab mt = mode_tab(S, d);
-    // whole wavefronts: the reductions use data-parallel-primitive moves and read lane 63 (threads beyond TX * NSEG only keep the barriers company)
-    dim3 grid((unsigned)((S->nx + TX - 1) / TX), (unsigned)nouter, (unsigned)mt.n), block((unsigned)((TX * NSEG + 63) / 64 * 64));
-    if (nparts) *nparts = (int)(grid.x * grid.y * grid.z);
-    if (T->dry) return NF_OK;
+    if (nparts) *nparts = sp.nparts;
     const double *L = S->d_L[d] + g * N, *DR = S->d_DR[d] + g * N, *D0 = S->d_D0[d] + g * S->nlines[d];
-    hipStream_t st = S->pass_stream ? S->pass_stream : T->stream;
+    hipStream_t st = P.stream ? P.stream : T->stream;
     SlabArgs sa; memset(&sa, 0, sizeof sa);
-    sa.noacc = S->pass_noacc ? 1 : 0; sa.yadd = S->pass_yadd;
+    sa.noacc = P.noacc ? 1 : 0; sa.yadd = P.yadd;
     // XCD-contiguous tile order (k_schur_s): bit 0 = y passes, bit 1 = z passes; -1 (default) = the y passes of meshes in the streaming
     // regime -- the 8 x tiles of a row set then run on one XCD back to back (256^3: y 133 -> 123 us, 501 -> 493 us per CG iteration;
     // z passes lose 10 us with it; neutral to -0.5 % at 96^3 ... 192^3)
@@ -1314,31 +1343,31 @@ static int launch_s(nf_solver *S, int d, int g, const ModeArgs &ma, const Geom &
     // 848 -> 835 us per CG iteration; 4 slabs 800 -> 773; on 8.4 M / 16.8 M-cell slabs it loses: 93 -> 101 / 191 -> 201 us; profiles/r04_o_slab_options.txt)
     sa.xcd = T->opt_xcd >= 0 ? (T->opt_xcd >> (d - 1)) & 1 : ((d == 1 && T->opt_nt_loads && S->N > T->nt_min_cells) || ((zmode == 1 || zmode == 2) && S->N <= (6L << 20)));
     sa.wsmin = T->opt_wsmin;
-    const size_t lds = (size_t)(4 * TX * (NSEG + 1) + TX + 32) * sizeof(double);   // + reduction scratch (block_sum: 8, block_sum3: 24 doubles at 512 threads)
-    const CgFuse fz = (zmode == 1 && S->nloc == 1) ? S->fuse : CgFuse{ nullptr, nullptr, nullptr };
-    const CgLean lz = (zmode == 1 && S->nloc == 1 && fz.p) ? S->lean_z1 : CgLean{ nullptr, nullptr, 0, 0, 0 };
+    const CgFuse fz = (zmode == 1 && S->nloc == 1) ? P.fuse : CgFuse{ nullptr, nullptr, nullptr };
+    const CgLean lz = (zmode == 1 && S->nloc == 1 && fz.p) ? P.lean_z1 : CgLean{ nullptr, nullptr, 0, 0, 0 };
     // undivided meshes beyond the caches (the classic path's sizes): the variant with streaming loads (SF doubles as that flag for !SLAB)
     const bool nt = zmode == 0 && S->nb == 0 && SEG == 8 && T->opt_nt_loads && S->N > T->nt_min_cells;
     const bool nts = zmode != 0 && zmode != 3 && S->nb == 0 && SEG == 8 && T->opt_nt_loads && S->N > T->nt_min_cells;   // the same for the z passes of a slab
-    const bool zw = zmode == 0 && S->nb == 0 && S->zw_dot && last && partials;                                              // z.w form of the pass's share of x.y
+    const bool zw = zmode == 0 && S->nb == 0 && P.zw_dot && last && partials;                                              // z.w form of the pass's share of x.y
     // single-reduction CG (Cg1): the endpoint pass (mode 1) consumes the reduction of the previous iteration and carries r -= alpha q, the
     // accumulation pass (mode 2) leaves p.q, q.q, r.q; |r|^2 comes from the endpoint pass (row 3 of the partial buffer)
-    const bool sr = S->cg1.red != nullptr && S->nb == 0 && SEG == 8 && d == 2 && ((zmode == 1 && fz.p) || (zmode == 2 && last && partials));
+    const bool sr = P.cg1.red != nullptr && S->nb == 0 && SEG == 8 && d == 2 && ((zmode == 1 && fz.p) || (zmode == 2 && last && partials));
     if (sr) {
-        sa.sr = S->cg1; sa.sr_r = S->d_r; sa.sr_q = S->d_q; sa.sr_stride = T->partial_stride;
+        sa.sr = P.cg1; sa.sr_r = S->d_r; sa.sr_q = S->d_q; sa.sr_stride = T->partial_stride;
         sa.sr_part = T->d_partials + 3 * T->partial_stride + (long)S->slab_index * T->slab_cap;
     }
-#define NF_S(SEGV, DIRV, SLABV, NBV) do { if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && sr && zmode == 1 && nts) hipLaunchKernelGGL((k_schur_s<SEGV, DIRV, SLABV, NBV, SLABV && NBV == 0, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>), grid, block, lds, st, ma, mt, G, L, DR, D0, n, sl, ostride, S->nx, TX, NSEG, last, partials, cg, sa, fz, lz); \
-        else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && sr && zmode == 1) hipLaunchKernelGGL((k_schur_s<SEGV, DIRV, SLABV, NBV, SLABV && NBV == 0, false, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>), grid, block, lds, st, ma, mt, G, L, DR, D0, n, sl, ostride, S->nx, TX, NSEG, last, partials, cg, sa, fz, lz); \
-        else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && sr && nts) hipLaunchKernelGGL((k_schur_s<SEGV, DIRV, SLABV, NBV, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>), grid, block, lds, st, ma, mt, G, L, DR, D0, n, sl, ostride, S->nx, TX, NSEG, last, partials, cg, sa, fz, lz); \
-        else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && sr) hipLaunchKernelGGL((k_schur_s<SEGV, DIRV, SLABV, NBV, false, false, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>), grid, block, lds, st, ma, mt, G, L, DR, D0, n, sl, ostride, S->nx, TX, NSEG, last, partials, cg, sa, fz, lz); \
-        else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && nts && fz.p) hipLaunchKernelGGL((k_schur_s<SEGV, DIRV, SLABV, NBV, SLABV && NBV == 0, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>), grid, block, lds, st, ma, mt, G, L, DR, D0, n, sl, ostride, S->nx, TX, NSEG, last, partials, cg, sa, fz, lz); \
-        else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && nts) hipLaunchKernelGGL((k_schur_s<SEGV, DIRV, SLABV, NBV, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>), grid, block, lds, st, ma, mt, G, L, DR, D0, n, sl, ostride, S->nx, TX, NSEG, last, partials, cg, sa, fz, lz); \
-        else if (SLABV && NBV == 0 && fz.p) hipLaunchKernelGGL((k_schur_s<SEGV, DIRV, SLABV, NBV, SLABV && NBV == 0>), grid, block, lds, st, ma, mt, G, L, DR, D0, n, sl, ostride, S->nx, TX, NSEG, last, partials, cg, sa, fz, lz); \
-        else if (!SLABV && NBV == 0 && zw && SEGV == 8 && nt) hipLaunchKernelGGL((k_schur_s<SEGV, DIRV, SLABV, NBV, !SLABV && NBV == 0 && SEGV == 8, false, !SLABV && NBV == 0>), grid, block, lds, st, ma, mt, G, L, DR, D0, n, sl, ostride, S->nx, TX, NSEG, last, partials, cg, sa, fz, lz); \
-        else if (!SLABV && NBV == 0 && zw) hipLaunchKernelGGL((k_schur_s<SEGV, DIRV, SLABV, NBV, false, false, !SLABV && NBV == 0>), grid, block, lds, st, ma, mt, G, L, DR, D0, n, sl, ostride, S->nx, TX, NSEG, last, partials, cg, sa, fz, lz); \
-        else if (!SLABV && NBV == 0 && SEGV == 8 && nt) hipLaunchKernelGGL((k_schur_s<SEGV, DIRV, SLABV, NBV, !SLABV && NBV == 0 && SEGV == 8>), grid, block, lds, st, ma, mt, G, L, DR, D0, n, sl, ostride, S->nx, TX, NSEG, last, partials, cg, sa, fz, lz); \
-        else hipLaunchKernelGGL((k_schur_s<SEGV, DIRV, SLABV, NBV, false>), grid, block, lds, st, ma, mt, G, L, DR, D0, n, sl, ostride, S->nx, TX, NSEG, last, partials, cg, sa, fz, lz); } while (0)
+    const SchurSLaunch A = { sp, st, ma, mt, G, L, DR, D0, n, sl, ostride, S->nx, last, partials, cg, sa, fz, lz };   // sa by reference: its slab fields follow
+#define NF_S(SEGV, DIRV, SLABV, NBV) do { if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && sr && zmode == 1 && nts) launch_s_t<SEGV, DIRV, SLABV, NBV, SLABV && NBV == 0, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
+        else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && sr && zmode == 1) launch_s_t<SEGV, DIRV, SLABV, NBV, SLABV && NBV == 0, false, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
+        else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && sr && nts) launch_s_t<SEGV, DIRV, SLABV, NBV, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
+        else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && sr) launch_s_t<SEGV, DIRV, SLABV, NBV, false, false, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
+        else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && nts && fz.p) launch_s_t<SEGV, DIRV, SLABV, NBV, SLABV && NBV == 0, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
+        else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && nts) launch_s_t<SEGV, DIRV, SLABV, NBV, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
+        else if (SLABV && NBV == 0 && fz.p) launch_s_t<SEGV, DIRV, SLABV, NBV, SLABV && NBV == 0>(A); \
+        else if (!SLABV && NBV == 0 && zw && SEGV == 8 && nt) launch_s_t<SEGV, DIRV, SLABV, NBV, !SLABV && NBV == 0 && SEGV == 8, false, !SLABV && NBV == 0>(A); \
+        else if (!SLABV && NBV == 0 && zw) launch_s_t<SEGV, DIRV, SLABV, NBV, false, false, !SLABV && NBV == 0>(A); \
+        else if (!SLABV && NBV == 0 && SEGV == 8 && nt) launch_s_t<SEGV, DIRV, SLABV, NBV, !SLABV && NBV == 0 && SEGV == 8>(A); \
+        else launch_s_t<SEGV, DIRV, SLABV, NBV, false>(A); } while (0)
 #define NF_S_SEG(DIRV, SLABV, NBV) do { if (SEG == 4) NF_S(4, DIRV, SLABV, NBV); else if (SEG == 8) NF_S(8, DIRV, SLABV, NBV); \
         else if (SEG == 16 && NBV == 0) NF_S(16, DIRV, SLABV, 0); else if (SEG == 32 && NBV == 0) NF_S(32, DIRV, SLABV, 0); else return fail(NF_ERR_ARG, "bad s_seg"); } while (0)
     if (zmode != 0) {
@@ -1372,26 +1401,29 @@ static int launch_s(nf_solver *S, int d, int g, const ModeArgs &ma, const Geom &
 // Partition method, first half (slab teams): the endpoint pass of every slab (mode 1), the plane exchange and the separator
 // values (+ Jacobi sweeps for thin slabs).  The exchange and the separator kernels run on the comm stream; ev_xchg marks
 // their end -- the caller's z pass (or current reconstruction) waits for it, the x / y passes do not.
-static int team_endpoint_phase(nf_team *T, int g, const std::vector<const double *> &xs, const std::vector<double *> &ys, const CgScalars *cg,
-                               hipEvent_t after_z1, bool need_u = false)
+// cnt3 (if given): per slab, the |r|^2 partials that k_endpoint_w left in row 3 of the partial buffer (0 where the chain solve ran).
+static int team_endpoint_phase(nf_team *T, int g, const std::vector<const double *> &xs, const std::vector<double *> &ys, const ApplyCg &A,
+                               hipEvent_t after_z1, bool need_u = false, std::vector<int> *cnt3 = nullptr)
 {
-    const int ns = (int)T->slabs.size();
+    const int ns = (int)T->slabs.size(); const CgScalars *cg = A.cg;
     for (int i = 0; i < ns; ++i) {
-        nf_solver *S = T->slabs[i];
+        const nf_solver *S = T->slabs[i];
+        if (cnt3) (*cnt3)[i] = 0;
         if (!(S->if_lo || S->if_hi)) continue;
-        S->sr_cnt3 = 0;
-        if (S->cg1.red && S->w_valid && T->opt_endpoint_w && S->fuse.p == xs[i]) {
+        const PassCg P = pass_cg(A, S, i);
+        if (P.cg1.red && S->w_valid && T->opt_endpoint_w && P.fuse.p == xs[i]) {
             // single-reduction CG: the chain-end responses as weighted sums of the line's cells + the deferred CG update (k_endpoint_w)
             const dim3 gr((unsigned)((S->nx + 63) / 64), (unsigned)S->ny);
             if ((long)gr.x * gr.y <= T->slab_cap) {
-                hipLaunchKernelGGL(k_endpoint_w, gr, dim3(256), 0, T->stream, S->fuse.p, const_cast<double *>(S->fuse.r), (const double *)S->d_q, S->fuse.xsol,
+                hipLaunchKernelGGL(k_endpoint_w, gr, dim3(256), 0, T->stream, P.fuse.p, const_cast<double *>(P.fuse.r), (const double *)S->d_q, P.fuse.xsol,
                                    (const double *)(S->d_Wlo + (size_t)g * S->N), (const double *)(S->d_Whi + (size_t)g * S->N), S->d_clo, S->d_chi,
-                                   S->nx, S->ny, S->nz, S->if_lo, S->if_hi, 40, S->cg1, cg, T->d_partials + 3 * T->partial_stride + (long)S->slab_index * T->slab_cap);
-                S->sr_cnt3 = (int)(gr.x * gr.y); T->last_endpoint_w = 1;
+                                   S->nx, S->ny, S->nz, S->if_lo, S->if_hi, 40, P.cg1, cg, T->d_partials + 3 * T->partial_stride + (long)S->slab_index * T->slab_cap);
+                if (cnt3) (*cnt3)[i] = (int)(gr.x * gr.y);
+                T->last_endpoint_w = 1;
                 continue;
             }
         }
-        NFCHK(launch_s(S, 2, g, mode_args(S, g, 2, 0, xs[i], ys[i]), make_geom(S), 0, nullptr, cg, nullptr, 1));
+        NFCHK(launch_s(S, 2, g, mode_args(S, g, 2, 0, xs[i], ys[i]), make_geom(S), 0, nullptr, P, nullptr, 1));
     }
     if (after_z1) (void)hipEventRecord(after_z1, T->stream);
     HIPCHK(hipEventRecord(T->ev_z1, T->stream));
@@ -1423,9 +1455,9 @@ static int team_endpoint_phase(nf_team *T, int g, const std::vector<const double
 static bool team_is_single(const nf_team *T) { return T->slabs.size() == 1 && !T->slabs[0]->if_lo && !T->slabs[0]->if_hi; }
 
 // y = S_g x on every local slab.  xs / ys: per-slab device pointers (nphi doubles, layout [p][e]).  With `want_dot` the
-// passes of the last direction leave the block partials of x.y in the team buffer and counts[] receives the number per slab.
+// passes of the last direction leave the block partials of x.y in the team buffer and counts[] receives the number per slab (cnt3[]: team_endpoint_phase).
 static int team_schur_apply(nf_team *T, int g, const std::vector<const double *> &xs, const std::vector<double *> &ys, bool want_dot,
-                            const CgScalars *cg, std::vector<int> *counts)
+                            const ApplyCg &A, std::vector<int> *counts = nullptr, std::vector<int> *cnt3 = nullptr)
 {
     const int ns = (int)T->slabs.size();
     const int dim = T->slabs[0]->dim;
@@ -1437,7 +1469,7 @@ static int team_schur_apply(nf_team *T, int g, const std::vector<const double *>
     if (prof) prof_begin(T, 3, &ta, &tb);
     if (any_if) {                                                 // partition method step 1 + interface exchange
         if (prof) prof_begin(T, 4, &a, &b);
-        NFCHK(team_endpoint_phase(T, g, xs, ys, cg, prof ? b : nullptr));
+        NFCHK(team_endpoint_phase(T, g, xs, ys, A, prof ? b : nullptr, false, cnt3));
     }
     // Split dot product (undivided RT0-P0 meshes outside the lean path, i.e. the big ones): every pass leaves the partials of ITS share
     // of x.y -- the x pass x.(C x + S_x x), the y / z passes T_a sum z_f w_f from their forward sweeps (schur_s_tile, ZW) -- one after
@@ -1446,7 +1478,7 @@ static int team_schur_apply(nf_team *T, int g, const std::vector<const double *>
     // Taken where a chunked long-line pass runs (it has no x left when its parked chunk comes back) or on request (split_dot = 2: tests);
     // elsewhere the last pass sums x_i y_i with x still in its registers, which is cheaper than three sets of partials (256^3: 504 vs
     // 531 us per CG iteration, profiles/r03_e_ab_cg.txt).
-    bool split = want_dot && dim >= 2 && team_is_single(T) && T->slabs[0]->nb == 0 && !T->slabs[0]->lean.st && T->opt_split_dot;
+    bool split = want_dot && dim >= 2 && team_is_single(T) && T->slabs[0]->nb == 0 && !A.lean.st && T->opt_split_dot;
     if (split && T->opt_split_dot < 2) split = chunk_plan(T->slabs[0], dim - 1).ok;      // only the LAST pass forms the dot product
     std::vector<int> totals(ns, 0);
     for (int d = 0; d < dim; ++d) {
@@ -1467,20 +1499,15 @@ static int team_schur_apply(nf_team *T, int g, const std::vector<const double *>
                 double *part = (want_dot && (last || split)) ? T->d_partials + i * T->slab_cap + totals[i] : nullptr;
                 const ModeArgs ma = mode_args(S, g, d, 0, xs[i], ys[i]);     // mode 0; the kernels derive the others (ModeTab)
                 int np = 0;
-                S->zw_dot = split;
-                if (d == 0) NFCHK(launch_x(S, g, ma, G, last || split, part, cg, &np));
+                PassCg P = pass_cg(A, S, i); P.zw_dot = split;
+                if (d == 0) NFCHK(launch_x(S, g, ma, G, last || split, part, P, &np));
                 else if (d == 2 && (S->if_lo || S->if_hi)) {
-                    S->pass_yadd = xy_all ? S->d_qy : nullptr;
-                    const int rz = launch_s(S, 2, g, ma, G, last, part, cg, &np, 2);
-                    S->pass_yadd = nullptr;
-                    NFCHK(rz);
+                    P.yadd = xy_all ? S->d_qy : nullptr;
+                    NFCHK(launch_s(S, 2, g, ma, G, last, part, P, &np, 2));
                 } else if (d == 1 && xy_all) {
-                    S->pass_stream = T->y_stream; S->pass_noacc = true;
-                    const int ry = launch_s(S, 1, g, mode_args(S, g, 1, 0, xs[i], S->d_qy), G, 0, nullptr, cg, &np, 0);
-                    S->pass_stream = nullptr; S->pass_noacc = false;
-                    NFCHK(ry);
-                } else NFCHK(launch_s(S, d, g, ma, G, last || split, part, cg, &np, 0));
-                S->zw_dot = false;
+                    P.stream = T->y_stream; P.noacc = true;
+                    NFCHK(launch_s(S, 1, g, mode_args(S, g, 1, 0, xs[i], S->d_qy), G, 0, nullptr, P, &np, 0));
+                } else NFCHK(launch_s(S, d, g, ma, G, last || split, part, P, &np, 0));
                 if (part) totals[i] += np;
             }
             if (counts && last) (*counts)[i] = totals[i];
@@ -1499,7 +1526,7 @@ int nf_schur_apply(nf_handle S, int g, const double *x_dev, double *y_dev)
     nf_team *T = S->team;
     if (!team_is_single(T)) return fail(NF_ERR_STATE, "nf_schur_apply works on an undivided mesh; use nf_team_schur_apply for slabs");
     HIPCHK(hipSetDevice(S->device));
-    NFCHK(team_schur_apply(T, g, { x_dev }, { y_dev }, false, nullptr, nullptr));
+    NFCHK(team_schur_apply(T, g, { x_dev }, { y_dev }, false, ApplyCg()));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(T->stream));
     if (T->profile) prof_collect(T);
@@ -1515,7 +1542,7 @@ int nf_team_schur_apply(nf_handle S, int g, const double *const *x_dev, double *
     HIPCHK(hipSetDevice(T->device));
     NFCHK(team_prepare(T));
     std::vector<const double *> xs(x_dev, x_dev + T->slabs.size()); std::vector<double *> ys(y_dev, y_dev + T->slabs.size());
-    NFCHK(team_schur_apply(T, g, xs, ys, false, nullptr, nullptr));
+    NFCHK(team_schur_apply(T, g, xs, ys, false, ApplyCg()));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(T->stream));
     if (T->profile) prof_collect(T);
@@ -1676,7 +1703,7 @@ static int cg_solve(nf_team *T, int g, const std::vector<const double *> &rhs, c
                     int *its_out, double *res_out, bool inited = false)
 {
     const int ns = (int)T->slabs.size();
-    std::vector<int> gcnt(ns), acnt(ns);
+    std::vector<int> gcnt(ns), acnt(ns), cnt3(ns, 0);              // cnt3: |r|^2 partials of k_endpoint_w per slab (team_endpoint_phase)
     std::vector<const double *> ps(ns); std::vector<double *> qs(ns);
     for (int i = 0; i < ns; ++i) {
         nf_solver *S = T->slabs[i];
@@ -1692,14 +1719,12 @@ static int cg_solve(nf_team *T, int g, const std::vector<const double *> &rhs, c
     // fused variant (RT0-P0, undivided mesh): x_sol / p updates ride in the next x pass (k_schur_x, CgFuse)
     // (undivided mesh: in the x pass; slab teams: in the endpoint pass of the z lines, the first pass to read p)
     const bool fused = T->opt_fuse != 0 && (team_is_single(T) || T->slabs[0]->nloc == 1);   // undivided: any order (x pass); slab teams: P0 (z endpoint pass)
-    for (int i = 0; i < ns; ++i) T->slabs[i]->fuse = fused ? CgFuse{ T->slabs[i]->d_p, T->slabs[i]->d_r, x[i] } : CgFuse{ nullptr, nullptr, nullptr };
     // lean variant on top of the fused one (undivided mesh, no RCCL): no k_finalize launches, see CgLean.  Row 0 of the partial
     // buffer holds the p.q partials of the last direction pass, row 1 the |r|^2 partials of k_cg_rupdate.
     const bool lean = fused && T->opt_lean && team_is_single(T) && !T->rccl_reduce && T->slabs[0]->N <= T->lean_max_cells;
     // every block of the next x pass sums the |r|^2 partials; fewer partials (cg_lean_grid) cost k_cg_rupdate more than they save (measured)
     const int gru = lean ? grid_for(T->slabs[0]->nphi, 256, T->opt_lean_grid) : 0;
     double *row1 = T->d_partials + T->partial_stride;
-    const CgLean no_lean = { nullptr, nullptr, 0, 0, 0 };
     int rc = NF_OK;
     // lean variant for slab teams (fused, RT0-P0): the endpoint pass of the z lines and k_cg_rupdate consume the all-reduced
     // totals (d_red[2] = |r|^2, d_red[0] = p.q, each followed by the ranks' error flags) and derive beta / alpha and the stop tests themselves: no k_cg_logic launches
@@ -1722,7 +1747,6 @@ static int cg_solve(nf_team *T, int g, const std::vector<const double *> &rhs, c
     if (f3.ok && xcd_eligible(T, S0, f3) && pub_ready(T)) {
         // the whole solve in one launch on one XCD (k_cg_xcd); the kernel hands the final scalars to the host itself
         const unsigned long long seq = ++T->pub_seq;
-        for (int i = 0; i < ns; ++i) T->slabs[i]->fuse = CgFuse{ nullptr, nullptr, nullptr };
         NFCHK(launch_cg_xcd(S0, g, f3, x[0], seq));
         NFCHK(pub_wait(T, seq, &sc, nullptr, 0));
         if (sc.err == 4) {
@@ -1748,7 +1772,6 @@ static int cg_solve(nf_team *T, int g, const std::vector<const double *> &rhs, c
         // the workgroups did not assemble (nothing placed on the XCD, or it is busy): no vector has been touched -- this solve and the
         // following ones of this solver go through the launch path
         if (sc.err == 3) { T->opt_cgx = 0; ++T->xcd_refused; }
-        for (int i = 0; i < ns; ++i) T->slabs[i]->fuse = fused ? CgFuse{ T->slabs[i]->d_p, T->slabs[i]->d_r, x[i] } : CgFuse{ nullptr, nullptr, nullptr };
         NFCHK(team_finalize(T, FIN_RHS, gcnt, 1, T->d_out, tol, maxit));
         memset(&sc, 0, sizeof sc);
     }
@@ -1802,17 +1825,16 @@ static int cg_solve(nf_team *T, int g, const std::vector<const double *> &rhs, c
                                    (const double *)(S0->dim == 3 ? S0->d_qz : nullptr), S0->nphi, T->d_cg, row1, CgLean{ T->d_cg, T->d_partials, f3.nblocks, index & 1, 0 });
                 continue;
             }
-            if (lean) T->slabs[0]->lean = CgLean{ T->d_cg, row1, gru, index & 1, index == 0 ? 1 : 0 };
-            if (sr) for (auto *S : T->slabs) S->cg1 = Cg1{ T->d_red, T->d_cg, index };
-            else if (tlean) for (auto *S : T->slabs) S->lean_z1 = vred ? CgLean{ T->d_cg, vec_rr, T->vec_cnt_rr, index & 1, index == 0 ? 1 : 0, T->vec_cnt_rr }
-                                                                   : CgLean{ T->d_cg, T->d_red + 2, -1, index & 1, index == 0 ? 1 : 0 };
+            ApplyCg A; A.cg = T->d_cg; A.fused = fused; A.xsol = &x;
+            if (lean) A.lean = CgLean{ T->d_cg, row1, gru, index & 1, index == 0 ? 1 : 0 };
+            if (sr) A.cg1 = Cg1{ T->d_red, T->d_cg, index };
+            else if (tlean) A.lean_z1 = vred ? CgLean{ T->d_cg, vec_rr, T->vec_cnt_rr, index & 1, index == 0 ? 1 : 0, T->vec_cnt_rr }
+                                             : CgLean{ T->d_cg, T->d_red + 2, -1, index & 1, index == 0 ? 1 : 0 };
             T->xchg_in_apply = 0;
             int ra = NF_OK;
             if (multi && T->rank == T->inject_rank && global_it == T->inject_iter)
                 { ra = fail(NF_ERR_HIP, "injected failure on rank %d at CG iteration %ld (NEUTFEM_INJECT_FAIL)", T->rank, global_it); TRACE_COMM("rank %d INJECT at %ld", T->rank, global_it); }
-            else if (!T->poisoned) ra = team_schur_apply(T, g, ps, qs, true, T->d_cg, &acnt);
-            if (lean) T->slabs[0]->lean = no_lean;
-            if (tlean) for (auto *S : T->slabs) { S->lean_z1 = no_lean; S->cg1 = Cg1{ nullptr, nullptr, 0 }; }
+            else if (!T->poisoned) ra = team_schur_apply(T, g, ps, qs, true, A, &acnt, &cnt3);
             if (bad(ra)) break;
             if (T->poisoned && any_if) {
                 // the interface exchanges this apply still owes its neighbours: one per apply + one per separator sweep (team_endpoint_phase)
@@ -1823,10 +1845,12 @@ static int cg_solve(nf_team *T, int g, const std::vector<const double *> &rhs, c
                 if (T->xchg_in_apply == 0) { (void)hipEventRecord(T->ev_z1, T->stream); (void)hipStreamWaitEvent(T->comm_stream, T->ev_z1, 0); }
                 for (int k = T->xchg_in_apply; k < 1 + T->sep_sweeps; ++k) (void)exchange_planes(T, k == 0 ? 0 : 2, 0, T->comm_stream);
                 (void)hipEventRecord(T->ev_xchg, T->comm_stream); (void)hipStreamWaitEvent(T->stream, T->ev_xchg, 0);
-                for (int i = 0; i < ns; ++i) acnt[i] = 0;
+                // a poisoned rank skips the apply, so cnt3 still holds the counts of its last one: cleared with acnt.  team_reduce_sr reads
+                // cnt3[i] only where acnt[i] > 0, so the reduction sees no partials of this rank in any row either way
+                for (int i = 0; i < ns; ++i) acnt[i] = cnt3[i] = 0;
             }
             if (sr) {                                             // the one reduction of this iteration; its consumer is the next endpoint pass
-                if (bad(team_reduce_sr(T, acnt))) break;
+                if (bad(team_reduce_sr(T, acnt, cnt3))) break;
                 continue;
             }
             if (vred) {
@@ -1857,7 +1881,7 @@ static int cg_solve(nf_team *T, int g, const std::vector<const double *> &rhs, c
                     nf_solver *S = T->slabs[i];
                     if (lean) hipLaunchKernelGGL(k_cg_rupdate, dim3(gru), dim3(256), 0, T->stream, S->d_r, S->d_q, S->nphi, T->d_cg, row1,
                                                  CgLean{ T->d_cg, T->d_partials, acnt[0], index & 1, 0 });
-                    else if (fused) hipLaunchKernelGGL(k_cg_rupdate, dim3(gcnt[i]), dim3(256), 0, T->stream, S->d_r, S->d_q, S->nphi, T->d_cg, T->d_partials + i * T->slab_cap, no_lean);
+                    else if (fused) hipLaunchKernelGGL(k_cg_rupdate, dim3(gcnt[i]), dim3(256), 0, T->stream, S->d_r, S->d_q, S->nphi, T->d_cg, T->d_partials + i * T->slab_cap, CgLean{});
                     else hipLaunchKernelGGL(k_cg_update, dim3(gcnt[i]), dim3(256), 0, T->stream, x[i], S->d_r, S->d_p, S->d_q, S->nphi, T->d_cg, T->d_partials + i * T->slab_cap);
                 }
             if (lean) continue;
@@ -1888,7 +1912,6 @@ static int cg_solve(nf_team *T, int g, const std::vector<const double *> &rhs, c
         batch = T->cg_batch > 0 ? T->cg_batch : (launched < 8 ? 1 : grow);
         if (launched >= 8) grow = std::min(64, 2 * grow);
     }
-    for (int i = 0; i < ns; ++i) T->slabs[i]->fuse = CgFuse{ nullptr, nullptr, nullptr };
     NFCHK(rc);
     if (T->poisoned) {                                            // the flag has stopped every rank (or maxit did): this rank reports what hit it
         const int code = T->poison_rc; char msg[256]; snprintf(msg, sizeof msg, "%s", T->poison_msg);
@@ -2043,11 +2066,11 @@ static int team_reconstruct_Jz(nf_team *T)
     std::vector<const double *> xs(ns); std::vector<double *> ys(ns);
     for (int g = 0; g < ng; ++g) {
         for (int i = 0; i < ns; ++i) { xs[i] = T->slabs[i]->d_raw + (size_t)g * T->slabs[i]->nphi; ys[i] = T->slabs[i]->d_q; }
-        NFCHK(team_endpoint_phase(T, g, xs, ys, nullptr, nullptr, true));
+        NFCHK(team_endpoint_phase(T, g, xs, ys, ApplyCg(), nullptr, true));
         HIPCHK(hipStreamWaitEvent(T->stream, T->ev_xchg, 0));
         for (int i = 0; i < ns; ++i) {
             nf_solver *S = T->slabs[i];
-            NFCHK(launch_s(S, 2, g, mode_args(S, g, 2, 0, xs[i], ys[i]), make_geom(S), 0, nullptr, nullptr, nullptr, 3));
+            NFCHK(launch_s(S, 2, g, mode_args(S, g, 2, 0, xs[i], ys[i]), make_geom(S), 0, nullptr, PassCg(), nullptr, 3));
         }
         NFCHK(team_stream_wait(T, T->stream));                  // the exchange buffers are reused by the next group
     }
@@ -2172,7 +2195,7 @@ static int dense_prepare(nf_team *T)
         double *M = S->d_Sdense + (size_t)g * nn;
         for (int j = 0; j < n; ++j) {
             hipLaunchKernelGGL(k_unit_vector, dim3(grid_for(n)), dim3(256), 0, st, S->d_p, (long)n, (long)j);
-            NFCHK(team_schur_apply(T, g, { S->d_p }, { M + (size_t)j * n }, false, nullptr, nullptr));
+            NFCHK(team_schur_apply(T, g, { S->d_p }, { M + (size_t)j * n }, false, ApplyCg()));
         }
         double *a = M, *b = work.p;
         const unsigned gr = (unsigned)((nn + 255) / 256);
@@ -3528,14 +3551,14 @@ int nf_time_schur_apply(nf_handle S, int g, int reps, double *avg_ms)
         hipLaunchKernelGGL(k_fill_pattern, dim3(grid_for(X->nphi)), dim3(256), 0, T->stream, X->d_p, X->nphi);
         xs.push_back(X->d_p); ys.push_back(X->d_q);
     }
-    NFCHK(team_schur_apply(T, g, xs, ys, false, nullptr, nullptr));   // warm-up
+    NFCHK(team_schur_apply(T, g, xs, ys, false, ApplyCg()));   // warm-up
     T->profile = true; const int every = T->prof_every; T->prof_every = 1;
-    for (int i = 0; i < std::min(reps, 8); ++i) NFCHK(team_schur_apply(T, g, xs, ys, false, nullptr, nullptr));
+    for (int i = 0; i < std::min(reps, 8); ++i) NFCHK(team_schur_apply(T, g, xs, ys, false, ApplyCg()));
     HIPCHK(hipStreamSynchronize(T->stream));
     prof_collect(T); T->profile = false; T->prof_every = every;
     hipEvent_t a, b; HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
     HIPCHK(hipEventRecord(a, T->stream));
-    for (int i = 0; i < reps; ++i) NFCHK(team_schur_apply(T, g, xs, ys, false, nullptr, nullptr));
+    for (int i = 0; i < reps; ++i) NFCHK(team_schur_apply(T, g, xs, ys, false, ApplyCg()));
     HIPCHK(hipEventRecord(b, T->stream));
     HIPCHK(hipEventSynchronize(b));
     float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, a, b));
