@@ -224,6 +224,18 @@ int nf_profile_get(nf_handle h, const char *name, long *count, double *total_ms)
 int nf_profile_reset(nf_handle h);
 /* the same counters, with the iteration counts of the last solve, as one JSON object */
 int nf_timers(nf_handle h, char *json_buf, size_t len);
+/* Read-only report of the launch plan: what the next Schur apply on this handle's mesh (or slab) would launch, as one JSON object
+ * {"in_cg", "slab", "fused", "lean", "single_reduce", "split_dot", "xy_overlap", "passes": [...]}.  in_cg = 0: a plain nf_schur_apply /
+ * nf_team_schur_apply; in_cg = 1: the apply inside an iteration of the launch-path CG (not the fused-direction or one-XCD solves).
+ * One entry of "passes" per direction that exists; the z direction of a slab has two (mode 1 = endpoint pass, mode 2 = accumulation
+ * pass).  Per entry: "dir" (x / y / z), "mode", "family" (x = k_schur_x, s = k_schur_s, c = k_schur_c, endpoint_w = k_endpoint_w),
+ * "SEG" (cells per segment), "NCH" (chunks per lane / block), "TX" (columns per block; lanes per line for x), "NSEG" (segments per
+ * line; NS of the chunked kernel), "grid" [x, y, z], "block", "nt" (streaming loads), "p2" (two load phases), "zw" (the pass's share
+ * of x.y in the z.w form), "xcd_order" (the XCD-contiguous tile order is requested) and "xcd_permutes" (requested, and the tile count
+ * is a multiple of 8 beyond 8: tiles really move) and "fold" (accumulation pass of a slab: it forms the separator values
+ * itself).  Built from the predicates the launch functions themselves call; launches nothing
+ * and changes no state.  A slab team must have been prepared (one team apply or solve since its options last changed). */
+int nf_apply_plan(nf_handle h, int in_cg, char *json_buf, size_t len);
 /* times `reps` back-to-back Schur applies on group g (random x) with HIP events; average ms per apply */
 int nf_time_schur_apply(nf_handle h, int g, int reps, double *avg_ms);
 /* LocalMatrices::Compute(e, D, Sigma) (src/FEM.cpp:748-953) on the device, literally: the dense A_loc (n_Jloc x n_Jloc), B_loc

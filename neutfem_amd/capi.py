@@ -14,7 +14,7 @@ SYMBOLS = [
     "nf_last_error", "nf_device_count", "nf_create", "nf_destroy", "nf_create_slab", "nf_link_slabs", "nf_comm_unique_id",
     "nf_comm_init", "nf_comm_info", "nf_comm_selftest", "nf_team_schur_apply", "nf_info", "nf_set_bc", "nf_upload_xs", "nf_build",
     "nf_schur_apply", "nf_solve_group", "nf_build_diagonal_cache", "nf_get_diagonal_cache", "nf_solve_keff",
-    "nf_upload_source", "nf_solve_subcritical", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_project_flux", "nf_project_power", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
+    "nf_upload_source", "nf_solve_subcritical", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_apply_plan", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_project_flux", "nf_project_power", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
     "nf_get_warm_state", "nf_get_history", "nf_profile_get", "nf_profile_reset", "nf_time_schur_apply", "nf_time_device_copy", "nf_progress", "nf_set_progress_callback", "nf_local_matrices",
     "nf_set_option", "nf_mem_info", "nf_dev_alloc", "nf_dev_free", "nf_memcpy_h2d", "nf_memcpy_d2h", "nf_synchronize", "nf_stream",
 ]
@@ -81,6 +81,7 @@ def load():
     L.nf_coarsen.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     L.nf_prolong.argtypes = [vp, vp]
     L.nf_timers.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.nf_apply_plan.argtypes = [vp, C.c_int, C.c_char_p, C.c_size_t]
     L.nf_initialize_cmfd.argtypes = [vp]
     L.nf_set_cmfd_relaxation.argtypes = [vp, C.c_double]
     L.nf_get_cmfd_coefficients.argtypes = [vp, C.c_int, C.c_int, dp, dp]
@@ -252,6 +253,17 @@ class HipSolver:
         buf = C.create_string_buffer(2048)
         self._chk(self.L.nf_timers(self.h, buf, 2048))
         return json.loads(buf.value.decode())
+
+    def apply_plan(self, in_cg=False):
+        """what the next Schur apply would launch (nf_apply_plan): the report as a dict, its passes also keyed by direction --
+        plan["x"], plan["y"], plan["z"] (undivided mesh) or plan["z1"] / plan["z2"] (the two z passes of a slab)"""
+        import json
+        buf = C.create_string_buffer(8192)
+        self._chk(self.L.nf_apply_plan(self.h, int(bool(in_cg)), buf, 8192))
+        plan = json.loads(buf.value.decode())
+        for p in plan["passes"]:
+            plan[p["dir"] + (str(p["mode"]) if p["mode"] else "")] = p
+        return plan
 
     def initialize_cmfd(self): self._chk(self.L.nf_initialize_cmfd(self.h))
     def set_cmfd_relaxation(self, omega): self._chk(self.L.nf_set_cmfd_relaxation(self.h, float(omega)))

@@ -1188,6 +1188,27 @@ static bool lds_opt_in(const void *fn, size_t lds)
     return true;
 }
 // ---- Schur apply -----------------------------------------------------------------------------
+// The choices of the launch functions below as small predicates: the launches and nf_apply_plan (the read-only report) both call them.
+static bool nt_regime(const nf_solver *S) { return S->team->opt_nt_loads && S->N > S->team->nt_min_cells; }   // streaming loads beyond the caches (per slab on teams)
+static bool x_nt(const nf_solver *S, int NB) { return NB == 0 && S->nx % 2 == 0 && nt_regime(S); }
+// inside CG: two load phases (schur_x_task, P2): 116 instead of 140 VGPRs at four chunks per lane, four waves per SIMD instead of
+// three -- and no faster (512^3: 1548 vs 1529 us, 256^3: 185.9 vs 186.3; profiles/r03_e_ab_cg.txt).  Kept as an option, off.
+// Instantiated next to the streaming loads only.
+static bool x_p2(const nf_solver *S, int NB, int NCH, bool fused_here, bool nt) { return nt && NB == 0 && NCH >= 2 && fused_here && S->team->opt_x_p2 == 1; }
+static bool x_xcd(const nf_solver *S, bool nt) { return nt && S->team->opt_xcd >= 0 && (S->team->opt_xcd & 4); }   // bit 1 of k_schur_x's `first`: the streaming instantiations only
+static bool x_fuses(const nf_solver *S) { return !(S->if_lo || S->if_hi); }                                       // slabs fuse in their endpoint pass instead
+struct XPlan { int lpl_log2 = 0, NCH = 0; unsigned grid = 0; };  // NCH: the instantiation's chunks per lane (0: the line is refused)
+static XPlan x_plan(const nf_solver *S)
+{
+    XPlan P; const int K = 2;
+    const int lanes = (S->nx + K - 1) / K;
+    while ((1 << P.lpl_log2) < lanes && P.lpl_log2 < 6) ++P.lpl_log2;
+    const int LPL = 1 << P.lpl_log2, LPW = 64 / LPL;
+    const int nch = (S->nx + LPL * K - 1) / (LPL * K);
+    P.grid = (unsigned)((S->nlines[0] + 4 * LPW - 1) / (4 * LPW));
+    for (int c = 1; c <= (S->nb == 0 ? 32 : 8); c *= 2) if (nch <= c) { P.NCH = c; break; }   // long lines (16, 32: RT0-P0 only): more registers per lane, lower occupancy
+    return P;
+}
 template <int NCH, int NB>
 static void launch_x_t(const nf_solver *S, int g, const ModeArgs &ma, const Geom &G, int lpl_log2, int first, int last,
                        double *partials, const PassCg &P, unsigned grid)
@@ -1196,36 +1217,30 @@ static void launch_x_t(const nf_solver *S, int g, const ModeArgs &ma, const Geom
     const bool vec = (S->nx % 2 == 0);
     hipStream_t st = S->team->stream;
     const double *L = S->d_L[0] + g * N, *DR = S->d_DR[0] + g * N, *D0 = S->d_D0[0] + g * S->nlines[0];
-    const CgFuse fz = (S->if_lo || S->if_hi) ? CgFuse{ nullptr, nullptr, nullptr } : P.fuse;   // slabs fuse in their endpoint pass instead
+    const CgFuse fz = x_fuses(S) ? P.fuse : CgFuse{ nullptr, nullptr, nullptr };
     const ModeTab mt = mode_tab(S, 0);
     const dim3 gr(grid, (unsigned)mt.n);                          // all transverse modes in one launch
-    const bool nt = NB == 0 && vec && S->team->opt_nt_loads && N > S->team->nt_min_cells;   // streaming loads beyond the caches (per slab on teams)
-    // inside CG: two load phases (schur_x_task, P2): 116 instead of 140 VGPRs at four chunks per lane, four waves per SIMD instead of
-    // three -- and no faster (512^3: 1548 vs 1529 us, 256^3: 185.9 vs 186.3; profiles/r03_e_ab_cg.txt).  Kept as an option, off.
-    const bool p2 = NB == 0 && NCH >= 2 && fz.p && S->team->opt_x_p2 == 1;
-    if (nt && p2) hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB, NB == 0, NB == 0 && (NCH >= 2)>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2,
-                               first | ((S->team->opt_xcd >= 0 && (S->team->opt_xcd & 4)) ? 2 : 0), last, partials, P.cg, fz, P.lean);
+    const bool nt = x_nt(S, NB), p2 = x_p2(S, NB, NCH, fz.p != nullptr, nt);
+    const int first_x = first | (x_xcd(S, nt) ? 2 : 0);
+    if (p2) hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB, NB == 0, NB == 0 && (NCH >= 2)>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2,
+                               first_x, last, partials, P.cg, fz, P.lean);
     else if (nt) hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB, NB == 0>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2,
-                               first | ((S->team->opt_xcd >= 0 && (S->team->opt_xcd & 4)) ? 2 : 0), last, partials, P.cg, fz, P.lean);
+                               first_x, last, partials, P.cg, fz, P.lean);
     else if (vec) hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2, first, last, partials, P.cg, fz, P.lean);
     else hipLaunchKernelGGL((k_schur_x<2, NCH, false, NB>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2, first, last, partials, P.cg, fz, P.lean);
 }
 template <int NB>
 static int launch_x_nb(const nf_solver *S, int g, const ModeArgs &ma, const Geom &G, int last, double *partials, const PassCg &P, int *nparts)
 {
-    const int K = 2;
-    int lanes = (S->nx + K - 1) / K, lpl_log2 = 0;
-    while ((1 << lpl_log2) < lanes && lpl_log2 < 6) ++lpl_log2;
-    const int LPL = 1 << lpl_log2, LPW = 64 / LPL;
-    const int nch = (S->nx + LPL * K - 1) / (LPL * K);
-    const unsigned grid = (unsigned)((S->nlines[0] + 4 * LPW - 1) / (4 * LPW));
+    const XPlan xp = x_plan(S);
+    const int lpl_log2 = xp.lpl_log2; const unsigned grid = xp.grid;
     if (nparts) *nparts = (int)grid * n_modes(S);
-    if (nch <= 1) launch_x_t<1, NB>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
-    else if (nch <= 2) launch_x_t<2, NB>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
-    else if (nch <= 4) launch_x_t<4, NB>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
-    else if (nch <= 8) launch_x_t<8, NB>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
-    else if (nch <= 16 && NB == 0) launch_x_t<16, 0>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);   // long lines: more registers per lane, lower occupancy
-    else if (nch <= 32 && NB == 0) launch_x_t<32, 0>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
+    if (xp.NCH == 1) launch_x_t<1, NB>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
+    else if (xp.NCH == 2) launch_x_t<2, NB>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
+    else if (xp.NCH == 4) launch_x_t<4, NB>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
+    else if (xp.NCH == 8) launch_x_t<8, NB>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
+    else if (xp.NCH == 16 && NB == 0) launch_x_t<16, 0>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
+    else if (xp.NCH == 32 && NB == 0) launch_x_t<32, 0>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
     else return fail(NF_ERR_UNSUPPORTED, "nx = %d exceeds the x-line kernel limit (%d cells)", S->nx, NB == 0 ? 4096 : 1024);
     return NF_OK;
 }
@@ -1268,6 +1283,31 @@ static ChunkPlan chunk_plan(const nf_solver *S, int d)
     return P;
 }
 
+static ChunkPlan pass_chunk_plan(const nf_solver *S, int d, int zmode) { return zmode == 0 ? chunk_plan(S, d) : ChunkPlan(); }   // the slab chain passes never take it
+// launch shape and load / order flags of the chunked kernel; taken: this pass really goes to it (its share of x.y comes in the z.w form only)
+static bool c_taken(const ChunkPlan &cp, bool want_dot, bool zw_dot) { return cp.ok && (!want_dot || zw_dot); }
+static dim3 c_grid(const nf_solver *S, int d, const ChunkPlan &cp) { return dim3((unsigned)((S->nx + cp.TX - 1) / cp.TX), (unsigned)(d == 1 ? S->nz : S->ny)); }
+static unsigned c_block(const ChunkPlan &cp) { return (unsigned)((cp.TX * cp.NS + 63) / 64 * 64); }   // whole wavefronts, as in seg_plan
+static const int C_SEG = 8, C_NCH = 2;                           // k_schur_c: segments of 8 cells, two chunks per block (chunk_plan's NS counts 16 cells)
+static bool c_nt(const nf_solver *S) { return nt_regime(S); }
+static int c_xcd(const nf_solver *S, int d, bool nt) { const nf_team *T = S->team; return T->opt_xcd >= 0 ? (T->opt_xcd >> (d - 1)) & 1 : (d == 1 && nt); }
+// one-chunk kernel (k_schur_s).  XCD-contiguous tile order: bit 0 = y passes, bit 1 = z passes; -1 (default) = the y passes of meshes in the streaming
+// regime -- the 8 x tiles of a row set then run on one XCD back to back (256^3: y 133 -> 123 us, 501 -> 493 us per CG iteration;
+// z passes lose 10 us with it; neutral to -0.5 % at 96^3 ... 192^3)
+// z passes of SMALL slabs (at most 6 Mi cells): the XCD-contiguous order by default too (8-slab loopback at 256^3: accumulation pass 33.3 -> 30.7 us,
+// 848 -> 835 us per CG iteration; 4 slabs 800 -> 773; on 8.4 M / 16.8 M-cell slabs it loses: 93 -> 101 / 191 -> 201 us; profiles/r04_o_slab_options.txt)
+static int s_xcd(const nf_solver *S, int d, int zmode)
+{
+    const nf_team *T = S->team;
+    return T->opt_xcd >= 0 ? (T->opt_xcd >> (d - 1)) & 1 : ((d == 1 && nt_regime(S)) || ((zmode == 1 || zmode == 2) && S->N <= (6L << 20)));
+}
+// undivided meshes beyond the caches (the classic path's sizes): the variant with streaming loads (SF doubles as that flag for !SLAB)
+static bool s_nt(const nf_solver *S, int zmode, int SEG) { return zmode == 0 && S->nb == 0 && SEG == 8 && nt_regime(S); }
+static bool s_nts(const nf_solver *S, int zmode, int SEG) { return zmode != 0 && zmode != 3 && S->nb == 0 && SEG == 8 && nt_regime(S); }   // the same for the z passes of a slab
+static bool s_zw(const nf_solver *S, int zmode, bool zw_dot, bool want_dot) { return zmode == 0 && S->nb == 0 && zw_dot && want_dot; }     // z.w form of the pass's share of x.y
+static bool s_fold(const nf_team *T, int zmode) { return zmode == 2 && T->sep_sweeps == 0 && T->opt_sepfold; }   // thick slabs: the accumulation pass forms the separator values itself
+// tiles of a (gx, gy) launch move under the XCD-contiguous order only when their count is a multiple of 8 (the kernels' own test) beyond 8 (the identity)
+static bool xcd_permutes(bool order, unsigned tiles) { return order && tiles % 8 == 0 && tiles > 8; }
 // 8-cell segments up to 1024 cells per line (16 / 32 cells spill to scratch: 1.4x slower even though TX drops to 8 at 1024)
 // higher orders: 4-cell segments up to 256 cells per line; beyond, RT1 keeps 8 (148 B / lane of scratch and still faster: y 97 vs 122 us on
 // 48 x 512 x 48), RT2 takes 4 up to 512 cells (8 columns per block, no scratch: y 352 vs 383 us, z 412 vs 431; profiles/r04_g_higher_orders.txt)
@@ -1307,17 +1347,16 @@ static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const 
     const int n = d == 1 ? S->ny : S->nz;
     const long nxy = (long)S->nx * S->ny;
     const long sl = d == 1 ? S->nx : nxy, ostride = d == 1 ? nxy : S->nx;
-    const int nouter = d == 1 ? S->nz : S->ny;
     // long plain lines of RT0-P0 meshes: two chunks per block, twice the tile width (k_schur_c).  Its share of x.y comes in the z.w
     // form only: inside CG it needs the split dot product of team_schur_apply
-    const ChunkPlan cp = zmode == 0 ? chunk_plan(S, d) : ChunkPlan();
-    if (cp.ok && (!(last && partials) || P.zw_dot)) {
+    const ChunkPlan cp = pass_chunk_plan(S, d, zmode);
+    if (c_taken(cp, last && partials, P.zw_dot)) {
         const int NS = cp.NS, TXc = cp.TX; const size_t ldsc = cp.lds;
         {
-            dim3 grid((unsigned)((S->nx + TXc - 1) / TXc), (unsigned)nouter), block((unsigned)((TXc * NS + 63) / 64 * 64));
+            dim3 grid = c_grid(S, d, cp), block(c_block(cp));
             const double *L = S->d_L[d] + g * N, *DR = S->d_DR[d] + g * N, *D0 = S->d_D0[d] + g * S->nlines[d];
-            const bool nt = T->opt_nt_loads && S->N > T->nt_min_cells;
-            const int xcd = T->opt_xcd >= 0 ? (T->opt_xcd >> (d - 1)) & 1 : (d == 1 && nt);
+            const bool nt = c_nt(S);
+            const int xcd = c_xcd(S, d, nt);
             bool launched = false;                                    // false: the device refused the LDS -> the one-chunk kernel below
 #define NF_C(DIRV, NTV) do { if (lds_opt_in((const void *)k_schur_c<DIRV, NTV>, ldsc)) { \
             hipLaunchKernelGGL((k_schur_c<DIRV, NTV>), grid, block, ldsc, T->stream, ma.x[0], ma.y[0], ma.Ta, L, DR, D0, n, sl, ostride, S->nx, TXc, NS, last, partials, cg, xcd); \
@@ -1336,19 +1375,11 @@ static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const 
     hipStream_t st = P.stream ? P.stream : T->stream;
     SlabArgs sa; memset(&sa, 0, sizeof sa);
     sa.noacc = P.noacc ? 1 : 0; sa.yadd = P.yadd;
-    // XCD-contiguous tile order (k_schur_s): bit 0 = y passes, bit 1 = z passes; -1 (default) = the y passes of meshes in the streaming
-    // regime -- the 8 x tiles of a row set then run on one XCD back to back (256^3: y 133 -> 123 us, 501 -> 493 us per CG iteration;
-    // z passes lose 10 us with it; neutral to -0.5 % at 96^3 ... 192^3)
-    // z passes of SMALL slabs (at most 6 Mi cells): the XCD-contiguous order by default too (8-slab loopback at 256^3: accumulation pass 33.3 -> 30.7 us,
-    // 848 -> 835 us per CG iteration; 4 slabs 800 -> 773; on 8.4 M / 16.8 M-cell slabs it loses: 93 -> 101 / 191 -> 201 us; profiles/r04_o_slab_options.txt)
-    sa.xcd = T->opt_xcd >= 0 ? (T->opt_xcd >> (d - 1)) & 1 : ((d == 1 && T->opt_nt_loads && S->N > T->nt_min_cells) || ((zmode == 1 || zmode == 2) && S->N <= (6L << 20)));
+    sa.xcd = s_xcd(S, d, zmode);
     sa.wsmin = T->opt_wsmin;
     const CgFuse fz = (zmode == 1 && S->nloc == 1) ? P.fuse : CgFuse{ nullptr, nullptr, nullptr };
     const CgLean lz = (zmode == 1 && S->nloc == 1 && fz.p) ? P.lean_z1 : CgLean{ nullptr, nullptr, 0, 0, 0 };
-    // undivided meshes beyond the caches (the classic path's sizes): the variant with streaming loads (SF doubles as that flag for !SLAB)
-    const bool nt = zmode == 0 && S->nb == 0 && SEG == 8 && T->opt_nt_loads && S->N > T->nt_min_cells;
-    const bool nts = zmode != 0 && zmode != 3 && S->nb == 0 && SEG == 8 && T->opt_nt_loads && S->N > T->nt_min_cells;   // the same for the z passes of a slab
-    const bool zw = zmode == 0 && S->nb == 0 && P.zw_dot && last && partials;                                              // z.w form of the pass's share of x.y
+    const bool nt = s_nt(S, zmode, SEG), nts = s_nts(S, zmode, SEG), zw = s_zw(S, zmode, P.zw_dot, last && partials);
     // single-reduction CG (Cg1): the endpoint pass (mode 1) consumes the reduction of the previous iteration and carries r -= alpha q, the
     // accumulation pass (mode 2) leaves p.q, q.q, r.q; |r|^2 comes from the endpoint pass (row 3 of the partial buffer)
     const bool sr = P.cg1.red != nullptr && S->nb == 0 && SEG == 8 && d == 2 && ((zmode == 1 && fz.p) || (zmode == 2 && last && partials));
@@ -1384,7 +1415,7 @@ static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const 
                 sa.amode[m] = amode;
             }
         }
-        if (zmode == 2 && T->sep_sweeps == 0 && T->opt_sepfold) {     // separators formed inside the pass (no k_separators launch)
+        if (s_fold(T, zmode)) {                                     // separators formed inside the pass (no k_separators launch)
             sa.fold = 1; sa.rlo = S->d_rlo; sa.rhi = S->d_rhi; sa.sinv_lo = S->d_sinv_lo + g * nl; sa.sinv_hi = S->d_sinv_hi + g * nl;
         }
         if (S->nb == 0) NF_S_SEG(2, true, 0); else if (S->nb == 1) NF_S_SEG(2, true, 1); else NF_S_SEG(2, true, 2);
@@ -1398,6 +1429,14 @@ static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const 
     return NF_OK;
 }
 
+// the endpoint pass of a slab as weighted sums (k_endpoint_w) instead of a chain solve: inside the single-reduction CG (sr), weights measured,
+// the fused update reading the vector the pass is applied to, and its |r|^2 partials fitting the slab's share of the partial buffer
+static dim3 endpoint_w_grid(const nf_solver *S) { return dim3((unsigned)((S->nx + 63) / 64), (unsigned)S->ny); }
+static bool endpoint_w_taken(const nf_team *T, const nf_solver *S, bool sr, bool fuse_reads_x)
+{
+    const dim3 gr = endpoint_w_grid(S);
+    return sr && S->w_valid && T->opt_endpoint_w && fuse_reads_x && (long)gr.x * gr.y <= T->slab_cap;
+}
 // Partition method, first half (slab teams): the endpoint pass of every slab (mode 1), the plane exchange and the separator
 // values (+ Jacobi sweeps for thin slabs).  The exchange and the separator kernels run on the comm stream; ev_xchg marks
 // their end -- the caller's z pass (or current reconstruction) waits for it, the x / y passes do not.
@@ -1411,10 +1450,10 @@ static int team_endpoint_phase(nf_team *T, int g, const std::vector<const double
         if (cnt3) (*cnt3)[i] = 0;
         if (!(S->if_lo || S->if_hi)) continue;
         const PassCg P = pass_cg(A, S, i);
-        if (P.cg1.red && S->w_valid && T->opt_endpoint_w && P.fuse.p == xs[i]) {
+        if (endpoint_w_taken(T, S, P.cg1.red != nullptr, P.fuse.p == xs[i])) {
             // single-reduction CG: the chain-end responses as weighted sums of the line's cells + the deferred CG update (k_endpoint_w)
-            const dim3 gr((unsigned)((S->nx + 63) / 64), (unsigned)S->ny);
-            if ((long)gr.x * gr.y <= T->slab_cap) {
+            const dim3 gr = endpoint_w_grid(S);
+            {
                 hipLaunchKernelGGL(k_endpoint_w, gr, dim3(256), 0, T->stream, P.fuse.p, const_cast<double *>(P.fuse.r), (const double *)S->d_q, P.fuse.xsol,
                                    (const double *)(S->d_Wlo + (size_t)g * S->N), (const double *)(S->d_Whi + (size_t)g * S->N), S->d_clo, S->d_chi,
                                    S->nx, S->ny, S->nz, S->if_lo, S->if_hi, 40, P.cg1, cg, T->d_partials + 3 * T->partial_stride + (long)S->slab_index * T->slab_cap);
@@ -1436,7 +1475,7 @@ static int team_endpoint_phase(nf_team *T, int g, const std::vector<const double
         }
     };
     // thick slabs (no separator sweeps): the accumulation pass forms u = (c_below + c_above) S_red^-1 itself (SlabArgs::fold)
-    if (need_u || T->sep_sweeps > 0 || !T->opt_sepfold)
+    if (need_u || !s_fold(T, 2))
         each_slab([&](nf_solver *S, long nl, dim3 gr) {
             hipLaunchKernelGGL(k_separators, gr, dim3(256), 0, T->comm_stream, S->d_clo, S->d_chi, S->d_rlo, S->d_rhi, S->d_sinv_lo + g * nl, S->d_sinv_hi + g * nl,
                                S->d_ulo, S->d_uhi, S->d_ctlo, S->d_cthi, nl, nl * n_modes(S), S->if_lo, S->if_hi, cg); });
@@ -1453,6 +1492,35 @@ static int team_endpoint_phase(nf_team *T, int g, const std::vector<const double
 }
 
 static bool team_is_single(const nf_team *T) { return T->slabs.size() == 1 && !T->slabs[0]->if_lo && !T->slabs[0]->if_hi; }
+// The forms of the CG iteration (cg_solve), as far as they change what a Schur apply launches:
+// fused (RT0-P0, undivided mesh: x_sol / p updates ride in the next x pass, k_schur_x, CgFuse; slab teams: P0, in the endpoint pass of the z
+// lines, the first pass to read p); lean on top of it (undivided mesh, no RCCL: no k_finalize launches, see CgLean); the lean form of slab
+// teams; its single-reduction variant (Cg1: one reduction per iteration; needs the 8-cell-segment z passes on every local slab)
+static bool cg_fused(const nf_team *T) { return T->opt_fuse != 0 && (team_is_single(T) || T->slabs[0]->nloc == 1); }
+static bool cg_lean(const nf_team *T) { return cg_fused(T) && T->opt_lean && team_is_single(T) && !T->rccl_reduce && T->slabs[0]->N <= T->lean_max_cells; }
+static bool cg_tlean(const nf_team *T) { return cg_fused(T) && T->opt_lean && !team_is_single(T); }
+static bool cg_sr(const nf_team *T)
+{
+    bool sr = cg_tlean(T) && (T->opt_cg1 > 0 || (T->opt_cg1 < 0 && T->team_max_cells <= T->cg1_max_cells));
+    for (auto *S : T->slabs) sr = sr && S->dim == 3 && S->nb == 0 && (T->opt_s_seg == 0 || T->opt_s_seg == 8) && S->nz <= 1024;
+    return sr;
+}
+// Split dot product of an apply inside CG (see team_schur_apply): on undivided RT0-P0 meshes outside the lean path, where a chunked long-line
+// pass forms the last share (only the LAST pass forms the dot product otherwise) or on request (split_dot = 2)
+static bool split_dot(const nf_team *T, bool want_dot, bool lean)
+{
+    const int dim = T->slabs[0]->dim;
+    bool split = want_dot && dim >= 2 && team_is_single(T) && T->slabs[0]->nb == 0 && !lean && T->opt_split_dot;
+    if (split && T->opt_split_dot < 2) split = chunk_plan(T->slabs[0], dim - 1).ok;
+    return split;
+}
+// x || y (slab teams, RT0-P0, slabs small enough not to fill the chip)
+static bool xy_overlap(const nf_team *T, bool any_if, bool prof)
+{
+    const bool xy = T->slabs[0]->dim == 3 && any_if && T->opt_xy_overlap && T->slabs[0]->nb == 0 && T->y_stream && !prof;
+    bool xy_all = xy; if (xy) for (auto *X : T->slabs) xy_all = xy_all && X->N <= T->xy_overlap_max_cells && !chunk_plan(X, 1).ok;
+    return xy_all;
+}
 
 // y = S_g x on every local slab.  xs / ys: per-slab device pointers (nphi doubles, layout [p][e]).  With `want_dot` the
 // passes of the last direction leave the block partials of x.y in the team buffer and counts[] receives the number per slab (cnt3[]: team_endpoint_phase).
@@ -1478,8 +1546,7 @@ static int team_schur_apply(nf_team *T, int g, const std::vector<const double *>
     // Taken where a chunked long-line pass runs (it has no x left when its parked chunk comes back) or on request (split_dot = 2: tests);
     // elsewhere the last pass sums x_i y_i with x still in its registers, which is cheaper than three sets of partials (256^3: 504 vs
     // 531 us per CG iteration, profiles/r03_e_ab_cg.txt).
-    bool split = want_dot && dim >= 2 && team_is_single(T) && T->slabs[0]->nb == 0 && !A.lean.st && T->opt_split_dot;
-    if (split && T->opt_split_dot < 2) split = chunk_plan(T->slabs[0], dim - 1).ok;      // only the LAST pass forms the dot product
+    const bool split = split_dot(T, want_dot, A.lean.st != nullptr);
     std::vector<int> totals(ns, 0);
     for (int d = 0; d < dim; ++d) {
         const int last = d == dim - 1;
@@ -1487,8 +1554,7 @@ static int team_schur_apply(nf_team *T, int g, const std::vector<const double *>
         if (prof) prof_begin(T, d, &a, &b);
         // x || y (slab teams, RT0-P0, slabs small enough not to fill the chip): fork after the endpoint pass -- the new p is complete --,
         // the y pass of every local slab on y_stream into d_qy, join before the accumulation pass, which adds d_qy
-        const bool xy = dim == 3 && any_if && T->opt_xy_overlap && T->slabs[0]->nb == 0 && T->y_stream && !prof;
-        bool xy_all = xy; if (xy) for (auto *X : T->slabs) xy_all = xy_all && X->N <= T->xy_overlap_max_cells && !chunk_plan(X, 1).ok;
+        const bool xy_all = xy_overlap(T, any_if, prof);
         if (d == 0 && xy_all) { HIPCHK(hipEventRecord(T->ev_fork, T->stream)); HIPCHK(hipStreamWaitEvent(T->y_stream, T->ev_fork, 0)); }
         if (d == 2 && xy_all) { HIPCHK(hipEventRecord(T->ev_join, T->y_stream)); HIPCHK(hipStreamWaitEvent(T->stream, T->ev_join, 0)); }
         for (int i = 0; i < ns; ++i) {
@@ -1546,6 +1612,76 @@ int nf_team_schur_apply(nf_handle S, int g, const double *const *x_dev, double *
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(T->stream));
     if (T->profile) prof_collect(T);
+    return NF_OK;
+}
+
+// ---- read-only report of the launch plan -------------------------------------------------------
+// What the next Schur apply on this handle's mesh (or slab) would launch, per direction, as one JSON object.  Built from the predicates
+// the launch functions call (x_plan / x_nt / x_p2 / x_xcd, pass_chunk_plan / c_taken / c_nt / c_xcd, seg_plan / s_nt / s_nts / s_zw / s_xcd,
+// endpoint_w_taken, the cg_* forms, split_dot, xy_overlap); launches nothing, writes no state.  The one thing it cannot know is a device
+// that refuses the chunked kernel's LDS at launch time (launch_s then falls back to the one-chunk kernel).
+struct PlanPass { const char *dir, *family; int mode, SEG, NCH, TX, NSEG; dim3 grid; unsigned block; bool nt, p2, zw, order; unsigned tiles; bool fold = false; };
+static void plan_emit(std::string &js, const PlanPass &p)
+{
+    char tmp[384];
+    snprintf(tmp, sizeof tmp, "%s{\"dir\": \"%s\", \"mode\": %d, \"family\": \"%s\", \"SEG\": %d, \"NCH\": %d, \"TX\": %d, \"NSEG\": %d, \"grid\": [%u, %u, %u], "
+             "\"block\": %u, \"nt\": %d, \"p2\": %d, \"zw\": %d, \"xcd_order\": %d, \"xcd_permutes\": %d, \"fold\": %d}", js.back() == '[' ? "" : ", ", p.dir, p.mode, p.family,
+             p.SEG, p.NCH, p.TX, p.NSEG, p.grid.x, p.grid.y, p.grid.z, p.block, p.nt ? 1 : 0, p.p2 ? 1 : 0, p.zw ? 1 : 0, p.order ? 1 : 0, xcd_permutes(p.order, p.tiles) ? 1 : 0, p.fold ? 1 : 0);
+    js += tmp;
+}
+static int plan_s(std::string &js, const nf_solver *S, int d, int zmode, bool want_dot, bool zw_dot)   // a launch_s call
+{
+    const char *dir = d == 1 ? "y" : "z";
+    const ChunkPlan cp = pass_chunk_plan(S, d, zmode);
+    if (c_taken(cp, want_dot, zw_dot)) {
+        const dim3 gr = c_grid(S, d, cp); const bool nt = c_nt(S);
+        plan_emit(js, { dir, "c", zmode, C_SEG, C_NCH, cp.TX, cp.NS, gr, c_block(cp), nt, false, want_dot, c_xcd(S, d, nt) != 0, gr.x * gr.y });
+        return NF_OK;
+    }
+    const SegPlan sp = seg_plan(S, d, zmode);
+    if (sp.rc != NF_OK) return sp.rc;
+    plan_emit(js, { dir, "s", zmode, sp.SEG, 1, sp.TX, sp.NSEG, sp.grid, sp.block.x, s_nt(S, zmode, sp.SEG) || s_nts(S, zmode, sp.SEG), false, s_zw(S, zmode, zw_dot, want_dot),
+                    s_xcd(S, d, zmode) != 0, sp.grid.x * sp.grid.y, s_fold(S->team, zmode) });
+    return NF_OK;
+}
+int nf_apply_plan(nf_handle S, int in_cg, char *json_buf, size_t len)
+{
+    if (!S || !json_buf || len < 2) return fail(NF_ERR_ARG, "nf_apply_plan: bad arguments");
+    if (!S->built) return fail(NF_ERR_STATE, "nf_apply_plan: call nf_build first");
+    const nf_team *T = S->team;
+    const bool slab = S->if_lo || S->if_hi;
+    // a team settles the separator sweeps, the endpoint weights and its largest slab when it is prepared (the first team apply or solve)
+    if (!team_is_single(T) && !T->linked_ready) return fail(NF_ERR_STATE, "nf_apply_plan: run a team apply or solve first (the team has not been prepared since its options changed)");
+    // How the CG forms reach a launch is taken from cg_solve and team_schur_apply, not shared with them: cg_solve applies S to d_p with
+    // CgFuse::p = d_p when fused (so `P.fuse.p == xs[i]` of team_endpoint_phase is `fused`), sets Cg1::red exactly when cg_sr() holds (so
+    // `P.cg1.red != nullptr` is `sr`), sets ApplyCg::lean exactly when cg_lean() holds, and asks for the dot product of every apply; the
+    // last pass, and every pass under the split dot product, then gets a partial buffer (`last && partials` of the launch functions).
+    const bool cg = in_cg != 0, fused = cg && cg_fused(T), lean = cg && cg_lean(T), sr = cg && cg_sr(T);
+    const bool split = split_dot(T, cg, lean);
+    bool any_if = false; for (auto *X : T->slabs) any_if |= X->if_lo || X->if_hi;
+    const bool xy_all = xy_overlap(T, any_if, false);
+    char tmp[256];
+    snprintf(tmp, sizeof tmp, "{\"in_cg\": %d, \"slab\": %d, \"fused\": %d, \"lean\": %d, \"single_reduce\": %d, \"split_dot\": %d, \"xy_overlap\": %d, \"passes\": [",
+             cg ? 1 : 0, slab ? 1 : 0, fused ? 1 : 0, lean ? 1 : 0, sr ? 1 : 0, split ? 1 : 0, xy_all ? 1 : 0);
+    std::string js = tmp;
+    for (int d = 0; d < S->dim; ++d) {
+        const bool last = d == S->dim - 1, want_dot = cg && (last || split);
+        if (d == 0) {
+            const XPlan xp = x_plan(S);
+            if (!xp.NCH) return fail(NF_ERR_UNSUPPORTED, "nx = %d exceeds the x-line kernel limit (%d cells)", S->nx, S->nb == 0 ? 4096 : 1024);
+            const bool nt = x_nt(S, S->nb), order = x_xcd(S, nt);
+            plan_emit(js, { "x", "x", 0, 0, xp.NCH, 1 << xp.lpl_log2, 0, dim3(xp.grid, (unsigned)n_modes(S)), 256u, nt, x_p2(S, S->nb, xp.NCH, fused && x_fuses(S), nt), false, order, xp.grid });
+        } else if (d == 2 && slab) {
+            // endpoint pass: inside the fused CG the update reads the vector the pass is applied to (cg_solve applies to d_p)
+            if (endpoint_w_taken(T, S, sr, fused)) { const dim3 gr = endpoint_w_grid(S); plan_emit(js, { "z", "endpoint_w", 1, 0, 0, 64, 0, gr, 256u, false, false, false, false, gr.x * gr.y }); }
+            else NFCHK(plan_s(js, S, 2, 1, false, false));
+            NFCHK(plan_s(js, S, 2, 2, want_dot, split));
+        } else if (d == 1 && xy_all) NFCHK(plan_s(js, S, 1, 0, false, split));
+        else NFCHK(plan_s(js, S, d, 0, want_dot, split));
+    }
+    js += "]}";
+    if (js.size() + 1 > len) return fail(NF_ERR_ARG, "nf_apply_plan: buffer of %zu bytes is too small (%zu needed)", len, js.size() + 1);
+    memcpy(json_buf, js.c_str(), js.size() + 1);
     return NF_OK;
 }
 
@@ -1716,22 +1852,16 @@ static int cg_solve(nf_team *T, int g, const std::vector<const double *> &rhs, c
     // first batch: what the previous solve of this group needed, plus two (an iteration launched past convergence costs five
     // early-exit kernels, ~10 us; a second host check costs a D2H copy and a stream drain, ~50 us)
     int batch = T->cg_batch > 0 ? T->cg_batch : (T->last_its[g] > 0 ? T->last_its[g] + 2 : 1), grow = 2;
-    // fused variant (RT0-P0, undivided mesh): x_sol / p updates ride in the next x pass (k_schur_x, CgFuse)
-    // (undivided mesh: in the x pass; slab teams: in the endpoint pass of the z lines, the first pass to read p)
-    const bool fused = T->opt_fuse != 0 && (team_is_single(T) || T->slabs[0]->nloc == 1);   // undivided: any order (x pass); slab teams: P0 (z endpoint pass)
-    // lean variant on top of the fused one (undivided mesh, no RCCL): no k_finalize launches, see CgLean.  Row 0 of the partial
-    // buffer holds the p.q partials of the last direction pass, row 1 the |r|^2 partials of k_cg_rupdate.
-    const bool lean = fused && T->opt_lean && team_is_single(T) && !T->rccl_reduce && T->slabs[0]->N <= T->lean_max_cells;
+    // fused and lean variants (cg_fused / cg_lean).  Lean: row 0 of the partial buffer holds the p.q partials of the last direction pass,
+    // row 1 the |r|^2 partials of k_cg_rupdate.
+    const bool fused = cg_fused(T), lean = cg_lean(T);
     // every block of the next x pass sums the |r|^2 partials; fewer partials (cg_lean_grid) cost k_cg_rupdate more than they save (measured)
     const int gru = lean ? grid_for(T->slabs[0]->nphi, 256, T->opt_lean_grid) : 0;
     double *row1 = T->d_partials + T->partial_stride;
     int rc = NF_OK;
     // lean variant for slab teams (fused, RT0-P0): the endpoint pass of the z lines and k_cg_rupdate consume the all-reduced
     // totals (d_red[2] = |r|^2, d_red[0] = p.q, each followed by the ranks' error flags) and derive beta / alpha and the stop tests themselves: no k_cg_logic launches
-    const bool tlean = fused && T->opt_lean && !team_is_single(T);
-    // single-reduction variant of it (Cg1): one reduction per iteration; needs the 8-cell-segment z passes on every local slab
-    bool sr = tlean && (T->opt_cg1 > 0 || (T->opt_cg1 < 0 && T->team_max_cells <= T->cg1_max_cells));
-    for (auto *S : T->slabs) sr = sr && S->dim == 3 && S->nb == 0 && (T->opt_s_seg == 0 || T->opt_s_seg == 8) && S->nz <= 1024;
+    const bool tlean = cg_tlean(T), sr = cg_sr(T);                // the single-reduction variant (Cg1) of the slab teams' lean form
     T->last_cg_reductions = team_is_single(T) ? 0 : (sr ? 1 : 2); T->last_endpoint_w = 0;
     // fused-direction variant on top of the lean one (small / medium meshes): two launches per iteration, see k_apply3
     Fuse3Plan f3;
