@@ -198,6 +198,45 @@ int nf_project_flux(nf_handle h, int rx, int ry, int rz, int adjoint, int g, dou
  * non-finite values -> NF_ERR_ARG. */
 int nf_project_power(nf_handle h, int rx, int ry, int rz, int adjoint, const double *ksf_host, double *out_dev);
 
+/* ---- zoom: re-solve on a refined mesh with the coarse solution's fission source frozen ----
+ * NeutFEM::ZoomResolved (declared include/NeutFEM.hpp:311, bound src/wrapper.cpp:1045-1065, never defined there; its docstring: unlike
+ * project_flux, which interpolates, this method re-solves the problem on a refined mesh with the sources of the coarse mesh frozen).
+ *
+ * nf_refine: twin of nf_coarsen.  Returns a BUILT handle of the same RT / P orders, groups and boundary types on the mesh whose every
+ * cell is cut into rx x ry x rz equal parts (breaks xb[i] + a (xb[i+1] - xb[i]) / rx, every coarse break kept exactly; cell order of
+ * nf_project_flux); a fine cell has the cross sections of its parent.  The factors are taken literally, as nf_project_flux takes them.
+ * Undivided meshes only (slab teams: NF_ERR_UNSUPPORTED); needs nf_upload_xs.  On a failure the partial handle is destroyed, *fine is
+ * NULL and h stays usable.  The caller destroys the twin. */
+int nf_refine(nf_handle h, int rx, int ry, int rz, nf_handle *fine);
+/* Fills the load vector of `fine` (what nf_upload_source fills) from the coarse handle's current flux (adjoint = 1: its adjoint flux):
+ * the fission source chi_g(e) / keff sum_g' nuSigf_g'(e) phi_g'(x) of every coarse cell e, a polynomial, restricted exactly to every
+ * fine cell E in e and tested against every moment of E: q_g[E, p'] = chi_g(e) / keff sum_g' Mf'_g'[E, p'] c'_g'[E, p'] with Mf' the
+ * fine fission matrix.  All moments are loaded, no 1e-14 drop.  Adjoint: chi and nuSigf swap roles.
+ * Errors: fine is not a refinement of coarse (device, groups, orders, divisibility) or keff non-finite / <= 0 -> NF_ERR_ARG; a source
+ * that is zero everywhere -> NF_ERR_ARG; a non-finite source -> NF_ERR_NUMERIC; adjoint without an adjoint flux -> NF_ERR_STATE. */
+int nf_zoom_source(nf_handle coarse, nf_handle fine, int adjoint, double keff);
+/* the load vector (nf_upload_source or nf_zoom_source) in the host DOF layout [g*n_phi + e*n_loc + p]; NF_ERR_STATE without one */
+int nf_get_source(nf_handle h, double *q_host);
+/* twin of nf_set_phi for the adjoint field Sol_Phi_adj_ (include/NeutFEM.hpp:380-388); allocates it if needed */
+int nf_set_phi_adj(nf_handle h, const double *phi_adj_host);
+
+typedef struct nf_zoom_result {
+    double source;              /* sum over g, E of q_g[E, dof 0]: the frozen source integrated over the mesh */
+    double phi_int;             /* sum over g, E of |E| phibar_g(E) of the zoomed flux */
+    double production;          /* sum over g, E of nuSigf_g(E) |E| phibar_g(E) (the same weights for the adjoint field) */
+    int n_outer, cg_total, converged;
+    long n_cells;               /* cells of the refined mesh */
+} nf_zoom_result;
+/* nf_refine + nf_zoom_source + the fixed-source solve without fission on the refined mesh: per group
+ * S_g phi_g = q_g + sum_{g' != g} Ms[g <- g'] phi_g' (adjoint: the transposed scatter blocks, forward sweep as nf_solve_adjoint), Gauss-Seidel
+ * source iteration from phi = 0 with the group solver nf_solve_keff picks, stopped like phase 0 of nf_solve_subcritical (max_outer
+ * reached: NF_OK, converged = 0).  No normalisation: the fine flux is in the units of the coarse one; with factors (1, 1, 1) and a
+ * converged (phi, keff) it reproduces the coarse flux.  Reads tol_keff, tol_flux, max_outer, max_inner, solver_type, solver_type_pushed
+ * from opts; use_coarse_init, use_cmfd and use_diagonal_solver must be 0 (NF_ERR_ARG).  *fine is the refined handle with the zoomed flux
+ * as its current flux (nf_get_phi, nf_get_J, nf_project_flux work on it); the caller destroys it (NULL after an error).  Nothing of h
+ * changes: flux, warm state, history and nf_progress stay as they are.  Undivided meshes only (NF_ERR_UNSUPPORTED). */
+int nf_zoom_resolved(nf_handle h, const nf_keff_opts *opts, int rx, int ry, int rz, int adjoint, double keff, nf_handle *fine, nf_zoom_result *res);
+
 /* NeutFEM::SolveCoarse (src/NeutFEM.cpp:2380-2611): returns k_coarse and the prolonged flux
  * (ng*n_phi doubles, host) without touching the fine solution. */
 int nf_solve_coarse(nf_handle h, const nf_keff_opts *opts, double *k_coarse, double *phi_host);

@@ -14,7 +14,7 @@ SYMBOLS = [
     "nf_last_error", "nf_device_count", "nf_create", "nf_destroy", "nf_create_slab", "nf_link_slabs", "nf_comm_unique_id",
     "nf_comm_init", "nf_comm_info", "nf_comm_selftest", "nf_team_schur_apply", "nf_info", "nf_set_bc", "nf_upload_xs", "nf_build",
     "nf_schur_apply", "nf_solve_group", "nf_build_diagonal_cache", "nf_get_diagonal_cache", "nf_solve_keff",
-    "nf_upload_source", "nf_solve_subcritical", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_apply_plan", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_project_flux", "nf_project_power", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
+    "nf_upload_source", "nf_solve_subcritical", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_apply_plan", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_project_flux", "nf_project_power", "nf_refine", "nf_zoom_source", "nf_get_source", "nf_set_phi_adj", "nf_zoom_resolved", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
     "nf_get_warm_state", "nf_get_history", "nf_profile_get", "nf_profile_reset", "nf_time_schur_apply", "nf_time_device_copy", "nf_progress", "nf_set_progress_callback", "nf_local_matrices",
     "nf_set_option", "nf_mem_info", "nf_dev_alloc", "nf_dev_free", "nf_memcpy_h2d", "nf_memcpy_d2h", "nf_synchronize", "nf_stream",
 ]
@@ -31,6 +31,13 @@ class SubcritResult(C.Structure):
     _fields_ = [("M", C.c_double), ("k_source", C.c_double), ("ratio", C.c_double), ("phi_int", C.c_double),
                 ("phi_int_nofission", C.c_double), ("production", C.c_double), ("source", C.c_double),
                 ("n_outer", C.c_int), ("n_outer_nofission", C.c_int), ("cg_total", C.c_int), ("converged", C.c_int)]
+
+    def as_dict(self): return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class ZoomResult(C.Structure):
+    _fields_ = [("source", C.c_double), ("phi_int", C.c_double), ("production", C.c_double),
+                ("n_outer", C.c_int), ("cg_total", C.c_int), ("converged", C.c_int), ("n_cells", C.c_long)]
 
     def as_dict(self): return {name: getattr(self, name) for name, _ in self._fields_}
 
@@ -75,6 +82,11 @@ def load():
     L.nf_get_phi_adj.argtypes = [vp, dp]
     L.nf_project_flux.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.nf_project_power.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, dp, vp]
+    L.nf_refine.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.nf_zoom_source.argtypes = [vp, vp, C.c_int, C.c_double]
+    L.nf_get_source.argtypes = [vp, dp]
+    L.nf_set_phi_adj.argtypes = [vp, dp]
+    L.nf_zoom_resolved.argtypes = [vp, C.POINTER(KeffOpts), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(vp), C.POINTER(ZoomResult)]
     L.nf_set_phi.argtypes = [vp, dp]
     L.nf_get_phi.argtypes = [vp, dp]
     L.nf_get_J.argtypes = [vp, dp]
@@ -234,10 +246,8 @@ class HipSolver:
         self._chk(self.L.nf_solve_subcritical(self.h, C.byref(o), C.byref(r)))
         return r.as_dict()
 
-    def coarsen(self, rx, ry=1, rz=1):
-        """built coarse twin (HipSolver over the merged mesh, block-mean XS); close() it when done"""
-        h = C.c_void_p()
-        self._chk(self.L.nf_coarsen(self.h, rx, ry, rz, C.byref(h)))
+    def _adopt(self, h):
+        """a HipSolver over a handle the library derived from this one (nf_coarsen, nf_refine, nf_zoom_resolved)"""
         c = HipSolver.__new__(HipSolver)
         c.L, c.h = self.L, h
         c.tol, c.solver_type, c.solver_pushed = self.tol, self.solver_type, self.solver_pushed
@@ -245,6 +255,40 @@ class HipSolver:
             setattr(c, key, c.L.nf_info(c.h, key.encode()))
         c.n_loc = c.L.nf_info(c.h, b"n_loc")
         return c
+
+    def coarsen(self, rx, ry=1, rz=1):
+        """built coarse twin (HipSolver over the merged mesh, block-mean XS); close() it when done"""
+        h = C.c_void_p()
+        self._chk(self.L.nf_coarsen(self.h, rx, ry, rz, C.byref(h)))
+        return self._adopt(h)
+
+    def refine(self, rx, ry=1, rz=1):
+        """built refined twin (nf_refine: same orders and boundary types, every cell cut into rx x ry x rz parts with its parent's
+        cross sections); close() it when done"""
+        h = C.c_void_p()
+        self._chk(self.L.nf_refine(self.h, rx, ry, rz, C.byref(h)))
+        return self._adopt(h)
+
+    def zoom_source(self, fine, keff, adjoint=False):
+        """nf_zoom_source: the frozen fission source of this handle's flux (adjoint: its adjoint flux) as the load vector of `fine`"""
+        self._chk(self.L.nf_zoom_source(self.h, fine.h, int(adjoint), float(keff)))
+
+    def get_source(self):
+        """the load vector (upload_source / zoom_source), (ng, n_phi) in the host DOF layout"""
+        out = np.empty(self.ng * self.n_phi); self._chk(self.L.nf_get_source(self.h, _dp(out))); return out.reshape(self.ng, self.n_phi)
+
+    def set_phi_adj(self, phi_adj):
+        a = np.ascontiguousarray(phi_adj, dtype=np.float64).ravel(); assert a.size == self.ng * self.n_phi
+        self._chk(self.L.nf_set_phi_adj(self.h, _dp(a)))
+
+    def zoom_resolved(self, refine, keff, adjoint=False, use_diag=False, use_cmfd=False):
+        """nf_zoom_resolved with the tolerances / linear solver of this object: (fine HipSolver holding the zoomed flux, result dict);
+        refine = (rx[, ry[, rz]]) taken literally.  close() the fine solver when done"""
+        r = tuple(int(f) for f in refine) + (1,) * (3 - len(refine))
+        o = self.opts(use_diag=use_diag, use_cmfd=use_cmfd)
+        h, res = C.c_void_p(), ZoomResult()
+        self._chk(self.L.nf_zoom_resolved(self.h, C.byref(o), r[0], r[1], r[2], int(adjoint), float(keff), C.byref(h), C.byref(res)))
+        return self._adopt(h), res.as_dict()
 
     def prolong_from(self, coarse): self._chk(self.L.nf_prolong(coarse.h, self.h))
 

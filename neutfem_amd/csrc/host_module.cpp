@@ -3,9 +3,8 @@
 //
 // The class keeps what the reference keeps on the host -- cross-section arrays, flux, tolerances,
 // BC map, warm-start flags -- and hands the hot path (BuildMatrices, SolveKeff, SolveCoarse,
-// build_diagonal_cache, SolveSubcritical, project_flux, project_power) to the HIP library.  There is NO CPU fallback: without a
-// HIP device those methods raise RuntimeError.  Methods the reference binds but that lie outside the accelerated
-// path (zoom_resolved, never defined; reflectors) raise RuntimeError with that explanation.
+// build_diagonal_cache, SolveSubcritical, project_flux, project_power, zoom_resolved) to the HIP library.  There is NO CPU fallback:
+// without a HIP device those methods raise RuntimeError.  The reflector methods the reference binds are accepted and ignored.
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -296,9 +295,50 @@ public:
         f.close();
         Log(VerbosityLevel::NORMAL, "  Export termine: " + std::to_string(nc) + " cellules");
     }
-    [[noreturn]] void oos(const char *what, const char *ref) const
+    // ZoomResolved (include/NeutFEM.hpp:311, src/wrapper.cpp:1045-1065; declared, never defined there): the problem solved again on the
+    // mesh refined by `refine` (clamped as project() clamps it) with the fission source of the coarse solution frozen.  k and the field
+    // come from the host mirrors: last_keff_ / Phi_ after a SolveKeff, last_keff_adj_ / PhiAdj_ after a SolveAdjoint.  Returns the fine
+    // cell means (DOF 0), (ng, [NZ,] [NY,] NX) like project_flux; changes neither mirror.
+    py::array_t<double> ZoomResolved(const std::vector<int> &refine, bool adjoint)
     {
-        throw std::runtime_error(std::string(what) + " is outside the accelerated hot path of neutfem_amd (reference: " + ref + ")");
+        // without a built device handle there is nothing to re-solve on, and there is no CPU fallback
+        if (!h_) throw std::runtime_error("zoom_resolved: the re-solve is outside the accelerated hot path of neutfem_amd until the device "
+                                          "handle is built (there is no CPU fallback): call BuildMatrices() first");
+        if (adjoint ? !has_valid_adjoint_ : !has_valid_keff_)
+            throw std::runtime_error(std::string("zoom_resolved: call ") + (adjoint ? "SolveAdjoint()" : "SolveKeff()") + " first (the zoom freezes the fission source of a solved "
+                                     + (adjoint ? "adjoint " : "") + "flux and its k-eff)");
+        const int rx = refine.size() > 0 ? std::max(refine[0], 1) : 1;
+        const int ry = refine.size() > 1 && dim_ >= 2 ? std::max(refine[1], 1) : 1;
+        const int rz = refine.size() > 2 && dim_ >= 3 ? std::max(refine[2], 1) : 1;
+        Log(VerbosityLevel::NORMAL, "\n=== ZOOM RESOLU (SOURCES FIGEES) ===");
+        chk(adjoint ? nf_set_phi_adj(h_, PhiAdj_.data()) : nf_set_phi(h_, Phi_.data()));
+        nf_keff_opts o = make_opts(false, {}, false);
+        struct Fine { nf_handle h = nullptr; ~Fine() { if (h) nf_destroy(h); } } fine;   // destroyed on every path out
+        nf_zoom_result r{};
+        chk(nf_zoom_resolved(h_, &o, rx, ry, rz, adjoint ? 1 : 0, adjoint ? last_keff_adj_ : last_keff_, &fine.h, &r));
+        const long NX = (long)nx_ * rx, NY = (long)ny_ * ry, NZ = (long)nz_ * rz, NE = NX * NY * NZ;
+        std::vector<double> phi((size_t)ng_ * NE * nloc_);
+        chk(nf_get_phi(fine.h, phi.data()));
+        std::vector<py::ssize_t> shape; shape.push_back(ng_);
+        if (dim_ >= 3) shape.push_back(NZ);
+        if (dim_ >= 2) shape.push_back(NY);
+        shape.push_back(NX);
+        py::array_t<double> out(shape);
+        double *po = out.mutable_data();
+        for (long i = 0; i < (long)ng_ * NE; ++i) po[i] = phi[(size_t)i * nloc_];    // host layout [g][E*nloc + p]: DOF 0 = the cell mean
+        zoom_ = r; has_zoom_ = true;
+        if (verb_ >= VerbosityLevel::NORMAL)
+            std::cout << "  Zoom " << rx << " x " << ry << " x " << rz << " : " << r.n_outer << " iterations, " << r.cg_total << " iterations CG, "
+                      << r.n_cells << " cellules" << (r.converged ? "" : " (non converge)") << std::endl;
+        return out;
+    }
+    py::dict GetZoomInfo() const
+    {
+        if (!has_zoom_) throw std::runtime_error("get_zoom_info: call zoom_resolved() first");
+        py::dict d;
+        d["source"] = zoom_.source; d["phi_int"] = zoom_.phi_int; d["production"] = zoom_.production; d["n_outer"] = zoom_.n_outer;
+        d["cg_total"] = zoom_.cg_total; d["converged"] = zoom_.converged; d["n_cells"] = zoom_.n_cells;
+        return d;
     }
 
     // ---- numpy views (src/NeutFEM.cpp:2626-2730) ---------------------------------------------------
@@ -375,6 +415,7 @@ private:
     VerbosityLevel verb_ = VerbosityLevel::NORMAL; double cmfd_omega_ = 1.0;
     bool has_valid_keff_ = false, has_valid_adjoint_ = false;
     nf_subcrit_result subcrit_{}; bool has_subcrit_ = false;     // the last SolveSubcritical (get_subcritical_info)
+    nf_zoom_result zoom_{}; bool has_zoom_ = false;               // the last zoom_resolved (get_zoom_info)
 };
 
 PYBIND11_MODULE(_neutfem_eigen, m)
@@ -453,5 +494,8 @@ PYBIND11_MODULE(_neutfem_eigen, m)
              "mean flux of every sub-cell of the mesh refined by [rx, ry, rz]: (ng, [NZ,] [NY,] NX) like get_flux()")
         .def("project_power", &NeutFEM::ProjectPower, py::arg("refine"), py::arg("adjoint") = false,
              "sum over groups of get_KSF() times project_flux: ([NZ,] [NY,] NX), no normalisation")
-        .def("zoom_resolved", [](NeutFEM &s, const std::vector<int> &, bool) { s.oos("zoom_resolved", "bound at src/wrapper.cpp:1045, never defined"); }, py::arg("refine"), py::arg("adjoint") = false);
+        .def("zoom_resolved", &NeutFEM::ZoomResolved, py::arg("refine"), py::arg("adjoint") = false,
+             "re-solve on the mesh refined by [rx, ry, rz] with the coarse fission source frozen: fine cell means (ng, [NZ,] [NY,] NX)")
+        .def("get_zoom_info", &NeutFEM::GetZoomInfo,
+             "extension: the last zoom_resolved's nf_zoom_result as a dict (source, phi_int, production, n_outer, cg_total, converged, n_cells)");
 }

@@ -3272,11 +3272,81 @@ int nf_upload_source(nf_handle S, const double *src)
     return NF_OK;
 }
 
-// Two phases of the host-driven loop of solve_keff_impl: phase 0 with the fission term off (the flux without fission, phi0), phase 1
-// from phi0 with fission at scale 1 (no eigenvalue).  Each outer: tf from the previous outer's flux, Gauss-Seidel group sweep with the
-// same group solver SolveKeff picks (inner_plan / diagonal S^-1), then one streaming pass (k_subcrit_reduce) for Phi, P, the norms and
-// the copy raw -> phi.  No normalisation, no acceleration.  Phase 0 starts from phi = 0, so the result does not depend on the flux the
-// handle held before.
+// One outer of the fixed-source iteration on every slab of the team: tf from the previous outer's flux, Gauss-Seidel group sweep with the
+// group solver of `ip` (or the diagonal S^-1), then one streaming pass (k_subcrit_reduce) for Phi, P, the norms and the copy raw -> phi;
+// hout = { Phi, P, ||phi||^2, ||dphi||^2 }.  fscale scales the fission term (0: off, 1: on, no eigenvalue).  transposed: the scatter
+// blocks Ms[g' <- g] in place of Ms[g <- g'] (adjoint zoom), the sweep stays in forward order as nf_solve_adjoint has it.
+static int source_outer(nf_team *T, const InnerPlan &ip, int use_diag, double fscale, bool transposed, int *cg_total, double *hout)
+{
+    const int ns = (int)T->slabs.size();
+    const int ng = T->slabs[0]->ng;
+    ScatterArgs sa; sa.ng = ng;
+    std::vector<int> gN(ns), gT(ns);
+    std::vector<const double *> rhs(ns); std::vector<double *> sol(ns);
+    for (int i = 0; i < ns; ++i) { gN[i] = grid_for(T->slabs[i]->nphi); gT[i] = grid_for(T->slabs[i]->nphi * ng); }
+    for (int i = 0; i < ns; ++i) {                                // tf = sum_g Mf_g phi_g of the previous outer (finite, also when scaled by 0)
+        nf_solver *S = T->slabs[i];
+        hipLaunchKernelGGL(k_fission, dim3(gN[i]), dim3(256), 0, T->stream, S->d_Mf, S->d_phi, ng, S->nphi, S->d_tf, T->d_partials + i * T->slab_cap, (const double *)nullptr, 0L);
+    }
+    for (int g = 0; g < ng; ++g) {
+        for (int i = 0; i < ns; ++i) {
+            nf_solver *S = T->slabs[i]; const long N = S->N, NP = S->nphi;
+            for (int gp = 0; gp < 64; ++gp) sa.M[gp] = gp < ng ? S->d_Ms[transposed ? gp * ng + g : g * ng + gp] : nullptr;
+            double *dst = use_diag ? S->d_raw + g * NP : S->d_rhs;
+            const bool cgi = !use_diag && !ip.dense;              // CG start rides in the same launch (cg_solve(..., inited))
+            hipLaunchKernelGGL(k_group_rhs<true>, dim3(gN[i]), dim3(256), 0, T->stream, sa, g, S->d_Chi + g * N, S->d_tf, fscale, S->d_raw, S->d_phi,
+                               use_diag ? S->d_Sinv + g * N : (const double *)nullptr, dst, NP, N,
+                               cgi ? S->d_raw + g * NP : (double *)nullptr, cgi ? S->d_r : (double *)nullptr, cgi ? S->d_p : (double *)nullptr,
+                               cgi ? T->d_partials + i * T->slab_cap : (double *)nullptr, (const double *)(S->d_qsrc + g * NP));
+            rhs[i] = S->d_rhs; sol[i] = S->d_raw + g * NP;
+        }
+        int its = 0; double cres = 0.0;
+        if (use_diag) { }
+        else if (ip.dense) { dense_solve(T, g, rhs[0], sol[0]); its = 1; }
+        else {
+            NFCHK(cg_solve(T, g, rhs, sol, ip.cg_tol, ip.cg_max, &its, &cres, true));
+            if (ip.direct && !(cres <= 1e-14)) ++T->standin_unconverged;
+        }
+        *cg_total += its;
+    }
+    for (int i = 0; i < ns; ++i) {
+        nf_solver *S = T->slabs[i];
+        hipLaunchKernelGGL(k_subcrit_reduce, dim3(gT[i]), dim3(256), 0, T->stream, S->d_Mf, (const double *)S->d_raw, S->d_phi, S->d_hx, S->d_hy, S->d_hz,
+                           S->nx, S->ny, S->N, S->nphi, S->nphi * ng, T->d_partials + i * T->slab_cap, T->partial_stride);
+    }
+    NFCHK(team_finalize(T, FIN_SUM, gT, 4, T->d_out, 0.0, 0));
+    return readback(T, nullptr, nullptr, T->d_out, hout, 4);
+}
+
+// The fixed-source iteration with the fission term off, from phi = 0 (so the result does not depend on the flux the handles held before):
+// per group S_g phi_g = q_g + scatter_g(phi) with q = d_qsrc.  Stops when |Phi_n - Phi_{n-1}| / Phi_n < tol_keff and
+// ||phi_n - phi_{n-1}|| / ||phi_n|| < tol_flux (*conv = true) or after max_outer outers.  Shared by nf_solve_subcritical (its phase 0)
+// and nf_zoom_resolved (the whole solve; transposed = adjoint).  *n outers are added to *outers and published through nf_progress.
+static int nofission_phase(nf_team *T, const nf_keff_opts *o, const InnerPlan &ip, int use_diag, bool transposed, const char *who,
+                           double *phi_int, double *production, int *n, int *cg_total, bool *conv, long *outers)
+{
+    for (auto *S : T->slabs) HIPCHK(hipMemsetAsync(S->d_phi, 0, (size_t)S->nphi * S->ng * sizeof(double), T->stream));
+    double q_old = 0.0, hout[4] = { 0, 0, 0, 0 };
+    *conv = false; *n = 0;
+    for (int it = 0; it < o->max_outer; ++it) {
+        NFCHK(source_outer(T, ip, use_diag, 0.0, transposed, cg_total, hout));
+        const double Phi = hout[0], P = hout[1], nsq = hout[2], dsq = hout[3];
+        const double dq = Phi - q_old, dphi = std::sqrt(dsq / nsq);
+        const double rel = dq == 0.0 ? 0.0 : std::fabs(dq) / std::fabs(Phi);
+        *n = it + 1; ++*outers;
+        __atomic_store_n(&T->outers_done, *outers, __ATOMIC_RELEASE);
+        if (!std::isfinite(Phi) || !std::isfinite(P) || !std::isfinite(dphi))
+            return fail(NF_ERR_NUMERIC, "%s: the source iteration without fission produced non-finite sums (outer %d: Phi=%g P=%g)", who, it, Phi, P);
+        *phi_int = Phi; *production = P;
+        q_old = Phi;
+        if (rel < o->tol_keff && dphi < o->tol_flux) { *conv = true; break; }
+    }
+    return NF_OK;
+}
+
+// Two phases of the host-driven loop of solve_keff_impl: phase 0 with the fission term off (the flux without fission, phi0:
+// nofission_phase), phase 1 from phi0 with fission at scale 1 (no eigenvalue).  Each outer is one source_outer with the same group
+// solver SolveKeff picks (inner_plan / diagonal S^-1).  No normalisation, no acceleration.
 static int solve_subcritical_impl(nf_team *T, const nf_keff_opts *o, nf_subcrit_result *res)
 {
     if (T->nproc > 1) return fail(NF_ERR_UNSUPPORTED, "nf_solve_subcritical: multi-rank teams are not supported (one process, undivided mesh or linked slabs)");
@@ -3298,85 +3368,44 @@ static int solve_subcritical_impl(nf_team *T, const nf_keff_opts *o, nf_subcrit_
     T->last_direct = ip.dense ? 1 : ip.direct ? 2 : 0;
     if (ip.dense) NFCHK(dense_prepare(T));
     T->last_path = 0; T->profile = false;
-    ScatterArgs sa; sa.ng = ng;
-    std::vector<int> gN(ns), gT(ns);
-    std::vector<const double *> rhs(ns); std::vector<double *> sol(ns);
-    for (int i = 0; i < ns; ++i) { gN[i] = grid_for(T->slabs[i]->nphi); gT[i] = grid_for(T->slabs[i]->nphi * ng); }
+    std::vector<int> gT(ns);
+    for (int i = 0; i < ns; ++i) gT[i] = grid_for(T->slabs[i]->nphi * ng);
     nf_subcrit_result r; memset(&r, 0, sizeof r);
     r.source = src_total; r.ratio = 0.0;
     double hout[4] = { 0, 0, 0, 0 };
     long outers = 0;
-    for (auto *S : T->slabs) HIPCHK(hipMemsetAsync(S->d_phi, 0, (size_t)S->nphi * ng * sizeof(double), T->stream));   // phase 0 starts from phi = 0
-    int rc = NF_OK;
     bool conv[2] = { false, false };
-    for (int phase = 0; phase < 2 && rc == NF_OK; ++phase) {
-        const double fscale = phase;                              // 0: flux without fission, 1: with fission
-        double q_old = 0.0, dq_old = 0.0;                         // Phi (phase 0) / P (phase 1) and its change at the previous outer
+    int rc = nofission_phase(T, o, ip, use_diag, false, "nf_solve_subcritical", &r.phi_int, &r.production, &r.n_outer_nofission, &r.cg_total, &conv[0], &outers);
+    r.phi_int_nofission = r.phi_int;
+    if (rc == NF_OK) {
+        double q_old = r.production, dq_old = 0.0;                // P of phi0 and its change at the previous outer
         int streak = 0, n = 0;
-        if (phase == 1) q_old = r.production;                     // P of phi0
         for (int it = 0; it < o->max_outer; ++it) {
-            for (int i = 0; i < ns; ++i) {                        // tf = sum_g Mf_g phi_g of the previous outer (finite, also when scaled by 0)
-                nf_solver *S = T->slabs[i];
-                hipLaunchKernelGGL(k_fission, dim3(gN[i]), dim3(256), 0, T->stream, S->d_Mf, S->d_phi, ng, S->nphi, S->d_tf, T->d_partials + i * T->slab_cap, (const double *)nullptr, 0L);
-            }
-            for (int g = 0; g < ng && rc == NF_OK; ++g) {
-                for (int i = 0; i < ns; ++i) {
-                    nf_solver *S = T->slabs[i]; const long N = S->N, NP = S->nphi;
-                    for (int gp = 0; gp < 64; ++gp) sa.M[gp] = gp < ng ? S->d_Ms[g * ng + gp] : nullptr;
-                    double *dst = use_diag ? S->d_raw + g * NP : S->d_rhs;
-                    const bool cgi = !use_diag && !ip.dense;      // CG start rides in the same launch (cg_solve(..., inited))
-                    hipLaunchKernelGGL(k_group_rhs<true>, dim3(gN[i]), dim3(256), 0, T->stream, sa, g, S->d_Chi + g * N, S->d_tf, fscale, S->d_raw, S->d_phi,
-                                       use_diag ? S->d_Sinv + g * N : (const double *)nullptr, dst, NP, N,
-                                       cgi ? S->d_raw + g * NP : (double *)nullptr, cgi ? S->d_r : (double *)nullptr, cgi ? S->d_p : (double *)nullptr,
-                                       cgi ? T->d_partials + i * T->slab_cap : (double *)nullptr, (const double *)(S->d_qsrc + g * NP));
-                    rhs[i] = S->d_rhs; sol[i] = S->d_raw + g * NP;
-                }
-                int its = 0; double cres = 0.0;
-                if (use_diag) { }
-                else if (ip.dense) { dense_solve(T, g, rhs[0], sol[0]); its = 1; }
-                else {
-                    rc = cg_solve(T, g, rhs, sol, ip.cg_tol, ip.cg_max, &its, &cres, true);
-                    if (rc == NF_OK && ip.direct && !(cres <= 1e-14)) ++T->standin_unconverged;
-                }
-                r.cg_total += its;
-            }
-            if (rc != NF_OK) break;
-            for (int i = 0; i < ns; ++i) {
-                nf_solver *S = T->slabs[i];
-                hipLaunchKernelGGL(k_subcrit_reduce, dim3(gT[i]), dim3(256), 0, T->stream, S->d_Mf, (const double *)S->d_raw, S->d_phi, S->d_hx, S->d_hy, S->d_hz,
-                                   S->nx, S->ny, S->N, S->nphi, S->nphi * ng, T->d_partials + i * T->slab_cap, T->partial_stride);
-            }
-            if ((rc = team_finalize(T, FIN_SUM, gT, 4, T->d_out, 0.0, 0)) != NF_OK) break;
-            if ((rc = readback(T, nullptr, nullptr, T->d_out, hout, 4)) != NF_OK) break;
+            if ((rc = source_outer(T, ip, use_diag, 1.0, false, &r.cg_total, hout)) != NF_OK) break;
             const double Phi = hout[0], P = hout[1], nsq = hout[2], dsq = hout[3];
-            const double qn = phase ? P : Phi;
-            const double dq = qn - q_old, dphi = std::sqrt(dsq / nsq);
-            const double rel = dq == 0.0 ? 0.0 : std::fabs(dq) / std::fabs(qn);
+            const double dq = P - q_old, dphi = std::sqrt(dsq / nsq);
+            const double rel = dq == 0.0 ? 0.0 : std::fabs(dq) / std::fabs(P);
             n = it + 1; ++outers;
             __atomic_store_n(&T->outers_done, outers, __ATOMIC_RELEASE);
             if (!std::isfinite(Phi) || !std::isfinite(P) || !std::isfinite(dphi)) {
-                rc = fail(NF_ERR_NUMERIC, "nf_solve_subcritical: the system is not subcritical: the source iteration diverged (phase %d, outer %d: Phi=%g P=%g; contraction estimate %g)",
-                          phase, it, Phi, P, r.ratio);
+                rc = fail(NF_ERR_NUMERIC, "nf_solve_subcritical: the system is not subcritical: the source iteration diverged (outer %d: Phi=%g P=%g; contraction estimate %g)",
+                          it, Phi, P, r.ratio);
                 break;
             }
-            if (phase == 1) {
-                // contraction of the iteration dP_n / dP_{n-1}; below 1e-6 P the differences are inner-solve noise
-                const bool meaningful = dq != 0.0 && std::fabs(dq) >= 1e-6 * std::fabs(qn) && dq_old != 0.0;
-                if (meaningful) r.ratio = dq / dq_old;
-                streak = (it >= 4 && meaningful && dq / dq_old >= 1.0) ? streak + 1 : 0;
-                if (streak >= 5) {
-                    rc = fail(NF_ERR_NUMERIC, "nf_solve_subcritical: the system is not subcritical: the source iteration does not contract "
-                              "(estimate %.6f >= 1 over 5 consecutive outers, outer %d; k-eff of the core is about that value or above)", r.ratio, it);
-                    break;
-                }
+            // contraction of the iteration dP_n / dP_{n-1}; below 1e-6 P the differences are inner-solve noise
+            const bool meaningful = dq != 0.0 && std::fabs(dq) >= 1e-6 * std::fabs(P) && dq_old != 0.0;
+            if (meaningful) r.ratio = dq / dq_old;
+            streak = (it >= 4 && meaningful && dq / dq_old >= 1.0) ? streak + 1 : 0;
+            if (streak >= 5) {
+                rc = fail(NF_ERR_NUMERIC, "nf_solve_subcritical: the system is not subcritical: the source iteration does not contract "
+                          "(estimate %.6f >= 1 over 5 consecutive outers, outer %d; k-eff of the core is about that value or above)", r.ratio, it);
+                break;
             }
             r.phi_int = Phi; r.production = P;
-            dq_old = dq; q_old = qn;
-            if (rel < o->tol_keff && dphi < o->tol_flux) { conv[phase] = true; break; }
+            dq_old = dq; q_old = P;
+            if (rel < o->tol_keff && dphi < o->tol_flux) { conv[1] = true; break; }
         }
-        if (rc != NF_OK) break;
-        if (phase == 0) { r.n_outer_nofission = n; r.phi_int_nofission = r.phi_int; }
-        else r.n_outer = n;
+        r.n_outer = n;
     }
     HIPCHK(hipStreamSynchronize(T->stream));
     HIPCHK(hipGetLastError());
@@ -3580,6 +3609,23 @@ static void launch_project_d(int m, bool power, int grid, hipStream_t st, const 
     else launch_project_dm<DIM, 2>(power, grid, st, phi, ksf, out, S, rx, ry, rz, NX, NY, crows, npairs, vec, step_rows, step_pairs);
 }
 
+// launch shape of the kernels that walk the mesh refined by (rx, ry, rz) (k_project_refined, k_zoom_source): a thread owns one pair of
+// fine columns of one coarse row, all its ry rz fine rows; 32 waves per CU, then grid-stride by step_rows rows + step_pairs pairs
+struct RefinePlan { int NX, NY, crows, npairs, grid, step_rows, step_pairs; long NE; };
+static int refine_plan(const nf_solver *S, int rx, int ry, int rz, const char *who, RefinePlan *P)
+{
+    const long NXl = (long)S->nx * rx, rowsl = (long)S->ny * ry * S->nz * rz;
+    if (NXl >= INT_MAX || rowsl > INT_MAX / 2) return fail(NF_ERR_ARG, "%s: refined mesh of %ld x %ld cells is too large", who, NXl, rowsl);
+    P->NX = (int)NXl; P->NY = S->ny * ry; P->crows = S->ny * S->nz; P->npairs = (P->NX + 1) / 2;
+    P->NE = (long)S->N * rx * ry * rz;
+    int ncu = 256; (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, S->device);
+    const long items = (long)P->crows * P->npairs;
+    P->grid = (int)std::max<long>(1, std::min<long>((items + 255) / 256, 8L * ncu));
+    const long stride = (long)P->grid * 256;
+    P->step_rows = (int)(stride / P->npairs); P->step_pairs = (int)(stride % P->npairs);
+    return NF_OK;
+}
+
 // flux (ksf == nullptr): group g >= 0, or every group (g = -1) into consecutive N R blocks; power: sum over the groups weighted by ksf
 static int project_impl(nf_solver *S, int rx, int ry, int rz, int adjoint, int g, const double *ksf_host, double *out, const char *who)
 {
@@ -3590,10 +3636,10 @@ static int project_impl(nf_solver *S, int rx, int ry, int rz, int adjoint, int g
     if ((S->dim < 2 && ry > 1) || (S->dim < 3 && rz > 1))
         return fail(NF_ERR_ARG, "%s: refine factor > 1 on an axis the %dD mesh does not have (%d, %d, %d)", who, S->dim, rx, ry, rz);
     if (!S->built) return fail(NF_ERR_STATE, "%s: call nf_build first", who);
-    const long NXl = (long)S->nx * rx, rowsl = (long)S->ny * ry * S->nz * rz;
-    if (NXl >= INT_MAX || rowsl > INT_MAX / 2) return fail(NF_ERR_ARG, "%s: refined mesh of %ld x %ld cells is too large", who, NXl, rowsl);
-    const int NX = (int)NXl, NY = S->ny * ry, crows = S->ny * S->nz, npairs = (NX + 1) / 2;
-    const long NE = (long)S->N * rx * ry * rz;
+    RefinePlan P;
+    NFCHK(refine_plan(S, rx, ry, rz, who, &P));
+    const int NX = P.NX, NY = P.NY, crows = P.crows, npairs = P.npairs;
+    const long NE = P.NE;
     const long N = S->N;
     if (power)
         for (int gg = 0; gg < S->ng; ++gg)
@@ -3614,11 +3660,7 @@ static int project_impl(nf_solver *S, int rx, int ry, int rz, int adjoint, int g
         NFCHK(dalloc(&ksf.p, (size_t)N * S->ng));
         HIPCHK(hipMemcpyAsync(ksf.p, ksf_host, (size_t)N * S->ng * sizeof(double), hipMemcpyHostToDevice, st));
     }
-    int ncu = 256; (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, S->device);
-    const long items = (long)crows * npairs;                     // a thread: one x pair of one coarse row, all its ry rz fine rows
-    const int grid = (int)std::max<long>(1, std::min<long>((items + 255) / 256, 8L * ncu));   // 32 waves per CU, then grid-stride
-    const long stride = (long)grid * 256;
-    const int step_rows = (int)(stride / npairs), step_pairs = (int)(stride % npairs);
+    const int grid = P.grid, step_rows = P.step_rows, step_pairs = P.step_pairs;
     const int vec = (NX % 2 == 0 && ((uintptr_t)out & 15) == 0) ? 1 : 0;
     const int g0 = power ? 0 : (g < 0 ? 0 : g), g1 = power ? 1 : (g < 0 ? S->ng : g + 1);
     for (int gg = g0; gg < g1; ++gg) {
@@ -3641,6 +3683,178 @@ int nf_project_power(nf_handle S, int rx, int ry, int rz, int adjoint, const dou
 {
     if (!ksf_host) return fail(NF_ERR_ARG, "nf_project_power: bad arguments");
     return project_impl(S, rx, ry, rz, adjoint, 0, ksf_host, out_dev, "nf_project_power");
+}
+
+// ---- zoom_resolved (NeutFEM::ZoomResolved, include/NeutFEM.hpp:311, bound src/wrapper.cpp:1045-1065; declared, never defined there):
+// the problem is solved again on the mesh refined by (rx, ry, rz) with the fission source of the coarse solution frozen
+
+// a per-cell array of `nfields` fields [f*N + e] replicated onto the refined mesh [f*NE + E] (injection of the cross sections): the P0
+// instantiation of k_project_refined copies DOF 0 of the parent into every sub-cell
+static void refine_replicate(const nf_solver *S, const RefinePlan &P, int rx, int ry, int rz, const double *src, double *dst, int nfields)
+{
+    hipStream_t st = S->team->stream;
+    const int vec = P.NX % 2 == 0 ? 1 : 0;                        // hipMalloc'ed arrays, NE even: every field starts 16-byte aligned
+    for (int f = 0; f < nfields; ++f) {
+        const double *a = src + (size_t)f * S->N; double *o = dst + (size_t)f * P.NE;
+        if (S->dim == 1) launch_project_dm<1, 0>(false, P.grid, st, a, nullptr, o, S, rx, ry, rz, P.NX, P.NY, P.crows, P.npairs, vec, P.step_rows, P.step_pairs);
+        else if (S->dim == 2) launch_project_dm<2, 0>(false, P.grid, st, a, nullptr, o, S, rx, ry, rz, P.NX, P.NY, P.crows, P.npairs, vec, P.step_rows, P.step_pairs);
+        else launch_project_dm<3, 0>(false, P.grid, st, a, nullptr, o, S, rx, ry, rz, P.NX, P.NY, P.crows, P.npairs, vec, P.step_rows, P.step_pairs);
+    }
+}
+static int refine_args(const nf_solver *S, int rx, int ry, int rz, const char *who)
+{
+    if (rx < 1 || ry < 1 || rz < 1) return fail(NF_ERR_ARG, "%s: refine factors must be >= 1 (got %d, %d, %d)", who, rx, ry, rz);
+    if ((S->dim < 2 && ry > 1) || (S->dim < 3 && rz > 1))
+        return fail(NF_ERR_ARG, "%s: refine factor > 1 on an axis the %dD mesh does not have (%d, %d, %d)", who, S->dim, rx, ry, rz);
+    return NF_OK;
+}
+static int refine_impl(nf_solver *S, int rx, int ry, int rz, nf_handle *out)
+{
+    RefinePlan P;
+    NFCHK(refine_plan(S, rx, ry, rz, "nf_refine", &P));
+    if ((long)S->nz * rz >= INT_MAX || (long)S->ny * ry >= INT_MAX) return fail(NF_ERR_ARG, "nf_refine: refined mesh is too large");
+    const int dim = S->dim, ng = S->ng;
+    auto cut = [](const std::vector<double> &b, int n, int r, bool active) {   // every coarse break is kept exactly
+        std::vector<double> f(active ? (size_t)n * r + 1 : 1, active ? 0.0 : b[0]);
+        if (!active) return f;
+        for (int i = 0; i < n; ++i) for (int a = 0; a < r; ++a) f[(size_t)i * r + a] = b[i] + a * (b[i + 1] - b[i]) / r;
+        f[(size_t)n * r] = b[n];
+        return f;
+    };
+    const std::vector<double> xf = cut(S->xb, S->nx, rx, true), yf = cut(S->yb, S->ny, ry, dim >= 2), zf = cut(S->zb, S->nz, rz, dim >= 3);
+    nf_handle F = nullptr;
+    NFCHK(create_impl(S->k, S->m, ng, (int)xf.size(), xf.data(), (int)yf.size(), yf.data(), (int)zf.size(), zf.data(), 0, 0, S->device, &F));
+    *out = F;
+    if (F->dim != dim || F->N != P.NE) return fail(NF_ERR_ARG, "nf_refine: the refined mesh lost a dimension");
+    for (int a = 0; a < 8; ++a) if (S->bc_set[a]) nf_set_bc(F, a, S->bc_type[a]);
+    const size_t NN = (size_t)P.NE * ng;
+    NFCHK(dalloc(&F->d_D, NN)); NFCHK(dalloc(&F->d_SigR, NN)); NFCHK(dalloc(&F->d_NSF, NN)); NFCHK(dalloc(&F->d_Chi, NN));
+    refine_replicate(S, P, rx, ry, rz, S->d_D, F->d_D, ng); refine_replicate(S, P, rx, ry, rz, S->d_SigR, F->d_SigR, ng);
+    refine_replicate(S, P, rx, ry, rz, S->d_NSF, F->d_NSF, ng); refine_replicate(S, P, rx, ry, rz, S->d_Chi, F->d_Chi, ng);
+    for (int b = 0; b < ng * ng; ++b)
+        if (S->d_SigS[b]) { NFCHK(dalloc(&F->d_SigS[b], (size_t)P.NE)); refine_replicate(S, P, rx, ry, rz, S->d_SigS[b], F->d_SigS[b], 1); }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(S->team->stream));                // the copies ran on the parent's stream; nf_build uses the twin's
+    F->xs_uploaded = true;
+    return nf_build(F);
+}
+int nf_refine(nf_handle S, int rx, int ry, int rz, nf_handle *fine)
+{
+    if (!S || !fine) return fail(NF_ERR_ARG, "nf_refine: bad arguments");
+    *fine = nullptr;
+    NFCHK(refine_args(S, rx, ry, rz, "nf_refine"));
+    if (!team_is_single(S->team)) return fail(NF_ERR_UNSUPPORTED, "nf_refine works on an undivided mesh (not on the slabs of a team)");
+    if (!S->xs_uploaded) return fail(NF_ERR_STATE, "nf_refine: call nf_upload_xs first");
+    HIPCHK(hipSetDevice(S->device));
+    (void)hipGetLastError();
+    int rc = refine_impl(S, rx, ry, rz, fine);
+    if (rc != NF_OK && *fine) { std::string keep = g_err; nf_destroy(*fine); *fine = nullptr; g_err = keep; (void)hipGetLastError(); }
+    return rc;
+}
+
+template <int DIM>
+static void launch_zoom_d(int m, const RefinePlan &P, hipStream_t st, const double *phi, const double *win, const double *wout, double *q,
+                          const nf_solver *C, double inv_k, int rx, int ry, int rz, int *flags, double *part)
+{
+    const int vec = P.NX % 2 == 0 ? 1 : 0;
+#define NF_ZOOM(M) hipLaunchKernelGGL((k_zoom_source<DIM, M>), dim3(P.grid), dim3(256), 0, st, phi, win, wout, q, C->d_hx, C->d_hy, C->d_hz, inv_k, \
+                                      C->nx, C->ny, C->N, C->nphi, C->ng, rx, ry, rz, P.NX, P.NY, P.NE, P.crows, P.npairs, vec, P.step_rows, P.step_pairs, flags, part)
+    if (m == 0) NF_ZOOM(0); else if (m == 1) NF_ZOOM(1); else NF_ZOOM(2);
+#undef NF_ZOOM
+}
+int nf_zoom_source(nf_handle C, nf_handle F, int adjoint, double keff)
+{
+    if (!C || !F || C == F) return fail(NF_ERR_ARG, "nf_zoom_source: bad arguments");
+    if (!team_is_single(C->team) || !team_is_single(F->team)) return fail(NF_ERR_UNSUPPORTED, "nf_zoom_source works on undivided meshes (not on the slabs of a team)");
+    if (C->device != F->device || C->ng != F->ng || C->dim != F->dim || C->k != F->k || C->m != F->m ||
+        F->nx % C->nx || F->ny % C->ny || F->nz % C->nz)
+        return fail(NF_ERR_ARG, "nf_zoom_source: %d x %d x %d (RT%d-P%d, %d groups) is not a refinement of %d x %d x %d (RT%d-P%d, %d groups) on the same device",
+                    F->nx, F->ny, F->nz, F->k, F->m, F->ng, C->nx, C->ny, C->nz, C->k, C->m, C->ng);
+    if (!std::isfinite(keff) || !(keff > 0.0)) return fail(NF_ERR_ARG, "nf_zoom_source: keff must be finite and positive (got %g)", keff);
+    if (!C->built || !F->built) return fail(NF_ERR_STATE, "nf_zoom_source: call nf_build first (both handles)");
+    if (adjoint && !C->d_phi_adj) return fail(NF_ERR_STATE, "nf_zoom_source: the coarse handle has no adjoint flux (nf_solve_adjoint or nf_set_phi_adj first)");
+    const int rx = F->nx / C->nx, ry = F->ny / C->ny, rz = F->nz / C->nz;
+    RefinePlan P;
+    NFCHK(refine_plan(C, rx, ry, rz, "nf_zoom_source", &P));
+    HIPCHK(hipSetDevice(C->device));
+    (void)hipGetLastError();
+    nf_team *T = F->team;
+    hipStream_t st = T->stream;
+    HIPCHK(hipStreamSynchronize(C->team->stream));                // the coarse flux is final
+    if (!F->d_qsrc) NFCHK(dalloc(&F->d_qsrc, (size_t)F->nphi * F->ng));
+    F->src_total = 0.0; F->src_any = false;
+    DevTmp<int> flags; NFCHK(dalloc(&flags.p, 1));
+    DevTmp<double> part; NFCHK(dalloc(&part.p, (size_t)P.grid + 1));   // the blocks' shares of the source total, then the total
+    HIPCHK(hipMemsetAsync(flags.p, 0, sizeof(int), st));
+    const double *phi = adjoint ? C->d_phi_adj : C->d_phi;
+    const double *win = adjoint ? C->d_Chi : C->d_NSF, *wout = adjoint ? C->d_NSF : C->d_Chi;
+    if (C->dim == 1) launch_zoom_d<1>(C->m, P, st, phi, win, wout, F->d_qsrc, C, 1.0 / keff, rx, ry, rz, flags.p, part.p);
+    else if (C->dim == 2) launch_zoom_d<2>(C->m, P, st, phi, win, wout, F->d_qsrc, C, 1.0 / keff, rx, ry, rz, flags.p, part.p);
+    else launch_zoom_d<3>(C->m, P, st, phi, win, wout, F->d_qsrc, C, 1.0 / keff, rx, ry, rz, flags.p, part.p);
+    hipLaunchKernelGGL(k_zoom_total, dim3(1), dim3(256), 0, st, (const double *)part.p, P.grid, part.p + P.grid);
+    int hf = 0; double tot = 0.0;
+    HIPCHK(hipMemcpyAsync(&hf, flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&tot, part.p + P.grid, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    if (hf & 2) return fail(NF_ERR_NUMERIC, "nf_zoom_source: the frozen source is not finite (non-finite %s flux or keff = %g too small)", adjoint ? "adjoint" : "coarse", keff);
+    if (!(hf & 1)) return fail(NF_ERR_ARG, "nf_zoom_source: the frozen source is zero on every cell (a zero %s flux, or no cell with both nuSigf and chi)", adjoint ? "adjoint" : "coarse");
+    F->src_total = tot; F->src_any = true;
+    return NF_OK;
+}
+int nf_get_source(nf_handle S, double *q_host)
+{
+    if (!S || !q_host) return fail(NF_ERR_ARG, "nf_get_source: bad arguments");
+    if (!S->d_qsrc) return fail(NF_ERR_STATE, "nf_get_source: the handle has no source (nf_upload_source or nf_zoom_source first)");
+    return phi_transfer(S, q_host, false, S->d_qsrc);
+}
+int nf_set_phi_adj(nf_handle S, const double *phi_adj_host)
+{
+    if (!S || !phi_adj_host) return fail(NF_ERR_ARG, "nf_set_phi_adj: bad arguments");
+    HIPCHK(hipSetDevice(S->device));
+    if (!S->d_phi_adj) NFCHK(dalloc(&S->d_phi_adj, (size_t)S->nphi * S->ng));
+    return phi_transfer(S, const_cast<double *>(phi_adj_host), true, S->d_phi_adj);
+}
+
+static int zoom_solve(nf_handle C, nf_handle F, const nf_keff_opts *o, int adjoint, double keff, nf_zoom_result *res)
+{
+    NFCHK(nf_zoom_source(C, F, adjoint, keff));
+    nf_team *T = F->team;
+    NFCHK(team_prepare(T));
+    const InnerPlan ip = inner_plan(T, o);
+    T->last_direct = ip.dense ? 1 : ip.direct ? 2 : 0;
+    if (ip.dense) NFCHK(dense_prepare(T));
+    T->last_path = 0; T->profile = false;
+    nf_zoom_result r; memset(&r, 0, sizeof r);
+    r.source = F->src_total; r.n_cells = F->N;
+    bool conv = false; long outers = 0;
+    __atomic_store_n(&T->outers_done, 0L, __ATOMIC_RELEASE);
+    NFCHK(nofission_phase(T, o, ip, 0, adjoint != 0, "nf_zoom_resolved", &r.phi_int, &r.production, &r.n_outer, &r.cg_total, &conv, &outers));
+    HIPCHK(hipStreamSynchronize(T->stream));
+    HIPCHK(hipGetLastError());
+    F->raw_valid = true; F->raw_is_diag = false; F->jz_valid = false;
+    r.converged = conv ? 1 : 0;
+    if (res) *res = r;
+    return NF_OK;
+}
+int nf_zoom_resolved(nf_handle S, const nf_keff_opts *o, int rx, int ry, int rz, int adjoint, double keff, nf_handle *fine, nf_zoom_result *res)
+{
+    if (!S || !o || !fine) return fail(NF_ERR_ARG, "nf_zoom_resolved: bad arguments");
+    *fine = nullptr;
+    if (o->use_coarse_init || o->use_cmfd || o->use_diagonal_solver)
+        return fail(NF_ERR_ARG, "nf_zoom_resolved: coarse start, CMFD and the diagonal solver do not apply to the zoom's fixed-source iteration");
+    if (o->max_outer < 1) return fail(NF_ERR_ARG, "nf_zoom_resolved: max_outer must be at least 1");
+    if (!std::isfinite(keff) || !(keff > 0.0)) return fail(NF_ERR_ARG, "nf_zoom_resolved: keff must be finite and positive (got %g)", keff);
+    NFCHK(refine_args(S, rx, ry, rz, "nf_zoom_resolved"));
+    if (!team_is_single(S->team)) return fail(NF_ERR_UNSUPPORTED, "nf_zoom_resolved works on an undivided mesh (slab teams and multi-rank teams are not supported)");
+    if (!S->built) return fail(NF_ERR_STATE, "nf_zoom_resolved: call nf_build first");
+    if (adjoint && !S->d_phi_adj) return fail(NF_ERR_STATE, "nf_zoom_resolved: no adjoint flux (nf_solve_adjoint or nf_set_phi_adj first)");
+    nf_handle F = nullptr;
+    NFCHK(nf_refine(S, rx, ry, rz, &F));
+    const int rc = zoom_solve(S, F, o, adjoint, keff, res);
+    if (rc != NF_OK) { std::string keep = g_err; nf_destroy(F); g_err = keep; (void)hipGetLastError(); return rc; }
+    *fine = F;
+    return NF_OK;
 }
 
 int nf_get_history(nf_handle S, double *k, double *dk, double *dphi, int *cg, int cap)

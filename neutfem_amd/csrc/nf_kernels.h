@@ -3761,6 +3761,151 @@ __global__ __launch_bounds__(256) void k_project_refined(const double *__restric
     }
 }
 
+// ---- zoom: the coarse solution's fission source as the load vector of the refined mesh (nf_zoom_source) -------------------
+// Legendre coefficients of a polynomial of degree M on sub-interval s of r equal parts of [-1, 1]: c'_i' = sum_i T[i'][i] c_i, T upper
+// triangular, row-major (M+1) x (M+1).  With [al, be] as in sub_means, mu = (al + be) / 2, w = 1 / r:
+// T = [[1, mu, (3 mu^2 + w^2 - 1) / 2], [0, w, 3 mu w], [0, 0, w^2]]; row 0 is sub_means itself.  r = 1 gives the identity exactly.
+template <int M>
+__device__ __forceinline__ void sub_restrict(int s, int r, double *T)
+{
+    sub_means<M>(s, r, T);
+    if (M >= 1) {
+        const double w = 1.0 / (double)r, mu = T[1];
+        T[(M + 1) + 0] = 0.0; T[(M + 1) + 1] = w;
+        if (M >= 2) { T[(M + 1) + 2] = 3.0 * mu * w; T[2 * (M + 1) + 0] = 0.0; T[2 * (M + 1) + 1] = 0.0; T[2 * (M + 1) + 2] = w * w; }
+    }
+}
+// t[p] = sum_g w[g*N + e] c_g[p*N + e] over the ng groups (c = all groups' coefficients, stride nphi): one load per coefficient and weight
+template <int NLOC>
+__device__ __forceinline__ void zoom_contract(const double *__restrict__ c, const double *__restrict__ w, long N, long nphi, int ng, long e, double *t)
+{
+#pragma unroll
+    for (int p = 0; p < NLOC; ++p) t[p] = 0.0;
+    for (int g = 0; g < ng; ++g) {
+        const double wg = w[(long)g * N + e];
+        const double *cg = c + (long)g * nphi + e;
+#pragma unroll
+        for (int p = 0; p < NLOC; ++p) t[p] += wg * cg[(long)p * N];
+    }
+}
+// the x restriction in place: t[i' + n1 q] = sum_{i >= i'} T[i'][i] t[i + n1 q] (ascending i' only reads entries not yet overwritten)
+template <int DIM, int M>
+__device__ __forceinline__ void zoom_restrict_x(double *t, const double *T)
+{
+    constexpr int n1 = M + 1, nq = (DIM >= 2 ? n1 : 1) * (DIM == 3 ? n1 : 1);
+#pragma unroll
+    for (int q = 0; q < nq; ++q)
+#pragma unroll
+        for (int ip = 0; ip <= M; ++ip) {
+            double v = T[ip * n1 + ip] * t[ip + n1 * q];
+#pragma unroll
+            for (int i = ip + 1; i <= M; ++i) v += T[ip * n1 + i] * t[i + n1 * q];
+            t[ip + n1 * q] = v;
+        }
+}
+// moment (i', j', k') of the fine cell from the x-restricted values u: sum_{j >= j', k >= k'} Ty[j'][j] Tz[k'][k] u[i' + n1 j + n1^2 k]
+template <int DIM, int M>
+__device__ __forceinline__ double zoom_restrict_yz(const double *u, const double *Ty, const double *Tz, int ip, int jp, int kp)
+{
+    constexpr int n1 = M + 1;
+    if (DIM == 1) return u[ip];
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k <= (DIM == 3 ? M : 0); ++k)
+#pragma unroll
+        for (int j = 0; j <= M; ++j)
+            if (j >= jp && k >= kp) v += (Ty[jp * n1 + j] * (DIM == 3 ? Tz[kp * n1 + k] : 1.0)) * u[ip + n1 * j + n1 * n1 * k];
+    return v;
+}
+// q_g[E, p'] = wout_g(e) inv_k |E| prod_t 1 / (2 i'_t + 1) * (restriction to E of sum_g' win_g'(e) c_g'(e))[p'] for every fine cell E of the
+// mesh refined by (rx, ry, rz), every group g and every moment p': the fine mesh's fission-matrix entry nuSigf |E| C-hat_p'p' (k_cell_coef,
+// without its 1e-14 drop) times the restricted coefficient, summed over the source groups and scaled by chi_g / k.  Direct: win = nuSigf,
+// wout = chi; adjoint: win = chi, wout = nuSigf (both [g*N + e] on the COARSE mesh: a fine cell has its parent's cross sections).
+// Shaped like k_project_refined: a thread owns a pair of fine columns (X, X+1) of one coarse row.  It contracts the ng groups' coefficients
+// with the in-weights once per coarse cell (one load per coefficient and pair), restricts over xi once, and then, group by group, walks the
+// ry rz fine rows applying the y / z restrictions -- the arithmetic of a row is redone per group (at most 9 FMAs per value), the loads are
+// not.  Output in the fine handle's device layout q[g*nphiF + p'*NF + E], E = (Z NY + Y) NX + X: one 16-byte store per pair when `vec`
+// (NX even: every offset g*nphiF + p'*NF + row*NX + X0 is then even), else 8-byte stores.  Fine indices are 64-bit.
+// flags: bit 0 is raised once a non-zero value was written, bit 1 for a non-finite one (read first: after the first waves nobody writes).
+// part[block] = the block's share of sum_g sum_E q_g[E, dof 0], the source total of nf_zoom_result (k_zoom_total adds the shares up).
+template <int DIM, int M>
+__global__ __launch_bounds__(256) void k_zoom_source(const double *__restrict__ phi, const double *__restrict__ win, const double *__restrict__ wout,
+                                                     double *__restrict__ q, const double *__restrict__ hx, const double *__restrict__ hy,
+                                                     const double *__restrict__ hz, double inv_k, int nx, int ny, long N, long nphi, int ng,
+                                                     int rx, int ry, int rz, int NX, int NY, long NF, int crows, int npairs, int vec,
+                                                     int step_rows, int step_pairs, int *__restrict__ flags, double *__restrict__ part)
+{
+    __shared__ double sred[4];
+    double tot = 0.0;
+    constexpr int n1 = M + 1, nj = DIM >= 2 ? n1 : 1, nk = DIM == 3 ? n1 : 1, nloc = n1 * nj * nk;
+    const long nphiF = (long)nloc * NF;
+    const long i0 = (long)blockIdx.x * 256 + threadIdx.x;
+    int row = (int)(i0 / npairs), pr = (int)(i0 - (long)row * npairs);
+    int seen = 0;
+    while (row < crows) {
+        const int iz = row / ny, iy = row - iz * ny;
+        const int X0 = 2 * pr;
+        const bool two = X0 + 1 < NX;
+        const int ix0 = X0 / rx, ix1 = two ? (X0 + 1) / rx : ix0;
+        const long e0 = (long)row * nx + ix0, e1 = (long)row * nx + ix1;
+        double u0[nloc], u1[nloc], T[n1 * n1];
+        zoom_contract<nloc>(phi, win, N, nphi, ng, e0, u0);
+        if (e1 != e0) zoom_contract<nloc>(phi, win, N, nphi, ng, e1, u1);
+        else {
+#pragma unroll
+            for (int p = 0; p < nloc; ++p) u1[p] = u0[p];
+        }
+        sub_restrict<M>(X0 - ix0 * rx, rx, T); zoom_restrict_x<DIM, M>(u0, T);
+        sub_restrict<M>((two ? X0 + 1 : X0) - ix1 * rx, rx, T); zoom_restrict_x<DIM, M>(u1, T);
+        const double vyz = (DIM >= 2 ? hy[iy] / (double)ry : 1.0) * (DIM == 3 ? hz[iz] / (double)rz : 1.0);   // |E| = |e| / (rx ry rz)
+        const double V0 = hx[ix0] / (double)rx * vyz, V1 = hx[ix1] / (double)rx * vyz;
+        for (int g = 0; g < ng; ++g) {
+            const double s0 = wout[(long)g * N + e0] * inv_k * V0, s1 = wout[(long)g * N + e1] * inv_k * V1;
+            double *qg = q + (long)g * nphiF;
+            for (int cz = 0; cz < rz; ++cz) {
+                double Tz[n1 * n1];
+                sub_restrict<M>(cz, rz, Tz);
+                for (int b = 0; b < ry; ++b) {
+                    double Ty[n1 * n1];
+                    sub_restrict<M>(b, ry, Ty);
+                    const long o = ((long)(iz * rz + cz) * NY + (iy * ry + b)) * NX + X0;
+#pragma unroll
+                    for (int kp = 0; kp < nk; ++kp)
+#pragma unroll
+                        for (int jp = 0; jp < nj; ++jp)
+#pragma unroll
+                            for (int ip = 0; ip < n1; ++ip) {
+                                const int p = ip + n1 * jp + n1 * nj * kp;
+                                const double ch = 1.0 / (double)((2 * ip + 1) * (2 * jp + 1) * (2 * kp + 1));   // C-hat_pp detJ' = |E| ch
+                                const double v0 = (s0 * ch) * zoom_restrict_yz<DIM, M>(u0, Ty, Tz, ip, jp, kp);
+                                const double v1 = (s1 * ch) * zoom_restrict_yz<DIM, M>(u1, Ty, Tz, ip, jp, kp);
+                                double *dst = qg + (long)p * NF + o;
+                                if (vec) { nf_d2 v = { v0, v1 }; __builtin_nontemporal_store(v, reinterpret_cast<nf_d2 *>(dst)); }
+                                else { __builtin_nontemporal_store(v0, dst); if (two) __builtin_nontemporal_store(v1, dst + 1); }
+                                if (p == 0) tot += two ? v0 + v1 : v0;
+                                if (v0 != 0.0 || (two && v1 != 0.0)) seen |= 1;
+                                if (!isfinite(v0) || (two && !isfinite(v1))) seen |= 2;
+                            }
+                }
+            }
+        }
+        pr += step_pairs; row += step_rows;                       // advance by the grid's stride: step_rows rows + step_pairs pairs
+        if (pr >= npairs) { pr -= npairs; ++row; }
+    }
+    if (seen & ~__hip_atomic_load(flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicOr(flags, seen);
+    tot = block_sum(tot, sred);
+    if (threadIdx.x == 0) part[blockIdx.x] = tot;
+}
+// one block: *out = the sum of the n block shares k_zoom_source left in part (a fixed order: the total is reproducible)
+__global__ __launch_bounds__(256) void k_zoom_total(const double *__restrict__ part, int n, double *__restrict__ out)
+{
+    __shared__ double sred[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) s += part[i];
+    s = block_sum(s, sred);
+    if (threadIdx.x == 0) *out = s;
+}
+
 // fill with a deterministic pseudo-random pattern (profiling helper)
 __global__ void k_fill_pattern(double *__restrict__ v, long n)
 {
