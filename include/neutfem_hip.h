@@ -271,8 +271,11 @@ int nf_timers(nf_handle h, char *json_buf, size_t len);
  * "SEG" (cells per segment), "NCH" (chunks per lane / block), "TX" (columns per block; lanes per line for x), "NSEG" (segments per
  * line; NS of the chunked kernel), "grid" [x, y, z], "block", "nt" (streaming loads), "p2" (two load phases), "zw" (the pass's share
  * of x.y in the z.w form), "xcd_order" (the XCD-contiguous tile order is requested) and "xcd_permutes" (requested, and the tile count
- * is a multiple of 8 beyond 8: tiles really move) and "fold" (accumulation pass of a slab: it forms the separator values
- * itself).  Built from the predicates the launch functions themselves call; launches nothing
+ * is a multiple of 8 beyond 8: tiles really move), "fold" (accumulation pass of a slab: it forms the separator values
+ * itself) and "dict" (the pass reads its line factors from the table of distinct lines, see "line_dict"); at the top level "line_dict":
+ * {"x", "y", "z"}, the distinct lines of the largest group per direction (0: no table in use).  Built from the predicates the launch functions
+ * themselves call.  The one thing it does besides reporting: where the next apply would first build the tables of distinct lines
+ * (once per build), the report builds them, since whether a direction verifies is part of the plan; otherwise it launches nothing
  * and changes no state.  A slab team must have been prepared (one team apply or solve since its options last changed). */
 int nf_apply_plan(nf_handle h, int in_cg, char *json_buf, size_t len);
 /* times `reps` back-to-back Schur applies on group g (random x) with HIP events; average ms per apply */
@@ -330,9 +333,20 @@ int nf_time_device_copy(nf_handle h, size_t bytes, int reps, double *gbps);
  *   (weights measured once per BuildMatrices with the chain solve itself: nz launches per group, 16 B per cell and group of HBM) instead of
  *   solving the chain -- a streaming kernel with the deferred CG update in the same sweep (nf_info "endpoint_weights");
  *   "xchg_comm" (default 0): the interface planes travel on a communicator of their own (created collectively before the next solve;
- *   nf_info "xchg_comm") instead of sharing the one the all-reduces use.
+ *   nf_info "xchg_comm") instead of sharing the one the all-reduces use;
+ *   "line_dict" (default -1): undivided RT0-P0 meshes in the streaming regime ("nt_min_cells") whose lines repeat -- cores built from a few
+ *   assembly types on a uniform mesh -- read L, 1/d (and the C diagonal, x pass) from a table of the DISTINCT lines of a direction instead of
+ *   streaming them per cell.  The lines are identified on the stored factors (128-bit fingerprints, grouped on the host) and every line is
+ *   compared bit for bit with its representative before a table is used, so the results are bit-identical to the streaming path; the tables
+ *   are built by the first apply, solve or nf_apply_plan after a build.  -1 = the directions that gain at the benchmark size,
+ *   0 = off, 1 = every direction whose lines qualify (every group verified, at least fourfold repeats, table within the cap);
+ *   "line_dict_dirs" (default 7): bit 0 = x, bit 1 = y, bit 2 = z; "line_dict_max_bytes" (default 524288): cap of one group's table of one
+ *   direction; "line_dict_fp_bits" (default 128, tests only): low bits of the fingerprint that are kept, so that collisions can be made.
+ *   Changing any option drops the tables; nf_apply_plan reports "dict" per pass and "line_dict": {"x", "y", "z"} = distinct lines of the
+ *   largest group (0: the direction streams).
  * nf_info keys beyond the mesh sizes: "last_path" (0 host-driven outer loop, 1 diagonal device loop, 2 resident kernel, 3 one-XCD kernel),
- * "last_direct" (0 CG as configured, 1 dense S^-1, 2 CG to 1e-14 standing in). */
+ * "last_direct" (0 CG as configured, 1 dense S^-1, 2 CG to 1e-14 standing in), "line_dict_rejected" (mask of the directions whose table the
+ * bit-for-bit verification refused: a fingerprint collision, not an error), "line_dict_bytes" (device memory of the tables and line ids). */
 int nf_set_option(nf_handle h, const char *key, long value);
 
 /* raw device-memory helpers so callers without torch can drive the *_dev entry points */

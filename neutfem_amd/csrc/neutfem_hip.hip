@@ -13,6 +13,7 @@
 #include "../../include/neutfem_hip.h"
 #include "nf_kernels.h"
 #include "nf_assembly.h"
+#include "nf_line_groups.h"
 
 #include <dlfcn.h>
 #include <unistd.h>
@@ -177,6 +178,11 @@ struct nf_team {
     int opt_split_dot = 1;                                // big undivided RT0-P0 meshes: per-pass shares of p.q (team_schur_apply)
     int opt_s_long_dirs = 3;                              // directions that may take the chunked kernel: bit 0 = y, bit 1 = z
     int s_long_min_y = 255;                               // y lines longer than this take the chunked kernel (s_long_min: z lines)
+    // tables of distinct lines (LineDict in nf_kernels.h) for the streaming passes of undivided RT0-P0 meshes.  line_dict: -1 = the directions
+    // that measurably gain (LINE_DICT_AUTO_DIRS), 0 = off, 1 = every direction whose lines qualify; line_dict_dirs: bit 0 = x, 1 = y, 2 = z;
+    // line_dict_max_bytes: per group and direction (three 512 KiB tables stay below half of one XCD's 4 MiB L2; not swept -- the benchmark's
+    // tables are 12 - 110 KB); line_dict_fp_bits < 128 truncates the fingerprints so that tests can make them collide
+    int opt_line_dict = -1, line_dict_dirs = 7, line_dict_fp_bits = 128; long line_dict_max_bytes = 512L * 1024;
     int opt_s_long = -1, s_long_min = 256;                // chunked long-line pass (k_schur_c): -1 auto (lines longer than s_long_min), 0 off, 1 always
     size_t lds_limit = 160 * 1024;                        // dynamic LDS a block may ask for (hipDeviceAttributeMaxSharedMemoryPerBlock at team creation)
     // fused-direction CG (two launches per iteration) up to this many cells.  Measured crossover against the four-launch lean path after
@@ -221,6 +227,11 @@ struct nf_solver {
     const double **d_Ms_tab = nullptr;                   // the same ng*ng pointers on the device (resident kernel)
     double *d_L[3] = {nullptr, nullptr, nullptr}, *d_DR[3] = {nullptr, nullptr, nullptr}, *d_D0[3] = {nullptr, nullptr, nullptr};
     long nlines[3] = {0, 0, 0};
+    // tables of distinct lines, built on first need (line_dict_prepare) and dropped with the factors: ids [ng][nlines] and, per group, the
+    // rows of L, 1/d (and the C diagonal, x) at ld_off[d][g] doubles into d_ltab[d]; ld_rows: distinct lines per group
+    bool ld_tried = false, ld_use[3] = {false, false, false}; int ld_rejected = 0, ld_pitch[3] = {0, 0, 0};
+    int *d_lid[3] = {nullptr, nullptr, nullptr}; double *d_ltab[3] = {nullptr, nullptr, nullptr};
+    std::vector<long> ld_off[3]; std::vector<int> ld_rows[3]; size_t ld_bytes = 0;
     double *d_Sinv = nullptr;
     double *d_Sdense = nullptr; bool dense_valid = false;   // explicit-S branch: S^-1 per group, ng * nphi^2, column-major
     // slab interfaces (partition method for the z lines), all per z-line
@@ -273,6 +284,14 @@ template <class T> static int dalloc(T **p, size_t n)
 template <class T> static void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
 // scratch device buffer of one function call: released on every return path
 template <class T> struct DevTmp { T *p = nullptr; ~DevTmp() { if (p) (void)hipFree(p); } DevTmp() = default; DevTmp(const DevTmp &) = delete; DevTmp &operator=(const DevTmp &) = delete; };
+
+// the tables of distinct lines go with the factors they were taken from (nf_build, nf_upload_xs, nf_set_bc) and with the options that shaped them
+static void line_dict_drop(nf_solver *S)
+{
+    if (S->team && S->team->stream && (S->d_lid[0] || S->d_lid[1] || S->d_lid[2])) (void)hipStreamSynchronize(S->team->stream);
+    for (int d = 0; d < 3; ++d) { dfree(S->d_lid[d]); dfree(S->d_ltab[d]); S->ld_use[d] = false; S->ld_pitch[d] = 0; S->ld_off[d].clear(); S->ld_rows[d].clear(); }
+    S->ld_tried = false; S->ld_rejected = 0; S->ld_bytes = 0;
+}
 
 static const char *SLOT_NAMES[5] = { "schur_x", "schur_y", "schur_z", "schur_apply", "schur_z1" };
 
@@ -542,7 +561,7 @@ int nf_destroy(nf_handle S)
     for (auto &p : S->d_Ms) dfree(p);
     dfree(S->d_Ms_tab);
     dfree(S->d_Cd); dfree(S->d_Mf); dfree(S->d_Mchi); dfree(S->d_phi_adj); dfree(S->d_Sinv); dfree(S->d_Sdense);
-    for (int d = 0; d < 3; ++d) { dfree(S->d_L[d]); dfree(S->d_DR[d]); dfree(S->d_D0[d]); }
+    for (int d = 0; d < 3; ++d) { dfree(S->d_L[d]); dfree(S->d_DR[d]); dfree(S->d_D0[d]); dfree(S->d_lid[d]); dfree(S->d_ltab[d]); }
     dfree(S->d_alo); dfree(S->d_ahi); dfree(S->d_hlo); dfree(S->d_hhi); dfree(S->d_gfl); dfree(S->d_sinv_lo); dfree(S->d_sinv_hi);
     dfree(S->d_clo); dfree(S->d_chi); dfree(S->d_rlo); dfree(S->d_rhi); dfree(S->d_ulo); dfree(S->d_uhi);
     dfree(S->d_Wlo); dfree(S->d_Whi);
@@ -676,6 +695,7 @@ long nf_info(nf_handle S, const char *key)
     K("n_phi", S->nphi); K("n_J", S->nJ); K("n_loc", S->nloc); K("rt_order", S->k); K("p_order", S->m); K("last_outer", T->last_outer);
     K("last_cg_total", T->last_cg_total); K("coarse_outer", T->coarse_outer); K("device", S->device);
     K("last_path", T->last_path); K("last_resident_serial", T->last_resident_serial); K("last_direct", T->last_direct); K("direct_standin_unconverged", T->standin_unconverged); K("n_local_slabs", T->slabs.size()); K("n_ranks", T->nproc); K("rank", T->rank); K("vec_reduce", T->last_vec_reduce); K("cg_reductions", T->last_cg_reductions); K("endpoint_weights", T->last_endpoint_w); K("xchg_comm", T->comm_x ? 1 : 0); K("last_xcd", T->last_xcd); K("xcd_solves", T->xcd_solves); K("xcd_refused", T->xcd_refused);
+    K("line_dict_rejected", S->ld_rejected); K("line_dict_bytes", S->ld_bytes);
 #undef K
     return -1;
 }
@@ -684,7 +704,7 @@ int nf_set_bc(nf_handle S, int attr, int bc_type)
 {
     if (!S || attr < 0 || attr >= 8) return fail(NF_ERR_ARG, "nf_set_bc: bad attribute %d", attr);
     S->bc_set[attr] = 1; S->bc_type[attr] = bc_type; S->dense_valid = false;
-    coarse_cache_drop(S->team);
+    coarse_cache_drop(S->team); line_dict_drop(S);
     return NF_OK;
 }
 
@@ -697,7 +717,7 @@ int nf_upload_xs(nf_handle S, const double *D, const double *SigR, const double 
     // the device copies are overwritten from here on: whatever was built from the old ones is stale until the next nf_build,
     // also when this upload is refused below (a refused upload leaves the handle un-built, never half-valid)
     S->xs_uploaded = false; S->built = false; S->diag_valid = false; S->cmfd_init = false; S->cmfd_iface = false; S->dense_valid = false;
-    coarse_cache_drop(S->team);
+    coarse_cache_drop(S->team); line_dict_drop(S);
     NFCHK(dalloc(&S->d_D, NN)); NFCHK(dalloc(&S->d_SigR, NN)); NFCHK(dalloc(&S->d_NSF, NN)); NFCHK(dalloc(&S->d_Chi, NN));
     HIPCHK(hipMemcpyAsync(S->d_D, D, B, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(S->d_SigR, SigR, B, hipMemcpyHostToDevice, st));
@@ -742,7 +762,7 @@ int nf_build(nf_handle S)
     if (!S) return fail(NF_ERR_ARG, "nf_build: null handle");
     if (!S->xs_uploaded) return fail(NF_ERR_STATE, "nf_build: call nf_upload_xs first");
     HIPCHK(hipSetDevice(S->device));
-    coarse_cache_drop(S->team);
+    coarse_cache_drop(S->team); line_dict_drop(S);
     hipStream_t st = S->team->stream;
     const int ng = S->ng; const long N = S->N, NP = S->nphi; const size_t NN = (size_t)N * ng;
     NFCHK(dalloc(&S->d_Cd, (size_t)NP * ng)); NFCHK(dalloc(&S->d_Mf, (size_t)NP * ng)); NFCHK(dalloc(&S->d_Mchi, (size_t)NP * ng));
@@ -963,8 +983,10 @@ struct SegPlan { int rc = NF_OK, SEG = 0, NSEG = 0, TX = 0, nparts = 0; dim3 gri
 static SegPlan seg_plan(const nf_solver *S, int d, int zmode);
 static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const Geom &G, int last, double *partials, const PassCg &P, int *nparts, int zmode);
 // build-time: S_red = own half + neighbour's half for every separator; checks that separators decouple
+static int line_dict_prepare(nf_team *T);
 static int team_prepare(nf_team *T)
 {
+    NFCHK(line_dict_prepare(T));                                 // once per build too, but on its own flag: options may drop the tables alone
     if (T->linked_ready) return NF_OK;
     if (T->opt_xchg_comm && T->nproc > 1 && T->comm && !T->comm_x) {
         // collective: rank 0 draws a second unique id and hands it to the others through the first communicator (an all-reduce(sum) of
@@ -1191,6 +1213,21 @@ static bool lds_opt_in(const void *fn, size_t lds)
 // The choices of the launch functions below as small predicates: the launches and nf_apply_plan (the read-only report) both call them.
 static bool nt_regime(const nf_solver *S) { return S->team->opt_nt_loads && S->N > S->team->nt_min_cells; }   // streaming loads beyond the caches (per slab on teams)
 static bool x_nt(const nf_solver *S, int NB) { return NB == 0 && S->nx % 2 == 0 && nt_regime(S); }
+// Table of distinct lines instead of the line's own factors (LineDict): where the streaming instantiation is taken and line_dict_prepare
+// found the direction's lines repeating and verified them.  x_dict / c_dict / s_dict sit next to x_nt / c_nt / s_nt in the launches.
+static bool dict_dir(const nf_solver *S, int d) { return S->ld_use[d]; }
+static const int X_DICT_MAX_NCH = 16;                            // 32 chunks per lane (x lines beyond 2048 cells) spill with or without a table: not instantiated
+static bool x_dict(const nf_solver *S, int NB, int NCH, bool nt) { return nt && NB == 0 && NCH <= X_DICT_MAX_NCH && dict_dir(S, 0); }
+struct DictArgs { bool on = false; const double *L = nullptr, *DR = nullptr, *C = nullptr; LineDict ld; };   // what a table launch passes in place of L, DR (and Cd)
+static DictArgs dict_args(const nf_solver *S, int d, int g, bool on)
+{
+    DictArgs A; A.on = on;
+    if (!on) return A;
+    const long rows = (long)S->ld_rows[d][g] * S->ld_pitch[d];
+    A.L = S->d_ltab[d] + S->ld_off[d][g]; A.DR = A.L + rows; A.C = d == 0 ? A.DR + rows : nullptr;
+    A.ld.id = S->d_lid[d] + (long)g * S->nlines[d]; A.ld.pitch = S->ld_pitch[d];
+    return A;
+}
 // inside CG: two load phases (schur_x_task, P2): 116 instead of 140 VGPRs at four chunks per lane, four waves per SIMD instead of
 // three -- and no faster (512^3: 1548 vs 1529 us, 256^3: 185.9 vs 186.3; profiles/r03_e_ab_cg.txt).  Kept as an option, off.
 // Instantiated next to the streaming loads only.
@@ -1222,7 +1259,15 @@ static void launch_x_t(const nf_solver *S, int g, const ModeArgs &ma, const Geom
     const dim3 gr(grid, (unsigned)mt.n);                          // all transverse modes in one launch
     const bool nt = x_nt(S, NB), p2 = x_p2(S, NB, NCH, fz.p != nullptr, nt);
     const int first_x = first | (x_xcd(S, nt) ? 2 : 0);
-    if (p2) hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB, NB == 0, NB == 0 && (NCH >= 2)>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2,
+    const DictArgs da = dict_args(S, 0, g, x_dict(S, NB, NCH, nt));
+    if (da.on) {                                                  // the line's row of the table instead of its own L, 1/d and C diagonal
+        ModeArgs mad = ma; mad.Cd[0] = da.C;
+        if (p2) hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB, NB == 0, NB == 0 && (NCH >= 2), NB == 0 && NCH <= X_DICT_MAX_NCH>), gr, dim3(256), 0, st, mad, mt, G, da.L, da.DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2,
+                                   first_x, last, partials, P.cg, fz, P.lean, da.ld);
+        else hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB, NB == 0, false, NB == 0 && NCH <= X_DICT_MAX_NCH>), gr, dim3(256), 0, st, mad, mt, G, da.L, da.DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2,
+                                first_x, last, partials, P.cg, fz, P.lean, da.ld);
+    }
+    else if (p2) hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB, NB == 0, NB == 0 && (NCH >= 2)>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2,
                                first_x, last, partials, P.cg, fz, P.lean);
     else if (nt) hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB, NB == 0>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2,
                                first_x, last, partials, P.cg, fz, P.lean);
@@ -1290,6 +1335,7 @@ static dim3 c_grid(const nf_solver *S, int d, const ChunkPlan &cp) { return dim3
 static unsigned c_block(const ChunkPlan &cp) { return (unsigned)((cp.TX * cp.NS + 63) / 64 * 64); }   // whole wavefronts, as in seg_plan
 static const int C_SEG = 8, C_NCH = 2;                           // k_schur_c: segments of 8 cells, two chunks per block (chunk_plan's NS counts 16 cells)
 static bool c_nt(const nf_solver *S) { return nt_regime(S); }
+static bool c_dict(const nf_solver *S, int d, bool nt) { return nt && dict_dir(S, d); }
 static int c_xcd(const nf_solver *S, int d, bool nt) { const nf_team *T = S->team; return T->opt_xcd >= 0 ? (T->opt_xcd >> (d - 1)) & 1 : (d == 1 && nt); }
 // one-chunk kernel (k_schur_s).  XCD-contiguous tile order: bit 0 = y passes, bit 1 = z passes; -1 (default) = the y passes of meshes in the streaming
 // regime -- the 8 x tiles of a row set then run on one XCD back to back (256^3: y 133 -> 123 us, 501 -> 493 us per CG iteration;
@@ -1303,6 +1349,7 @@ static int s_xcd(const nf_solver *S, int d, int zmode)
 }
 // undivided meshes beyond the caches (the classic path's sizes): the variant with streaming loads (SF doubles as that flag for !SLAB)
 static bool s_nt(const nf_solver *S, int zmode, int SEG) { return zmode == 0 && S->nb == 0 && SEG == 8 && nt_regime(S); }
+static bool s_dict(const nf_solver *S, int d, int zmode, int SEG) { return s_nt(S, zmode, SEG) && dict_dir(S, d); }
 static bool s_nts(const nf_solver *S, int zmode, int SEG) { return zmode != 0 && zmode != 3 && S->nb == 0 && SEG == 8 && nt_regime(S); }   // the same for the z passes of a slab
 static bool s_zw(const nf_solver *S, int zmode, bool zw_dot, bool want_dot) { return zmode == 0 && S->nb == 0 && zw_dot && want_dot; }     // z.w form of the pass's share of x.y
 static bool s_fold(const nf_team *T, int zmode) { return zmode == 2 && T->sep_sweeps == 0 && T->opt_sepfold; }   // thick slabs: the accumulation pass forms the separator values itself
@@ -1329,15 +1376,90 @@ static SegPlan seg_plan(const nf_solver *S, int d, int zmode)     // direction d
     P.lds = (size_t)(4 * P.TX * (P.NSEG + 1) + P.TX + 32) * sizeof(double);   // + reduction scratch (block_sum: 8, block_sum3: 24 doubles at 512 threads)
     return P;
 }
+// Directions that take their table under line_dict = -1: those whose pass measurably gains at the benchmark size
+static const int LINE_DICT_AUTO_DIRS = 7;
+// would direction d stream its factors today, and do the options allow a table for it?  (undivided RT0-P0 meshes only)
+static bool line_dict_eligible(const nf_solver *S, int d)
+{
+    const nf_team *T = S->team;
+    if (T->opt_line_dict == 0 || d >= S->dim || T->slabs.size() != 1 || S->if_lo || S->if_hi || S->k != 0 || S->nb != 0 || S->nloc != 1 || !nt_regime(S)) return false;
+    const int dirs = T->line_dict_dirs & (T->opt_line_dict < 0 ? LINE_DICT_AUTO_DIRS : 7);
+    if (!((dirs >> d) & 1)) return false;
+    if (d == 0) { const int nch = x_plan(S).NCH; return x_nt(S, 0) && nch >= 1 && nch <= X_DICT_MAX_NCH; }
+    if (chunk_plan(S, d).ok && c_nt(S)) return true;
+    const SegPlan sp = seg_plan(S, d, 0);
+    return sp.rc == NF_OK && s_nt(S, 0, sp.SEG);
+}
+// Once per build, on the first apply or solve that could use them: fingerprints of every line's stored factors, grouped on the host, verified
+// bit for bit against the group's representative, the representatives' rows gathered.  A direction uses its table only if EVERY group
+// verified, repeats at least fourfold (a core without repeats keeps the streaming path) and fits line_dict_max_bytes.
+static int line_dict_prepare(nf_team *T)
+{
+    static_assert(sizeof(LineFp) == sizeof(nf_fp128), "fingerprints travel as they are");
+    for (auto *S : T->slabs) {
+        if (S->ld_tried || !S->built) continue;
+        S->ld_tried = true;
+        hipStream_t st = T->stream;
+        const int ng = S->ng;
+        for (int d = 0; d < S->dim; ++d) {
+            if (!line_dict_eligible(S, d)) continue;
+            const long nl = S->nlines[d], N = S->N;
+            const int n = d == 0 ? S->nx : d == 1 ? S->ny : S->nz, pitch = (n + 15) / 16 * 16, narr = d == 0 ? 3 : 2;
+            const unsigned gl = (unsigned)((nl + 63) / 64);
+            auto Cd = [&](int g) { return d == 0 ? (const double *)(S->d_Cd + (size_t)g * S->nphi) : (const double *)nullptr; };
+            DevTmp<LineFp> fp; NFCHK(dalloc(&fp.p, (size_t)nl * ng));
+            for (int g = 0; g < ng; ++g)
+                hipLaunchKernelGGL(k_line_fp, dim3(gl), dim3(64), 0, st, d, S->nx, S->ny, S->nz, (const double *)(S->d_L[d] + g * N), (const double *)(S->d_DR[d] + g * N),
+                                   (const double *)(S->d_D0[d] + g * nl), Cd(g), nl, T->line_dict_fp_bits, fp.p + (size_t)g * nl);
+            std::vector<nf_fp128> h((size_t)nl * ng);
+            HIPCHK(hipMemcpyAsync(h.data(), fp.p, h.size() * sizeof(nf_fp128), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            std::vector<int> ids((size_t)nl * ng), reps, rows(ng), idg, repg;
+            std::vector<long> off(ng);
+            bool fits = true; long total = 0;
+            for (int g = 0; g < ng; ++g) {
+                rows[g] = nf_group_lines(h.data() + (size_t)g * nl, nl, idg, repg);
+                std::copy(idg.begin(), idg.end(), ids.begin() + (size_t)g * nl);
+                reps.insert(reps.end(), repg.begin(), repg.end());
+                off[g] = total; total += (long)rows[g] * pitch * narr;
+                fits = fits && (long)rows[g] * 4 <= nl && (long)rows[g] * pitch * narr * (long)sizeof(double) <= T->line_dict_max_bytes;
+            }
+            if (!fits) continue;
+            DevTmp<int> drep, dmis; int mism = 0;
+            NFCHK(dalloc(&drep.p, reps.size())); NFCHK(dalloc(&dmis.p, 1));
+            NFCHK(dalloc(&S->d_lid[d], ids.size())); NFCHK(dalloc(&S->d_ltab[d], (size_t)total));
+            HIPCHK(hipMemcpyAsync(S->d_lid[d], ids.data(), ids.size() * sizeof(int), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(drep.p, reps.data(), reps.size() * sizeof(int), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemsetAsync(dmis.p, 0, sizeof(int), st));
+            long roff = 0;
+            for (int g = 0; g < ng; ++g) {
+                const double *L = S->d_L[d] + g * N, *DR = S->d_DR[d] + g * N;
+                double *tL = S->d_ltab[d] + off[g], *tR = tL + (long)rows[g] * pitch, *tC = d == 0 ? tR + (long)rows[g] * pitch : nullptr;
+                hipLaunchKernelGGL(k_line_verify, dim3(gl), dim3(64), 0, st, d, S->nx, S->ny, S->nz, L, DR, (const double *)(S->d_D0[d] + g * nl), Cd(g), nl,
+                                   (const int *)(S->d_lid[d] + (size_t)g * nl), (const int *)(drep.p + roff), dmis.p);
+                hipLaunchKernelGGL(k_line_gather, dim3((unsigned)(((long)rows[g] * pitch + 255) / 256)), dim3(256), 0, st, d, S->nx, S->ny, S->nz, L, DR, Cd(g),
+                                   (const int *)(drep.p + roff), rows[g], pitch, tL, tR, tC);
+                roff += rows[g];
+            }
+            HIPCHK(hipMemcpyAsync(&mism, dmis.p, sizeof(int), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            HIPCHK(hipGetLastError());
+            if (mism) { S->ld_rejected |= 1 << d; dfree(S->d_lid[d]); dfree(S->d_ltab[d]); continue; }   // fingerprints collided: this direction keeps streaming
+            S->ld_use[d] = true; S->ld_pitch[d] = pitch; S->ld_off[d] = off; S->ld_rows[d] = rows;
+            S->ld_bytes += (size_t)total * sizeof(double) + ids.size() * sizeof(int);
+        }
+    }
+    return NF_OK;
+}
 struct SchurSLaunch {                                             // every argument of a k_schur_s launch
     const SegPlan &sp; hipStream_t st; const ModeArgs &ma; const ModeTab &mt; const Geom &G; const double *L, *DR, *D0; int n; long sl, ostride; int nx, last;
-    double *partials; const CgScalars *cg; const SlabArgs &sa; const CgFuse &fz; const CgLean &lz;
+    double *partials; const CgScalars *cg; const SlabArgs &sa; const CgFuse &fz; const CgLean &lz; LineDict ld = LineDict();
 };
-template <int SEG, int DIR, bool SLAB, int NB, bool SF = false, bool NTS = false, bool ZW = false, bool SR = false>
+template <int SEG, int DIR, bool SLAB, int NB, bool SF = false, bool NTS = false, bool ZW = false, bool SR = false, bool DICT = false>
 static void launch_s_t(const SchurSLaunch &a)
 {
-    hipLaunchKernelGGL((k_schur_s<SEG, DIR, SLAB, NB, SF, NTS, ZW, SR>), a.sp.grid, a.sp.block, a.sp.lds, a.st, a.ma, a.mt, a.G, a.L, a.DR, a.D0, a.n, a.sl, a.ostride, a.nx,
-                       a.sp.TX, a.sp.NSEG, a.last, a.partials, a.cg, a.sa, a.fz, a.lz);
+    hipLaunchKernelGGL((k_schur_s<SEG, DIR, SLAB, NB, SF, NTS, ZW, SR, DICT>), a.sp.grid, a.sp.block, a.sp.lds, a.st, a.ma, a.mt, a.G, a.L, a.DR, a.D0, a.n, a.sl, a.ostride, a.nx,
+                       a.sp.TX, a.sp.NSEG, a.last, a.partials, a.cg, a.sa, a.fz, a.lz, a.ld);
 }
 // zmode: 0 = plain line kernel (y lines, or z lines of an undivided mesh); 1 / 2 = slab chain passes (z lines)
 static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const Geom &G, int last, double *partials, const PassCg &P, int *nparts, int zmode)
@@ -1361,7 +1483,13 @@ static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const 
 #define NF_C(DIRV, NTV) do { if (lds_opt_in((const void *)k_schur_c<DIRV, NTV>, ldsc)) { \
             hipLaunchKernelGGL((k_schur_c<DIRV, NTV>), grid, block, ldsc, T->stream, ma.x[0], ma.y[0], ma.Ta, L, DR, D0, n, sl, ostride, S->nx, TXc, NS, last, partials, cg, xcd); \
             launched = hipGetLastError() == hipSuccess; } } while (0)   /* a refused launch (LDS, block size) falls through to the one-chunk kernel */
-            if (d == 1) { if (nt) NF_C(1, true); else NF_C(1, false); } else { if (nt) NF_C(2, true); else NF_C(2, false); }
+#define NF_CD(DIRV) do { if (lds_opt_in((const void *)k_schur_c<DIRV, true, true>, ldsc)) { \
+            hipLaunchKernelGGL((k_schur_c<DIRV, true, true>), grid, block, ldsc, T->stream, ma.x[0], ma.y[0], ma.Ta, da.L, da.DR, D0, n, sl, ostride, S->nx, TXc, NS, last, partials, cg, xcd, da.ld); \
+            launched = hipGetLastError() == hipSuccess; } } while (0)
+            const DictArgs da = dict_args(S, d, g, c_dict(S, d, nt));
+            if (da.on) { if (d == 1) NF_CD(1); else NF_CD(2); }
+            else if (d == 1) { if (nt) NF_C(1, true); else NF_C(1, false); } else { if (nt) NF_C(2, true); else NF_C(2, false); }
+#undef NF_CD
 #undef NF_C
             if (launched) { if (nparts) *nparts = (int)(grid.x * grid.y); return NF_OK; }
         }
@@ -1387,7 +1515,9 @@ static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const 
         sa.sr = P.cg1; sa.sr_r = S->d_r; sa.sr_q = S->d_q; sa.sr_stride = T->partial_stride;
         sa.sr_part = T->d_partials + 3 * T->partial_stride + (long)S->slab_index * T->slab_cap;
     }
-    const SchurSLaunch A = { sp, st, ma, mt, G, L, DR, D0, n, sl, ostride, S->nx, last, partials, cg, sa, fz, lz };   // sa by reference: its slab fields follow
+    const DictArgs da = dict_args(S, d, g, s_dict(S, d, zmode, SEG));   // the column's row of the table instead of its own L, 1/d
+    const bool dict = da.on;
+    const SchurSLaunch A = { sp, st, ma, mt, G, dict ? da.L : L, dict ? da.DR : DR, D0, n, sl, ostride, S->nx, last, partials, cg, sa, fz, lz, da.ld };   // sa by reference: its slab fields follow
 #define NF_S(SEGV, DIRV, SLABV, NBV) do { if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && sr && zmode == 1 && nts) launch_s_t<SEGV, DIRV, SLABV, NBV, SLABV && NBV == 0, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
         else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && sr && zmode == 1) launch_s_t<SEGV, DIRV, SLABV, NBV, SLABV && NBV == 0, false, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
         else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && sr && nts) launch_s_t<SEGV, DIRV, SLABV, NBV, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
@@ -1395,6 +1525,8 @@ static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const 
         else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && nts && fz.p) launch_s_t<SEGV, DIRV, SLABV, NBV, SLABV && NBV == 0, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
         else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && nts) launch_s_t<SEGV, DIRV, SLABV, NBV, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
         else if (SLABV && NBV == 0 && fz.p) launch_s_t<SEGV, DIRV, SLABV, NBV, SLABV && NBV == 0>(A); \
+        else if (!SLABV && NBV == 0 && zw && SEGV == 8 && nt && dict) launch_s_t<SEGV, DIRV, SLABV, NBV, !SLABV && NBV == 0 && SEGV == 8, false, !SLABV && NBV == 0, false, !SLABV && NBV == 0 && SEGV == 8>(A); \
+        else if (!SLABV && NBV == 0 && SEGV == 8 && nt && dict) launch_s_t<SEGV, DIRV, SLABV, NBV, !SLABV && NBV == 0 && SEGV == 8, false, false, false, !SLABV && NBV == 0 && SEGV == 8>(A); \
         else if (!SLABV && NBV == 0 && zw && SEGV == 8 && nt) launch_s_t<SEGV, DIRV, SLABV, NBV, !SLABV && NBV == 0 && SEGV == 8, false, !SLABV && NBV == 0>(A); \
         else if (!SLABV && NBV == 0 && zw) launch_s_t<SEGV, DIRV, SLABV, NBV, false, false, !SLABV && NBV == 0>(A); \
         else if (!SLABV && NBV == 0 && SEGV == 8 && nt) launch_s_t<SEGV, DIRV, SLABV, NBV, !SLABV && NBV == 0 && SEGV == 8>(A); \
@@ -1592,6 +1724,7 @@ int nf_schur_apply(nf_handle S, int g, const double *x_dev, double *y_dev)
     nf_team *T = S->team;
     if (!team_is_single(T)) return fail(NF_ERR_STATE, "nf_schur_apply works on an undivided mesh; use nf_team_schur_apply for slabs");
     HIPCHK(hipSetDevice(S->device));
+    NFCHK(line_dict_prepare(T));                                 // an undivided mesh needs nothing else of team_prepare
     NFCHK(team_schur_apply(T, g, { x_dev }, { y_dev }, false, ApplyCg()));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(T->stream));
@@ -1618,15 +1751,16 @@ int nf_team_schur_apply(nf_handle S, int g, const double *const *x_dev, double *
 // ---- read-only report of the launch plan -------------------------------------------------------
 // What the next Schur apply on this handle's mesh (or slab) would launch, per direction, as one JSON object.  Built from the predicates
 // the launch functions call (x_plan / x_nt / x_p2 / x_xcd, pass_chunk_plan / c_taken / c_nt / c_xcd, seg_plan / s_nt / s_nts / s_zw / s_xcd,
-// endpoint_w_taken, the cg_* forms, split_dot, xy_overlap); launches nothing, writes no state.  The one thing it cannot know is a device
+// endpoint_w_taken, the cg_* forms, split_dot, xy_overlap, x_dict / c_dict / s_dict); apart from building the tables of distinct lines where the next
+// apply would (line_dict_prepare) it launches nothing and writes no state.  The one thing it cannot know is a device
 // that refuses the chunked kernel's LDS at launch time (launch_s then falls back to the one-chunk kernel).
-struct PlanPass { const char *dir, *family; int mode, SEG, NCH, TX, NSEG; dim3 grid; unsigned block; bool nt, p2, zw, order; unsigned tiles; bool fold = false; };
+struct PlanPass { const char *dir, *family; int mode, SEG, NCH, TX, NSEG; dim3 grid; unsigned block; bool nt, p2, zw, order; unsigned tiles; bool fold = false, dict = false; };
 static void plan_emit(std::string &js, const PlanPass &p)
 {
     char tmp[384];
     snprintf(tmp, sizeof tmp, "%s{\"dir\": \"%s\", \"mode\": %d, \"family\": \"%s\", \"SEG\": %d, \"NCH\": %d, \"TX\": %d, \"NSEG\": %d, \"grid\": [%u, %u, %u], "
-             "\"block\": %u, \"nt\": %d, \"p2\": %d, \"zw\": %d, \"xcd_order\": %d, \"xcd_permutes\": %d, \"fold\": %d}", js.back() == '[' ? "" : ", ", p.dir, p.mode, p.family,
-             p.SEG, p.NCH, p.TX, p.NSEG, p.grid.x, p.grid.y, p.grid.z, p.block, p.nt ? 1 : 0, p.p2 ? 1 : 0, p.zw ? 1 : 0, p.order ? 1 : 0, xcd_permutes(p.order, p.tiles) ? 1 : 0, p.fold ? 1 : 0);
+             "\"block\": %u, \"nt\": %d, \"p2\": %d, \"zw\": %d, \"xcd_order\": %d, \"xcd_permutes\": %d, \"fold\": %d, \"dict\": %d}", js.back() == '[' ? "" : ", ", p.dir, p.mode, p.family,
+             p.SEG, p.NCH, p.TX, p.NSEG, p.grid.x, p.grid.y, p.grid.z, p.block, p.nt ? 1 : 0, p.p2 ? 1 : 0, p.zw ? 1 : 0, p.order ? 1 : 0, xcd_permutes(p.order, p.tiles) ? 1 : 0, p.fold ? 1 : 0, p.dict ? 1 : 0);
     js += tmp;
 }
 static int plan_s(std::string &js, const nf_solver *S, int d, int zmode, bool want_dot, bool zw_dot)   // a launch_s call
@@ -1635,19 +1769,22 @@ static int plan_s(std::string &js, const nf_solver *S, int d, int zmode, bool wa
     const ChunkPlan cp = pass_chunk_plan(S, d, zmode);
     if (c_taken(cp, want_dot, zw_dot)) {
         const dim3 gr = c_grid(S, d, cp); const bool nt = c_nt(S);
-        plan_emit(js, { dir, "c", zmode, C_SEG, C_NCH, cp.TX, cp.NS, gr, c_block(cp), nt, false, want_dot, c_xcd(S, d, nt) != 0, gr.x * gr.y });
+        plan_emit(js, { dir, "c", zmode, C_SEG, C_NCH, cp.TX, cp.NS, gr, c_block(cp), nt, false, want_dot, c_xcd(S, d, nt) != 0, gr.x * gr.y, false, c_dict(S, d, nt) });
         return NF_OK;
     }
     const SegPlan sp = seg_plan(S, d, zmode);
     if (sp.rc != NF_OK) return sp.rc;
     plan_emit(js, { dir, "s", zmode, sp.SEG, 1, sp.TX, sp.NSEG, sp.grid, sp.block.x, s_nt(S, zmode, sp.SEG) || s_nts(S, zmode, sp.SEG), false, s_zw(S, zmode, zw_dot, want_dot),
-                    s_xcd(S, d, zmode) != 0, sp.grid.x * sp.grid.y, s_fold(S->team, zmode) });
+                    s_xcd(S, d, zmode) != 0, sp.grid.x * sp.grid.y, s_fold(S->team, zmode), s_dict(S, d, zmode, sp.SEG) });
     return NF_OK;
 }
 int nf_apply_plan(nf_handle S, int in_cg, char *json_buf, size_t len)
 {
     if (!S || !json_buf || len < 2) return fail(NF_ERR_ARG, "nf_apply_plan: bad arguments");
     if (!S->built) return fail(NF_ERR_STATE, "nf_apply_plan: call nf_build first");
+    // the tables of distinct lines are part of what the next apply does: it would build them first, so the report does (its only side effect)
+    HIPCHK(hipSetDevice(S->team->device));
+    NFCHK(line_dict_prepare(S->team));
     const nf_team *T = S->team;
     const bool slab = S->if_lo || S->if_hi;
     // a team settles the separator sweeps, the endpoint weights and its largest slab when it is prepared (the first team apply or solve)
@@ -1670,7 +1807,7 @@ int nf_apply_plan(nf_handle S, int in_cg, char *json_buf, size_t len)
             const XPlan xp = x_plan(S);
             if (!xp.NCH) return fail(NF_ERR_UNSUPPORTED, "nx = %d exceeds the x-line kernel limit (%d cells)", S->nx, S->nb == 0 ? 4096 : 1024);
             const bool nt = x_nt(S, S->nb), order = x_xcd(S, nt);
-            plan_emit(js, { "x", "x", 0, 0, xp.NCH, 1 << xp.lpl_log2, 0, dim3(xp.grid, (unsigned)n_modes(S)), 256u, nt, x_p2(S, S->nb, xp.NCH, fused && x_fuses(S), nt), false, order, xp.grid });
+            plan_emit(js, { "x", "x", 0, 0, xp.NCH, 1 << xp.lpl_log2, 0, dim3(xp.grid, (unsigned)n_modes(S)), 256u, nt, x_p2(S, S->nb, xp.NCH, fused && x_fuses(S), nt), false, order, xp.grid, false, x_dict(S, S->nb, xp.NCH, nt) });
         } else if (d == 2 && slab) {
             // endpoint pass: inside the fused CG the update reads the vector the pass is applied to (cg_solve applies to d_p)
             if (endpoint_w_taken(T, S, sr, fused)) { const dim3 gr = endpoint_w_grid(S); plan_emit(js, { "z", "endpoint_w", 1, 0, 0, 64, 0, gr, 256u, false, false, false, false, gr.x * gr.y }); }
@@ -1679,7 +1816,12 @@ int nf_apply_plan(nf_handle S, int in_cg, char *json_buf, size_t len)
         } else if (d == 1 && xy_all) NFCHK(plan_s(js, S, 1, 0, false, split));
         else NFCHK(plan_s(js, S, d, 0, want_dot, split));
     }
-    js += "]}";
+    {   // distinct lines of the largest group per direction, 0 where the direction does not use its table
+        int nd[3] = { 0, 0, 0 };
+        for (int d = 0; d < S->dim; ++d) if (dict_dir(S, d)) nd[d] = *std::max_element(S->ld_rows[d].begin(), S->ld_rows[d].end());
+        snprintf(tmp, sizeof tmp, "], \"line_dict\": {\"x\": %d, \"y\": %d, \"z\": %d}}", nd[0], nd[1], nd[2]);
+        js += tmp;
+    }
     if (js.size() + 1 > len) return fail(NF_ERR_ARG, "nf_apply_plan: buffer of %zu bytes is too small (%zu needed)", len, js.size() + 1);
     memcpy(json_buf, js.c_str(), js.size() + 1);
     return NF_OK;
@@ -2075,6 +2217,7 @@ int nf_solve_group(nf_handle S, int g, const double *rhs_dev, double *phi_dev, d
     if (!S->built) return fail(NF_ERR_STATE, "nf_solve_group: call nf_build first");
     if (!team_is_single(S->team)) return fail(NF_ERR_STATE, "nf_solve_group works on an undivided mesh");
     HIPCHK(hipSetDevice(S->device));
+    NFCHK(line_dict_prepare(S->team));
     return cg_solve(S->team, g, { rhs_dev }, { phi_dev }, tol, maxit, its, res);
 }
 
@@ -4047,6 +4190,14 @@ int nf_set_option(nf_handle S, const char *key, long value)
     else if (!strcmp(key, "s_long_dirs")) T->opt_s_long_dirs = (int)(value & 3);
     else if (!strcmp(key, "s_long_min_y")) T->s_long_min_y = (int)std::max(1L, std::min(1000000L, value));
     else if (!strcmp(key, "s_long_min")) T->s_long_min = (int)std::max(1L, std::min(1000000L, value));
+    else if (!strcmp(key, "line_dict") || !strcmp(key, "line_dict_dirs") || !strcmp(key, "line_dict_max_bytes") || !strcmp(key, "line_dict_fp_bits")) {
+        if (!strcmp(key, "line_dict")) T->opt_line_dict = value < 0 ? -1 : (value > 0 ? 1 : 0);
+        else if (!strcmp(key, "line_dict_dirs")) T->line_dict_dirs = (int)(value & 7);
+        else if (!strcmp(key, "line_dict_max_bytes")) T->line_dict_max_bytes = std::max(0L, std::min(1L << 30, value));   // 32-bit byte offsets inside the kernels
+        else T->line_dict_fp_bits = (int)std::max(0L, std::min(128L, value));
+        HIPCHK(hipSetDevice(T->device));
+        for (auto *X : T->slabs) line_dict_drop(X);
+    }
     else if (!strcmp(key, "cg_batch")) T->cg_batch = (int)value;
     else if (!strcmp(key, "cg_fuse")) T->opt_fuse = value != 0;
     else if (!strcmp(key, "xcd")) T->opt_xcd = value < 0 ? -1 : (int)(value & 7);
@@ -4075,6 +4226,10 @@ int nf_set_option(nf_handle S, const char *key, long value)
     else if (!strcmp(key, "cg_fuse3_max_cells")) T->fuse3_max_cells = value;
     else if (!strcmp(key, "cg_lean_grid")) T->opt_lean_grid = (int)std::max(1L, std::min(1024L, value));
     else return fail(NF_ERR_ARG, "nf_set_option: unknown key %s", key);
+    // options that move a mesh into or out of the streaming kernels: look again at the next apply (a mesh whose lines do not repeat pays the
+    // fingerprints and the host sort once per build, not once per option)
+    if (!strcmp(key, "nt_loads") || !strcmp(key, "nt_min_cells") || !strncmp(key, "s_long", 6) || !strcmp(key, "s_seg") || !strcmp(key, "s_tx"))
+        for (auto *X : T->slabs) if (!X->d_lid[0] && !X->d_lid[1] && !X->d_lid[2]) X->ld_tried = false;
     return NF_OK;
 }
 

@@ -726,6 +726,79 @@ __device__ __forceinline__ void sto(double *p, unsigned byte_off, double v) { *r
 // buffer of a pair.  Every site evaluates fma(beta, p, r) / fma(alpha, p, x_sol): same bits everywhere.
 struct CgFuse { double *p; const double *r; double *xsol; double *pout; };
 
+// Tables of distinct lines.  A core built from a few assembly types and axial zones on a uniform mesh has only a handful of DIFFERENT lines per
+// direction (IAEA-3D at 256^3: 12 / 12 / 3 of 65 536), and lines with equal stored factors need those factors once: the streaming passes then
+// read L, 1/d (and the C diagonal, x pass) from a table [id][cell] that stays in L2 instead of streaming 16 (24) bytes per cell from HBM.
+// The ids are found on the stored factors themselves: a 128-bit fingerprint of every line's bit patterns (k_line_fp), grouped on the host,
+// every line compared bit for bit with its group's representative (k_line_verify: a collision switches the direction's table off), the
+// representatives' rows gathered (k_line_gather).  Same values, same arithmetic: the table path is bit-identical to the streaming path.
+struct LineDict { const int *id = nullptr; int pitch = 0; };     // id per line of the group; doubles per table row (multiple of 16)
+struct LineFp { unsigned long long lo, hi; };
+__device__ __forceinline__ void line_span(int d, long line, int nx, int ny, int nz, long &base, long &sl, int &n)   // as in k_factor_lines
+{
+    const long nxy = (long)nx * ny;
+    if (d == 0) { n = nx; base = line * nx; sl = 1; }
+    else if (d == 1) { n = ny; base = (line / nx) * nxy + line % nx; sl = nx; }
+    else { n = nz; base = line; sl = nxy; }
+}
+__device__ __forceinline__ void fp_mix(unsigned long long &a, unsigned long long &b, double v)
+{
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    a ^= u; a *= 0xff51afd7ed558ccdull; a ^= a >> 33;
+    b = ((b << 27) | (b >> 37)) + u; b *= 0xc4ceb9fe1a85ec53ull; b ^= b >> 31;
+}
+// bits: how many low bits of the fingerprint are kept (128 = all; fewer only to provoke collisions in tests)
+__global__ void k_line_fp(int d, int nx, int ny, int nz, const double *__restrict__ L, const double *__restrict__ DR, const double *__restrict__ D0,
+                          const double *__restrict__ Cd, long nlines, int bits, LineFp *__restrict__ out)
+{
+    const long line = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (line >= nlines) return;
+    long base, sl; int n;
+    line_span(d, line, nx, ny, nz, base, sl, n);
+    unsigned long long a = 0x9e3779b97f4a7c15ull, b = 0xd1b54a32d192ed03ull;
+    fp_mix(a, b, D0[line]);
+    for (int c = 0; c < n; ++c) {
+        const long e = base + c * sl;
+        fp_mix(a, b, L[e]); fp_mix(a, b, DR[e]);
+        if (Cd) fp_mix(a, b, Cd[e]);
+    }
+    if (bits < 64) { b = 0; a &= bits <= 0 ? 0ull : (~0ull >> (64 - bits)); }
+    else if (bits < 128) b &= bits == 64 ? 0ull : (~0ull >> (128 - bits));
+    out[line].lo = a; out[line].hi = b;
+}
+// every line against the representative of its id, bit for bit; *mism counts the lines that differ
+__global__ void k_line_verify(int d, int nx, int ny, int nz, const double *__restrict__ L, const double *__restrict__ DR, const double *__restrict__ D0,
+                              const double *__restrict__ Cd, long nlines, const int *__restrict__ id, const int *__restrict__ rep, int *__restrict__ mism)
+{
+    const long line = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (line >= nlines) return;
+    const long other = rep[id[line]];
+    if (other == line) return;
+    long base, sl, ob, osl; int n;
+    line_span(d, line, nx, ny, nz, base, sl, n);
+    line_span(d, other, nx, ny, nz, ob, osl, n);
+    bool same = __double_as_longlong(D0[line]) == __double_as_longlong(D0[other]);
+    for (int c = 0; c < n; ++c) {
+        const long e = base + c * sl, o = ob + c * osl;
+        same = same && __double_as_longlong(L[e]) == __double_as_longlong(L[o]) && __double_as_longlong(DR[e]) == __double_as_longlong(DR[o]);
+        if (Cd) same = same && __double_as_longlong(Cd[e]) == __double_as_longlong(Cd[o]);
+    }
+    if (!same) atomicAdd(mism, 1);
+}
+// table rows [id][cell], pitch doubles apart (the tail of a row stays zero): tL, tR and, for x lines, tC
+__global__ void k_line_gather(int d, int nx, int ny, int nz, const double *__restrict__ L, const double *__restrict__ DR, const double *__restrict__ Cd,
+                              const int *__restrict__ rep, int nrows, int pitch, double *__restrict__ tL, double *__restrict__ tR, double *__restrict__ tC)
+{
+    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (i >= (long)nrows * pitch) return;
+    const int row = (int)(i / pitch), c = (int)(i % pitch);
+    long base, sl; int n;
+    line_span(d, rep[row], nx, ny, nz, base, sl, n);
+    const bool in = c < n; const long e = base + c * sl;
+    tL[i] = in ? L[e] : 0.0; tR[i] = in ? DR[e] : 0.0;
+    if (tC) tC[i] = in ? Cd[e] : 0.0;
+}
+
 // One wave-task of the x pass: 64/LPL lines, lane = (line of the task, position in the line).  Returns the lane's share of x.y.
 // DPPS: cross-lane traffic of the scans through data-parallel primitives (VALU) instead of ds_bpermute (LDS crossbar).  That halves
 // the latency of a lone wave-task (resident kernel: 14.2 k -> 10.9 k cycles per x pass) but costs VALU issue slots: with many waves
@@ -733,18 +806,25 @@ struct CgFuse { double *p; const double *r; double *xsol; double *pout; };
 // P2 (long lines inside CG, NCH >= 4): two load phases instead of one -- p, r, x_sol first (the deferred CG update consumes r and
 // x_sol at once), then L, 1/d and the C diagonal.  Everything in flight at once costs 140 VGPRs at four chunks per lane (three waves
 // per SIMD); in two phases the peak is the sweep's own working set.
-template <int K, int NCH, bool VEC, int NB, class Mid = NoMid, bool DPPS = false, bool NT = false, bool P2 = false>
+// DICT (streaming instantiations of RT0-P0 meshes whose lines repeat, see LineDict): L, DR and ma.Cd[0] point at the table of distinct lines
+// and the line's row replaces its own cells -- plain loads (the table is meant to stay in L2), same shapes, bit-equal values.
+template <int K, int NCH, bool VEC, int NB, class Mid = NoMid, bool DPPS = false, bool NT = false, bool P2 = false, bool DICT = false>
 __device__ __forceinline__ double schur_x_task(const ModeArgs &ma, const Geom &G, const double *__restrict__ L, const double *__restrict__ DR,
                                                const double *__restrict__ D0, int nx, int ny, long nlines, int lpl_log2, int first,
-                                               long task, int lane, bool active, bool fuse, double f_alpha, double f_beta, const CgFuse &fz, Mid mid = Mid())
+                                               long task, int lane, bool active, bool fuse, double f_alpha, double f_beta, const CgFuse &fz, Mid mid = Mid(),
+                                               const LineDict &ld = LineDict())
 {
     static_assert(K == 2, "two cells per lane and chunk");
+    static_assert(!DICT || (NB == 0 && NT), "line tables: next to the streaming RT0-P0 instantiations only");
     const int LPL = 1 << lpl_log2, LPW = 64 >> lpl_log2;
     const int li = lane & (LPL - 1), sub = lane >> lpl_log2;
     const long line = task * LPW + sub;
     const bool lv = active && line < nlines;
     const long base = lv ? line * nx : 0;
     const int iy = lv ? (int)(line % ny) : 0, iz = lv ? (int)(line / ny) : 0;
+    long cbase = base;                                           // where the line's coefficients start: its own cells, or its row of the table
+    if (DICT) cbase = lv ? (long)((unsigned)ld.id[line] * (unsigned)ld.pitch) : 0;
+    constexpr bool NTC = NT && !DICT;
     double xm[NB + 1][NCH][K], yo[NB + 1][NCH][K], Ls[NCH][K], Rs[NCH][K], w[NCH][K], xL[NCH][K], xR[NCH][K], ic[NCH][K];
     double rq[NB + 1][NCH][K], sq[NB + 1][NCH][K], dq[NB > 0 ? NCH : 1][K];   // fused variants: r and x_sol of the same cells; D (1 / c_e)
     double *pw = fz.pout ? fz.pout : fz.p;
@@ -754,13 +834,16 @@ __device__ __forceinline__ double schur_x_task(const ModeArgs &ma, const Geom &G
         const int c0 = (ch * LPL + li) * K;
         const bool ok = lv && c0 < nx, ok2 = lv && c0 + 1 < nx;
         if (!P2) {
-            ld2<NT>(L, base + c0, ok, VEC, Ls[ch][0], Ls[ch][1], ok2);
-            ld2<NT>(DR, base + c0, ok, VEC, Rs[ch][0], Rs[ch][1], ok2);
+            ld2<NTC>(L, cbase + c0, ok, VEC, Ls[ch][0], Ls[ch][1], ok2);
+            ld2<NTC>(DR, cbase + c0, ok, VEC, Rs[ch][0], Rs[ch][1], ok2);
         }
 #pragma unroll
         for (int q = 0; q <= NB; ++q) {
             ld2<NT>(ma.x[q], base + c0, ok, VEC, xm[q][ch][0], xm[q][ch][1], ok2);
-            if (!P2) ld2<NT>(first ? ma.Cd[q] : ma.y[q], base + c0, ok, VEC, yo[q][ch][0], yo[q][ch][1], ok2);
+            if (!P2) {
+                if (DICT && first) ld2<false>(ma.Cd[q], cbase + c0, ok, VEC, yo[q][ch][0], yo[q][ch][1], ok2);
+                else ld2<NT>(first ? ma.Cd[q] : ma.y[q], base + c0, ok, VEC, yo[q][ch][0], yo[q][ch][1], ok2);
+            }
             if (fuse) {                                          // ma.x[q] points into p: the same offset addresses r and x_sol
                 const long mo = (ma.x[q] - fz.p) + base + c0;
                 ld2<NT>(fz.r, mo, ok, VEC, rq[q][ch][0], rq[q][ch][1], ok2);
@@ -809,10 +892,13 @@ __device__ __forceinline__ double schur_x_task(const ModeArgs &ma, const Geom &G
         for (int ch = 0; ch < NCH; ++ch) {                       // second load phase: what the sweeps and the output need
             const int c0 = (ch * LPL + li) * K;
             const bool ok = lv && c0 < nx, ok2 = lv && c0 + 1 < nx;
-            ld2<NT>(L, base + c0, ok, VEC, Ls[ch][0], Ls[ch][1], ok2);
-            ld2<NT>(DR, base + c0, ok, VEC, Rs[ch][0], Rs[ch][1], ok2);
+            ld2<NTC>(L, cbase + c0, ok, VEC, Ls[ch][0], Ls[ch][1], ok2);
+            ld2<NTC>(DR, cbase + c0, ok, VEC, Rs[ch][0], Rs[ch][1], ok2);
 #pragma unroll
-            for (int q = 0; q <= NB; ++q) ld2<NT>(first ? ma.Cd[q] : ma.y[q], base + c0, ok, VEC, yo[q][ch][0], yo[q][ch][1], ok2);
+            for (int q = 0; q <= NB; ++q) {
+                if (DICT && first) ld2<false>(ma.Cd[q], cbase + c0, ok, VEC, yo[q][ch][0], yo[q][ch][1], ok2);
+                else ld2<NT>(first ? ma.Cd[q] : ma.y[q], base + c0, ok, VEC, yo[q][ch][0], yo[q][ch][1], ok2);
+            }
         }
     }
     const double d0 = lv ? D0[line] : 0.0;
@@ -897,11 +983,11 @@ __device__ __forceinline__ double schur_x_task(const ModeArgs &ma, const Geom &G
     return dot;
 }
 
-template <int K, int NCH, bool VEC, int NB, bool NT = false, bool P2 = false>
+template <int K, int NCH, bool VEC, int NB, bool NT = false, bool P2 = false, bool DICT = false>
 __global__ __launch_bounds__(256) void k_schur_x(ModeArgs ma0, ModeTab mt, Geom G, const double *__restrict__ L, const double *__restrict__ DR,
                                                  const double *__restrict__ D0, int nx, int ny, long nlines, int lpl_log2,
                                                  int first, int last, double *__restrict__ partials,
-                                                 const CgScalars *__restrict__ cg, CgFuse fz, CgLean lean)
+                                                 const CgScalars *__restrict__ cg, CgFuse fz, CgLean lean, LineDict ld = LineDict())
 {
     __shared__ double sred[4];
     if (cg && cg->done) return;
@@ -920,8 +1006,8 @@ __global__ __launch_bounds__(256) void k_schur_x(ModeArgs ma0, ModeTab mt, Geom 
     // bit 1 of `first`: XCD-contiguous block order (consecutive workgroups go round-robin to the 8 XCDs; each then walks one eighth of the lines)
     unsigned bx = blockIdx.x;
     if ((first & 2) && gridDim.x % 8 == 0) bx = (blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8;
-    const double dot = schur_x_task<K, NCH, VEC, NB, decltype(mid), false, NT, P2>(ma, G, L, DR, D0, nx, ny, nlines, lpl_log2, first & 1, (long)bx * 4 + (threadIdx.x >> 6),
-                                                                               threadIdx.x & 63, true, fuse, alpha0, beta0, fz, mid);
+    const double dot = schur_x_task<K, NCH, VEC, NB, decltype(mid), false, NT, P2, DICT>(ma, G, L, DR, D0, nx, ny, nlines, lpl_log2, first & 1, (long)bx * 4 + (threadIdx.x >> 6),
+                                                                               threadIdx.x & 63, true, fuse, alpha0, beta0, fz, mid, ld);
     if (stopped) return;                                         // decided inside, the same in every block: nothing to reduce
     if (last && partials) {
         const double s = block_sum(dot, sred);
@@ -971,14 +1057,17 @@ struct SlabArgs {
 // (eight doubles fewer live through the scans, and the chunked long-line pass has nothing to re-read for its parked chunk).
 // XC (k_cg_xcd: the producers of x and r are other workgroups of the SAME launch on the same XCD): every load of x and r bypasses the
 // compute unit's L1 -- the overlap cell too
-template <int SEG, int DIR, bool SLAB, int NB, bool SF = false, bool NTS = false, class Mid = NoMid, bool ZW = false, bool XC = false, bool SR = false>   // NTS: streaming loads in a slab variant
+// DICT (plain RT0-P0 lines in the streaming regime, see LineDict): L and DR point at the table of distinct lines; a lane carries the byte
+// offset of its line's row and reaches the cells of its segment from there -- contiguous along the line, plain loads, bit-equal values
+template <int SEG, int DIR, bool SLAB, int NB, bool SF = false, bool NTS = false, class Mid = NoMid, bool ZW = false, bool XC = false, bool SR = false, bool DICT = false>   // NTS: streaming loads in a slab variant
 __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G, const double *__restrict__ L, const double *__restrict__ DR,
                                                const double *__restrict__ D0, int n, long sl, long outer_stride, int nx, int TX, int NSEG,
                                                unsigned bx, unsigned by, unsigned bz, unsigned gy, int tid, bool act, double *sm,
                                                const SlabArgs &sa, const CgFuse &fz, bool fuse, bool fro, double f_alpha, double f_beta, bool acc,
-                                               long long *stamp = nullptr, Mid mid = Mid(), double *extra = nullptr)
+                                               long long *stamp = nullptr, Mid mid = Mid(), double *extra = nullptr, const LineDict &ld = LineDict())
 {
     static_assert(!SR || (SLAB && NB == 0), "single-reduction CG: RT0-P0 slab passes");
+    static_assert(!DICT || (!SLAB && NB == 0 && SF), "line tables: next to the streaming instantiations of plain RT0-P0 lines only");
     constexpr bool NT = SLAB ? NTS : SF;                         // big meshes: streaming loads (ldg); SF doubles as that flag on undivided meshes
     const double *x = ma.x[0];                                   // no __restrict__: the fused slab pass rewrites this vector (fz.p)
     double *__restrict__ y = ma.y[0];
@@ -1054,7 +1143,10 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
     // higher-order passes of undivided meshes touch up to eleven arrays per cell: 32-bit byte offsets from the wave-uniform bases (ldo / sto)
     constexpr bool O32 = NB > 0 && !SLAB;
     const unsigned ob8 = (unsigned)(base * 8), sl8 = (unsigned)(sl * 8);
+    unsigned tb8 = 0;                                            // DICT: byte offset of this column's row in the table
+    if (DICT) tb8 = valid ? (unsigned)ld.id[lineid] * (unsigned)ld.pitch * 8u : 0u;
 #define NF_A8(c) (ob8 + (unsigned)(c) * sl8)
+#define NF_T8(c) (tb8 + (unsigned)(c) * 8u)
     double rv[(SLAB && !SF) ? 1 : SEG + 1], sv[(SLAB && SF) ? SEG : 1];   // r of the same cells; slab fuse: x_sol of the owned cells
     double qv[(SR && SF) ? SEG + 1 : 1], rq_[(SR && !SF) ? SEG : 1];      // SR: q of the same cells (endpoint pass); r of the owned cells (accumulation pass)
     double srr = 0.0, sqq = 0.0, srq = 0.0;
@@ -1069,7 +1161,8 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
         if (!SLAB || SF) rv[(SLAB && !SF) ? 0 : i] = (fr && ok) ? (SLAB ? fz.r[a] : (O32 ? ldo<NT>(x + roff, NF_A8(c)) : ldg<NT>(x + a + roff))) : 0.0;
         if (SLAB && SF && i < SEG) sv[(SLAB && SF) ? i : 0] = (fuse && ok) ? fz.xsol[a] : 0.0;
         if (SR && SF) qv[(SR && SF) ? i : 0] = (fuse && ok) ? sa.sr_q[a] : 0.0;
-        if (O32) { Lv[i] = ok ? ldo<NT>(L, NF_A8(c)) : 0.0; if (i < SEG) Rv[i] = ok ? ldo<NT>(DR, NF_A8(c)) : 0.0; }
+        if (DICT) { Lv[i] = ok ? ldo<false>(L, NF_T8(c)) : 0.0; if (i < SEG) Rv[i] = ok ? ldo<false>(DR, NF_T8(c)) : 0.0; }
+        else if (O32) { Lv[i] = ok ? ldo<NT>(L, NF_A8(c)) : 0.0; if (i < SEG) Rv[i] = ok ? ldo<NT>(DR, NF_A8(c)) : 0.0; }
         else {
             if (i < SEG) Lv[i] = ok ? ldg<NT>(L + a) : 0.0; else Lv[i] = ok ? L[a] : 0.0;
             if (i < SEG) Rv[i] = ok ? ldg<NT>(DR + a) : 0.0;
@@ -1089,7 +1182,8 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
         }
     }
     double dinv_s = 0.0;
-    if (valid && c0 < n) dinv_s = c0 == 0 ? D0[lineid] : DR[base + (long)(c0 - 1) * sl];
+    if (DICT) { if (valid && c0 < n) dinv_s = c0 == 0 ? D0[lineid] : ldo<false>(DR, NF_T8(c0 - 1)); }
+    else if (valid && c0 < n) dinv_s = c0 == 0 ? D0[lineid] : DR[base + (long)(c0 - 1) * sl];
     NF_STAMP(stamp, 3);
     if (mid(f_alpha, f_beta)) return 0.0;                        // e.g. the reduction that yields beta: runs with the loads above in flight
     // ---- arithmetic on the loaded values (cells outside the line hold zeros throughout)
@@ -1370,14 +1464,16 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
     if (SR && extra) { extra[0] = sqq; extra[1] = srq; }
     return dot;
 #undef NF_A8
+#undef NF_T8
 }
 
 // Slab variants keep r and x_sol of their cells in registers next to x, L, 1/d (loads first, see schur_s_tile): blocks of at most 512
 // threads, so that the register budget is 256 per thread (the host picks TX accordingly)
-template <int SEG, int DIR, bool SLAB, int NB, bool SF = false, bool NTS = false, bool ZW = false, bool SR = false>
+template <int SEG, int DIR, bool SLAB, int NB, bool SF = false, bool NTS = false, bool ZW = false, bool SR = false, bool DICT = false>
 __global__ __launch_bounds__(SLAB ? 512 : 1024, SLAB ? (NB > 0 ? 2 : (SF ? (SR ? NF_SR_Z1_WAVES : 3) : (SR ? NF_SR_Z2_WAVES : 4))) : 1) void k_schur_s(ModeArgs ma0, ModeTab mt, Geom G, const double *__restrict__ L, const double *__restrict__ DR,
                           const double *__restrict__ D0, int n, long sl, long outer_stride, int nx, int TX, int NSEG,
-                          int last, double *__restrict__ partials, const CgScalars *__restrict__ cg, SlabArgs sa, CgFuse fz, CgLean lean)
+                          int last, double *__restrict__ partials, const CgScalars *__restrict__ cg, SlabArgs sa, CgFuse fz, CgLean lean,
+                          LineDict ld = LineDict())
 {
     extern __shared__ double sm[];
     if (cg && cg->done) return;
@@ -1403,9 +1499,9 @@ __global__ __launch_bounds__(SLAB ? 512 : 1024, SLAB ? (NB > 0 ? 2 : (SF ? (SR ?
     }
     static_assert(!ZW || (!SLAB && NB == 0), "the z.w form of the dot product is for plain RT0-P0 lines");
     double extra[2] = { 0.0, 0.0 };
-    const double dot = schur_s_tile<SEG, DIR, SLAB, NB, SF, NTS, NoMid, ZW, false, SR>(ma, G, L, DR, D0, n, sl, outer_stride, nx, TX, NSEG, bx, by, blockIdx.z, gridDim.y,
+    const double dot = schur_s_tile<SEG, DIR, SLAB, NB, SF, NTS, NoMid, ZW, false, SR, DICT>(ma, G, L, DR, D0, n, sl, outer_stride, nx, TX, NSEG, bx, by, blockIdx.z, gridDim.y,
                                                             (int)threadIdx.x, true, sm, sa, fz, fuse, false, f_alpha, f_beta, !(!SLAB && NB == 0 && sa.noacc),
-                                                            nullptr, NoMid(), SR ? extra : nullptr);
+                                                            nullptr, NoMid(), SR ? extra : nullptr, ld);
     if (SLAB && sa.mode == 3) return;
     double *sred = sm + 4 * TX * (NSEG + 1) + TX;
     const long pidx = ((long)blockIdx.z * gridDim.y + by) * gridDim.x + bx;
@@ -1495,12 +1591,14 @@ __global__ __launch_bounds__(256) void k_endpoint_w(double *__restrict__ p, doub
 // below 4 GiB.  One VGPR per cell address, shared by x, L, 1/d and y, instead of a 64-bit pair per array: that is what keeps the
 // two-chunk body inside the 128 registers of a 1024-thread block (with 64-bit addresses it spilled 10-12 registers to scratch,
 // +31 % bytes written and +6 % fetched per pass by the PMC counters, profiles/r03_b_pmc_512_chunked.json).
-template <int DIR, bool NT>
+// DICT (see LineDict): L and DR point at the table of distinct lines, reached from the byte offset of the column's row; x and y stream as before.
+template <int DIR, bool NT, bool DICT = false>
 __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ x, double *__restrict__ y, double Ta,
                                                      const double *__restrict__ L, const double *__restrict__ DR, const double *__restrict__ D0,
                                                      int n, long sl, long outer_stride, int nx, int TX, int NS, int last,
-                                                     double *__restrict__ partials, const CgScalars *__restrict__ cg, int xcd)
+                                                     double *__restrict__ partials, const CgScalars *__restrict__ cg, int xcd, LineDict ld = LineDict())
 {
+    static_assert(!DICT || NT, "line tables: next to the streaming instantiations only");
     extern __shared__ double sm[];
     if (cg && cg->done) return;
     constexpr int SEG = 8;
@@ -1520,6 +1618,8 @@ __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ 
     const unsigned ob = (unsigned)(((long)by * outer_stride + ix) * 8);   // byte offset of the line's first cell
     const long lineid = (long)by * nx + ix;
     const bool need_dot = last && partials;
+    unsigned tb = 0;                                             // DICT: byte offset of this column's row in the table
+    if (DICT) tb = valid ? (unsigned)ld.id[lineid] * (unsigned)ld.pitch * 8u : 0u;
     double xv[SEG + 1], Lv[SEG + 1], Rv[SEG], w[SEG], yo[SEG];
     double zin = 0.0, dinv_s = 0.0, zc = 0.0, dot = 0.0;
     // ---- forward sweeps, chunk 0 then chunk 1
@@ -1533,11 +1633,16 @@ __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ 
             // the overlap cell (i == SEG) is the next segment's first: a plain load keeps that line for it.  Two statements, not a
             // ternary on i: before the loop is unrolled a ternary is one load in each arm of a branch, which the optimiser merges
             // into a single load WITHOUT the hint (that is what round 2's kernels ran: every load of x was a plain one)
-            if (i < SEG) { xv[i] = ok ? ldo<NT>(x, a) : 0.0; Lv[i] = ok ? ldo<NT>(L, a) : 0.0; Rv[i] = ok ? ldo<NT>(DR, a) : 0.0; }
+            if (DICT) {
+                const unsigned ta = tb + (unsigned)(c0 + i) * 8u;
+                if (i < SEG) { xv[i] = ok ? ldo<NT>(x, a) : 0.0; Lv[i] = ok ? ldo<false>(L, ta) : 0.0; Rv[i] = ok ? ldo<false>(DR, ta) : 0.0; }
+                else { xv[i] = ok ? ldo<false>(x, a) : 0.0; Lv[i] = ok ? ldo<false>(L, ta) : 0.0; }
+            } else if (i < SEG) { xv[i] = ok ? ldo<NT>(x, a) : 0.0; Lv[i] = ok ? ldo<NT>(L, a) : 0.0; Rv[i] = ok ? ldo<NT>(DR, a) : 0.0; }
             else { xv[i] = ok ? ldo<false>(x, a) : 0.0; Lv[i] = ok ? ldo<false>(L, a) : 0.0; }
         }
         double ds = 0.0;
-        if (valid && c0 < n) ds = c0 == 0 ? D0[lineid] : ldo<false>(DR, o0 - slb);
+        if (DICT) { if (valid && c0 < n) ds = c0 == 0 ? D0[lineid] : ldo<false>(DR, tb + (unsigned)(c0 - 1) * 8u); }
+        else if (valid && c0 < n) ds = c0 == 0 ? D0[lineid] : ldo<false>(DR, o0 - slb);
         if (ch) __syncthreads();                                 // chunk 0's summaries and carry have been consumed
         double P = 1.0, lz = 0.0;
 #pragma unroll
@@ -1576,7 +1681,8 @@ __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ 
             Lv[SEG] = seg < NS - 1 ? pL[(seg + 1) * SEG * TX + ixl] : sL1[ixl];   // written before the barriers in between
             zin = pZ[si];
             dinv_s = 0.0;
-            if (valid && c0 < n) dinv_s = c0 == 0 ? D0[lineid] : ldo<false>(DR, o0 - slb);
+            if (DICT) { if (valid && c0 < n) dinv_s = c0 == 0 ? D0[lineid] : ldo<false>(DR, tb + (unsigned)(c0 - 1) * 8u); }
+            else if (valid && c0 < n) dinv_s = c0 == 0 ? D0[lineid] : ldo<false>(DR, o0 - slb);
         }
 #pragma unroll
         for (int i = 0; i < SEG; ++i) yo[i] = (valid && c0 + i < n) ? ldo<NT>(y, o0 + (unsigned)i * slb) : 0.0;
