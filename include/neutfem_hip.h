@@ -237,6 +237,35 @@ typedef struct nf_zoom_result {
  * changes: flux, warm state, history and nf_progress stay as they are.  Undivided meshes only (NF_ERR_UNSUPPORTED). */
 int nf_zoom_resolved(nf_handle h, const nf_keff_opts *opts, int rx, int ry, int rz, int adjoint, double keff, nf_handle *fine, nf_zoom_result *res);
 
+/* ---- sensitivity maps (no counterpart in the reference) ----------------------------------------------------------------
+ * First-order perturbation theory on the built operator: with phi the current flux (nf_get_phi), phi+ the adjoint flux (nf_get_phi_adj),
+ * the eigenvalue keff, j_g = A_g^-1 B^T phi_g and j+_g = A_g^-1 B^T phi+_g (the line solves of nf_get_J), W_p(e) = detJ(e) C-hat_pp the
+ * mass weight of a unit cross section (|e| at P0),
+ *   m[g,g',e] = sum_p phi+_g[e,p] W_p(e) phi_g'[e,p]
+ *   a[g,e]    = sum_d geometric factor_d(e) j+_loc^T A-hat_d j_loc over the cell's local current DOFs of direction d
+ *   b[g,e]    = sum over the Dirichlet boundary faces f of e and their transverse modes of I_f(a) j+_{f,a} j_{f,a} (the build adds I_f(a) 2 D)
+ *   Nrm       = sum_{g,g',e} chi_g(e) nuSigf_g'(e) m[g,g',e] = phi+^T F phi,      c = -keff^2 / Nrm
+ * the maps are the absolute derivatives dk/dp of every cross section of every cell:
+ *   dSigR[g,e] = c m[g,g,e]                      dSigS[g<-g',e] = -c m[g,g',e] (g != g'; 0 for g = g': the solver never reads the diagonal)
+ *   dNSF[g',e] = -(c/keff) sum_g chi_g(e) m[g,g',e]          dChi[g,e] = -(c/keff) sum_g' nuSigf_g'(e) m[g,g',e]
+ *   dD[g,e]    = c (a[g,e] / D_g(e)^2 - 2 b[g,e])
+ * dD, dSigR, dNSF, dChi: ng N doubles [g*N + e]; dSigS: ng ng N doubles [(g_to*ng + g_from)*N + e] (the layouts of nf_upload_xs).  The
+ * 1e-14 drop thresholds of the build (chi / k, the scatter blocks, the RT0 line entries) are ignored: the maps describe the operator
+ * without them, and always the full operator (never the diagonal model).
+ * The outputs are DEVICE buffers; any of them may be NULL and is then skipped (the others come out bit-identical).  res (may be NULL)
+ * receives Nrm, the keff used and the cell count.  The call changes no state of the handle and is deterministic.
+ * Errors: not built -> NF_ERR_STATE; no adjoint flux (nf_solve_adjoint or nf_set_phi_adj first) -> NF_ERR_STATE; keff non-finite or <= 0 ->
+ * NF_ERR_ARG; Nrm non-finite or zero -> NF_ERR_NUMERIC (the outputs are then untouched); slabs and multi-rank teams -> NF_ERR_UNSUPPORTED
+ * (the z currents cross slabs), and meshes of 2^32 cells or more.  nf_set_option "sens_grid" = blocks of 256 threads per launch (default 1024; the
+ * kernels walk larger meshes with a grid stride). */
+typedef struct nf_sens_result {
+    double norm;                /* Nrm = phi+^T F phi */
+    double keff;                /* the eigenvalue the maps were scaled with */
+    long n_cells;               /* N */
+} nf_sens_result;
+int nf_sensitivity(nf_handle h, double keff, double *dD_dev, double *dSigR_dev, double *dNSF_dev, double *dChi_dev, double *dSigS_dev,
+                   nf_sens_result *res);
+
 /* NeutFEM::SolveCoarse (src/NeutFEM.cpp:2380-2611): returns k_coarse and the prolonged flux
  * (ng*n_phi doubles, host) without touching the fine solution. */
 int nf_solve_coarse(nf_handle h, const nf_keff_opts *opts, double *k_coarse, double *phi_host);

@@ -14,7 +14,7 @@ SYMBOLS = [
     "nf_last_error", "nf_device_count", "nf_create", "nf_destroy", "nf_create_slab", "nf_link_slabs", "nf_comm_unique_id",
     "nf_comm_init", "nf_comm_info", "nf_comm_selftest", "nf_team_schur_apply", "nf_info", "nf_set_bc", "nf_upload_xs", "nf_build",
     "nf_schur_apply", "nf_solve_group", "nf_build_diagonal_cache", "nf_get_diagonal_cache", "nf_solve_keff",
-    "nf_upload_source", "nf_solve_subcritical", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_apply_plan", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_project_flux", "nf_project_power", "nf_refine", "nf_zoom_source", "nf_get_source", "nf_set_phi_adj", "nf_zoom_resolved", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
+    "nf_upload_source", "nf_solve_subcritical", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_apply_plan", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_project_flux", "nf_project_power", "nf_refine", "nf_zoom_source", "nf_get_source", "nf_set_phi_adj", "nf_zoom_resolved", "nf_sensitivity", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
     "nf_get_warm_state", "nf_get_history", "nf_profile_get", "nf_profile_reset", "nf_time_schur_apply", "nf_time_device_copy", "nf_progress", "nf_set_progress_callback", "nf_local_matrices",
     "nf_set_option", "nf_mem_info", "nf_dev_alloc", "nf_dev_free", "nf_memcpy_h2d", "nf_memcpy_d2h", "nf_synchronize", "nf_stream",
 ]
@@ -38,6 +38,12 @@ class SubcritResult(C.Structure):
 class ZoomResult(C.Structure):
     _fields_ = [("source", C.c_double), ("phi_int", C.c_double), ("production", C.c_double),
                 ("n_outer", C.c_int), ("cg_total", C.c_int), ("converged", C.c_int), ("n_cells", C.c_long)]
+
+    def as_dict(self): return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class SensResult(C.Structure):
+    _fields_ = [("norm", C.c_double), ("keff", C.c_double), ("n_cells", C.c_long)]
 
     def as_dict(self): return {name: getattr(self, name) for name, _ in self._fields_}
 
@@ -87,6 +93,7 @@ def load():
     L.nf_get_source.argtypes = [vp, dp]
     L.nf_set_phi_adj.argtypes = [vp, dp]
     L.nf_zoom_resolved.argtypes = [vp, C.POINTER(KeffOpts), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(vp), C.POINTER(ZoomResult)]
+    L.nf_sensitivity.argtypes = [vp, C.c_double, vp, vp, vp, vp, vp, C.POINTER(SensResult)]
     L.nf_set_phi.argtypes = [vp, dp]
     L.nf_get_phi.argtypes = [vp, dp]
     L.nf_get_J.argtypes = [vp, dp]
@@ -289,6 +296,23 @@ class HipSolver:
         h, res = C.c_void_p(), ZoomResult()
         self._chk(self.L.nf_zoom_resolved(self.h, C.byref(o), r[0], r[1], r[2], int(adjoint), float(keff), C.byref(h), C.byref(res)))
         return self._adopt(h), res.as_dict()
+
+    SENS_MAPS = ("D", "SigR", "NSF", "Chi", "SigS")
+
+    def sensitivity(self, keff, which=SENS_MAPS):
+        """nf_sensitivity: the maps dk/dXS per cell named in `which` as host arrays -- "D", "SigR", "NSF", "Chi": (ng, cells), "SigS":
+        (ng, ng, cells) [g_to, g_from] -- plus "result": the nf_sens_result as a dict.  Maps not asked for are not computed"""
+        bad = [w for w in which if w not in self.SENS_MAPS]
+        if bad: raise ValueError(f"sensitivity: unknown map {bad[0]!r} (known: {self.SENS_MAPS})")
+        bufs = {w: DeviceVector(self, self.ng * self.ne * (self.ng if w == "SigS" else 1)) for w in self.SENS_MAPS if w in which}
+        res = SensResult()
+        try:
+            self._chk(self.L.nf_sensitivity(self.h, float(keff), *[bufs[w].ptr if w in bufs else None for w in self.SENS_MAPS], C.byref(res)))
+            out = {w: b.download().reshape((self.ng, self.ng, self.ne) if w == "SigS" else (self.ng, self.ne)) for w, b in bufs.items()}
+        finally:
+            for b in bufs.values(): b.free()
+        out["result"] = res.as_dict()
+        return out
 
     def prolong_from(self, coarse): self._chk(self.L.nf_prolong(coarse.h, self.h))
 

@@ -3,7 +3,7 @@
 //
 // The class keeps what the reference keeps on the host -- cross-section arrays, flux, tolerances,
 // BC map, warm-start flags -- and hands the hot path (BuildMatrices, SolveKeff, SolveCoarse,
-// build_diagonal_cache, SolveSubcritical, project_flux, project_power, zoom_resolved) to the HIP library.  There is NO CPU fallback:
+// build_diagonal_cache, SolveSubcritical, project_flux, project_power, zoom_resolved, sensitivity_maps) to the HIP library.  There is NO CPU fallback:
 // without a HIP device those methods raise RuntimeError.  The reflector methods the reference binds are accepted and ignored.
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -341,6 +341,46 @@ public:
         return d;
     }
 
+    // sensitivity_maps (extension): dk/dXS per cell by first-order perturbation theory (nf_sensitivity) with k = last_keff_
+    // and the fields of the host mirrors Phi_ / PhiAdj_, pushed to the device the way zoom_resolved pushes them.  A dict of arrays shaped
+    // like get_D() .. get_SigS(); changes neither mirror.
+    py::dict SensitivityMaps()
+    {
+        if (!h_) throw std::runtime_error("sensitivity_maps: call BuildMatrices() first (there is no CPU fallback)");
+        if (!has_valid_keff_ || !has_valid_adjoint_)
+            throw std::runtime_error(std::string("sensitivity_maps: call ") + (!has_valid_keff_ ? "SolveKeff()" : "SolveAdjoint()") +
+                                     " first (the maps need a solved flux, a solved adjoint flux and k-eff)");
+        Log(VerbosityLevel::NORMAL, "\n=== CARTES DE SENSIBILITE (dk/dXS) ===");
+        chk(nf_set_phi(h_, Phi_.data())); chk(nf_set_phi_adj(h_, PhiAdj_.data()));
+        const size_t n1 = (size_t)ng_ * ne_, n2 = n1 * ng_;
+        struct DevBuf { nf_handle h; void *p = nullptr; ~DevBuf() { if (p) nf_dev_free(h, p); } } buf{h_};
+        chk(nf_dev_alloc(h_, (4 * n1 + n2) * sizeof(double), &buf.p));
+        double *d = static_cast<double *>(buf.p);
+        nf_sens_result r{};
+        chk(nf_sensitivity(h_, last_keff_, d, d + n1, d + 2 * n1, d + 3 * n1, d + 4 * n1, &r));
+        std::vector<py::ssize_t> shape; shape.push_back(ng_);
+        if (dim_ >= 3) shape.push_back(nz_);
+        if (dim_ >= 2) shape.push_back(ny_);
+        shape.push_back(nx_);
+        std::vector<py::ssize_t> shape2(shape); shape2.insert(shape2.begin(), ng_);
+        py::dict out;
+        const char *names[5] = { "D", "SigR", "NSF", "Chi", "SigS" };
+        for (int i = 0; i < 5; ++i) {
+            py::array_t<double> a(i == 4 ? shape2 : shape);
+            chk(nf_memcpy_d2h(h_, a.mutable_data(), d + (size_t)i * n1, (i == 4 ? n2 : n1) * sizeof(double)));
+            out[names[i]] = a;
+        }
+        sens_ = r; has_sens_ = true;
+        return out;
+    }
+    py::dict GetSensitivityInfo() const
+    {
+        if (!has_sens_) throw std::runtime_error("get_sensitivity_info: call sensitivity_maps() first");
+        py::dict d;
+        d["norm"] = sens_.norm; d["keff"] = sens_.keff; d["n_cells"] = sens_.n_cells;
+        return d;
+    }
+
     // ---- numpy views (src/NeutFEM.cpp:2626-2730) ---------------------------------------------------
     py::array_t<double> view(std::vector<double> &v, bool sigs = false)
     {
@@ -416,6 +456,7 @@ private:
     bool has_valid_keff_ = false, has_valid_adjoint_ = false;
     nf_subcrit_result subcrit_{}; bool has_subcrit_ = false;     // the last SolveSubcritical (get_subcritical_info)
     nf_zoom_result zoom_{}; bool has_zoom_ = false;               // the last zoom_resolved (get_zoom_info)
+    nf_sens_result sens_{}; bool has_sens_ = false;               // the last sensitivity_maps (get_sensitivity_info)
 };
 
 PYBIND11_MODULE(_neutfem_eigen, m)
@@ -497,5 +538,8 @@ PYBIND11_MODULE(_neutfem_eigen, m)
         .def("zoom_resolved", &NeutFEM::ZoomResolved, py::arg("refine"), py::arg("adjoint") = false,
              "re-solve on the mesh refined by [rx, ry, rz] with the coarse fission source frozen: fine cell means (ng, [NZ,] [NY,] NX)")
         .def("get_zoom_info", &NeutFEM::GetZoomInfo,
-             "extension: the last zoom_resolved's nf_zoom_result as a dict (source, phi_int, production, n_outer, cg_total, converged, n_cells)");
+             "extension: the last zoom_resolved's nf_zoom_result as a dict (source, phi_int, production, n_outer, cg_total, converged, n_cells)")
+        .def("sensitivity_maps", &NeutFEM::SensitivityMaps,
+             "extension: dk/dXS per cell from the solved flux, the solved adjoint flux and GetLastKeff(): {'D', 'SigR', 'NSF', 'Chi', 'SigS'} shaped like get_D() .. get_SigS()")
+        .def("get_sensitivity_info", &NeutFEM::GetSensitivityInfo, "extension: the last sensitivity_maps' nf_sens_result as a dict (norm, keff, n_cells)");
 }

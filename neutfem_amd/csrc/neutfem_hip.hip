@@ -188,6 +188,7 @@ struct nf_team {
     // fused-direction CG (two launches per iteration) up to this many cells.  Measured crossover against the four-launch lean path after
     // the round-2 latency work: 64^3 19.1 vs 27.2 us per CG iteration, 80^3 39.1 vs 34.5, 128^3 77.7 vs 70.9, 160^3 221 vs 150
     int opt_fuse3 = 1; long fuse3_max_cells = 400000;
+    int opt_sens_grid = RED_GRID;                         // blocks of the nf_sensitivity launches (grid stride beyond; option "sens_grid")
     // whole CG solve in one launch on the workgroups of one XCD (k_cg_xcd): RT0-P0 meshes between the one-workgroup resident kernel and
     // xcd_max_cells.  One XCD has an eighth of the chip's compute units and L2 (4 MiB): beyond that the launch path wins back.
     int opt_cgx = 1, opt_keffx = 1, xcd_id = 0, xcd_groups = 32, last_xcd = 0; long xcd_min_cells = 2000, xcd_max_cells = 28000, xcd_solves = 0, xcd_refused = 0;
@@ -2398,6 +2399,30 @@ static int team_reconstruct_Jz_diag(nf_team *T)
     return NF_OK;
 }
 
+// The current of one group's field into dJ (nJ doubles, the reference DOF order): dJ zeroed, then one k_flux_to_J launch per direction
+// d < ndirs and transverse mode that sees a phi moment.  field_g: nphi doubles in the device layout (the raw flux of the last solve for
+// nf_get_J, any field for nf_sensitivity); diag: the diagonal-path formula
+static int flux_to_J(nf_solver *S, int g, const double *field_g, double *dJ, int ndirs, int diag, hipStream_t st)
+{
+    const long N = S->N, nJ = S->nJ;
+    Geom G = make_geom(S);
+    int nfa = 1, ni = S->k; for (int t = 1; t < S->dim; ++t) { nfa *= S->k + 1; ni *= S->k + 1; }
+    const long nJface = S->nJx + S->nJy + S->nJz;
+    const long foff[3] = { 0, S->nJx, S->nJx + S->nJy };
+    HIPCHK(hipMemsetAsync(dJ, 0, (size_t)nJ * sizeof(double), st));                         // modes that see no phi moment stay 0
+    for (int d = 0; d < ndirs; ++d)
+        for (int mode = 0; mode < n_modes(S); ++mode) {
+            ModeArgs ma = mode_args(S, g, d, mode, field_g, const_cast<double *>(field_g));
+            // transverse mode index in the RT numbering: a = sum a_t (k+1)^t over the transverse axes (FEM.cpp:364-374)
+            int amode = 0, q = mode, mul = 1;
+            for (int t = 0; t < S->dim; ++t) { if (t == d) continue; amode += (q % S->n1) * mul; q /= S->n1; mul *= S->k + 1; }
+            hipLaunchKernelGGL(k_flux_to_J, dim3((unsigned)((S->nlines[d] + 63) / 64)), dim3(64), 0, st, G, ma, S->nb, amode, nfa, ni,
+                               S->d_D + g * N, S->d_L[d] + g * N, S->d_DR[d] + g * N, S->d_D0[d] + g * S->nlines[d],
+                               dJ + foff[d], dJ + nJface + (long)d * N * ni, S->nlines[d], diag);
+        }
+    return NF_OK;
+}
+
 int nf_get_J(nf_handle S, double *J_host)
 {
     if (!S || !J_host) return fail(NF_ERR_ARG, "nf_get_J: bad arguments");
@@ -2414,22 +2439,11 @@ int nf_get_J(nf_handle S, double *J_host)
         else NFCHK(team_reconstruct_Jz(S->team));
     }
     DevTmp<double> dJ_; NFCHK(dalloc(&dJ_.p, (size_t)nJ)); double *dJ = dJ_.p;
-    Geom G = make_geom(S);
-    int nfa = 1, ni = S->k; for (int t = 1; t < S->dim; ++t) { nfa *= S->k + 1; ni *= S->k + 1; }
+    int ni = S->k; for (int t = 1; t < S->dim; ++t) ni *= S->k + 1;
     const long nJface = S->nJx + S->nJy + S->nJz;
     const long foff[3] = { 0, S->nJx, S->nJx + S->nJy };
     for (int g = 0; g < S->ng; ++g) {
-        HIPCHK(hipMemsetAsync(dJ, 0, (size_t)nJ * sizeof(double), st));                     // modes that see no phi moment stay 0
-        for (int d = 0; d < (slab ? 2 : S->dim); ++d)
-            for (int mode = 0; mode < n_modes(S); ++mode) {
-                ModeArgs ma = mode_args(S, g, d, mode, S->d_raw + (size_t)g * S->nphi, S->d_raw + (size_t)g * S->nphi);
-                // transverse mode index in the RT numbering: a = sum a_t (k+1)^t over the transverse axes (FEM.cpp:364-374)
-                int amode = 0, q = mode, mul = 1;
-                for (int t = 0; t < S->dim; ++t) { if (t == d) continue; amode += (q % S->n1) * mul; q /= S->n1; mul *= S->k + 1; }
-                hipLaunchKernelGGL(k_flux_to_J, dim3((unsigned)((S->nlines[d] + 63) / 64)), dim3(64), 0, st, G, ma, S->nb, amode, nfa, ni,
-                                   S->d_D + g * N, S->d_L[d] + g * N, S->d_DR[d] + g * N, S->d_D0[d] + g * S->nlines[d],
-                                   dJ + foff[d], dJ + nJface + (long)d * N * ni, S->nlines[d], S->raw_is_diag ? 1 : 0);
-            }
+        NFCHK(flux_to_J(S, g, S->d_raw + (size_t)g * S->nphi, dJ, slab ? 2 : S->dim, S->raw_is_diag ? 1 : 0, st));
         if (slab) {
             HIPCHK(hipMemcpyAsync(dJ + foff[2], S->d_Jz + (size_t)g * S->nJz, S->nJz * sizeof(double), hipMemcpyDeviceToDevice, st));
             if (ni > 0 && !S->raw_is_diag && S->d_Jzb)
@@ -4000,6 +4014,79 @@ int nf_zoom_resolved(nf_handle S, const nf_keff_opts *o, int rx, int ry, int rz,
     return NF_OK;
 }
 
+// ---- sensitivity maps: dk/dXS per cell from the current flux, the adjoint flux and an eigenvalue -----------------------
+// one launch of a kernel template <DIM, M> over the handle's order: NF_SENS_DM(k_sens_norm, part) / NF_SENS_DM(k_sens_mass, sc, maps...)
+#define NF_SENS_FIELDS(S) (const double *)(S)->d_phi, (const double *)(S)->d_phi_adj, (const double *)(S)->d_Chi, (const double *)(S)->d_NSF, \
+                          (const double *)(S)->d_hx, (const double *)(S)->d_hy, (const double *)(S)->d_hz, (S)->nx, (S)->ny, (S)->N, (S)->nphi, (S)->ng
+#define NF_SENS_M(KERNEL, DIM, ...) do { \
+        if (S->m == 0) hipLaunchKernelGGL((KERNEL<DIM, 0>), dim3(grid), dim3(256), 0, st, NF_SENS_FIELDS(S), __VA_ARGS__); \
+        else if (S->m == 1) hipLaunchKernelGGL((KERNEL<DIM, 1>), dim3(grid), dim3(256), 0, st, NF_SENS_FIELDS(S), __VA_ARGS__); \
+        else hipLaunchKernelGGL((KERNEL<DIM, 2>), dim3(grid), dim3(256), 0, st, NF_SENS_FIELDS(S), __VA_ARGS__); } while (0)
+#define NF_SENS_DM(KERNEL, ...) do { \
+        if (S->dim == 1) NF_SENS_M(KERNEL, 1, __VA_ARGS__); else if (S->dim == 2) NF_SENS_M(KERNEL, 2, __VA_ARGS__); else NF_SENS_M(KERNEL, 3, __VA_ARGS__); } while (0)
+static void launch_sens_norm(const nf_solver *S, int grid, hipStream_t st, double *part) { NF_SENS_DM(k_sens_norm, part); }
+static void launch_sens_mass(const nf_solver *S, int grid, hipStream_t st, const double *sc, double *dSigR, double *dNSF, double *dChi, double *dSigS)
+{
+    NF_SENS_DM(k_sens_mass, sc, dSigR, dNSF, dChi, dSigS);
+}
+#undef NF_SENS_DM
+#undef NF_SENS_M
+#undef NF_SENS_FIELDS
+template <int DIM>
+static void launch_sens_current_d(const nf_solver *S, int grid, hipStream_t st, const Geom &G, const SensJ &O, const double *j, const double *ja,
+                                  const double *D, const double *sc, double *dD)
+{
+    if (S->k == 0) hipLaunchKernelGGL((k_sens_current<DIM, 0>), dim3(grid), dim3(256), 0, st, G, O, j, ja, D, sc, S->N, dD);
+    else if (S->k == 1) hipLaunchKernelGGL((k_sens_current<DIM, 1>), dim3(grid), dim3(256), 0, st, G, O, j, ja, D, sc, S->N, dD);
+    else hipLaunchKernelGGL((k_sens_current<DIM, 2>), dim3(grid), dim3(256), 0, st, G, O, j, ja, D, sc, S->N, dD);
+}
+int nf_sensitivity(nf_handle S, double keff, double *dD, double *dSigR, double *dNSF, double *dChi, double *dSigS, nf_sens_result *res)
+{
+    if (!S) return fail(NF_ERR_ARG, "nf_sensitivity: bad arguments");
+    if (!std::isfinite(keff) || !(keff > 0.0)) return fail(NF_ERR_ARG, "nf_sensitivity: keff must be finite and positive (got %g)", keff);
+    if (!team_is_single(S->team)) return fail(NF_ERR_UNSUPPORTED, "nf_sensitivity works on an undivided mesh (the z currents cross slabs: slab teams and multi-rank teams are not supported)");
+    if (S->N > 0xFFFFFFFFL) return fail(NF_ERR_UNSUPPORTED, "nf_sensitivity: %ld cells (the kernels index cells with 32 bits)", S->N);
+    if (!S->built) return fail(NF_ERR_STATE, "nf_sensitivity: call nf_build first");
+    if (!S->d_phi_adj) return fail(NF_ERR_STATE, "nf_sensitivity: no adjoint flux (nf_solve_adjoint or nf_set_phi_adj first)");
+    HIPCHK(hipSetDevice(S->device));
+    (void)hipGetLastError();
+    hipStream_t st = S->team->stream;
+    const long N = S->N;
+    const int ng = S->ng, grid = grid_for(N, 256, S->team->opt_sens_grid);
+    DevTmp<double> part; NFCHK(dalloc(&part.p, (size_t)grid + 3));     // the blocks' shares of Nrm, then Nrm, c, -c / k
+    double *sc = part.p + grid;
+    launch_sens_norm(S, grid, st, part.p);
+    hipLaunchKernelGGL(k_sens_scalars, dim3(1), dim3(256), 0, st, (const double *)part.p, grid, keff, sc);
+    double nrm = 0.0;
+    HIPCHK(hipMemcpyAsync(&nrm, sc, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    if (!std::isfinite(nrm) || nrm == 0.0)
+        return fail(NF_ERR_NUMERIC, "nf_sensitivity: the normalisation phi+^T F phi = %g is not usable (orthogonal, zero or non-finite fields, or no fission)", nrm);
+    if (dSigR || dNSF || dChi || dSigS) launch_sens_mass(S, grid, st, sc, dSigR, dNSF, dChi, dSigS);
+    DevTmp<double> J, Ja;
+    if (dD) {
+        NFCHK(dalloc(&J.p, (size_t)S->nJ)); NFCHK(dalloc(&Ja.p, (size_t)S->nJ));
+        const Geom G = make_geom(S);
+        int ni = S->k; for (int t = 1; t < S->dim; ++t) ni *= S->k + 1;
+        const long nJface = S->nJx + S->nJy + S->nJz;
+        SensJ O; O.foff[0] = 0; O.foff[1] = S->nJx; O.foff[2] = S->nJx + S->nJy;
+        for (int d = 0; d < 3; ++d) O.boff[d] = nJface + (long)d * N * ni;
+        for (int g = 0; g < ng; ++g) {                            // group by group: two temporaries of nJ doubles
+            NFCHK(flux_to_J(S, g, S->d_phi + (size_t)g * S->nphi, J.p, S->dim, 0, st));
+            NFCHK(flux_to_J(S, g, S->d_phi_adj + (size_t)g * S->nphi, Ja.p, S->dim, 0, st));
+            const double *Dg = S->d_D + (size_t)g * N; double *out = dD + (size_t)g * N;
+            if (S->dim == 1) launch_sens_current_d<1>(S, grid, st, G, O, J.p, Ja.p, Dg, sc, out);
+            else if (S->dim == 2) launch_sens_current_d<2>(S, grid, st, G, O, J.p, Ja.p, Dg, sc, out);
+            else launch_sens_current_d<3>(S, grid, st, G, O, J.p, Ja.p, Dg, sc, out);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));                             // the temporaries are freed on return
+    if (res) { res->norm = nrm; res->keff = keff; res->n_cells = N; }
+    return NF_OK;
+}
+
 int nf_get_history(nf_handle S, double *k, double *dk, double *dphi, int *cg, int cap)
 {
     if (!S) return fail(NF_ERR_ARG, "null handle");
@@ -4225,6 +4312,7 @@ int nf_set_option(nf_handle S, const char *key, long value)
     else if (!strcmp(key, "cg_xcd_groups")) T->xcd_groups = (int)std::max<long>(1, std::min<long>(value, 64));
     else if (!strcmp(key, "cg_fuse3_max_cells")) T->fuse3_max_cells = value;
     else if (!strcmp(key, "cg_lean_grid")) T->opt_lean_grid = (int)std::max(1L, std::min(1024L, value));
+    else if (!strcmp(key, "sens_grid")) T->opt_sens_grid = (int)std::max(1L, std::min(65536L, value));
     else return fail(NF_ERR_ARG, "nf_set_option: unknown key %s", key);
     // options that move a mesh into or out of the streaming kernels: look again at the next apply (a mesh whose lines do not repeat pays the
     // fingerprints and the host sort once per build, not once per option)

@@ -4012,6 +4012,180 @@ __global__ __launch_bounds__(256) void k_zoom_total(const double *__restrict__ p
     if (threadIdx.x == 0) *out = s;
 }
 
+// ---- sensitivity maps: dk/dXS per cell from the direct and the adjoint flux (nf_sensitivity) ------------------------------
+// With m[g,g',e] = sum_p phi+_g[e,p] W_p(e) phi_g'[e,p], W_p(e) = |e| / prod_t (2 p_t + 1) (the build's mass weight detJ C-hat_pp of a unit
+// cross section), Nrm = phi+^T F phi = sum chi_g nuSigf_g' m[g,g',e] and c = -k^2 / Nrm.  The build's 1e-14 drop thresholds (chi / k, the
+// scatter blocks, the RT0 cell_a entries) are ignored: the maps are the derivatives of the operator without them.
+// (ix, iy, iz) of cell e by 32-bit division (nf_sensitivity refuses meshes of 2^32 cells or more)
+__device__ __forceinline__ void sens_cell(long e, int nx, int ny, int &ix, int &iy, int &iz)
+{
+    const unsigned u = (unsigned)e, row = u / (unsigned)nx;
+    ix = (int)(u - row * (unsigned)nx); iz = (int)(row / (unsigned)ny); iy = (int)(row - (unsigned)iz * (unsigned)ny);
+}
+template <int DIM>
+__device__ __forceinline__ double sens_volume(const double *__restrict__ hx, const double *__restrict__ hy, const double *__restrict__ hz, int ix, int iy, int iz)
+{
+    return hx[ix] * (DIM >= 2 ? hy[iy] : 1.0) * (DIM == 3 ? hz[iz] : 1.0);
+}
+// 1 / prod_t (2 p_t + 1) of moment p = i + n1 j + n1^2 k (a constant once the loop over p is unrolled)
+template <int DIM, int M>
+__device__ __forceinline__ double sens_ch(int p)
+{
+    constexpr int n1 = M + 1;
+    const int i = p % n1, j = DIM >= 2 ? (p / n1) % n1 : 0, k = DIM == 3 ? p / (n1 * n1) : 0;
+    return 1.0 / (double)((2 * i + 1) * (2 * j + 1) * (2 * k + 1));
+}
+// Nrm factorises: sum_{e,p} W_p (sum_g chi_g phi+_g)[e,p] (sum_g' nuSigf_g' phi_g')[e,p].  part[block] = the block's share; k_sens_scalars
+// adds the shares in a fixed order (the two-stage pattern of every reduction here: the total is reproducible)
+template <int DIM, int M>
+__global__ __launch_bounds__(256) void k_sens_norm(const double *__restrict__ phi, const double *__restrict__ adj, const double *__restrict__ chi,
+                                                   const double *__restrict__ nsf, const double *__restrict__ hx, const double *__restrict__ hy,
+                                                   const double *__restrict__ hz, int nx, int ny, long N, long nphi, int ng, double *__restrict__ part)
+{
+    __shared__ double sred[4];
+    constexpr int n1 = M + 1, nloc = n1 * (DIM >= 2 ? n1 : 1) * (DIM == 3 ? n1 : 1);
+    double tot = 0.0;
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < N; e += gridDim.x * 256L) {
+        int ix, iy, iz; sens_cell(e, nx, ny, ix, iy, iz);
+        const double vol = sens_volume<DIM>(hx, hy, hz, ix, iy, iz);
+        double s1[nloc], s2[nloc];
+#pragma unroll
+        for (int p = 0; p < nloc; ++p) { s1[p] = 0.0; s2[p] = 0.0; }
+        for (int g = 0; g < ng; ++g) {
+            const double cg = chi[(long)g * N + e], fg = nsf[(long)g * N + e];
+            const double *a = adj + (long)g * nphi + e, *f = phi + (long)g * nphi + e;
+#pragma unroll
+            for (int p = 0; p < nloc; ++p) { s1[p] += cg * a[(long)p * N]; s2[p] += fg * f[(long)p * N]; }
+        }
+        double v = 0.0;
+#pragma unroll
+        for (int p = 0; p < nloc; ++p) v += (vol * sens_ch<DIM, M>(p)) * (s1[p] * s2[p]);
+        tot += v;
+    }
+    tot = block_sum(tot, sred);
+    if (threadIdx.x == 0) part[blockIdx.x] = tot;
+}
+// one block: sc[0] = Nrm (the n shares added in a fixed order), sc[1] = c = -k^2 / Nrm, sc[2] = -c / k; they stay on the device for the
+// map kernels (the host reads sc[0] for the result struct and the error check only)
+__global__ __launch_bounds__(256) void k_sens_scalars(const double *__restrict__ part, int n, double keff, double *__restrict__ sc)
+{
+    __shared__ double sred[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) s += part[i];
+    s = block_sum(s, sred);
+    if (threadIdx.x == 0) { const double c = -(keff * keff) / s; sc[0] = s; sc[1] = c; sc[2] = -c / keff; }
+}
+// One thread per cell, one streaming pass: dSigR[g,e] = c m[g,g,e], dSigS[(g*ng+g')*N+e] = -c m[g,g',e] (0 for g' = g: the solver never
+// reads the diagonal), dNSF[g',e] = -(c/k) sum_p W_p phi_g'[p] s1[p], dChi[g,e] = -(c/k) sum_p W_p phi+_g[p] s2[p] with the factorised sums
+// s1 = sum_g chi_g phi+_g, s2 = sum_g' nuSigf_g' phi_g' (formed once per cell: the ng^2 products only where dSigS asks for them).  Fields in
+// the device SoA layout [g*nphi + p*N + e]: consecutive lanes read and write consecutive doubles in every stream.  Every output is written
+// once, already scaled by the device-resident c, with non-temporal stores; a NULL output is skipped (the others are computed by the same
+// instructions: they come out bit-identical).  ng is a run-time loop: a group's coefficients are read again (from L2) when dSigS pairs it
+// with another group.
+template <int DIM, int M>
+__global__ __launch_bounds__(256) void k_sens_mass(const double *__restrict__ phi, const double *__restrict__ adj, const double *__restrict__ chi,
+                                                   const double *__restrict__ nsf, const double *__restrict__ hx, const double *__restrict__ hy,
+                                                   const double *__restrict__ hz, int nx, int ny, long N, long nphi, int ng,
+                                                   const double *__restrict__ sc, double *__restrict__ dSigR, double *__restrict__ dNSF,
+                                                   double *__restrict__ dChi, double *__restrict__ dSigS)
+{
+    constexpr int n1 = M + 1, nloc = n1 * (DIM >= 2 ? n1 : 1) * (DIM == 3 ? n1 : 1);
+    const double c = sc[1], ck = sc[2];
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < N; e += gridDim.x * 256L) {
+        int ix, iy, iz; sens_cell(e, nx, ny, ix, iy, iz);
+        const double vol = sens_volume<DIM>(hx, hy, hz, ix, iy, iz);
+        double s1[nloc], s2[nloc];
+#pragma unroll
+        for (int p = 0; p < nloc; ++p) { s1[p] = 0.0; s2[p] = 0.0; }
+        if (dNSF || dChi)
+            for (int g = 0; g < ng; ++g) {
+                const double cg = chi[(long)g * N + e], fg = nsf[(long)g * N + e];
+                const double *a = adj + (long)g * nphi + e, *f = phi + (long)g * nphi + e;
+#pragma unroll
+                for (int p = 0; p < nloc; ++p) { s1[p] += cg * a[(long)p * N]; s2[p] += fg * f[(long)p * N]; }
+            }
+        for (int g = 0; g < ng; ++g) {
+            const double *a = adj + (long)g * nphi + e, *f = phi + (long)g * nphi + e;
+            double wa[nloc];                                      // W_p phi+_g[p], kept for the pairs of dSigS
+            double mgg = 0.0, vn = 0.0, vc = 0.0;
+#pragma unroll
+            for (int p = 0; p < nloc; ++p) {
+                const double w = vol * sens_ch<DIM, M>(p), fp = f[(long)p * N];
+                wa[p] = w * a[(long)p * N];
+                mgg += wa[p] * fp; vn += (w * fp) * s1[p]; vc += wa[p] * s2[p];
+            }
+            if (dSigR) __builtin_nontemporal_store(c * mgg, dSigR + (long)g * N + e);
+            if (dNSF) __builtin_nontemporal_store(ck * vn, dNSF + (long)g * N + e);
+            if (dChi) __builtin_nontemporal_store(ck * vc, dChi + (long)g * N + e);
+            if (dSigS)
+                for (int gp = 0; gp < ng; ++gp) {
+                    double v = 0.0;
+                    if (gp != g) {
+                        const double *fo = phi + (long)gp * nphi + e;
+#pragma unroll
+                        for (int p = 0; p < nloc; ++p) v += wa[p] * fo[(long)p * N];
+                        v = -c * v;
+                    }
+                    __builtin_nontemporal_store(v, dSigS + ((long)g * ng + gp) * N + e);
+                }
+        }
+    }
+}
+// One thread per cell and one group per launch: dD[e] = c (a / D(e)^2 - 2 b) from the two currents j = A^-1 B^T phi_g and j+ = A^-1 B^T phi+_g
+// in the reference DOF order (k_flux_to_J; its sign cancels in every product).  Per direction d the 2 nf + ni local current DOFs decouple
+// into one chain of 2 + K unknowns (lower face, upper face, K bubbles) per transverse mode a, coupled by T_a times the 1-D matrix of
+// {(1-s)/2, (1+s)/2, (1-s^2) P_l(s)} (src/FEM.cpp:891-924, exact under the reference's quadrature):
+//   a = sum_d factor_d(e) sum_a T_a j+_a^T A1 j_a,   A1 = [[2/3, 1/3, 2/3, -2/15], [1/3, 2/3, 2/3, 2/15], [2/3, 2/3, 16/15, 0], [-2/15, 2/15, 0, 16/105]]
+//   b = sum over the Dirichlet boundary faces f of e and their modes of I_f(a) j+_{f,a} j_{f,a},  I_f(a) = T_a dirichlet_term / (2 D)
+// Face DOF (face, a) at face*nfa + a in the direction's face block (offsets foff), bubble (l, a) of cell e at e*ni + l + K a in its bubble
+// block; the faces of consecutive cells of a row are consecutive in x and a row apart in y / z: all three directions are read coalesced
+// across ix (with stride nfa doubles).  dD is written once, non-temporally.
+struct SensJ { long foff[3]; long boff[3]; };
+template <int DIM, int K>
+__global__ __launch_bounds__(256) void k_sens_current(Geom G, SensJ O, const double *__restrict__ j, const double *__restrict__ ja,
+                                                      const double *__restrict__ D, const double *__restrict__ sc, long N, double *__restrict__ dD)
+{
+    constexpr int nfa = (DIM >= 2 ? K + 1 : 1) * (DIM == 3 ? K + 1 : 1), ni = K * nfa;
+    constexpr int UNR = nfa <= 3 ? nfa : 1;                       // 3D, K >= 1: the 4 / 9 modes one after the other (unrolled they hold 196 / 490 registers)
+    const double c = sc[1];
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < N; e += gridDim.x * 256L) {
+        int ix, iy, iz; sens_cell(e, G.nx, G.ny, ix, iy, iz);
+        double av = 0.0, bv = 0.0;
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) {
+            const long flo = cmfd_face(G, d, ix, iy, iz);
+            const long fhi = flo + (d == 0 ? 1L : d == 1 ? (long)G.nx : (long)G.nx * G.ny);
+            const int ci = d == 0 ? ix : d == 1 ? iy : iz, n = d == 0 ? G.nx : d == 1 ? G.ny : G.nz;
+            const bool dlo = ci == 0 && G.dir_lo[d], dhi = ci == n - 1 && G.dir_hi[d];
+            const double area = d == 0 ? G.hy[iy] * G.hz[iz] : d == 1 ? G.hx[ix] * G.hz[iz] : G.hx[ix] * G.hy[iy];
+            const double I = DIM == 1 ? 1.0 : DIM == 2 ? 2.0 / area : 4.0 / area;
+            double q = 0.0, bq = 0.0;
+#pragma unroll UNR
+            for (int a = 0; a < nfa; ++a) {
+                const double Ta = DIM == 1 ? 1.0 : DIM == 2 ? 2.0 / (2 * a + 1) : (2.0 / (2 * (a % (K + 1)) + 1)) * (2.0 / (2 * (a / (K + 1)) + 1));
+                const double uL = j[O.foff[d] + flo * nfa + a], uR = j[O.foff[d] + fhi * nfa + a];
+                const double vL = ja[O.foff[d] + flo * nfa + a], vR = ja[O.foff[d] + fhi * nfa + a];
+                double t = vL * (2.0 / 3.0 * uL + 1.0 / 3.0 * uR) + vR * (1.0 / 3.0 * uL + 2.0 / 3.0 * uR);
+                if (K >= 1) {
+                    const long bo = O.boff[d] + e * ni + K * a;
+                    const double u0 = j[bo], v0 = ja[bo];
+                    t += 2.0 / 3.0 * ((vL + vR) * u0 + v0 * (uL + uR)) + 16.0 / 15.0 * (v0 * u0);
+                    if (K >= 2) {
+                        const double u1 = j[bo + 1], v1 = ja[bo + 1];
+                        t += 2.0 / 15.0 * ((vR - vL) * u1 + v1 * (uR - uL)) + 16.0 / 105.0 * (v1 * u1);
+                    }
+                }
+                q += Ta * t;
+                bq += Ta * ((dlo ? vL * uL : 0.0) + (dhi ? vR * uR : 0.0));
+            }
+            av += geom_factor(G, d, ix, iy, iz) * q;
+            bv += I * bq;
+        }
+        const double De = D[e];
+        __builtin_nontemporal_store(c * (av / (De * De) - 2.0 * bv), dD + e);
+    }
+}
+
 // fill with a deterministic pseudo-random pattern (profiling helper)
 __global__ void k_fill_pattern(double *__restrict__ v, long n)
 {
