@@ -301,7 +301,8 @@ int nf_timers(nf_handle h, char *json_buf, size_t len);
  * line; NS of the chunked kernel), "grid" [x, y, z], "block", "nt" (streaming loads), "p2" (two load phases), "zw" (the pass's share
  * of x.y in the z.w form), "xcd_order" (the XCD-contiguous tile order is requested) and "xcd_permutes" (requested, and the tile count
  * is a multiple of 8 beyond 8: tiles really move), "fold" (accumulation pass of a slab: it forms the separator values
- * itself) and "dict" (the pass reads its line factors from the table of distinct lines, see "line_dict"); at the top level "line_dict":
+ * itself), "dict" (the pass reads its line factors from the table of distinct lines, see "line_dict") and "early" (level of early vector
+ * loads of a table-backed chunked pass, option "c_early"; 0 for every other pass); at the top level "line_dict":
  * {"x", "y", "z"}, the distinct lines of the largest group per direction (0: no table in use).  Built from the predicates the launch functions
  * themselves call.  The one thing it does besides reporting: where the next apply would first build the tables of distinct lines
  * (once per build), the report builds them, since whether a direction verifies is part of the plan; otherwise it launches nothing
@@ -372,7 +373,11 @@ int nf_time_device_copy(nf_handle h, size_t bytes, int reps, double *gbps);
  *   "line_dict_dirs" (default 7): bit 0 = x, bit 1 = y, bit 2 = z; "line_dict_max_bytes" (default 524288): cap of one group's table of one
  *   direction; "line_dict_fp_bits" (default 128, tests only): low bits of the fingerprint that are kept, so that collisions can be made.
  *   Changing any option drops the tables; nf_apply_plan reports "dict" per pass and "line_dict": {"x", "y", "z"} = distinct lines of the
- *   largest group (0: the direction streams).
+ *   largest group (0: the direction streams);
+ *   "c_early" (default -1): the chunked y / z pass on its table (family c with "dict") requests the vector loads of its tile ahead of the
+ *   sweeps that hide them: 1 = x of both chunks in one round trip, 2 = also y of the upper chunk before that chunk's forward sweep and y of the
+ *   lower chunk before the backward half, 0 = each load where it is used, -1 = the level that measurably gains.  Only loads
+ *   move: the results are bit-identical at every level.  nf_apply_plan reports the level per pass as "early".
  * nf_info keys beyond the mesh sizes: "last_path" (0 host-driven outer loop, 1 diagonal device loop, 2 resident kernel, 3 one-XCD kernel),
  * "last_direct" (0 CG as configured, 1 dense S^-1, 2 CG to 1e-14 standing in), "line_dict_rejected" (mask of the directions whose table the
  * bit-for-bit verification refused: a fingerprint collision, not an error), "line_dict_bytes" (device memory of the tables and line ids). */

@@ -184,6 +184,7 @@ struct nf_team {
     // tables are 12 - 110 KB); line_dict_fp_bits < 128 truncates the fingerprints so that tests can make them collide
     int opt_line_dict = -1, line_dict_dirs = 7, line_dict_fp_bits = 128; long line_dict_max_bytes = 512L * 1024;
     int opt_s_long = -1, s_long_min = 256;                // chunked long-line pass (k_schur_c): -1 auto (lines longer than s_long_min), 0 off, 1 always
+    int opt_c_early = -1;                                 // its table-backed form: vector loads of both chunks issued up front (k_schur_c EARLY): -1 auto (C_EARLY_AUTO), 0, 1, 2
     size_t lds_limit = 160 * 1024;                        // dynamic LDS a block may ask for (hipDeviceAttributeMaxSharedMemoryPerBlock at team creation)
     // fused-direction CG (two launches per iteration) up to this many cells.  Measured crossover against the four-launch lean path after
     // the round-2 latency work: 64^3 19.1 vs 27.2 us per CG iteration, 80^3 39.1 vs 34.5, 128^3 77.7 vs 70.9, 160^3 221 vs 150
@@ -1337,6 +1338,9 @@ static unsigned c_block(const ChunkPlan &cp) { return (unsigned)((cp.TX * cp.NS 
 static const int C_SEG = 8, C_NCH = 2;                           // k_schur_c: segments of 8 cells, two chunks per block (chunk_plan's NS counts 16 cells)
 static bool c_nt(const nf_solver *S) { return nt_regime(S); }
 static bool c_dict(const nf_solver *S, int d, bool nt) { return nt && dict_dir(S, d); }
+static const int C_EARLY_AUTO = 2;                               // what c_early = -1 resolves to
+// early vector loads of the chunked kernel (k_schur_c EARLY): the table-backed passes only, 0 for every other pass
+static int c_early(const nf_solver *S, bool dict) { const int e = S->team->opt_c_early; return dict ? (e < 0 ? C_EARLY_AUTO : e) : 0; }
 static int c_xcd(const nf_solver *S, int d, bool nt) { const nf_team *T = S->team; return T->opt_xcd >= 0 ? (T->opt_xcd >> (d - 1)) & 1 : (d == 1 && nt); }
 // one-chunk kernel (k_schur_s).  XCD-contiguous tile order: bit 0 = y passes, bit 1 = z passes; -1 (default) = the y passes of meshes in the streaming
 // regime -- the 8 x tiles of a row set then run on one XCD back to back (256^3: y 133 -> 123 us, 501 -> 493 us per CG iteration;
@@ -1484,13 +1488,16 @@ static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const 
 #define NF_C(DIRV, NTV) do { if (lds_opt_in((const void *)k_schur_c<DIRV, NTV>, ldsc)) { \
             hipLaunchKernelGGL((k_schur_c<DIRV, NTV>), grid, block, ldsc, T->stream, ma.x[0], ma.y[0], ma.Ta, L, DR, D0, n, sl, ostride, S->nx, TXc, NS, last, partials, cg, xcd); \
             launched = hipGetLastError() == hipSuccess; } } while (0)   /* a refused launch (LDS, block size) falls through to the one-chunk kernel */
-#define NF_CD(DIRV) do { if (lds_opt_in((const void *)k_schur_c<DIRV, true, true>, ldsc)) { \
-            hipLaunchKernelGGL((k_schur_c<DIRV, true, true>), grid, block, ldsc, T->stream, ma.x[0], ma.y[0], ma.Ta, da.L, da.DR, D0, n, sl, ostride, S->nx, TXc, NS, last, partials, cg, xcd, da.ld); \
+#define NF_CDE(DIRV, EV) do { if (lds_opt_in((const void *)k_schur_c<DIRV, true, true, EV>, ldsc)) { \
+            hipLaunchKernelGGL((k_schur_c<DIRV, true, true, EV>), grid, block, ldsc, T->stream, ma.x[0], ma.y[0], ma.Ta, da.L, da.DR, D0, n, sl, ostride, S->nx, TXc, NS, last, partials, cg, xcd, da.ld); \
             launched = hipGetLastError() == hipSuccess; } } while (0)
+#define NF_CD(DIRV) do { if (early == 2) NF_CDE(DIRV, 2); else if (early == 1) NF_CDE(DIRV, 1); else NF_CDE(DIRV, 0); } while (0)
             const DictArgs da = dict_args(S, d, g, c_dict(S, d, nt));
+            const int early = c_early(S, da.on);
             if (da.on) { if (d == 1) NF_CD(1); else NF_CD(2); }
             else if (d == 1) { if (nt) NF_C(1, true); else NF_C(1, false); } else { if (nt) NF_C(2, true); else NF_C(2, false); }
 #undef NF_CD
+#undef NF_CDE
 #undef NF_C
             if (launched) { if (nparts) *nparts = (int)(grid.x * grid.y); return NF_OK; }
         }
@@ -1755,13 +1762,13 @@ int nf_team_schur_apply(nf_handle S, int g, const double *const *x_dev, double *
 // endpoint_w_taken, the cg_* forms, split_dot, xy_overlap, x_dict / c_dict / s_dict); apart from building the tables of distinct lines where the next
 // apply would (line_dict_prepare) it launches nothing and writes no state.  The one thing it cannot know is a device
 // that refuses the chunked kernel's LDS at launch time (launch_s then falls back to the one-chunk kernel).
-struct PlanPass { const char *dir, *family; int mode, SEG, NCH, TX, NSEG; dim3 grid; unsigned block; bool nt, p2, zw, order; unsigned tiles; bool fold = false, dict = false; };
+struct PlanPass { const char *dir, *family; int mode, SEG, NCH, TX, NSEG; dim3 grid; unsigned block; bool nt, p2, zw, order; unsigned tiles; bool fold = false, dict = false; int early = 0; };
 static void plan_emit(std::string &js, const PlanPass &p)
 {
-    char tmp[384];
+    char tmp[416];
     snprintf(tmp, sizeof tmp, "%s{\"dir\": \"%s\", \"mode\": %d, \"family\": \"%s\", \"SEG\": %d, \"NCH\": %d, \"TX\": %d, \"NSEG\": %d, \"grid\": [%u, %u, %u], "
-             "\"block\": %u, \"nt\": %d, \"p2\": %d, \"zw\": %d, \"xcd_order\": %d, \"xcd_permutes\": %d, \"fold\": %d, \"dict\": %d}", js.back() == '[' ? "" : ", ", p.dir, p.mode, p.family,
-             p.SEG, p.NCH, p.TX, p.NSEG, p.grid.x, p.grid.y, p.grid.z, p.block, p.nt ? 1 : 0, p.p2 ? 1 : 0, p.zw ? 1 : 0, p.order ? 1 : 0, xcd_permutes(p.order, p.tiles) ? 1 : 0, p.fold ? 1 : 0, p.dict ? 1 : 0);
+             "\"block\": %u, \"nt\": %d, \"p2\": %d, \"zw\": %d, \"xcd_order\": %d, \"xcd_permutes\": %d, \"fold\": %d, \"dict\": %d, \"early\": %d}", js.back() == '[' ? "" : ", ", p.dir, p.mode, p.family,
+             p.SEG, p.NCH, p.TX, p.NSEG, p.grid.x, p.grid.y, p.grid.z, p.block, p.nt ? 1 : 0, p.p2 ? 1 : 0, p.zw ? 1 : 0, p.order ? 1 : 0, xcd_permutes(p.order, p.tiles) ? 1 : 0, p.fold ? 1 : 0, p.dict ? 1 : 0, p.early);
     js += tmp;
 }
 static int plan_s(std::string &js, const nf_solver *S, int d, int zmode, bool want_dot, bool zw_dot)   // a launch_s call
@@ -1770,7 +1777,7 @@ static int plan_s(std::string &js, const nf_solver *S, int d, int zmode, bool wa
     const ChunkPlan cp = pass_chunk_plan(S, d, zmode);
     if (c_taken(cp, want_dot, zw_dot)) {
         const dim3 gr = c_grid(S, d, cp); const bool nt = c_nt(S);
-        plan_emit(js, { dir, "c", zmode, C_SEG, C_NCH, cp.TX, cp.NS, gr, c_block(cp), nt, false, want_dot, c_xcd(S, d, nt) != 0, gr.x * gr.y, false, c_dict(S, d, nt) });
+        plan_emit(js, { dir, "c", zmode, C_SEG, C_NCH, cp.TX, cp.NS, gr, c_block(cp), nt, false, want_dot, c_xcd(S, d, nt) != 0, gr.x * gr.y, false, c_dict(S, d, nt), c_early(S, c_dict(S, d, nt)) });
         return NF_OK;
     }
     const SegPlan sp = seg_plan(S, d, zmode);
@@ -4277,6 +4284,7 @@ int nf_set_option(nf_handle S, const char *key, long value)
     else if (!strcmp(key, "s_long_dirs")) T->opt_s_long_dirs = (int)(value & 3);
     else if (!strcmp(key, "s_long_min_y")) T->s_long_min_y = (int)std::max(1L, std::min(1000000L, value));
     else if (!strcmp(key, "s_long_min")) T->s_long_min = (int)std::max(1L, std::min(1000000L, value));
+    else if (!strcmp(key, "c_early")) T->opt_c_early = value < 0 ? -1 : (int)std::min(2L, value);
     else if (!strcmp(key, "line_dict") || !strcmp(key, "line_dict_dirs") || !strcmp(key, "line_dict_max_bytes") || !strcmp(key, "line_dict_fp_bits")) {
         if (!strcmp(key, "line_dict")) T->opt_line_dict = value < 0 ? -1 : (value > 0 ? 1 : 0);
         else if (!strcmp(key, "line_dict_dirs")) T->line_dict_dirs = (int)(value & 7);

@@ -1592,13 +1592,20 @@ __global__ __launch_bounds__(256) void k_endpoint_w(double *__restrict__ p, doub
 // two-chunk body inside the 128 registers of a 1024-thread block (with 64-bit addresses it spilled 10-12 registers to scratch,
 // +31 % bytes written and +6 % fetched per pass by the PMC counters, profiles/r03_b_pmc_512_chunked.json).
 // DICT (see LineDict): L and DR point at the table of distinct lines, reached from the byte offset of the column's row; x and y stream as before.
-template <int DIR, bool NT, bool DICT = false>
+// EARLY (table instantiations only: without L and 1/d to stream they have the registers for it): the block's own vector loads go out ahead of
+// the sweeps that hide them, instead of one dependent HBM round trip per chunk and half.  1: x of chunk 1 is requested right behind chunk 0's
+// loads (chunk 0 first, so that a counted wait lets its sweep start on its own data); 2: also y of chunk 1 before the barrier of chunk 1's
+// forward sweep and y of chunk 0 before the first barrier of the backward half.  Same predicates, same hints, no arithmetic moves: the bits
+// of y and of the dot product are those of EARLY = 0.  The tile, the grid and the LDS layout stay as they are.
+template <int DIR, bool NT, bool DICT = false, int EARLY = 0>
 __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ x, double *__restrict__ y, double Ta,
                                                      const double *__restrict__ L, const double *__restrict__ DR, const double *__restrict__ D0,
                                                      int n, long sl, long outer_stride, int nx, int TX, int NS, int last,
                                                      double *__restrict__ partials, const CgScalars *__restrict__ cg, int xcd, LineDict ld = LineDict())
 {
     static_assert(!DICT || NT, "line tables: next to the streaming instantiations only");
+    static_assert(EARLY == 0 || DICT, "early loads: the table instantiations only (the streaming one would carry L and 1/d of chunk 1 too: beyond 128 registers)");
+    static_assert(EARLY >= 0 && EARLY <= 2, "early loads: levels 0, 1, 2");
     extern __shared__ double sm[];
     if (cg && cg->done) return;
     constexpr int SEG = 8;
@@ -1621,8 +1628,10 @@ __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ 
     unsigned tb = 0;                                             // DICT: byte offset of this column's row in the table
     if (DICT) tb = valid ? (unsigned)ld.id[lineid] * (unsigned)ld.pitch * 8u : 0u;
     double xv[SEG + 1], Lv[SEG + 1], Rv[SEG], w[SEG], yo[SEG];
+    double x1[EARLY >= 1 ? SEG + 1 : 1], y0[EARLY >= 2 ? SEG : 1];   // EARLY: x of chunk 1, y of chunk 0, in flight under the sweeps before their use
     double zin = 0.0, dinv_s = 0.0, zc = 0.0, dot = 0.0;
-    // ---- forward sweeps, chunk 0 then chunk 1
+    // ---- forward sweeps, chunk 0 then chunk 1 (both ch loops unrolled: the early arrays must stay in registers)
+#pragma unroll
     for (int ch = 0; ch < 2; ++ch) {
         const int c0 = ch * CH + seg * SEG;
         const unsigned o0 = ob + (unsigned)c0 * slb;
@@ -1633,7 +1642,11 @@ __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ 
             // the overlap cell (i == SEG) is the next segment's first: a plain load keeps that line for it.  Two statements, not a
             // ternary on i: before the loop is unrolled a ternary is one load in each arm of a branch, which the optimiser merges
             // into a single load WITHOUT the hint (that is what round 2's kernels ran: every load of x was a plain one)
-            if (DICT) {
+            if (DICT && EARLY >= 1 && ch == 1) {                 // x came with chunk 0's loads
+                const unsigned ta = tb + (unsigned)(c0 + i) * 8u;
+                xv[i] = x1[i]; Lv[i] = ok ? ldo<false>(L, ta) : 0.0;
+                if (i < SEG) Rv[i] = ok ? ldo<false>(DR, ta) : 0.0;
+            } else if (DICT) {
                 const unsigned ta = tb + (unsigned)(c0 + i) * 8u;
                 if (i < SEG) { xv[i] = ok ? ldo<NT>(x, a) : 0.0; Lv[i] = ok ? ldo<false>(L, ta) : 0.0; Rv[i] = ok ? ldo<false>(DR, ta) : 0.0; }
                 else { xv[i] = ok ? ldo<false>(x, a) : 0.0; Lv[i] = ok ? ldo<false>(L, ta) : 0.0; }
@@ -1643,6 +1656,20 @@ __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ 
         double ds = 0.0;
         if (DICT) { if (valid && c0 < n) ds = c0 == 0 ? D0[lineid] : ldo<false>(DR, tb + (unsigned)(c0 - 1) * 8u); }
         else if (valid && c0 < n) ds = c0 == 0 ? D0[lineid] : ldo<false>(DR, o0 - slb);
+        if (EARLY >= 1 && ch == 0) {                             // chunk 1's x behind chunk 0's loads: same predicate, same hints, two statements
+#pragma unroll
+            for (int i = 0; i <= SEG; ++i) {
+                const int c1 = CH + seg * SEG + i;
+                const bool ok = valid && c1 < n;
+                const unsigned a = ob + (unsigned)c1 * slb;
+                if (i < SEG) x1[i] = ok ? ldo<NT>(x, a) : 0.0;
+                else x1[i] = ok ? ldo<false>(x, a) : 0.0;
+            }
+        }
+        if (EARLY >= 2 && ch == 1) {                             // chunk 1's y: lands under this sweep, consumed by the backward one
+#pragma unroll
+            for (int i = 0; i < SEG; ++i) yo[i] = (valid && c0 + i < n) ? ldo<NT>(y, o0 + (unsigned)i * slb) : 0.0;
+        }
         if (ch) __syncthreads();                                 // chunk 0's summaries and carry have been consumed
         double P = 1.0, lz = 0.0;
 #pragma unroll
@@ -1668,6 +1695,11 @@ __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ 
     }
     // ---- backward sweeps and output, chunk 1 (still in registers) then chunk 0 (from LDS)
     double ucar = 0.0;
+    if (EARLY >= 2) {                                            // chunk 0's y: lands under chunk 1's backward sweep
+#pragma unroll
+        for (int i = 0; i < SEG; ++i) { const int c = seg * SEG + i; y0[i] = (valid && c < n) ? ldo<NT>(y, ob + (unsigned)c * slb) : 0.0; }
+    }
+#pragma unroll
     for (int ch = 1; ch >= 0; --ch) {
         const int c0 = ch * CH + seg * SEG;
         const unsigned o0 = ob + (unsigned)c0 * slb;
@@ -1685,7 +1717,10 @@ __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ 
             else if (valid && c0 < n) dinv_s = c0 == 0 ? D0[lineid] : ldo<false>(DR, o0 - slb);
         }
 #pragma unroll
-        for (int i = 0; i < SEG; ++i) yo[i] = (valid && c0 + i < n) ? ldo<NT>(y, o0 + (unsigned)i * slb) : 0.0;
+        for (int i = 0; i < SEG; ++i) {
+            if (EARLY < 2) yo[i] = (valid && c0 + i < n) ? ldo<NT>(y, o0 + (unsigned)i * slb) : 0.0;
+            else if (ch == 0) yo[i] = y0[i];
+        }
         __syncthreads();                                         // the summaries of the previous sweep have been consumed
         double Q = 1.0, lu = 0.0;
 #pragma unroll
