@@ -266,6 +266,42 @@ typedef struct nf_sens_result {
 int nf_sensitivity(nf_handle h, double keff, double *dD_dev, double *dSigR_dev, double *dNSF_dev, double *dChi_dev, double *dSigS_dev,
                    nf_sens_result *res);
 
+/* ---- lambda-modes: the leading eigenpairs by block power iteration (no counterpart in the reference) -------------------
+ * With K0 = blockdiag(S_g) - Ms and F = chi (x) Mf (the matrices of nf_solve_subcritical): the n_modes largest eigenvalues
+ * k0 >= k1 >= ... of K0 phi = (1/k) F phi with their eigenvectors; adjoint = 1: K0^T phi+ = (1/k) F^T phi+ (chi and nuSigf swap roles,
+ * transposed scatter blocks, groups swept in descending order).  Subspace iteration with a Rayleigh-Ritz step on A = K0^-1 F over a
+ * block of n_block = n_modes + n_guard vectors (guard vectors speed the convergence up -- the rate is k[n_block] / k[n_modes - 1] -- and
+ * are not returned); the start block is deterministic (cosine harmonics of the cell index).  Stops when the invariant-subspace residual
+ * of the wanted block, max_i ||(Z_m - Q_m H_mm)_i|| / |k_i|, is below tol_flux and max_i |k_i - k_i,prev| below tol_keff, or after
+ * max_outer outers (NF_OK, converged = 0).  Reads tol_keff, tol_flux, max_outer, max_inner, use_diagonal_solver (RT0-P0), solver_type,
+ * solver_type_pushed from opts -- the group solver is the one nf_solve_keff picks; use_coarse_init / use_cmfd must be 0 (NF_ERR_ARG).
+ * 1 <= n_modes, n_modes + n_guard <= NF_MODES_MAX <= the number of cells, else NF_ERR_ARG.  Undivided meshes only (slab teams and
+ * multi-rank teams: NF_ERR_UNSUPPORTED, before any collective), and no upscatter block (NF_ERR_UNSUPPORTED: the Gauss-Seidel sweep
+ * would lag those terms and the iteration operator would no longer be K0^-1 F).  A block that loses rank (A has fewer than n_block
+ * independent directions) -> NF_ERR_NUMERIC.  A complex pair among the wanted modes at the stop: converged = 0, the pair's two vectors
+ * span its plane, both k are the real part and both residuals the plane's.
+ * Each returned mode has unit L2 norm over all groups and DOFs and the sign that makes sum Mf phi >= 0 (adjoint: the M_chi sum; where
+ * that sum is below 1e-10 sum |Mf phi| the sign is what the iteration left).  Nothing else of h changes: current flux, adjoint flux,
+ * warm state, history and nf_progress stay as they are.  The modes live on the handle until the next nf_build, nf_upload_xs or
+ * nf_destroy; direct and adjoint modes are kept side by side.  Device memory during the call: 2 n_block ng n_phi doubles. */
+#define NF_MODES_MAX 8
+typedef struct nf_modes_result {
+    double k[NF_MODES_MAX];        /* eigenvalues, descending; k[0] is k-eff */
+    double residual[NF_MODES_MAX]; /* ||A phi_i - k_i phi_i|| / ||k_i phi_i||, A = K0^-1 F, of the returned vectors, from the last outer */
+    double dominance_ratio;        /* k[1]/k[0]; 0 with n_modes == 1 */
+    int n_modes, n_block, n_outer, cg_total, converged;
+} nf_modes_result;
+int nf_solve_modes(nf_handle h, const nf_keff_opts *opts, int n_modes, int n_guard, int adjoint, nf_modes_result *res);
+/* mode i of the last nf_solve_modes of that kind (adjoint = 0 / 1) in the host DOF layout of nf_get_phi, all groups; NF_ERR_STATE before one */
+int nf_get_mode(nf_handle h, int i, int adjoint, double *phi_host);
+/* The two streaming kernels of the block iteration on their own, for blocks of b <= NF_MODES_MAX device vectors of length n, column-major
+ * with leading dimension n.  nf_block_gram: QtZ = Q^T Z and ZtZ = Z^T Z (full symmetric), b x b, column-major, in one pass.
+ * nf_block_rotate: Q <- Z C in place of Q (C: b x b, column-major) and, with the old Q in the same pass, res2[j] = the squared norm of
+ * column j of Z_m - Q_m H (H: m x m, column-major; m <= b; m = 0: no residual, H_host / res2_host may be NULL).  Sums are formed in a
+ * fixed order: the results are deterministic. */
+int nf_block_gram(nf_handle h, int b, long n, const double *Q_dev, const double *Z_dev, double *QtZ_host, double *ZtZ_host);
+int nf_block_rotate(nf_handle h, int b, int m, long n, double *Q_dev, const double *Z_dev, const double *C_host, const double *H_host, double *res2_host);
+
 /* NeutFEM::SolveCoarse (src/NeutFEM.cpp:2380-2611): returns k_coarse and the prolonged flux
  * (ng*n_phi doubles, host) without touching the fine solution. */
 int nf_solve_coarse(nf_handle h, const nf_keff_opts *opts, double *k_coarse, double *phi_host);

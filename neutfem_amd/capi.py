@@ -14,7 +14,7 @@ SYMBOLS = [
     "nf_last_error", "nf_device_count", "nf_create", "nf_destroy", "nf_create_slab", "nf_link_slabs", "nf_comm_unique_id",
     "nf_comm_init", "nf_comm_info", "nf_comm_selftest", "nf_team_schur_apply", "nf_info", "nf_set_bc", "nf_upload_xs", "nf_build",
     "nf_schur_apply", "nf_solve_group", "nf_build_diagonal_cache", "nf_get_diagonal_cache", "nf_solve_keff",
-    "nf_upload_source", "nf_solve_subcritical", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_apply_plan", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_project_flux", "nf_project_power", "nf_refine", "nf_zoom_source", "nf_get_source", "nf_set_phi_adj", "nf_zoom_resolved", "nf_sensitivity", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
+    "nf_upload_source", "nf_solve_subcritical", "nf_solve_modes", "nf_get_mode", "nf_block_gram", "nf_block_rotate", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_apply_plan", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_project_flux", "nf_project_power", "nf_refine", "nf_zoom_source", "nf_get_source", "nf_set_phi_adj", "nf_zoom_resolved", "nf_sensitivity", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
     "nf_get_warm_state", "nf_get_history", "nf_profile_get", "nf_profile_reset", "nf_time_schur_apply", "nf_time_device_copy", "nf_progress", "nf_set_progress_callback", "nf_local_matrices",
     "nf_set_option", "nf_mem_info", "nf_dev_alloc", "nf_dev_free", "nf_memcpy_h2d", "nf_memcpy_d2h", "nf_synchronize", "nf_stream",
 ]
@@ -33,6 +33,19 @@ class SubcritResult(C.Structure):
                 ("n_outer", C.c_int), ("n_outer_nofission", C.c_int), ("cg_total", C.c_int), ("converged", C.c_int)]
 
     def as_dict(self): return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+MODES_MAX = 8
+
+
+class ModesResult(C.Structure):
+    _fields_ = [("k", C.c_double * MODES_MAX), ("residual", C.c_double * MODES_MAX), ("dominance_ratio", C.c_double),
+                ("n_modes", C.c_int), ("n_block", C.c_int), ("n_outer", C.c_int), ("cg_total", C.c_int), ("converged", C.c_int)]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["k"], d["residual"] = list(self.k)[:self.n_modes], list(self.residual)[:self.n_modes]
+        return d
 
 
 class ZoomResult(C.Structure):
@@ -83,6 +96,10 @@ def load():
     L.nf_solve_keff.argtypes = [vp, C.POINTER(KeffOpts), dp, ip]
     L.nf_upload_source.argtypes = [vp, dp]
     L.nf_solve_subcritical.argtypes = [vp, C.POINTER(KeffOpts), C.POINTER(SubcritResult)]
+    L.nf_solve_modes.argtypes = [vp, C.POINTER(KeffOpts), C.c_int, C.c_int, C.c_int, C.POINTER(ModesResult)]
+    L.nf_get_mode.argtypes = [vp, C.c_int, C.c_int, dp]
+    L.nf_block_gram.argtypes = [vp, C.c_int, C.c_long, vp, vp, dp, dp]
+    L.nf_block_rotate.argtypes = [vp, C.c_int, C.c_int, C.c_long, vp, vp, dp, dp, dp]
     L.nf_solve_coarse.argtypes = [vp, C.POINTER(KeffOpts), dp, dp]
     L.nf_solve_adjoint.argtypes = [vp, C.POINTER(KeffOpts), C.c_int, C.c_int, dp, ip]
     L.nf_get_phi_adj.argtypes = [vp, dp]
@@ -252,6 +269,44 @@ class HipSolver:
         r = SubcritResult()
         self._chk(self.L.nf_solve_subcritical(self.h, C.byref(o), C.byref(r)))
         return r.as_dict()
+
+    def solve_modes(self, n_modes, n_guard=2, adjoint=False, use_diag=False, use_coarse=False, factors=(), use_cmfd=False):
+        """nf_solve_modes with the tolerances / linear solver of this object: the n_modes leading lambda-modes by block power iteration
+        over n_modes + n_guard vectors; the result struct as a dict, k and residual as lists (use_coarse / use_cmfd are refused)"""
+        o = self.opts(use_coarse, factors, use_diag, False, use_cmfd)
+        r = ModesResult()
+        self._chk(self.L.nf_solve_modes(self.h, C.byref(o), int(n_modes), int(n_guard), int(adjoint), C.byref(r)))
+        return r.as_dict()
+
+    def get_mode(self, i, adjoint=False):
+        """mode i of the last solve_modes of that kind, (ng, n_phi) in the host DOF layout of get_phi; unit L2 norm"""
+        out = np.empty(self.ng * self.n_phi); self._chk(self.L.nf_get_mode(self.h, int(i), int(adjoint), _dp(out))); return out.reshape(self.ng, self.n_phi)
+
+    def block_gram(self, Q, Z):
+        """nf_block_gram on two host blocks of shape (n, b): (Q^T Z, Z^T Z), both (b, b)"""
+        Q, Z = (np.asfortranarray(a, dtype=np.float64) for a in (Q, Z)); n, b = Q.shape; assert Z.shape == (n, b)
+        qd, zd = self.vector(n * b).upload(Q.ravel(order="F")), self.vector(n * b).upload(Z.ravel(order="F"))
+        H, G = np.empty(b * b), np.empty(b * b)
+        try:
+            self._chk(self.L.nf_block_gram(self.h, b, n, qd.ptr, zd.ptr, _dp(H), _dp(G)))
+        finally:
+            qd.free(); zd.free()
+        return H.reshape(b, b).T.copy(), G.reshape(b, b).T.copy()
+
+    def block_rotate(self, Q, Z, Cm, H=None):
+        """nf_block_rotate on two host blocks of shape (n, b): (Z C, squared column norms of Z_m - Q_m H) with m = len(H) (None: m = 0)"""
+        Q, Z = (np.asfortranarray(a, dtype=np.float64) for a in (Q, Z)); n, b = Q.shape; assert Z.shape == (n, b)
+        Cm = np.ascontiguousarray(np.asarray(Cm, dtype=np.float64).T).ravel(); assert Cm.size == b * b      # column-major
+        m = 0 if H is None else len(H)
+        Hm = np.ascontiguousarray(np.asarray(H, dtype=np.float64).T).ravel() if m else np.zeros(1)
+        qd, zd = self.vector(n * b).upload(Q.ravel(order="F")), self.vector(n * b).upload(Z.ravel(order="F"))
+        res2 = np.zeros(max(m, 1))
+        try:
+            self._chk(self.L.nf_block_rotate(self.h, b, m, n, qd.ptr, zd.ptr, _dp(Cm), _dp(Hm) if m else None, _dp(res2) if m else None))
+            out = qd.download().reshape(b, n).T.copy()
+        finally:
+            qd.free(); zd.free()
+        return out, res2[:m]
 
     def _adopt(self, h):
         """a HipSolver over a handle the library derived from this one (nf_coarsen, nf_refine, nf_zoom_resolved)"""

@@ -3,7 +3,7 @@
 //
 // The class keeps what the reference keeps on the host -- cross-section arrays, flux, tolerances,
 // BC map, warm-start flags -- and hands the hot path (BuildMatrices, SolveKeff, SolveCoarse,
-// build_diagonal_cache, SolveSubcritical, project_flux, project_power, zoom_resolved, sensitivity_maps) to the HIP library.  There is NO CPU fallback:
+// build_diagonal_cache, SolveSubcritical, SolveModes, project_flux, project_power, zoom_resolved, sensitivity_maps) to the HIP library.  There is NO CPU fallback:
 // without a HIP device those methods raise RuntimeError.  The reflector methods the reference binds are accepted and ignored.
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -198,6 +198,47 @@ public:
         d["M"] = r.M; d["k_source"] = r.k_source; d["ratio"] = r.ratio; d["phi_int"] = r.phi_int; d["phi_int_nofission"] = r.phi_int_nofission;
         d["production"] = r.production; d["source"] = r.source; d["n_outer"] = r.n_outer; d["n_outer_nofission"] = r.n_outer_nofission;
         d["cg_total"] = r.cg_total; d["converged"] = r.converged;
+        return d;
+    }
+    // SolveModes (extension; include/neutfem_hip.h, nf_solve_modes): the n_modes leading lambda-modes by block power iteration with the
+    // tolerances and the linear solver of this object; returns the eigenvalues, descending.  Flux, adjoint flux and GetLastKeff stay as they are
+    std::vector<double> SolveModes(int n_modes, int n_guard, bool adjoint)
+    {
+        need_built("SolveModes");
+        Log(VerbosityLevel::NORMAL, adjoint ? "\n=== MODES LAMBDA (ADJOINT) ===" : "\n=== MODES LAMBDA (DIRECT) ===");
+        nf_keff_opts o = make_opts(false, {}, false);
+        nf_modes_result r{};
+        chk(nf_solve_modes(h_, &o, n_modes, n_guard, adjoint ? 1 : 0, &r));
+        modes_[adjoint ? 1 : 0] = r; has_modes_[adjoint ? 1 : 0] = true; last_modes_ = adjoint ? 1 : 0;
+        if (verb_ >= VerbosityLevel::NORMAL) {
+            std::cout << "  " << r.n_outer << " iterations externes, bloc de " << r.n_block << (r.converged ? "" : " (non converge)") << std::endl;
+            for (int i = 0; i < r.n_modes; ++i)
+                std::cout << "  k[" << i << "] = " << std::fixed << std::setprecision(8) << r.k[i] << std::defaultfloat << "  residu = " << r.residual[i] << std::endl;
+        }
+        return std::vector<double>(r.k, r.k + r.n_modes);
+    }
+    py::array_t<double> GetMode(int i, bool adjoint)
+    {
+        need_built("get_mode");
+        std::vector<double> full((size_t)ng_ * nphi_);
+        chk(nf_get_mode(h_, i, adjoint ? 1 : 0, full.data()));
+        std::vector<py::ssize_t> shape; shape.push_back(ng_);
+        if (dim_ >= 3) shape.push_back(nz_);
+        if (dim_ >= 2) shape.push_back(ny_);
+        shape.push_back(nx_);
+        py::array_t<double> out(shape);                           // the cell means, shaped like get_flux()
+        double *o = out.mutable_data();
+        for (int g = 0; g < ng_; ++g) for (long e = 0; e < ne_; ++e) o[g * ne_ + e] = full[g * nphi_ + e * nloc_];
+        return out;
+    }
+    py::dict GetModesInfo() const
+    {
+        if (last_modes_ < 0) throw std::runtime_error("get_modes_info: call SolveModes() first");
+        const nf_modes_result &r = modes_[last_modes_];
+        py::dict d;
+        d["k"] = std::vector<double>(r.k, r.k + r.n_modes); d["residual"] = std::vector<double>(r.residual, r.residual + r.n_modes);
+        d["dominance_ratio"] = r.dominance_ratio; d["n_modes"] = r.n_modes; d["n_block"] = r.n_block; d["n_outer"] = r.n_outer;
+        d["cg_total"] = r.cg_total; d["converged"] = r.converged; d["adjoint"] = last_modes_ == 1;
         return d;
     }
     std::pair<double, py::array_t<double>> SolveCoarse(const std::vector<int> &refine)
@@ -455,6 +496,7 @@ private:
     VerbosityLevel verb_ = VerbosityLevel::NORMAL; double cmfd_omega_ = 1.0;
     bool has_valid_keff_ = false, has_valid_adjoint_ = false;
     nf_subcrit_result subcrit_{}; bool has_subcrit_ = false;     // the last SolveSubcritical (get_subcritical_info)
+    nf_modes_result modes_[2]{}; bool has_modes_[2] = {false, false}; int last_modes_ = -1;   // the last SolveModes, direct / adjoint (get_modes_info)
     nf_zoom_result zoom_{}; bool has_zoom_ = false;               // the last zoom_resolved (get_zoom_info)
     nf_sens_result sens_{}; bool has_sens_ = false;               // the last sensitivity_maps (get_sensitivity_info)
 };
@@ -504,6 +546,12 @@ PYBIND11_MODULE(_neutfem_eigen, m)
              py::arg("use_diagonal_solver") = false, py::arg("use_cmfd") = false)
         .def("SolveAdjoint", &NeutFEM::SolveAdjoint, py::arg("normalize_to_direct") = true, py::arg("use_direct_keff") = true)
         .def("SolveSubcritical", &NeutFEM::SolveSubcritical)
+        .def("SolveModes", &NeutFEM::SolveModes, py::arg("n_modes"), py::arg("n_guard") = 2, py::arg("adjoint") = false,
+             "extension: the n_modes leading lambda-modes by block power iteration; returns the list of k, descending")
+        .def("get_mode", &NeutFEM::GetMode, py::arg("i"), py::arg("adjoint") = false,
+             "extension: cell means of mode i of the last SolveModes of that kind, shaped like get_flux() (unit L2 norm over all DOFs)")
+        .def("get_modes_info", &NeutFEM::GetModesInfo,
+             "extension: the last SolveModes's nf_modes_result as a dict (k, residual, dominance_ratio, block size, outer counts, converged)")
         .def("SolveCoarse", &NeutFEM::SolveCoarse, py::arg("refine"))
         .def("build_diagonal_cache", &NeutFEM::BuildDiagonalCache)
         .def("initialize_cmfd", &NeutFEM::InitializeCMFD)

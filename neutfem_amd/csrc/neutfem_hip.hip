@@ -14,6 +14,7 @@
 #include "nf_kernels.h"
 #include "nf_assembly.h"
 #include "nf_line_groups.h"
+#include "nf_small_eig.h"
 
 #include <dlfcn.h>
 #include <unistd.h>
@@ -224,6 +225,7 @@ struct nf_solver {
     // operators
     double *d_Cd = nullptr, *d_Mf = nullptr, *d_Mchi = nullptr;   // ng*nphi diagonals: C, fission, chi-weighted mass (adjoint)
     double *d_phi_adj = nullptr;                        // adjoint flux, ng*nphi (allocated by the first adjoint solve)
+    double *d_modes[2] = {nullptr, nullptr}; int modes_n[2] = {0, 0}, modes_cap[2] = {0, 0};   // lambda-modes of the last nf_solve_modes (direct / adjoint), modes_n * ng*nphi
     int has_valid_adjoint = 0; double last_keff_adj = 1.0;
     std::vector<double *> d_Ms;                          // ng*ng
     const double **d_Ms_tab = nullptr;                   // the same ng*ng pointers on the device (resident kernel)
@@ -294,6 +296,8 @@ static void line_dict_drop(nf_solver *S)
     for (int d = 0; d < 3; ++d) { dfree(S->d_lid[d]); dfree(S->d_ltab[d]); S->ld_use[d] = false; S->ld_pitch[d] = 0; S->ld_off[d].clear(); S->ld_rows[d].clear(); }
     S->ld_tried = false; S->ld_rejected = 0; S->ld_bytes = 0;
 }
+
+static void modes_drop(nf_solver *S);
 
 static const char *SLOT_NAMES[5] = { "schur_x", "schur_y", "schur_z", "schur_apply", "schur_z1" };
 
@@ -570,7 +574,7 @@ int nf_destroy(nf_handle S)
     dfree(S->d_Jz); dfree(S->d_Jzb); dfree(S->d_ctlo); dfree(S->d_cthi); dfree(S->d_elo); dfree(S->d_ehi); dfree(S->d_relo); dfree(S->d_rehi);
     dfree(S->d_phi); dfree(S->d_raw); dfree(S->d_p0); dfree(S->d_p1);
     dfree(S->d_tf); dfree(S->d_rhs); dfree(S->d_r); dfree(S->d_p); dfree(S->d_q); dfree(S->d_p2); dfree(S->d_qy); dfree(S->d_qz);
-    dfree(S->d_qsrc);
+    dfree(S->d_qsrc); dfree(S->d_modes[0]); dfree(S->d_modes[1]);
     if (T) {
         T->slabs.erase(std::remove(T->slabs.begin(), T->slabs.end(), S), T->slabs.end());
         for (size_t i = 0; i < T->slabs.size(); ++i) T->slabs[i]->slab_index = (int)i;
@@ -719,7 +723,7 @@ int nf_upload_xs(nf_handle S, const double *D, const double *SigR, const double 
     // the device copies are overwritten from here on: whatever was built from the old ones is stale until the next nf_build,
     // also when this upload is refused below (a refused upload leaves the handle un-built, never half-valid)
     S->xs_uploaded = false; S->built = false; S->diag_valid = false; S->cmfd_init = false; S->cmfd_iface = false; S->dense_valid = false;
-    coarse_cache_drop(S->team); line_dict_drop(S);
+    coarse_cache_drop(S->team); line_dict_drop(S); modes_drop(S);
     NFCHK(dalloc(&S->d_D, NN)); NFCHK(dalloc(&S->d_SigR, NN)); NFCHK(dalloc(&S->d_NSF, NN)); NFCHK(dalloc(&S->d_Chi, NN));
     HIPCHK(hipMemcpyAsync(S->d_D, D, B, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(S->d_SigR, SigR, B, hipMemcpyHostToDevice, st));
@@ -764,7 +768,7 @@ int nf_build(nf_handle S)
     if (!S) return fail(NF_ERR_ARG, "nf_build: null handle");
     if (!S->xs_uploaded) return fail(NF_ERR_STATE, "nf_build: call nf_upload_xs first");
     HIPCHK(hipSetDevice(S->device));
-    coarse_cache_drop(S->team); line_dict_drop(S);
+    coarse_cache_drop(S->team); line_dict_drop(S); modes_drop(S);
     hipStream_t st = S->team->stream;
     const int ng = S->ng; const long N = S->N, NP = S->nphi; const size_t NN = (size_t)N * ng;
     NFCHK(dalloc(&S->d_Cd, (size_t)NP * ng)); NFCHK(dalloc(&S->d_Mf, (size_t)NP * ng)); NFCHK(dalloc(&S->d_Mchi, (size_t)NP * ng));
@@ -4092,6 +4096,269 @@ int nf_sensitivity(nf_handle S, double keff, double *dD, double *dSigR, double *
     HIPCHK(hipStreamSynchronize(st));                             // the temporaries are freed on return
     if (res) { res->norm = nrm; res->keff = keff; res->n_cells = N; }
     return NF_OK;
+}
+
+// ---- SolveModes: the leading lambda-modes by block power iteration (no counterpart in the reference) ---------------------
+// Subspace iteration with a Rayleigh-Ritz step on A = K0^-1 F (adjoint: K0^-T F^T), host-driven like solve_subcritical_impl: per outer
+// one application of A to every column of the block (the group sweep of the eigenvalue solve at inv_k = 1 with the group solver of
+// inner_plan), one Gram pass, the small algebra on the host (nf_small_eig.h) and one rotate pass.
+struct BlockWork {                                                // partial rows and their sums of the block kernels
+    DevTmp<double> part, out; long stride = RED_GRID; int rows = 0;
+    int ensure(int r)
+    {
+        if (r <= rows) return NF_OK;
+        NFCHK(dalloc(&part.p, (size_t)r * stride)); NFCHK(dalloc(&out.p, (size_t)r));
+        rows = r; return NF_OK;
+    }
+};
+// sums of `rows` partial rows of `cnt` blocks each -> host
+static int block_sums(nf_team *T, BlockWork &W, int rows, int cnt, double *host)
+{
+    hipLaunchKernelGGL(k_block_finalize, dim3(rows), dim3(256), 0, T->stream, (const double *)W.part.p, W.stride, cnt, W.out.p);
+    HIPCHK(hipMemcpyAsync(host, W.out.p, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, T->stream));
+    HIPCHK(stream_wait(T->stream));
+    return NF_OK;
+}
+// H = Q^T Z (b x b, column-major) and G = Z^T Z (full symmetric) of two blocks of b vectors of length n
+static int block_gram(nf_team *T, BlockWork &W, int b, long n, const double *Q, const double *Z, double *H, double *G)
+{
+    const int nt = (b + NF_BLOCK_TILE - 1) / NF_BLOCK_TILE, rows = b * b + b * (b + 1) / 2, gx = grid_for(n);
+    NFCHK(W.ensure(rows));
+    hipLaunchKernelGGL(k_block_gram, dim3(gx, nt * nt), dim3(256), 0, T->stream, Q, Z, b, n, W.part.p, W.stride);
+    double s[NF_BLOCK_MAX * NF_BLOCK_MAX * 2];
+    NFCHK(block_sums(T, W, rows, gx, s));
+    for (int i = 0; i < b; ++i)
+        for (int j = 0; j < b; ++j) {
+            H[i + j * b] = s[gram_row_qz(b, i, j)];
+            G[i + j * b] = s[i <= j ? gram_row_zz(b, i, j) : gram_row_zz(b, j, i)];
+        }
+    return NF_OK;
+}
+// Q <- Z C (C: b x b column-major) and res2[j] = |Z_j - sum_l Q_l Hm[l, j]|^2 for j < m with the old Q (Hm: m x m column-major; m = 0: none)
+static int block_rotate(nf_team *T, BlockWork &W, int b, int m, long n, double *Q, const double *Z, const double *C, const double *Hm, double *res2)
+{
+    BlockCoef cf; memset(&cf, 0, sizeof cf);
+    for (int j = 0; j < b; ++j) for (int l = 0; l < b; ++l) cf.C[l + j * b] = C[l + j * b];
+    for (int j = 0; j < m; ++j) for (int l = 0; l < m; ++l) cf.H[l + j * b] = Hm[l + j * m];
+    const int gx = grid_for(n);
+    NFCHK(W.ensure(std::max(m, 1)));
+#define NF_ROT(B) case B: hipLaunchKernelGGL((k_block_rotate<B>), dim3(gx), dim3(256), 0, T->stream, Q, Z, m, n, cf, W.part.p, W.stride); break;
+    switch (b) { NF_ROT(1) NF_ROT(2) NF_ROT(3) NF_ROT(4) NF_ROT(5) NF_ROT(6) NF_ROT(7) NF_ROT(8) default: return fail(NF_ERR_ARG, "block_rotate: bad block size %d", b); }
+#undef NF_ROT
+    if (m > 0) NFCHK(block_sums(T, W, m, gx, res2));
+    return NF_OK;
+}
+static int block_args(nf_handle S, int b, int m, long n, const void *Q, const void *Z, const char *who)
+{
+    if (!S || !Q || !Z) return fail(NF_ERR_ARG, "%s: bad arguments", who);
+    if (b < 1 || b > NF_BLOCK_MAX || m < 0 || m > b || n < 1) return fail(NF_ERR_ARG, "%s: needs 1 <= b <= %d, m <= b and n >= 1 (got b = %d, m = %d, n = %ld)", who, NF_BLOCK_MAX, b, m, n);
+    HIPCHK(hipSetDevice(S->device));
+    return NF_OK;
+}
+int nf_block_gram(nf_handle S, int b, long n, const double *Q_dev, const double *Z_dev, double *QtZ_host, double *ZtZ_host)
+{
+    NFCHK(block_args(S, b, 0, n, Q_dev, Z_dev, "nf_block_gram"));
+    if (!QtZ_host || !ZtZ_host) return fail(NF_ERR_ARG, "nf_block_gram: bad arguments");
+    BlockWork W;
+    NFCHK(block_gram(S->team, W, b, n, Q_dev, Z_dev, QtZ_host, ZtZ_host));
+    HIPCHK(hipGetLastError());
+    return NF_OK;
+}
+int nf_block_rotate(nf_handle S, int b, int m, long n, double *Q_dev, const double *Z_dev, const double *C_host, const double *H_host, double *res2_host)
+{
+    NFCHK(block_args(S, b, m, n, Q_dev, Z_dev, "nf_block_rotate"));
+    if (!C_host || (m > 0 && (!H_host || !res2_host))) return fail(NF_ERR_ARG, "nf_block_rotate: bad arguments");
+    BlockWork W;
+    NFCHK(block_rotate(S->team, W, b, m, n, Q_dev, Z_dev, C_host, H_host, res2_host));
+    HIPCHK(hipStreamSynchronize(S->team->stream));
+    HIPCHK(hipGetLastError());
+    return NF_OK;
+}
+
+static void modes_drop(nf_solver *S)
+{
+    if (S->team && S->team->stream && (S->d_modes[0] || S->d_modes[1])) (void)hipStreamSynchronize(S->team->stream);
+    for (int a = 0; a < 2; ++a) { dfree(S->d_modes[a]); S->modes_n[a] = 0; S->modes_cap[a] = 0; }
+}
+
+// the first nb index triples (i, j, k), i < nx, j < ny, k < nz, in order of i + j + k, then k, then j
+static void modes_harmonics(const nf_solver *S, int nb, StartArgs *sa)
+{
+    int c = 0;
+    for (int s = 0; c < nb && s <= S->nx + S->ny + S->nz; ++s)
+        for (int k = 0; c < nb && k < S->nz && k <= s; ++k)
+            for (int j = 0; c < nb && j < S->ny && j + k <= s; ++j) {
+                const int i = s - j - k;
+                if (i < S->nx) { sa->hi[c] = i; sa->hj[c] = j; sa->hk[c] = k; ++c; }
+            }
+}
+
+static int solve_modes_impl(nf_solver *S, const nf_keff_opts *o, int m, int b, int adjoint, nf_modes_result *res)
+{
+    nf_team *T = S->team;
+    const int ng = S->ng; const long N = S->N, NP = S->nphi, NT = NP * ng;
+    hipStream_t st = T->stream;
+    NFCHK(team_prepare(T));
+    const int use_diag = (o->use_diagonal_solver && S->k == 0 && S->m == 0) ? 1 : 0;
+    if (use_diag) NFCHK(nf_build_diagonal_cache(S));
+    const InnerPlan ip = inner_plan(T, o);
+    if (!use_diag && ip.dense) NFCHK(dense_prepare(T));
+    T->profile = false;
+    DevTmp<double> Qb, Zb;
+    NFCHK(dalloc(&Qb.p, (size_t)b * NT)); NFCHK(dalloc(&Zb.p, (size_t)b * NT));
+    double *Q = Qb.p, *Z = Zb.p;
+    BlockWork W;
+    NFCHK(W.ensure(std::max(b * b + b * (b + 1) / 2, 4 * NF_BLOCK_MAX)));
+    const double *fis = adjoint ? S->d_Mchi : S->d_Mf, *emi = adjoint ? S->d_NSF : S->d_Chi;
+    const int gN = grid_for(NP);
+    nf_modes_result r; memset(&r, 0, sizeof r);
+    r.n_modes = m; r.n_block = b;
+    ScatterArgs sa; sa.ng = ng;
+    // z_j = A q_j for the first nc columns: fission source of q_j, then the group sweep (direct: ascending; adjoint: descending on the
+    // transposed blocks); with downscatter only every scatter term reads a group of z_j the sweep has already solved
+    auto apply = [&](int nc) -> int {
+        for (int j = 0; j < nc; ++j) {
+            const double *q = Q + (size_t)j * NT; double *z = Z + (size_t)j * NT;
+            hipLaunchKernelGGL(k_fission, dim3(gN), dim3(256), 0, st, fis, q, ng, NP, S->d_tf, T->d_partials, (const double *)nullptr, 0L);
+            for (int s = 0; s < ng; ++s) {
+                const int g = adjoint ? ng - 1 - s : s;
+                for (int gp = 0; gp < 64; ++gp) sa.M[gp] = gp < ng ? S->d_Ms[adjoint ? gp * ng + g : g * ng + gp] : nullptr;
+                double *sol = z + (size_t)g * NP, *dst = use_diag ? sol : S->d_rhs;
+                const bool cgi = !use_diag && !ip.dense;
+                hipLaunchKernelGGL(k_group_rhs<false>, dim3(gN), dim3(256), 0, st, sa, g, emi + g * N, S->d_tf, 1.0, (const double *)z, (const double *)z,
+                                   use_diag ? S->d_Sinv + g * N : (const double *)nullptr, dst, NP, N,
+                                   cgi ? sol : (double *)nullptr, cgi ? S->d_r : (double *)nullptr, cgi ? S->d_p : (double *)nullptr,
+                                   cgi ? T->d_partials : (double *)nullptr);
+                int its = 0; double cres = 0.0;
+                if (use_diag) { }
+                else if (ip.dense) { dense_solve(T, g, S->d_rhs, sol); its = 1; }
+                else {
+                    NFCHK(cg_solve(T, g, { (const double *)S->d_rhs }, { sol }, ip.cg_tol, ip.cg_max, &its, &cres, true));
+                    if (ip.direct && !(cres <= 1e-14)) ++T->standin_unconverged;
+                }
+                r.cg_total += its;
+            }
+        }
+        return NF_OK;
+    };
+    double H[64], G[64], V[64], Gp[64], L[64], X[64], C[64], Hm[64], wr[8], wi[8], res2[8], kprev[8];
+    // start block: cosine harmonics into Z, orthonormalised into Q with the two block kernels
+    {
+        StartArgs hs; memset(&hs, 0, sizeof hs);
+        modes_harmonics(S, b, &hs);
+        hipLaunchKernelGGL(k_modes_start, dim3(grid_for((long)b * NT)), dim3(256), 0, st, Z, b, ng, NP, N, S->nx, S->ny, S->nz, hs);
+        HIPCHK(hipMemsetAsync(Q, 0, (size_t)b * NT * sizeof(double), st));
+        NFCHK(block_gram(T, W, b, NT, Z, Z, H, G));
+        if (small_cholesky(b, G, L) != 0) return fail(NF_ERR_NUMERIC, "nf_solve_modes: block lost rank (the start block of %d cosine harmonics is dependent on this mesh)", b);
+        small_inv_lt(b, L, C);
+        NFCHK(block_rotate(T, W, b, 0, NT, Q, Z, C, nullptr, nullptr));
+    }
+    bool conv = false;
+    for (int it = 0; it < o->max_outer; ++it) {
+        NFCHK(apply(b));
+        NFCHK(block_gram(T, W, b, NT, Q, Z, H, G));
+        for (int i = 0; i < b * b; ++i) if (!std::isfinite(H[i]) || !std::isfinite(G[i])) return fail(NF_ERR_NUMERIC, "nf_solve_modes: the block iteration produced non-finite sums (outer %d)", it);
+        if (small_eig(b, H, wr, wi, V) != 0) return fail(NF_ERR_NUMERIC, "nf_solve_modes: the eigenvalue iteration on the %d x %d projected matrix did not converge (outer %d)", b, b, it);
+        for (int i = 0; i < b; ++i)                               // G' = V^T G V
+            for (int j = 0; j < b; ++j) {
+                double v = 0.0;
+                for (int p = 0; p < b; ++p) for (int q = 0; q < b; ++q) v += V[p + i * b] * G[p + q * b] * V[q + j * b];
+                Gp[i + j * b] = v;
+            }
+        const int cr = small_cholesky(b, Gp, L);
+        if (cr != 0) return fail(NF_ERR_NUMERIC, "nf_solve_modes: block lost rank (pivot %d of %d at outer %d: A has fewer than n_block independent directions here; use fewer guard vectors)", -cr - 1, b, it);
+        small_inv_lt(b, L, X);
+        for (int i = 0; i < b; ++i)                               // C = V L^-T
+            for (int j = 0; j < b; ++j) { double v = 0.0; for (int p = 0; p < b; ++p) v += V[i + p * b] * X[p + j * b]; C[i + j * b] = v; }
+        for (int j = 0; j < m; ++j) for (int l = 0; l < m; ++l) Hm[l + j * m] = H[l + j * b];
+        NFCHK(block_rotate(T, W, b, m, NT, Q, Z, C, Hm, res2));
+        double rmax = 0.0, dk = 0.0; bool cplx = m < b && wi[m - 1] > 0.0;   // a pair cut by the block of wanted modes counts as complex
+        for (int i = 0; i < m; ++i) {
+            rmax = std::max(rmax, std::sqrt(res2[i]) / std::fabs(wr[i]));
+            dk = std::max(dk, it == 0 ? HUGE_VAL : std::fabs(wr[i] - kprev[i]));
+            cplx |= wi[i] != 0.0;
+            if (!std::isfinite(res2[i])) return fail(NF_ERR_NUMERIC, "nf_solve_modes: non-finite residual (outer %d)", it);
+            kprev[i] = wr[i];
+        }
+        r.n_outer = it + 1;
+        if (!cplx && rmax < o->tol_flux && dk < o->tol_keff) { conv = true; break; }
+    }
+    // the returned vectors: eigenvectors of H_mm of one more application of A to the leading m columns, X = Q_m W, with their own
+    // residuals A x_i - k_i x_i = Z_m w_i - k_i Q_m w_i (a complex pair: the residual of its plane)
+    NFCHK(apply(m));
+    NFCHK(block_gram(T, W, m, NT, Q, Z, H, G));
+    for (int i = 0; i < m * m; ++i) if (!std::isfinite(H[i])) return fail(NF_ERR_NUMERIC, "nf_solve_modes: non-finite projected matrix at the end");
+    if (small_eig(m, H, wr, wi, V) != 0) return fail(NF_ERR_NUMERIC, "nf_solve_modes: the eigenvalue iteration on the %d x %d projected matrix did not converge", m, m);
+    ExtractCoef ec; memset(&ec, 0, sizeof ec);
+    for (int j = 0; j < m; ++j)
+        for (int l = 0; l < m; ++l) {
+            ec.Wz[l + j * NF_BLOCK_MAX] = V[l + j * m];
+            double v = wr[j] * V[l + j * m];                       // W Theta: A (u + i w) = (a + i b)(u + i w) -> A u = a u - b w, A w = b u + a w
+            if (wi[j] > 0.0 && j + 1 < m) v -= wi[j] * V[l + (j + 1) * m];
+            if (wi[j] < 0.0 && j > 0) v -= wi[j] * V[l + (j - 1) * m];
+            ec.Wq[l + j * NF_BLOCK_MAX] = v;
+        }
+    if (!S->d_modes[adjoint] || S->modes_cap[adjoint] < m) { S->modes_n[adjoint] = 0; NFCHK(dalloc(&S->d_modes[adjoint], (size_t)m * NT)); S->modes_cap[adjoint] = m; }
+    S->modes_n[adjoint] = 0;
+    double *Xd = S->d_modes[adjoint];
+    const int gT = grid_for(NT);
+    hipLaunchKernelGGL(k_modes_extract, dim3(gT), dim3(256), 0, st, (const double *)Q, (const double *)Z, m, NT, fis, ec, Xd, W.part.p, W.stride);
+    double s[4 * NF_BLOCK_MAX];
+    NFCHK(block_sums(T, W, 4 * NF_BLOCK_MAX, gT, s));
+    bool cplx = false;
+    for (int i = 0; i < m; ++i) {
+        const double x2 = s[i], r2 = s[NF_BLOCK_MAX + i], prod = s[2 * NF_BLOCK_MAX + i], aprod = s[3 * NF_BLOCK_MAX + i];
+        if (!std::isfinite(x2) || !(x2 > 0.0) || !std::isfinite(r2)) return fail(NF_ERR_NUMERIC, "nf_solve_modes: mode %d came out non-finite or zero", i);
+        const double sign = (prod < 0.0 && std::fabs(prod) >= 1e-10 * aprod) ? -1.0 : 1.0;   // sum Mf phi >= 0 where that sum means something
+        hipLaunchKernelGGL(k_scale, dim3(gT), dim3(256), 0, st, Xd + (size_t)i * NT, NT, sign * std::sqrt(x2));
+        r.k[i] = wr[i];
+        r.residual[i] = std::sqrt(r2 / x2) / std::fabs(wr[i]);
+        cplx |= wi[i] != 0.0;
+    }
+    for (int i = 0; i + 1 < m; ++i)
+        if (wi[i] > 0.0) {                                        // the plane's residual for both members of a pair
+            const double v = std::sqrt((s[NF_BLOCK_MAX + i] + s[NF_BLOCK_MAX + i + 1]) / (s[i] + s[i + 1])) / std::hypot(wr[i], wi[i]);
+            r.residual[i] = r.residual[i + 1] = v;
+        }
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    S->modes_n[adjoint] = m;
+    r.dominance_ratio = m > 1 ? r.k[1] / r.k[0] : 0.0;
+    r.converged = conv && !cplx ? 1 : 0;
+    if (res) *res = r;
+    return NF_OK;
+}
+
+int nf_solve_modes(nf_handle S, const nf_keff_opts *o, int n_modes, int n_guard, int adjoint, nf_modes_result *res)
+{
+    if (!S || !o) return fail(NF_ERR_ARG, "nf_solve_modes: bad arguments");
+    nf_team *T = S->team;
+    if (T->dead) return fail(NF_ERR_COMM, "this team lost a collective (NF_ERR_COMM) and is unusable: destroy the handles and end the process with a non-zero code (never re-exec)");
+    if (n_modes < 1 || n_guard < 0 || n_modes + n_guard > NF_MODES_MAX)
+        return fail(NF_ERR_ARG, "nf_solve_modes: needs 1 <= n_modes and n_modes + n_guard <= %d (got %d + %d)", NF_MODES_MAX, n_modes, n_guard);
+    if (o->use_coarse_init || o->use_cmfd) return fail(NF_ERR_ARG, "nf_solve_modes: coarse start and CMFD do not apply to the block iteration");
+    if (o->max_outer < 1) return fail(NF_ERR_ARG, "nf_solve_modes: max_outer must be at least 1");
+    if (!team_is_single(T) || T->nproc > 1)
+        return fail(NF_ERR_UNSUPPORTED, "nf_solve_modes works on an undivided mesh (slab teams and multi-rank teams are not supported)");
+    if (!S->built) return fail(NF_ERR_STATE, "nf_solve_modes: call nf_build first");
+    for (int g = 0; g < S->ng; ++g)
+        for (int gp = g + 1; gp < S->ng; ++gp)
+            if (S->d_Ms[g * S->ng + gp])
+                return fail(NF_ERR_UNSUPPORTED, "nf_solve_modes: upscatter (group %d <- group %d) is not supported: the Gauss-Seidel group sweep lags "
+                            "those terms, so the iteration operator would no longer be K0^-1 F", g, gp);
+    if (S->N < n_modes + n_guard) return fail(NF_ERR_ARG, "nf_solve_modes: the mesh has %ld cells, fewer than the %d vectors of the block", S->N, n_modes + n_guard);
+    HIPCHK(hipSetDevice(S->device));
+    const int rc = solve_modes_impl(S, o, n_modes, n_modes + n_guard, adjoint ? 1 : 0, res);
+    if (rc != NF_OK) { (void)hipStreamSynchronize(T->stream); (void)hipGetLastError(); }
+    return rc;
+}
+int nf_get_mode(nf_handle S, int i, int adjoint, double *phi_host)
+{
+    if (!S || !phi_host) return fail(NF_ERR_ARG, "nf_get_mode: bad arguments");
+    const int a = adjoint ? 1 : 0;
+    if (!S->modes_n[a]) return fail(NF_ERR_STATE, "nf_get_mode: no %s modes on this handle (nf_solve_modes first; nf_build and nf_upload_xs drop them)", a ? "adjoint" : "direct");
+    if (i < 0 || i >= S->modes_n[a]) return fail(NF_ERR_ARG, "nf_get_mode: mode %d of %d", i, S->modes_n[a]);
+    return phi_transfer(S, phi_host, false, S->d_modes[a] + (size_t)i * S->nphi * S->ng);
 }
 
 int nf_get_history(nf_handle S, double *k, double *dk, double *dphi, int *cg, int cap)

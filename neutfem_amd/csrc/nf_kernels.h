@@ -4221,6 +4221,160 @@ __global__ __launch_bounds__(256) void k_sens_current(Geom G, SensJ O, const dou
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Block outer iteration (nf_solve_modes): Gram and rotate passes over two blocks of b <= NF_BLOCK_MAX long vectors
+// (column-major, leading dimension n).  Both are streaming kernels: every element of every column is read once per tile that needs it.
+// Block partials go to rows of `stride` doubles, one entry per block of gridDim.x -- the team partials layout; k_block_finalize sums
+// any number of rows in k_finalize's order (k_finalize itself takes four per launch).
+static const int NF_BLOCK_MAX = 8, NF_BLOCK_TILE = 4;
+// rows of the Gram partials: (Q^T Z)(i, j) at i * b + j, the upper triangle of Z^T Z, i <= j, behind them at b * b + j (j + 1) / 2 + i
+__host__ __device__ __forceinline__ int gram_row_qz(int b, int i, int j) { return i * b + j; }
+__host__ __device__ __forceinline__ int gram_row_zz(int b, int i, int j) { return b * b + j * (j + 1) / 2 + i; }
+// Tile (ti, tj) = blockIdx.y of 4 x 4 entries: columns 4 ti.. of Q (and of Z) against columns 4 tj.. of Z.  The tile forms its part of
+// Q^T Z and, for ti <= tj, of Z^T Z from the same loads: 32 accumulators, 8 (diagonal tile) or 12 loads per element.  Full 8 x 8 in one
+// thread would need 100 accumulators.  Columns beyond b are clamped to b - 1 (their sums are not stored).
+__global__ __launch_bounds__(256) void k_block_gram(const double *__restrict__ Q, const double *__restrict__ Z, int b, long n,
+                                                    double *__restrict__ partials, long stride)
+{
+    constexpr int TW = NF_BLOCK_TILE;
+    __shared__ double sred[4];
+    const int nt = (b + TW - 1) / TW, ti = blockIdx.y / nt, tj = blockIdx.y % nt;
+    const bool zz = ti <= tj, diag = ti == tj;
+    const double *qi[TW], *zi[TW], *zj[TW];
+#pragma unroll
+    for (int a = 0; a < TW; ++a) {
+        const int ci = min(ti * TW + a, b - 1), cj = min(tj * TW + a, b - 1);
+        qi[a] = Q + (long)ci * n; zi[a] = Z + (long)ci * n; zj[a] = Z + (long)cj * n;
+    }
+    double h[TW][TW], g[TW][TW];
+#pragma unroll
+    for (int a = 0; a < TW; ++a)
+#pragma unroll
+        for (int c = 0; c < TW; ++c) { h[a][c] = 0.0; g[a][c] = 0.0; }
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < n; e += gridDim.x * 256L) {
+        double q[TW], zc[TW], zr[TW];
+#pragma unroll
+        for (int a = 0; a < TW; ++a) { q[a] = qi[a][e]; zc[a] = zj[a][e]; }
+        if (zz && !diag) {
+#pragma unroll
+            for (int a = 0; a < TW; ++a) zr[a] = zi[a][e];
+        } else {
+#pragma unroll
+            for (int a = 0; a < TW; ++a) zr[a] = zc[a];
+        }
+#pragma unroll
+        for (int a = 0; a < TW; ++a)
+#pragma unroll
+            for (int c = 0; c < TW; ++c) { h[a][c] = fma(q[a], zc[c], h[a][c]); g[a][c] = fma(zr[a], zc[c], g[a][c]); }
+    }
+#pragma unroll
+    for (int a = 0; a < TW; ++a)
+#pragma unroll
+        for (int c = 0; c < TW; ++c) {
+            const int i = ti * TW + a, j = tj * TW + c;
+            const double hs = block_sum(h[a][c], sred), gs = block_sum(g[a][c], sred);
+            if (threadIdx.x == 0 && i < b && j < b) {
+                partials[gram_row_qz(b, i, j) * stride + blockIdx.x] = hs;
+                if (zz && i <= j) partials[gram_row_zz(b, i, j) * stride + blockIdx.x] = gs;
+            }
+        }
+}
+// out[row] = sum of the row's `cnt` block partials, in k_finalize's order (strided_sum256 + block_sum); one block per row
+__global__ __launch_bounds__(256) void k_block_finalize(const double *__restrict__ partials, long stride, int cnt, double *__restrict__ out)
+{
+    __shared__ double sred[4];
+    double s = strided_sum256(partials + blockIdx.x * stride, cnt);
+    s = block_sum(s, sred);
+    if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+// Q <- Z C in place of Q (every output element depends on the same element of the inputs only) and, from the OLD Q of the same loads,
+// block partials of the squared column norms of R = Z_m - Q_m H_mm, the invariant-subspace residual of the leading m columns (row j of
+// the partials = column j).  C and H: B x B, column-major, H zero outside its leading m x m part -- both in the kernel arguments.
+struct BlockCoef { double C[NF_BLOCK_MAX * NF_BLOCK_MAX], H[NF_BLOCK_MAX * NF_BLOCK_MAX]; };
+template <int B>
+__global__ __launch_bounds__(256) void k_block_rotate(double *Q, const double *__restrict__ Z, int m, long n, BlockCoef cf,
+                                                      double *__restrict__ partials, long stride)
+{
+    __shared__ double sred[4];
+    double r2[B];
+#pragma unroll
+    for (int j = 0; j < B; ++j) r2[j] = 0.0;
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < n; e += gridDim.x * 256L) {
+        double q[B], z[B];
+#pragma unroll
+        for (int l = 0; l < B; ++l) { q[l] = Q[(long)l * n + e]; z[l] = Z[(long)l * n + e]; }
+#pragma unroll
+        for (int j = 0; j < B; ++j) {
+            double v = 0.0, r = z[j];
+#pragma unroll
+            for (int l = 0; l < B; ++l) { v = fma(z[l], cf.C[l + j * B], v); r = fma(-q[l], cf.H[l + j * B], r); }
+            Q[(long)j * n + e] = v;
+            r2[j] = fma(r, r, r2[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < B; ++j) {
+        const double s = block_sum(r2[j], sred);
+        if (threadIdx.x == 0 && j < m) partials[j * stride + blockIdx.x] = s;
+    }
+}
+// start block of the block iteration: column c = the cosine harmonic (hi, hj, hk)[c] of the cell index,
+// cos(pi hi (x + 1/2) / nx) cos(pi hj (y + 1/2) / ny) cos(pi hk (z + 1/2) / nz), the same in every group, zero in the higher moments
+// (device DOF order [p][e]: the cell means are the first N entries of a group)
+struct StartArgs { int hi[NF_BLOCK_MAX], hj[NF_BLOCK_MAX], hk[NF_BLOCK_MAX]; };
+__global__ __launch_bounds__(256) void k_modes_start(double *__restrict__ Z, int b, int ng, long nphi, long N, int nx, int ny, int nz, StartArgs sa)
+{
+    const long nt = (long)ng * nphi, total = nt * b;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
+        const int c = (int)(i / nt);
+        const long d = (i - c * nt) % nphi;
+        double v = 0.0;
+        if (d < N) {
+            const int ix = (int)(d % nx); const long r = d / nx; const int iy = (int)(r % ny), iz = (int)(r / ny);
+            v = cospi(sa.hi[c] * (ix + 0.5) / nx) * cospi(sa.hj[c] * (iy + 0.5) / ny) * cospi(sa.hk[c] * (iz + 0.5) / nz);
+        }
+        Z[i] = v;
+    }
+}
+// the returned vectors of nf_solve_modes from the last application of A: x_i = sum_l q_l Wz[l, i] (written to X), its residual
+// r_i = sum_l z_l Wz[l, i] - sum_l q_l Wq[l, i] (Wq = Wz Theta, Theta the real block form of the eigenvalues), and block partials of
+// |x_i|^2 (rows 0..7), |r_i|^2 (8..15), sum w x_i (16..23) and sum |w x_i| (24..31) with w the fission (adjoint: chi-weighted mass)
+// diagonal over all groups.  Coefficients 8 x 8 column-major, zero beyond m; columns beyond m are clamped (their sums are ignored).
+struct ExtractCoef { double Wz[NF_BLOCK_MAX * NF_BLOCK_MAX], Wq[NF_BLOCK_MAX * NF_BLOCK_MAX]; };
+__global__ __launch_bounds__(256) void k_modes_extract(const double *__restrict__ Q, const double *__restrict__ Z, int m, long n,
+                                                       const double *__restrict__ w, ExtractCoef cf, double *__restrict__ X,
+                                                       double *__restrict__ partials, long stride)
+{
+    constexpr int B = NF_BLOCK_MAX;
+    __shared__ double sred[4];
+    double acc[4][B];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int j = 0; j < B; ++j) acc[t][j] = 0.0;
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < n; e += gridDim.x * 256L) {
+        double q[B], z[B];
+        const double we = w[e];
+#pragma unroll
+        for (int l = 0; l < B; ++l) { const long c = min(l, m - 1); q[l] = Q[c * n + e]; z[l] = Z[c * n + e]; }
+#pragma unroll
+        for (int j = 0; j < B; ++j) {
+            double x = 0.0, r = 0.0;
+#pragma unroll
+            for (int l = 0; l < B; ++l) { x = fma(q[l], cf.Wz[l + j * B], x); r = fma(z[l], cf.Wz[l + j * B], r); r = fma(-q[l], cf.Wq[l + j * B], r); }
+            if (j < m) X[(long)j * n + e] = x;
+            acc[0][j] = fma(x, x, acc[0][j]); acc[1][j] = fma(r, r, acc[1][j]); acc[2][j] = fma(we, x, acc[2][j]); acc[3][j] += fabs(we * x);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int j = 0; j < B; ++j) {
+            const double s = block_sum(acc[t][j], sred);
+            if (threadIdx.x == 0) partials[(t * B + j) * stride + blockIdx.x] = s;
+        }
+}
+
 // fill with a deterministic pseudo-random pattern (profiling helper)
 __global__ void k_fill_pattern(double *__restrict__ v, long n)
 {
