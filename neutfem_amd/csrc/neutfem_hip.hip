@@ -31,6 +31,8 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 using namespace nf;
@@ -1240,8 +1242,27 @@ static DictArgs dict_args(const nf_solver *S, int d, int g, bool on)
 static bool x_p2(const nf_solver *S, int NB, int NCH, bool fused_here, bool nt) { return nt && NB == 0 && NCH >= 2 && fused_here && S->team->opt_x_p2 == 1; }
 static bool x_xcd(const nf_solver *S, bool nt) { return nt && S->team->opt_xcd >= 0 && (S->team->opt_xcd & 4); }   // bit 1 of k_schur_x's `first`: the streaming instantiations only
 static bool x_fuses(const nf_solver *S) { return !(S->if_lo || S->if_hi); }                                       // slabs fuse in their endpoint pass instead
-struct XPlan { int lpl_log2 = 0, NCH = 0; unsigned grid = 0; };  // NCH: the instantiation's chunks per lane (0: the line is refused)
-static XPlan x_plan(const nf_solver *S)
+// f(std::integral_constant<unsigned, key>()), key < N: how a launch function gets from runtime values to an instantiation.  f decodes its index,
+// returns false under `if constexpr` where the combination is not legal and launches otherwise: exactly the legal ones are instantiated.
+template <class F, unsigned I> static bool call_index(F &f) { return f(std::integral_constant<unsigned, I>()); }
+template <class F, unsigned... I> static bool with_index(unsigned key, F &f, std::integer_sequence<unsigned, I...>)
+{
+    static constexpr bool (*tab[])(F &) = { &call_index<F, I>... };   // one indexed call, however many instantiations there are
+    return key < sizeof...(I) && tab[key](f);
+}
+template <unsigned N, class F> static bool with_index(unsigned key, F &&f) { return with_index(key, f, std::make_integer_sequence<unsigned, N>()); }
+
+// The instantiations of k_schur_x<2, NCH, VEC, NB, NT, P2, DICT>: up to 32 chunks per lane (16, 32: RT0-P0 only), streaming loads for RT0-P0 lines
+// of even length, two load phases and the table next to the streaming loads only
+constexpr bool schur_x_legal(int NCH, bool VEC, int NB, bool NT, bool P2, bool DICT)
+{
+    return NCH >= 1 && NCH <= (NB == 0 ? 32 : 8) && (NCH & (NCH - 1)) == 0 && NB >= 0 && NB <= 2
+        && (!NT || (VEC && NB == 0)) && (!P2 || (NT && NCH >= 2)) && (!DICT || (NT && NCH <= X_DICT_MAX_NCH));
+}
+// the x pass: launch shape, NCH = the instantiation's chunks per lane (0: the line is refused), and what else picks the instantiation.
+// fused: a fused CG update rides in this pass.
+struct XPlan { int lpl_log2 = 0, NCH = 0; unsigned grid = 0; bool vec = false, nt = false, p2 = false, xcd = false, dict = false; };
+static XPlan x_plan(const nf_solver *S, bool fused = false)
 {
     XPlan P; const int K = 2;
     const int lanes = (S->nx + K - 1) / K;
@@ -1250,56 +1271,33 @@ static XPlan x_plan(const nf_solver *S)
     const int nch = (S->nx + LPL * K - 1) / (LPL * K);
     P.grid = (unsigned)((S->nlines[0] + 4 * LPW - 1) / (4 * LPW));
     for (int c = 1; c <= (S->nb == 0 ? 32 : 8); c *= 2) if (nch <= c) { P.NCH = c; break; }   // long lines (16, 32: RT0-P0 only): more registers per lane, lower occupancy
+    P.vec = S->nx % 2 == 0; P.nt = x_nt(S, S->nb);
+    P.p2 = x_p2(S, S->nb, P.NCH, fused && x_fuses(S), P.nt); P.xcd = x_xcd(S, P.nt); P.dict = x_dict(S, S->nb, P.NCH, P.nt);
     return P;
 }
-template <int NCH, int NB>
-static void launch_x_t(const nf_solver *S, int g, const ModeArgs &ma, const Geom &G, int lpl_log2, int first, int last,
-                       double *partials, const PassCg &P, unsigned grid)
+static int launch_x(const nf_solver *S, int g, const ModeArgs &ma0, const Geom &G, int last, double *partials, const PassCg &P, int *nparts)
 {
-    const long N = S->N;
-    const bool vec = (S->nx % 2 == 0);
-    hipStream_t st = S->team->stream;
-    const double *L = S->d_L[0] + g * N, *DR = S->d_DR[0] + g * N, *D0 = S->d_D0[0] + g * S->nlines[0];
+    const XPlan xp = x_plan(S, P.fuse.p != nullptr);
+    if (!xp.NCH) return fail(NF_ERR_UNSUPPORTED, "nx = %d exceeds the x-line kernel limit (%d cells)", S->nx, S->nb == 0 ? 4096 : 1024);
+    if (nparts) *nparts = (int)xp.grid * n_modes(S);
     const CgFuse fz = x_fuses(S) ? P.fuse : CgFuse{ nullptr, nullptr, nullptr };
     const ModeTab mt = mode_tab(S, 0);
-    const dim3 gr(grid, (unsigned)mt.n);                          // all transverse modes in one launch
-    const bool nt = x_nt(S, NB), p2 = x_p2(S, NB, NCH, fz.p != nullptr, nt);
-    const int first_x = first | (x_xcd(S, nt) ? 2 : 0);
-    const DictArgs da = dict_args(S, 0, g, x_dict(S, NB, NCH, nt));
-    if (da.on) {                                                  // the line's row of the table instead of its own L, 1/d and C diagonal
-        ModeArgs mad = ma; mad.Cd[0] = da.C;
-        if (p2) hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB, NB == 0, NB == 0 && (NCH >= 2), NB == 0 && NCH <= X_DICT_MAX_NCH>), gr, dim3(256), 0, st, mad, mt, G, da.L, da.DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2,
-                                   first_x, last, partials, P.cg, fz, P.lean, da.ld);
-        else hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB, NB == 0, false, NB == 0 && NCH <= X_DICT_MAX_NCH>), gr, dim3(256), 0, st, mad, mt, G, da.L, da.DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2,
-                                first_x, last, partials, P.cg, fz, P.lean, da.ld);
-    }
-    else if (p2) hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB, NB == 0, NB == 0 && (NCH >= 2)>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2,
-                               first_x, last, partials, P.cg, fz, P.lean);
-    else if (nt) hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB, NB == 0>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2,
-                               first_x, last, partials, P.cg, fz, P.lean);
-    else if (vec) hipLaunchKernelGGL((k_schur_x<2, NCH, true, NB>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2, first, last, partials, P.cg, fz, P.lean);
-    else hipLaunchKernelGGL((k_schur_x<2, NCH, false, NB>), gr, dim3(256), 0, st, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], lpl_log2, first, last, partials, P.cg, fz, P.lean);
-}
-template <int NB>
-static int launch_x_nb(const nf_solver *S, int g, const ModeArgs &ma, const Geom &G, int last, double *partials, const PassCg &P, int *nparts)
-{
-    const XPlan xp = x_plan(S);
-    const int lpl_log2 = xp.lpl_log2; const unsigned grid = xp.grid;
-    if (nparts) *nparts = (int)grid * n_modes(S);
-    if (xp.NCH == 1) launch_x_t<1, NB>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
-    else if (xp.NCH == 2) launch_x_t<2, NB>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
-    else if (xp.NCH == 4) launch_x_t<4, NB>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
-    else if (xp.NCH == 8) launch_x_t<8, NB>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
-    else if (xp.NCH == 16 && NB == 0) launch_x_t<16, 0>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
-    else if (xp.NCH == 32 && NB == 0) launch_x_t<32, 0>(S, g, ma, G, lpl_log2, 1, last, partials, P, grid);
-    else return fail(NF_ERR_UNSUPPORTED, "nx = %d exceeds the x-line kernel limit (%d cells)", S->nx, NB == 0 ? 4096 : 1024);
-    return NF_OK;
-}
-static int launch_x(const nf_solver *S, int g, const ModeArgs &ma, const Geom &G, int last, double *partials, const PassCg &P, int *nparts)
-{
-    if (S->nb == 0) return launch_x_nb<0>(S, g, ma, G, last, partials, P, nparts);
-    if (S->nb == 1) return launch_x_nb<1>(S, g, ma, G, last, partials, P, nparts);
-    return launch_x_nb<2>(S, g, ma, G, last, partials, P, nparts);
+    const dim3 gr(xp.grid, (unsigned)mt.n);                       // all transverse modes in one launch
+    const int first = 1 | (xp.xcd ? 2 : 0);
+    const DictArgs da = dict_args(S, 0, g, xp.dict);              // the line's row of the table instead of its own L, 1/d and C diagonal
+    ModeArgs ma = ma0; if (da.on) ma.Cd[0] = da.C;
+    const double *L = da.on ? da.L : S->d_L[0] + g * S->N, *DR = da.on ? da.DR : S->d_DR[0] + g * S->N, *D0 = S->d_D0[0] + g * S->nlines[0];
+    int lg = 0; while ((1 << lg) < xp.NCH) ++lg;
+    const unsigned key = ((((unsigned)lg * 3 + (unsigned)S->nb) * 2 + xp.vec) * 2 + xp.nt) * 4 + xp.p2 * 2 + xp.dict;
+    const bool hit = with_index<6 * 3 * 16>(key, [&](auto i) {
+        constexpr unsigned I = decltype(i)::value;
+        constexpr int NCH = 1 << (I / 48), NB = I / 16 % 3; constexpr bool VEC = I & 8, NT = I & 4, P2 = I & 2, DICT = I & 1;
+        if constexpr (!schur_x_legal(NCH, VEC, NB, NT, P2, DICT)) return false;
+        else hipLaunchKernelGGL((k_schur_x<2, NCH, VEC, NB, NT, P2, DICT>), gr, dim3(256), 0, S->team->stream, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], xp.lpl_log2,
+                                first, last, partials, P.cg, fz, P.lean, da.ld);
+        return true;
+    });
+    return hit ? NF_OK : fail(NF_ERR_ARG, "k_schur_x: no instantiation for NCH = %d, NB = %d, vec %d, nt %d, p2 %d, dict %d", xp.NCH, S->nb, xp.vec, xp.nt, xp.p2, xp.dict);
 }
 
 // Does direction d (1 = y, 2 = z) of this mesh take the chunked long-line kernel (k_schur_c)?  Plain lines of RT0-P0 meshes beyond
@@ -1334,9 +1332,7 @@ static ChunkPlan chunk_plan(const nf_solver *S, int d)
     return P;
 }
 
-static ChunkPlan pass_chunk_plan(const nf_solver *S, int d, int zmode) { return zmode == 0 ? chunk_plan(S, d) : ChunkPlan(); }   // the slab chain passes never take it
-// launch shape and load / order flags of the chunked kernel; taken: this pass really goes to it (its share of x.y comes in the z.w form only)
-static bool c_taken(const ChunkPlan &cp, bool want_dot, bool zw_dot) { return cp.ok && (!want_dot || zw_dot); }
+// launch shape and load / order flags of the chunked kernel
 static dim3 c_grid(const nf_solver *S, int d, const ChunkPlan &cp) { return dim3((unsigned)((S->nx + cp.TX - 1) / cp.TX), (unsigned)(d == 1 ? S->nz : S->ny)); }
 static unsigned c_block(const ChunkPlan &cp) { return (unsigned)((cp.TX * cp.NS + 63) / 64 * 64); }   // whole wavefronts, as in seg_plan
 static const int C_SEG = 8, C_NCH = 2;                           // k_schur_c: segments of 8 cells, two chunks per block (chunk_plan's NS counts 16 cells)
@@ -1356,10 +1352,9 @@ static int s_xcd(const nf_solver *S, int d, int zmode)
     const nf_team *T = S->team;
     return T->opt_xcd >= 0 ? (T->opt_xcd >> (d - 1)) & 1 : ((d == 1 && nt_regime(S)) || ((zmode == 1 || zmode == 2) && S->N <= (6L << 20)));
 }
-// undivided meshes beyond the caches (the classic path's sizes): the variant with streaming loads (SF doubles as that flag for !SLAB)
-static bool s_nt(const nf_solver *S, int zmode, int SEG) { return zmode == 0 && S->nb == 0 && SEG == 8 && nt_regime(S); }
-static bool s_dict(const nf_solver *S, int d, int zmode, int SEG) { return s_nt(S, zmode, SEG) && dict_dir(S, d); }
-static bool s_nts(const nf_solver *S, int zmode, int SEG) { return zmode != 0 && zmode != 3 && S->nb == 0 && SEG == 8 && nt_regime(S); }   // the same for the z passes of a slab
+// undivided meshes beyond the caches (the classic path's sizes): the variant with streaming loads (SV_NT)
+static bool s_nt(const nf_solver *S, int zmode, int SEG) { return zmode != 3 && S->nb == 0 && SEG == 8 && nt_regime(S); }   // plain lines and the z passes of a slab
+static bool s_dict(const nf_solver *S, int d, int zmode, int SEG) { return zmode == 0 && s_nt(S, zmode, SEG) && dict_dir(S, d); }
 static bool s_zw(const nf_solver *S, int zmode, bool zw_dot, bool want_dot) { return zmode == 0 && S->nb == 0 && zw_dot && want_dot; }     // z.w form of the pass's share of x.y
 static bool s_fold(const nf_team *T, int zmode) { return zmode == 2 && T->sep_sweeps == 0 && T->opt_sepfold; }   // thick slabs: the accumulation pass forms the separator values itself
 // tiles of a (gx, gy) launch move under the XCD-contiguous order only when their count is a multiple of 8 (the kernels' own test) beyond 8 (the identity)
@@ -1460,15 +1455,41 @@ static int line_dict_prepare(nf_team *T)
     }
     return NF_OK;
 }
-struct SchurSLaunch {                                             // every argument of a k_schur_s launch
-    const SegPlan &sp; hipStream_t st; const ModeArgs &ma; const ModeTab &mt; const Geom &G; const double *L, *DR, *D0; int n; long sl, ostride; int nx, last;
-    double *partials; const CgScalars *cg; const SlabArgs &sa; const CgFuse &fz; const CgLean &lz; LineDict ld = LineDict();
-};
-template <int SEG, int DIR, bool SLAB, int NB, bool SF = false, bool NTS = false, bool ZW = false, bool SR = false, bool DICT = false>
-static void launch_s_t(const SchurSLaunch &a)
+// One y / z pass, chosen: launch_s executes this, plan_s prints it, and neither derives a flag of its own.
+// V: the k_schur_s variant (SV_* of nf_kernels.h); for the chunked kernel SV_NT and SV_DICT are its template flags and SV_ZW says that it forms a dot product.
+struct SPass { int rc = NF_OK; bool chunked = false; ChunkPlan cp; SegPlan seg; unsigned V = 0; int xcd = 0, early = 0; bool fold = false, fuse = false; };
+static std::string variant_name(unsigned V)                      // "fuse+nt+sr"; "" for the base kernel
 {
-    hipLaunchKernelGGL((k_schur_s<SEG, DIR, SLAB, NB, SF, NTS, ZW, SR, DICT>), a.sp.grid, a.sp.block, a.sp.lds, a.st, a.ma, a.mt, a.G, a.L, a.DR, a.D0, a.n, a.sl, a.ostride, a.nx,
-                       a.sp.TX, a.sp.NSEG, a.last, a.partials, a.cg, a.sa, a.fz, a.lz, a.ld);
+    static const char *const bit[] = { "fuse", "nt", "zw", "sr", "dict" };
+    std::string r;
+    for (int i = 0; i < 5; ++i) if (V >> i & 1) r += (r.empty() ? "" : "+") + std::string(bit[i]);
+    return r;
+}
+// want_dot: the pass leaves its share of x.y (zw_dot: in the z.w form); fuse / cg1: a fused CG update / the single-reduction state (Cg1) ride along;
+// chunks = false: the device refused the chunked kernel's LDS
+static SPass s_pass(const nf_solver *S, int d, int zmode, bool want_dot, bool zw_dot, bool fuse, bool cg1, bool chunks = true)
+{
+    SPass R;
+    // long plain lines of RT0-P0 meshes: two chunks per block, twice the tile width (k_schur_c).  Its share of x.y comes in the z.w
+    // form only: inside CG it needs the split dot product of team_schur_apply
+    if (chunks && zmode == 0) R.cp = chunk_plan(S, d);            // the slab chain passes never take it
+    if (R.cp.ok && (!want_dot || zw_dot)) {
+        const bool nt = c_nt(S), dict = c_dict(S, d, nt);
+        R.chunked = true; R.V = (nt ? SV_NT : 0) | (want_dot ? SV_ZW : 0) | (dict ? SV_DICT : 0);
+        R.xcd = c_xcd(S, d, nt); R.early = c_early(S, dict);
+        return R;
+    }
+    R.seg = seg_plan(S, d, zmode);
+    if ((R.rc = R.seg.rc) != NF_OK) return R;
+    const int SEG = R.seg.SEG; const bool p0 = S->nb == 0;
+    R.fuse = fuse && zmode == 1 && S->nloc == 1;                  // the endpoint pass of a slab carries the update
+    // single-reduction CG (Cg1): the endpoint pass (mode 1) consumes the reduction of the previous iteration and carries r -= alpha q, the
+    // accumulation pass (mode 2) leaves p.q, q.q, r.q; |r|^2 comes from the endpoint pass (row 3 of the partial buffer)
+    const bool sr = cg1 && p0 && SEG == 8 && d == 2 && ((zmode == 1 && R.fuse) || (zmode == 2 && want_dot));
+    R.V = (R.fuse && p0 ? SV_FUSE : 0) | (s_nt(S, zmode, SEG) ? SV_NT : 0) | (s_zw(S, zmode, zw_dot, want_dot) ? SV_ZW : 0)
+        | (sr ? SV_SR : 0) | (s_dict(S, d, zmode, SEG) ? SV_DICT : 0);
+    R.xcd = s_xcd(S, d, zmode); R.fold = s_fold(S->team, zmode);
+    return R;
 }
 // zmode: 0 = plain line kernel (y lines, or z lines of an undivided mesh); 1 / 2 = slab chain passes (z lines)
 static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const Geom &G, int last, double *partials, const PassCg &P, int *nparts, int zmode)
@@ -1478,73 +1499,45 @@ static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const 
     const int n = d == 1 ? S->ny : S->nz;
     const long nxy = (long)S->nx * S->ny;
     const long sl = d == 1 ? S->nx : nxy, ostride = d == 1 ? nxy : S->nx;
-    // long plain lines of RT0-P0 meshes: two chunks per block, twice the tile width (k_schur_c).  Its share of x.y comes in the z.w
-    // form only: inside CG it needs the split dot product of team_schur_apply
-    const ChunkPlan cp = pass_chunk_plan(S, d, zmode);
-    if (c_taken(cp, last && partials, P.zw_dot)) {
-        const int NS = cp.NS, TXc = cp.TX; const size_t ldsc = cp.lds;
-        {
-            dim3 grid = c_grid(S, d, cp), block(c_block(cp));
-            const double *L = S->d_L[d] + g * N, *DR = S->d_DR[d] + g * N, *D0 = S->d_D0[d] + g * S->nlines[d];
-            const bool nt = c_nt(S);
-            const int xcd = c_xcd(S, d, nt);
-            bool launched = false;                                    // false: the device refused the LDS -> the one-chunk kernel below
-#define NF_C(DIRV, NTV) do { if (lds_opt_in((const void *)k_schur_c<DIRV, NTV>, ldsc)) { \
-            hipLaunchKernelGGL((k_schur_c<DIRV, NTV>), grid, block, ldsc, T->stream, ma.x[0], ma.y[0], ma.Ta, L, DR, D0, n, sl, ostride, S->nx, TXc, NS, last, partials, cg, xcd); \
-            launched = hipGetLastError() == hipSuccess; } } while (0)   /* a refused launch (LDS, block size) falls through to the one-chunk kernel */
-#define NF_CDE(DIRV, EV) do { if (lds_opt_in((const void *)k_schur_c<DIRV, true, true, EV>, ldsc)) { \
-            hipLaunchKernelGGL((k_schur_c<DIRV, true, true, EV>), grid, block, ldsc, T->stream, ma.x[0], ma.y[0], ma.Ta, da.L, da.DR, D0, n, sl, ostride, S->nx, TXc, NS, last, partials, cg, xcd, da.ld); \
-            launched = hipGetLastError() == hipSuccess; } } while (0)
-#define NF_CD(DIRV) do { if (early == 2) NF_CDE(DIRV, 2); else if (early == 1) NF_CDE(DIRV, 1); else NF_CDE(DIRV, 0); } while (0)
-            const DictArgs da = dict_args(S, d, g, c_dict(S, d, nt));
-            const int early = c_early(S, da.on);
-            if (da.on) { if (d == 1) NF_CD(1); else NF_CD(2); }
-            else if (d == 1) { if (nt) NF_C(1, true); else NF_C(1, false); } else { if (nt) NF_C(2, true); else NF_C(2, false); }
-#undef NF_CD
-#undef NF_CDE
-#undef NF_C
-            if (launched) { if (nparts) *nparts = (int)(grid.x * grid.y); return NF_OK; }
-        }
-    }
-    const SegPlan sp = seg_plan(S, d, zmode);
-    if (sp.rc != NF_OK) return sp.rc;
-    const int SEG = sp.SEG;
-    const ModeTab mt = mode_tab(S, d);
-    if (nparts) *nparts = sp.nparts;
     const double *L = S->d_L[d] + g * N, *DR = S->d_DR[d] + g * N, *D0 = S->d_D0[d] + g * S->nlines[d];
+    auto pick = [&](bool chunks) { return s_pass(S, d, zmode, last && partials, P.zw_dot, P.fuse.p != nullptr, P.cg1.red != nullptr, chunks); };
+    SPass ps = pick(true);
+    if (ps.chunked) {
+        const ChunkPlan &cp = ps.cp;
+        const dim3 grid = c_grid(S, d, cp), block(c_block(cp));
+        const DictArgs da = dict_args(S, d, g, (ps.V & SV_DICT) != 0);
+        const unsigned key = ((unsigned)ps.early * 2 + da.on) * 4 + ((ps.V & SV_NT) ? 2 : 0) + (unsigned)(d - 1);
+        bool launched = false;                                    // false: the device refused the LDS, or the launch (LDS, block size) -> the one-chunk kernel below
+        const bool hit = with_index<3 * 2 * 2 * 2>(key, [&](auto i) {
+            constexpr unsigned I = decltype(i)::value;
+            constexpr int DIR = 1 + (I & 1), EARLY = I / 8; constexpr bool NT = I & 2, DICT = I & 4;
+            if constexpr (!schur_c_legal(DIR, NT, DICT, EARLY)) return false;
+            else if (lds_opt_in((const void *)k_schur_c<DIR, NT, DICT, EARLY>, cp.lds)) {
+                hipLaunchKernelGGL((k_schur_c<DIR, NT, DICT, EARLY>), grid, block, cp.lds, T->stream, ma.x[0], ma.y[0], ma.Ta, da.on ? da.L : L, da.on ? da.DR : DR, D0, n, sl, ostride,
+                                   S->nx, cp.TX, cp.NS, last, partials, cg, ps.xcd, da.ld);
+                launched = hipGetLastError() == hipSuccess;
+            }
+            return true;
+        });
+        if (!hit) return fail(NF_ERR_ARG, "k_schur_c: no instantiation for direction %d, nt %d, dict %d, early %d", d, (ps.V & SV_NT) ? 1 : 0, da.on ? 1 : 0, ps.early);
+        if (launched) { if (nparts) *nparts = (int)(grid.x * grid.y); return NF_OK; }
+        ps = pick(false);
+    }
+    if (ps.rc != NF_OK) return ps.rc;
+    const ModeTab mt = mode_tab(S, d);
+    if (nparts) *nparts = ps.seg.nparts;
     hipStream_t st = P.stream ? P.stream : T->stream;
     SlabArgs sa; memset(&sa, 0, sizeof sa);
     sa.noacc = P.noacc ? 1 : 0; sa.yadd = P.yadd;
-    sa.xcd = s_xcd(S, d, zmode);
+    sa.xcd = ps.xcd;
     sa.wsmin = T->opt_wsmin;
-    const CgFuse fz = (zmode == 1 && S->nloc == 1) ? P.fuse : CgFuse{ nullptr, nullptr, nullptr };
-    const CgLean lz = (zmode == 1 && S->nloc == 1 && fz.p) ? P.lean_z1 : CgLean{ nullptr, nullptr, 0, 0, 0 };
-    const bool nt = s_nt(S, zmode, SEG), nts = s_nts(S, zmode, SEG), zw = s_zw(S, zmode, P.zw_dot, last && partials);
-    // single-reduction CG (Cg1): the endpoint pass (mode 1) consumes the reduction of the previous iteration and carries r -= alpha q, the
-    // accumulation pass (mode 2) leaves p.q, q.q, r.q; |r|^2 comes from the endpoint pass (row 3 of the partial buffer)
-    const bool sr = P.cg1.red != nullptr && S->nb == 0 && SEG == 8 && d == 2 && ((zmode == 1 && fz.p) || (zmode == 2 && last && partials));
-    if (sr) {
+    const CgFuse fz = ps.fuse ? P.fuse : CgFuse{ nullptr, nullptr, nullptr };
+    const CgLean lz = fz.p ? P.lean_z1 : CgLean{ nullptr, nullptr, 0, 0, 0 };
+    if (ps.V & SV_SR) {
         sa.sr = P.cg1; sa.sr_r = S->d_r; sa.sr_q = S->d_q; sa.sr_stride = T->partial_stride;
         sa.sr_part = T->d_partials + 3 * T->partial_stride + (long)S->slab_index * T->slab_cap;
     }
-    const DictArgs da = dict_args(S, d, g, s_dict(S, d, zmode, SEG));   // the column's row of the table instead of its own L, 1/d
-    const bool dict = da.on;
-    const SchurSLaunch A = { sp, st, ma, mt, G, dict ? da.L : L, dict ? da.DR : DR, D0, n, sl, ostride, S->nx, last, partials, cg, sa, fz, lz, da.ld };   // sa by reference: its slab fields follow
-#define NF_S(SEGV, DIRV, SLABV, NBV) do { if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && sr && zmode == 1 && nts) launch_s_t<SEGV, DIRV, SLABV, NBV, SLABV && NBV == 0, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
-        else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && sr && zmode == 1) launch_s_t<SEGV, DIRV, SLABV, NBV, SLABV && NBV == 0, false, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
-        else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && sr && nts) launch_s_t<SEGV, DIRV, SLABV, NBV, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
-        else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && sr) launch_s_t<SEGV, DIRV, SLABV, NBV, false, false, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
-        else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && nts && fz.p) launch_s_t<SEGV, DIRV, SLABV, NBV, SLABV && NBV == 0, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
-        else if (SLABV && NBV == 0 && SEGV == 8 && DIRV == 2 && nts) launch_s_t<SEGV, DIRV, SLABV, NBV, false, SLABV && NBV == 0 && SEGV == 8 && DIRV == 2>(A); \
-        else if (SLABV && NBV == 0 && fz.p) launch_s_t<SEGV, DIRV, SLABV, NBV, SLABV && NBV == 0>(A); \
-        else if (!SLABV && NBV == 0 && zw && SEGV == 8 && nt && dict) launch_s_t<SEGV, DIRV, SLABV, NBV, !SLABV && NBV == 0 && SEGV == 8, false, !SLABV && NBV == 0, false, !SLABV && NBV == 0 && SEGV == 8>(A); \
-        else if (!SLABV && NBV == 0 && SEGV == 8 && nt && dict) launch_s_t<SEGV, DIRV, SLABV, NBV, !SLABV && NBV == 0 && SEGV == 8, false, false, false, !SLABV && NBV == 0 && SEGV == 8>(A); \
-        else if (!SLABV && NBV == 0 && zw && SEGV == 8 && nt) launch_s_t<SEGV, DIRV, SLABV, NBV, !SLABV && NBV == 0 && SEGV == 8, false, !SLABV && NBV == 0>(A); \
-        else if (!SLABV && NBV == 0 && zw) launch_s_t<SEGV, DIRV, SLABV, NBV, false, false, !SLABV && NBV == 0>(A); \
-        else if (!SLABV && NBV == 0 && SEGV == 8 && nt) launch_s_t<SEGV, DIRV, SLABV, NBV, !SLABV && NBV == 0 && SEGV == 8>(A); \
-        else launch_s_t<SEGV, DIRV, SLABV, NBV, false>(A); } while (0)
-#define NF_S_SEG(DIRV, SLABV, NBV) do { if (SEG == 4) NF_S(4, DIRV, SLABV, NBV); else if (SEG == 8) NF_S(8, DIRV, SLABV, NBV); \
-        else if (SEG == 16 && NBV == 0) NF_S(16, DIRV, SLABV, 0); else if (SEG == 32 && NBV == 0) NF_S(32, DIRV, SLABV, 0); else return fail(NF_ERR_ARG, "bad s_seg"); } while (0)
+    const DictArgs da = dict_args(S, d, g, (ps.V & SV_DICT) != 0);   // the column's row of the table instead of its own L, 1/d
     if (zmode != 0) {
         const long nl = S->nlines[2];
         sa.if_lo = S->if_lo; sa.if_hi = S->if_hi; sa.mode = zmode;
@@ -1559,18 +1552,21 @@ static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const 
                 sa.amode[m] = amode;
             }
         }
-        if (s_fold(T, zmode)) {                                     // separators formed inside the pass (no k_separators launch)
+        if (ps.fold) {                                              // separators formed inside the pass (no k_separators launch)
             sa.fold = 1; sa.rlo = S->d_rlo; sa.rhi = S->d_rhi; sa.sinv_lo = S->d_sinv_lo + g * nl; sa.sinv_hi = S->d_sinv_hi + g * nl;
         }
-        if (S->nb == 0) NF_S_SEG(2, true, 0); else if (S->nb == 1) NF_S_SEG(2, true, 1); else NF_S_SEG(2, true, 2);
-    } else if (d == 1) {
-        if (S->nb == 0) NF_S_SEG(1, false, 0); else if (S->nb == 1) NF_S_SEG(1, false, 1); else NF_S_SEG(1, false, 2);
-    } else {
-        if (S->nb == 0) NF_S_SEG(2, false, 0); else if (S->nb == 1) NF_S_SEG(2, false, 1); else NF_S_SEG(2, false, 2);
     }
-#undef NF_S_SEG
-#undef NF_S
-    return NF_OK;
+    int lg = 0; while ((4 << lg) < ps.seg.SEG) ++lg;
+    const unsigned key = (4 << lg) == ps.seg.SEG ? ((ps.V * 3 + (zmode != 0 ? 2u : d - 1u)) * 3 + (unsigned)S->nb) * 4 + (unsigned)lg : ~0u;   // shapes: y lines, z lines, z lines of a slab
+    const bool hit = with_index<(SV_ALL + 1) * 3 * 3 * 4>(key, [&](auto i) {
+        constexpr unsigned I = decltype(i)::value, V = I / 36;
+        constexpr int SEG = 4 << (I & 3), NB = I / 4 % 3, DIR = I / 12 % 3 == 0 ? 1 : 2; constexpr bool SLAB = I / 12 % 3 == 2;
+        if constexpr (!schur_s_legal(SEG, DIR, SLAB, NB, V)) return false;
+        else hipLaunchKernelGGL((k_schur_s<SEG, DIR, SLAB, NB, V>), ps.seg.grid, ps.seg.block, ps.seg.lds, st, ma, mt, G, da.on ? da.L : L, da.on ? da.DR : DR, D0, n, sl, ostride, S->nx,
+                                ps.seg.TX, ps.seg.NSEG, last, partials, cg, sa, fz, lz, da.ld);
+        return true;
+    });
+    return hit ? NF_OK : fail(NF_ERR_ARG, "k_schur_s: no instantiation for SEG = %d (s_seg), direction %d, zmode %d, NB = %d, variant \"%s\"", ps.seg.SEG, d, zmode, S->nb, variant_name(ps.V).c_str());
 }
 
 // the endpoint pass of a slab as weighted sums (k_endpoint_w) instead of a chain solve: inside the single-reduction CG (sr), weights measured,
@@ -1761,33 +1757,29 @@ int nf_team_schur_apply(nf_handle S, int g, const double *const *x_dev, double *
 }
 
 // ---- read-only report of the launch plan -------------------------------------------------------
-// What the next Schur apply on this handle's mesh (or slab) would launch, per direction, as one JSON object.  Built from the predicates
-// the launch functions call (x_plan / x_nt / x_p2 / x_xcd, pass_chunk_plan / c_taken / c_nt / c_xcd, seg_plan / s_nt / s_nts / s_zw / s_xcd,
-// endpoint_w_taken, the cg_* forms, split_dot, xy_overlap, x_dict / c_dict / s_dict); apart from building the tables of distinct lines where the next
+// What the next Schur apply on this handle's mesh (or slab) would launch, per direction, as one JSON object.  It prints what
+// the launch functions execute (x_plan for the x pass, s_pass for a y / z pass) and calls the predicates they call (endpoint_w_taken, the cg_*
+// forms, split_dot, xy_overlap); apart from building the tables of distinct lines where the next
 // apply would (line_dict_prepare) it launches nothing and writes no state.  The one thing it cannot know is a device
 // that refuses the chunked kernel's LDS at launch time (launch_s then falls back to the one-chunk kernel).
-struct PlanPass { const char *dir, *family; int mode, SEG, NCH, TX, NSEG; dim3 grid; unsigned block; bool nt, p2, zw, order; unsigned tiles; bool fold = false, dict = false; int early = 0; };
+struct PlanPass { const char *dir, *family; int mode, SEG, NCH, TX, NSEG; dim3 grid; unsigned block; bool nt, p2, zw, order; unsigned tiles; bool fold = false, dict = false; int early = 0; unsigned V = 0; };
 static void plan_emit(std::string &js, const PlanPass &p)
 {
     char tmp[416];
     snprintf(tmp, sizeof tmp, "%s{\"dir\": \"%s\", \"mode\": %d, \"family\": \"%s\", \"SEG\": %d, \"NCH\": %d, \"TX\": %d, \"NSEG\": %d, \"grid\": [%u, %u, %u], "
-             "\"block\": %u, \"nt\": %d, \"p2\": %d, \"zw\": %d, \"xcd_order\": %d, \"xcd_permutes\": %d, \"fold\": %d, \"dict\": %d, \"early\": %d}", js.back() == '[' ? "" : ", ", p.dir, p.mode, p.family,
+             "\"block\": %u, \"nt\": %d, \"p2\": %d, \"zw\": %d, \"xcd_order\": %d, \"xcd_permutes\": %d, \"fold\": %d, \"dict\": %d, \"early\": %d", js.back() == '[' ? "" : ", ", p.dir, p.mode, p.family,
              p.SEG, p.NCH, p.TX, p.NSEG, p.grid.x, p.grid.y, p.grid.z, p.block, p.nt ? 1 : 0, p.p2 ? 1 : 0, p.zw ? 1 : 0, p.order ? 1 : 0, xcd_permutes(p.order, p.tiles) ? 1 : 0, p.fold ? 1 : 0, p.dict ? 1 : 0, p.early);
     js += tmp;
+    if (!strcmp(p.family, "s")) js += ", \"variant\": \"" + variant_name(p.V) + "\"";   // which k_schur_s
+    js += "}";
 }
-static int plan_s(std::string &js, const nf_solver *S, int d, int zmode, bool want_dot, bool zw_dot)   // a launch_s call
+static int plan_s(std::string &js, const nf_solver *S, int d, int zmode, bool want_dot, bool zw_dot, bool fuse, bool cg1)   // a launch_s call
 {
-    const char *dir = d == 1 ? "y" : "z";
-    const ChunkPlan cp = pass_chunk_plan(S, d, zmode);
-    if (c_taken(cp, want_dot, zw_dot)) {
-        const dim3 gr = c_grid(S, d, cp); const bool nt = c_nt(S);
-        plan_emit(js, { dir, "c", zmode, C_SEG, C_NCH, cp.TX, cp.NS, gr, c_block(cp), nt, false, want_dot, c_xcd(S, d, nt) != 0, gr.x * gr.y, false, c_dict(S, d, nt), c_early(S, c_dict(S, d, nt)) });
-        return NF_OK;
-    }
-    const SegPlan sp = seg_plan(S, d, zmode);
-    if (sp.rc != NF_OK) return sp.rc;
-    plan_emit(js, { dir, "s", zmode, sp.SEG, 1, sp.TX, sp.NSEG, sp.grid, sp.block.x, s_nt(S, zmode, sp.SEG) || s_nts(S, zmode, sp.SEG), false, s_zw(S, zmode, zw_dot, want_dot),
-                    s_xcd(S, d, zmode) != 0, sp.grid.x * sp.grid.y, s_fold(S->team, zmode), s_dict(S, d, zmode, sp.SEG) });
+    const SPass ps = s_pass(S, d, zmode, want_dot, zw_dot, fuse, cg1);
+    if (ps.rc != NF_OK) return ps.rc;
+    const dim3 gr = ps.chunked ? c_grid(S, d, ps.cp) : ps.seg.grid;
+    plan_emit(js, { d == 1 ? "y" : "z", ps.chunked ? "c" : "s", zmode, ps.chunked ? C_SEG : ps.seg.SEG, ps.chunked ? C_NCH : 1, ps.chunked ? ps.cp.TX : ps.seg.TX, ps.chunked ? ps.cp.NS : ps.seg.NSEG,
+                    gr, ps.chunked ? c_block(ps.cp) : ps.seg.block.x, (ps.V & SV_NT) != 0, false, (ps.V & SV_ZW) != 0, ps.xcd != 0, gr.x * gr.y, ps.fold, (ps.V & SV_DICT) != 0, ps.early, ps.V });
     return NF_OK;
 }
 int nf_apply_plan(nf_handle S, int in_cg, char *json_buf, size_t len)
@@ -1816,17 +1808,16 @@ int nf_apply_plan(nf_handle S, int in_cg, char *json_buf, size_t len)
     for (int d = 0; d < S->dim; ++d) {
         const bool last = d == S->dim - 1, want_dot = cg && (last || split);
         if (d == 0) {
-            const XPlan xp = x_plan(S);
+            const XPlan xp = x_plan(S, fused);
             if (!xp.NCH) return fail(NF_ERR_UNSUPPORTED, "nx = %d exceeds the x-line kernel limit (%d cells)", S->nx, S->nb == 0 ? 4096 : 1024);
-            const bool nt = x_nt(S, S->nb), order = x_xcd(S, nt);
-            plan_emit(js, { "x", "x", 0, 0, xp.NCH, 1 << xp.lpl_log2, 0, dim3(xp.grid, (unsigned)n_modes(S)), 256u, nt, x_p2(S, S->nb, xp.NCH, fused && x_fuses(S), nt), false, order, xp.grid, false, x_dict(S, S->nb, xp.NCH, nt) });
+            plan_emit(js, { "x", "x", 0, 0, xp.NCH, 1 << xp.lpl_log2, 0, dim3(xp.grid, (unsigned)n_modes(S)), 256u, xp.nt, xp.p2, false, xp.xcd, xp.grid, false, xp.dict });
         } else if (d == 2 && slab) {
             // endpoint pass: inside the fused CG the update reads the vector the pass is applied to (cg_solve applies to d_p)
             if (endpoint_w_taken(T, S, sr, fused)) { const dim3 gr = endpoint_w_grid(S); plan_emit(js, { "z", "endpoint_w", 1, 0, 0, 64, 0, gr, 256u, false, false, false, false, gr.x * gr.y }); }
-            else NFCHK(plan_s(js, S, 2, 1, false, false));
-            NFCHK(plan_s(js, S, 2, 2, want_dot, split));
-        } else if (d == 1 && xy_all) NFCHK(plan_s(js, S, 1, 0, false, split));
-        else NFCHK(plan_s(js, S, d, 0, want_dot, split));
+            else NFCHK(plan_s(js, S, 2, 1, false, false, fused, sr));
+            NFCHK(plan_s(js, S, 2, 2, want_dot, split, fused, sr));
+        } else if (d == 1 && xy_all) NFCHK(plan_s(js, S, 1, 0, false, split, fused, sr));
+        else NFCHK(plan_s(js, S, d, 0, want_dot, split, fused, sr));
     }
     {   // distinct lines of the largest group per direction, 0 where the direction does not use its table
         int nd[3] = { 0, 0, 0 };

@@ -1049,26 +1049,37 @@ struct SlabArgs {
 // act == false only keep the barriers company.  acc: accumulate into y (the x pass ran before) or store the increment alone
 // (fused-direction launch: every direction has an output vector of its own).  fro ("read-only fuse"): the input vector is
 // r + beta x, formed on the fly (see CgFuse).  Returns the thread's share of x.y.
-// SF (slab variants): the instantiation that can carry the fused CG update (r and x_sol of the cells in registers: 160 instead of
+// V: the variant, a mask of SV_* bits.
+// SV_FUSE (slab passes): the instantiation that can carry the fused CG update (r and x_sol of the cells in registers: 160 instead of
 // 128 VGPRs); the accumulation / emit passes use the one without
-// ZW (plain RT0-P0 lines): the pass's share of x.y is not summed as x_i y_i over the cells -- x.(S_d x) = T_a t^T A^-1 t with
+// SV_NT (big meshes): streaming loads (ldg) of everything but the overlap cell
+// SV_ZW (plain RT0-P0 lines): the pass's share of x.y is not summed as x_i y_i over the cells -- x.(S_d x) = T_a t^T A^-1 t with
 // A = L D L^T is T_a sum_faces z_f^2 / d_f = T_a sum z_f w_f, and both factors are at hand in the forward sweep.  The x pass then
 // contributes x.(C x + S_x x) and the consumer adds the three sets of partials: the backward half of a y / z pass needs no x at all
 // (eight doubles fewer live through the scans, and the chunked long-line pass has nothing to re-read for its parked chunk).
+// SV_SR (RT0-P0 slab passes): single-reduction CG, see SlabArgs::sr
+// SV_DICT (plain RT0-P0 lines in the streaming regime, see LineDict): L and DR point at the table of distinct lines; a lane carries the byte
+// offset of its line's row and reaches the cells of its segment from there -- contiguous along the line, plain loads, bit-equal values
 // XC (k_cg_xcd: the producers of x and r are other workgroups of the SAME launch on the same XCD): every load of x and r bypasses the
 // compute unit's L1 -- the overlap cell too
-// DICT (plain RT0-P0 lines in the streaming regime, see LineDict): L and DR point at the table of distinct lines; a lane carries the byte
-// offset of its line's row and reaches the cells of its segment from there -- contiguous along the line, plain loads, bit-equal values
-template <int SEG, int DIR, bool SLAB, int NB, bool SF = false, bool NTS = false, class Mid = NoMid, bool ZW = false, bool XC = false, bool SR = false, bool DICT = false>   // NTS: streaming loads in a slab variant
+enum : unsigned { SV_FUSE = 1, SV_NT = 2, SV_ZW = 4, SV_SR = 8, SV_DICT = 16, SV_ALL = 31 };   // bit order = the order of the report's "variant"
+// The instantiations of k_schur_s: the shapes (16- and 32-cell segments for RT0-P0 only, slabs cut z lines only) and the bits that a shape admits.
+// The kernel asserts this and the host instantiates exactly the combinations for which it holds.
+constexpr bool schur_s_legal(int SEG, int DIR, bool SLAB, int NB, unsigned V)
+{
+    const bool p0 = NB == 0, s8 = p0 && SEG == 8;                // RT0-P0; its 8-cell segments
+    const unsigned admits = (SLAB && p0 ? SV_FUSE : 0) | (s8 ? SV_NT : 0) | (!SLAB && p0 ? SV_ZW : 0) | (SLAB && s8 && DIR == 2 ? SV_SR : 0) | (!SLAB && (V & SV_NT) ? SV_DICT : 0);
+    return (SEG == 4 || SEG == 8 || (p0 && (SEG == 16 || SEG == 32))) && (DIR == 2 || (DIR == 1 && !SLAB)) && NB >= 0 && NB <= 2 && !(V & ~admits);
+}
+template <int SEG, int DIR, bool SLAB, int NB, unsigned V = 0, class Mid = NoMid, bool XC = false>
 __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G, const double *__restrict__ L, const double *__restrict__ DR,
                                                const double *__restrict__ D0, int n, long sl, long outer_stride, int nx, int TX, int NSEG,
                                                unsigned bx, unsigned by, unsigned bz, unsigned gy, int tid, bool act, double *sm,
                                                const SlabArgs &sa, const CgFuse &fz, bool fuse, bool fro, double f_alpha, double f_beta, bool acc,
                                                long long *stamp = nullptr, Mid mid = Mid(), double *extra = nullptr, const LineDict &ld = LineDict())
 {
-    static_assert(!SR || (SLAB && NB == 0), "single-reduction CG: RT0-P0 slab passes");
-    static_assert(!DICT || (!SLAB && NB == 0 && SF), "line tables: next to the streaming instantiations of plain RT0-P0 lines only");
-    constexpr bool NT = SLAB ? NTS : SF;                         // big meshes: streaming loads (ldg); SF doubles as that flag on undivided meshes
+    constexpr bool FUSE = V & SV_FUSE, NT = V & SV_NT, ZW = V & SV_ZW, SR = V & SV_SR, DICT = V & SV_DICT;
+    static_assert(SLAB || !(FUSE || SR), "fused update, single-reduction sums: slab passes (k_schur_s checks the rest: schur_s_legal)");
     const double *x = ma.x[0];                                   // no __restrict__: the fused slab pass rewrites this vector (fz.p)
     double *__restrict__ y = ma.y[0];
     const int T = TX * NSEG;
@@ -1107,7 +1118,7 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
             if (sa.if_lo) {
                 a_lo = sa.alo[lineid]; x_before = x[edge_lo];
                 if (fuse) { if (seg == 0) fz.xsol[edge_lo] = fma(f_alpha, x_before, fz.xsol[edge_lo]);
-                            x_before = fma(f_beta, x_before, (SR && SF) ? fma(-f_alpha, sa.sr_q[edge_lo], fz.r[edge_lo]) : fz.r[edge_lo]); }
+                            x_before = fma(f_beta, x_before, (SR && FUSE) ? fma(-f_alpha, sa.sr_q[edge_lo], fz.r[edge_lo]) : fz.r[edge_lo]); }
                 xe_lo = x_before;
                 if (NB > 0) {
                     const double g1 = ma.Gc[0] * ma.x[1][edge_lo], g2 = NB > 1 ? ma.Gc[1] * ma.x[2][edge_lo] : 0.0;
@@ -1119,7 +1130,7 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
             if (sa.if_hi) {
                 a_hi = sa.ahi[lineid]; x_after = x[edge_hi];
                 if (fuse) { if (seg == 0) fz.xsol[edge_hi] = fma(f_alpha, x_after, fz.xsol[edge_hi]);
-                            x_after = fma(f_beta, x_after, (SR && SF) ? fma(-f_alpha, sa.sr_q[edge_hi], fz.r[edge_hi]) : fz.r[edge_hi]); }
+                            x_after = fma(f_beta, x_after, (SR && FUSE) ? fma(-f_alpha, sa.sr_q[edge_hi], fz.r[edge_hi]) : fz.r[edge_hi]); }
                 xe_hi = x_after;
                 if (NB > 0) {
                     const double g1 = ma.Gc[0] * ma.x[1][edge_hi], g2 = NB > 1 ? ma.Gc[1] * ma.x[2][edge_hi] : 0.0;
@@ -1138,7 +1149,7 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
     // ---- loads only.  Every load of this phase is issued before the first use of a loaded value: a use inside a predicated region
     // makes the compiler wait for ALL outstanding memory operations there (s_waitcnt vmcnt(0) per region), i.e. one memory round
     // trip per cell instead of one per phase (measured with in-kernel stamps: 9.6 k cycles for the 36 loads of a fused y / z block).
-    if (SLAB && !SF) fuse = false;
+    if (SLAB && !FUSE) fuse = false;
     const bool fr = SLAB ? fuse : fro;                           // the input vector is r + beta x (wave-uniform)
     // higher-order passes of undivided meshes touch up to eleven arrays per cell: 32-bit byte offsets from the wave-uniform bases (ldo / sto)
     constexpr bool O32 = NB > 0 && !SLAB;
@@ -1147,8 +1158,8 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
     if (DICT) tb8 = valid ? (unsigned)ld.id[lineid] * (unsigned)ld.pitch * 8u : 0u;
 #define NF_A8(c) (ob8 + (unsigned)(c) * sl8)
 #define NF_T8(c) (tb8 + (unsigned)(c) * 8u)
-    double rv[(SLAB && !SF) ? 1 : SEG + 1], sv[(SLAB && SF) ? SEG : 1];   // r of the same cells; slab fuse: x_sol of the owned cells
-    double qv[(SR && SF) ? SEG + 1 : 1], rq_[(SR && !SF) ? SEG : 1];      // SR: q of the same cells (endpoint pass); r of the owned cells (accumulation pass)
+    double rv[(SLAB && !FUSE) ? 1 : SEG + 1], sv[FUSE ? SEG : 1];   // r of the same cells; slab fuse: x_sol of the owned cells
+    double qv[(SR && FUSE) ? SEG + 1 : 1], rq_[(SR && !FUSE) ? SEG : 1];      // SR: q of the same cells (endpoint pass); r of the owned cells (accumulation pass)
     double srr = 0.0, sqq = 0.0, srq = 0.0;
     double r1[NB > 0 ? SEG + 1 : 1], r2[NB > 1 ? SEG + 1 : 1], v1a[NB > 0 ? SEG + 1 : 1], v2a[NB > 1 ? SEG + 1 : 1], Dv[NB > 0 ? SEG : 1];
 #pragma unroll
@@ -1158,9 +1169,9 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
         // the overlap cell (i == SEG) is the next segment's first: keep that line for it (see k_schur_c on why this is not a ternary on i)
         if (O32) xv[i] = ok ? ldo<NT>(x, NF_A8(c)) : 0.0;
         else if (i < SEG || XC) xv[i] = ok ? ldg<NT>(x + a) : 0.0; else xv[i] = ok ? x[a] : 0.0;
-        if (!SLAB || SF) rv[(SLAB && !SF) ? 0 : i] = (fr && ok) ? (SLAB ? fz.r[a] : (O32 ? ldo<NT>(x + roff, NF_A8(c)) : ldg<NT>(x + a + roff))) : 0.0;
-        if (SLAB && SF && i < SEG) sv[(SLAB && SF) ? i : 0] = (fuse && ok) ? fz.xsol[a] : 0.0;
-        if (SR && SF) qv[(SR && SF) ? i : 0] = (fuse && ok) ? sa.sr_q[a] : 0.0;
+        if (!SLAB || FUSE) rv[(SLAB && !FUSE) ? 0 : i] = (fr && ok) ? (SLAB ? fz.r[a] : (O32 ? ldo<NT>(x + roff, NF_A8(c)) : ldg<NT>(x + a + roff))) : 0.0;
+        if (FUSE && i < SEG) sv[FUSE ? i : 0] = (fuse && ok) ? fz.xsol[a] : 0.0;
+        if (SR && FUSE) qv[(SR && FUSE) ? i : 0] = (fuse && ok) ? sa.sr_q[a] : 0.0;
         if (DICT) { Lv[i] = ok ? ldo<false>(L, NF_T8(c)) : 0.0; if (i < SEG) Rv[i] = ok ? ldo<false>(DR, NF_T8(c)) : 0.0; }
         else if (O32) { Lv[i] = ok ? ldo<NT>(L, NF_A8(c)) : 0.0; if (i < SEG) Rv[i] = ok ? ldo<NT>(DR, NF_A8(c)) : 0.0; }
         else {
@@ -1190,12 +1201,12 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
 #pragma unroll
     for (int i = 0; i <= SEG; ++i) {
         const int c = c0 + i; const bool ok = valid && c < n;
-        if ((!SLAB || SF) && fr) {
-            if (SR && SF) rv[(SLAB && !SF) ? 0 : i] = fma(-f_alpha, qv[(SR && SF) ? i : 0], rv[(SLAB && !SF) ? 0 : i]);   // r -= alpha q (src/solvers.cpp:610)
-            if (SLAB && SF && i < SEG) sv[(SLAB && SF) ? i : 0] = fma(f_alpha, xv[i], sv[(SLAB && SF) ? i : 0]);   // owned cell; the overlap cell (i == SEG) belongs to the next segment
-            xv[i] = fma(f_beta, xv[i], rv[(SLAB && !SF) ? 0 : i]);
+        if ((!SLAB || FUSE) && fr) {
+            if (SR && FUSE) rv[(SLAB && !FUSE) ? 0 : i] = fma(-f_alpha, qv[(SR && FUSE) ? i : 0], rv[(SLAB && !FUSE) ? 0 : i]);   // r -= alpha q (src/solvers.cpp:610)
+            if (FUSE && i < SEG) sv[FUSE ? i : 0] = fma(f_alpha, xv[i], sv[FUSE ? i : 0]);   // owned cell; the overlap cell (i == SEG) belongs to the next segment
+            xv[i] = fma(f_beta, xv[i], rv[(SLAB && !FUSE) ? 0 : i]);
         }
-        if (SR && SF && i < SEG) { const double rn = fr ? rv[(SLAB && !SF) ? 0 : i] : xv[i]; srr += ok ? rn * rn : 0.0; }   // |r|^2 of the owned cells (first iteration: p = r)
+        if (SR && FUSE && i < SEG) { const double rn = fr ? rv[(SLAB && !FUSE) ? 0 : i] : xv[i]; srr += ok ? rn * rn : 0.0; }   // |r|^2 of the owned cells (first iteration: p = r)
         if (SLAB && valid && c == n) xv[i] = x_after;
         if (NB > 0) {
             double v1 = v1a[i], v2 = NB > 1 ? v2a[NB > 1 ? i : 0] : 0.0;
@@ -1212,9 +1223,9 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
             }
         }
     }
-    if (SLAB && SF && fuse) {                                    // x_sol += alpha p of the owned cells
+    if (FUSE && fuse) {                                    // x_sol += alpha p of the owned cells
 #pragma unroll
-        for (int i = 0; i < SEG; ++i) if (valid && c0 + i < n) fz.xsol[base + (long)(c0 + i) * sl] = sv[(SLAB && SF) ? i : 0];
+        for (int i = 0; i < SEG; ++i) if (valid && c0 + i < n) fz.xsol[base + (long)(c0 + i) * sl] = sv[FUSE ? i : 0];
     }
     double t[NB > 0 ? SEG : 1];                                  // NB == 0: t_i = xv_i - xv_{i+1} is recomputed where needed (registers)
     double P = 1.0, lz = 0.0;
@@ -1260,9 +1271,9 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
 #pragma unroll
         for (int i = 0; i < SEG; ++i) if (c0 + i < n) fz.p[base + (long)(c0 + i) * sl] = xv[i];
         if (seg == 0) { if (sa.if_lo) fz.p[edge_lo] = xe_lo; if (sa.if_hi) fz.p[edge_hi] = xe_hi; }
-        if (SR && SF) {                                          // the updated residual: other threads of the block read the old one above (overlap and edge cells)
+        if (SR && FUSE) {                                          // the updated residual: other threads of the block read the old one above (overlap and edge cells)
 #pragma unroll
-            for (int i = 0; i < SEG; ++i) if (c0 + i < n) sa.sr_r[base + (long)(c0 + i) * sl] = rv[(SLAB && !SF) ? 0 : i];
+            for (int i = 0; i < SEG; ++i) if (c0 + i < n) sa.sr_r[base + (long)(c0 + i) * sl] = rv[(SLAB && !FUSE) ? 0 : i];
             // edge cells: every thread of the column formed r - alpha q for its p above; the owner (segment 0) forms it once more here,
             // behind the barrier, rather than keeping it alive across the scans -- the old r and q are still in place, it is their only writer
             if (seg == 0) {
@@ -1271,7 +1282,7 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
             }
         }
     }
-    if (SR && SF && !fuse && valid && seg == 0) {                // first iteration: r = p, untouched
+    if (SR && FUSE && !fuse && valid && seg == 0) {                // first iteration: r = p, untouched
         if (sa.if_lo) { const double re = x[edge_lo]; srr += re * re; }
         if (sa.if_hi) { const double re = x[edge_hi]; srr += re * re; }
     }
@@ -1307,9 +1318,9 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
     NF_STAMP(stamp, 6);
     __syncthreads();
     NF_STAMP(stamp, 7);
-    if (SR && !SF) {                                             // r of the owned cells (for r.q): asked for behind the barrier, so that it is not alive across
+    if (SR && !FUSE) {                                             // r of the owned cells (for r.q): asked for behind the barrier, so that it is not alive across
 #pragma unroll                                                   // the scans (the pass sits at 128 VGPRs = four blocks of 256 threads per CU); it flies during the backward replay
-        for (int i = 0; i < SEG; ++i) rq_[(SR && !SF) ? i : 0] = (valid && c0 + i < n && wr) ? sa.sr_r[base + (long)(c0 + i) * sl] : 0.0;
+        for (int i = 0; i < SEG; ++i) rq_[(SR && !FUSE) ? i : 0] = (valid && c0 + i < n && wr) ? sa.sr_r[base + (long)(c0 + i) * sl] : 0.0;
     }
     double u = 0.0;
     if (wscan) {
@@ -1341,7 +1352,7 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
             const double lo = i == 0 ? ulo : w[i > 0 ? i - 1 : 0];
             const bool in = valid && c0 + i < n;                 // a select, not a branch (slab chains: xv of the cell behind the chain end is the edge cell)
             yo[i] = yo[i] + ma.Ta * (w[i] - lo); if (!ZW) dot += in ? xv[i] * yo[i] : 0.0;
-            if (SR && !SF) { sqq += in ? yo[i] * yo[i] : 0.0; srq += in ? rq_[(SR && !SF) ? i : 0] * yo[i] : 0.0; }
+            if (SR && !FUSE) { sqq += in ? yo[i] * yo[i] : 0.0; srq += in ? rq_[(SR && !FUSE) ? i : 0] * yo[i] : 0.0; }
             if (NB > 0) {
                 const double v = ma.Gc[0] * x1[i] * ma.iM[0] * icv[i] - (ma.eL[0] * lo + ma.eR[0] * w[i]);
                 y1o[i] = y1o[i] + ma.Ta * ma.Gc[0] * v; dot += in ? x1[i] * y1o[i] : 0.0;
@@ -1423,7 +1434,7 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
             else {
                 const double u_lo = sa.fold ? (sa.rlo[lm] + sa.clo[lm]) * sa.sinv_lo[lineid] : sa.ulo[lm];
                 const double xe = x[edge_lo]; const double yv = (y[edge_lo] + ((NB == 0 && sa.yadd) ? sa.yadd[edge_lo] : 0.0)) + ma.Ta * (ulo - u_lo); y[edge_lo] = yv; dot += xe * yv;
-                if (SR && !SF) { sqq += yv * yv; srq += sa.sr_r[edge_lo] * yv; }
+                if (SR && !FUSE) { sqq += yv * yv; srq += sa.sr_r[edge_lo] * yv; }
                 if (NB > 0) {                                    // bubbles of the edge cell: faces (separator, first chain face)
                     const double ice = ma.D[edge_lo] / geom_factor(G, DIR, ix, (int)by, 0);
 #pragma unroll
@@ -1445,7 +1456,7 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
             else {
                 const double u_hi = sa.fold ? (sa.chi[lm] + sa.rhi[lm]) * sa.sinv_hi[lineid] : sa.uhi[lm];
                 const double xe = x[edge_hi]; const double yv = (y[edge_hi] + ((NB == 0 && sa.yadd) ? sa.yadd[edge_hi] : 0.0)) + ma.Ta * (u_hi - ulast); y[edge_hi] = yv; dot += xe * yv;
-                if (SR && !SF) { sqq += yv * yv; srq += sa.sr_r[edge_hi] * yv; }
+                if (SR && !FUSE) { sqq += yv * yv; srq += sa.sr_r[edge_hi] * yv; }
                 if (NB > 0) {                                    // faces (last chain face, separator)
                     const int fsz = sa.if_lo ? 1 : 0;
                     const double ice = ma.D[edge_hi] / geom_factor(G, DIR, ix, (int)by, fsz + n);
@@ -1460,7 +1471,7 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
             }
         }
     }
-    if (SR && SF) return srr;                                    // endpoint pass: this thread's share of |r|^2
+    if (SR && FUSE) return srr;                                    // endpoint pass: this thread's share of |r|^2
     if (SR && extra) { extra[0] = sqq; extra[1] = srq; }
     return dot;
 #undef NF_A8
@@ -1469,19 +1480,21 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
 
 // Slab variants keep r and x_sol of their cells in registers next to x, L, 1/d (loads first, see schur_s_tile): blocks of at most 512
 // threads, so that the register budget is 256 per thread (the host picks TX accordingly)
-template <int SEG, int DIR, bool SLAB, int NB, bool SF = false, bool NTS = false, bool ZW = false, bool SR = false, bool DICT = false>
-__global__ __launch_bounds__(SLAB ? 512 : 1024, SLAB ? (NB > 0 ? 2 : (SF ? (SR ? NF_SR_Z1_WAVES : 3) : (SR ? NF_SR_Z2_WAVES : 4))) : 1) void k_schur_s(ModeArgs ma0, ModeTab mt, Geom G, const double *__restrict__ L, const double *__restrict__ DR,
+template <int SEG, int DIR, bool SLAB, int NB, unsigned V = 0>
+__global__ __launch_bounds__(SLAB ? 512 : 1024, SLAB ? (NB > 0 ? 2 : ((V & SV_FUSE) ? ((V & SV_SR) ? NF_SR_Z1_WAVES : 3) : ((V & SV_SR) ? NF_SR_Z2_WAVES : 4))) : 1) void k_schur_s(ModeArgs ma0, ModeTab mt, Geom G, const double *__restrict__ L, const double *__restrict__ DR,
                           const double *__restrict__ D0, int n, long sl, long outer_stride, int nx, int TX, int NSEG,
                           int last, double *__restrict__ partials, const CgScalars *__restrict__ cg, SlabArgs sa, CgFuse fz, CgLean lean,
                           LineDict ld = LineDict())
 {
+    static_assert(schur_s_legal(SEG, DIR, SLAB, NB, V), "not a variant of k_schur_s");
+    constexpr bool FUSE = V & SV_FUSE, SR = V & SV_SR;
     extern __shared__ double sm[];
     if (cg && cg->done) return;
     const ModeArgs ma = select_mode(ma0, mt, blockIdx.z, NB + 1);
     // fused CG on slabs: the endpoint pass (mode 1) is the first to read p in an iteration, so it carries the deferred
     // x_sol += alpha p, p = r + beta p (see CgFuse); every cell of the local line is owned by exactly one thread.
     // With lean.st it is also the consumer of the all-reduced |r|^2 (FIN_RR: beta, stop tests), like the x pass of an undivided mesh.
-    bool fuse = SLAB && SF && NB == 0 && sa.mode == 1 && fz.p != nullptr && (SR ? sa.sr.index > 0 : (lean.st ? !lean.first : cg->its > 0));
+    bool fuse = FUSE && sa.mode == 1 && fz.p != nullptr && (SR ? sa.sr.index > 0 : (lean.st ? !lean.first : cg->its > 0));
     double f_beta = fuse && !lean.st && !SR ? cg->beta : 0.0;
     if (SLAB && !SR && lean.st && !lean.first) {
         double *sred_l = sm + 4 * TX * (NSEG + 1) + TX;
@@ -1489,7 +1502,7 @@ __global__ __launch_bounds__(SLAB ? 512 : 1024, SLAB ? (NB > 0 ? 2 : (SF ? (SR ?
     }
     double f_alpha = fuse && !SR ? cg->alpha : 0.0;
     // single-reduction CG: every block derives alpha, beta and the stop decision from the same five all-reduced doubles (see Cg1)
-    if (SR && SF && fuse) { if (cg1_step(sa.sr, blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0, &f_alpha, &f_beta)) return; }
+    if (SR && FUSE && fuse) { if (cg1_step(sa.sr, blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0, &f_alpha, &f_beta)) return; }
     // XCD-aware tile order (experiment, sa.xcd): hardware deals consecutive workgroups round-robin to the 8 XCDs; remap so that
     // each XCD works on one contiguous range of tiles
     unsigned bx = blockIdx.x, by = blockIdx.y;
@@ -1497,15 +1510,14 @@ __global__ __launch_bounds__(SLAB ? 512 : 1024, SLAB ? (NB > 0 ? 2 : (SF ? (SR ?
         const unsigned nblk = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
         if (nblk % 8 == 0) { const unsigned nl = (lin % 8) * (nblk / 8) + lin / 8; bx = nl % gridDim.x; by = nl / gridDim.x; }
     }
-    static_assert(!ZW || (!SLAB && NB == 0), "the z.w form of the dot product is for plain RT0-P0 lines");
     double extra[2] = { 0.0, 0.0 };
-    const double dot = schur_s_tile<SEG, DIR, SLAB, NB, SF, NTS, NoMid, ZW, false, SR, DICT>(ma, G, L, DR, D0, n, sl, outer_stride, nx, TX, NSEG, bx, by, blockIdx.z, gridDim.y,
+    const double dot = schur_s_tile<SEG, DIR, SLAB, NB, V>(ma, G, L, DR, D0, n, sl, outer_stride, nx, TX, NSEG, bx, by, blockIdx.z, gridDim.y,
                                                             (int)threadIdx.x, true, sm, sa, fz, fuse, false, f_alpha, f_beta, !(!SLAB && NB == 0 && sa.noacc),
                                                             nullptr, NoMid(), SR ? extra : nullptr, ld);
     if (SLAB && sa.mode == 3) return;
     double *sred = sm + 4 * TX * (NSEG + 1) + TX;
     const long pidx = ((long)blockIdx.z * gridDim.y + by) * gridDim.x + bx;
-    if (SR && SF) {                                              // endpoint pass: |r|^2 of the residual this iteration starts with
+    if (SR && FUSE) {                                            // endpoint pass: |r|^2 of the residual this iteration starts with
         const double s = block_sum(dot, sred);
         if (threadIdx.x == 0) sa.sr_part[pidx] = s;
         return;
@@ -1597,15 +1609,15 @@ __global__ __launch_bounds__(256) void k_endpoint_w(double *__restrict__ p, doub
 // loads (chunk 0 first, so that a counted wait lets its sweep start on its own data); 2: also y of chunk 1 before the barrier of chunk 1's
 // forward sweep and y of chunk 0 before the first barrier of the backward half.  Same predicates, same hints, no arithmetic moves: the bits
 // of y and of the dot product are those of EARLY = 0.  The tile, the grid and the LDS layout stay as they are.
+// The instantiations: the table next to the streaming loads only; early loads (levels 1, 2) with the table only, see EARLY
+constexpr bool schur_c_legal(int DIR, bool NT, bool DICT, int EARLY) { return (DIR == 1 || DIR == 2) && (!DICT || NT) && EARLY >= 0 && EARLY <= (DICT ? 2 : 0); }
 template <int DIR, bool NT, bool DICT = false, int EARLY = 0>
 __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ x, double *__restrict__ y, double Ta,
                                                      const double *__restrict__ L, const double *__restrict__ DR, const double *__restrict__ D0,
                                                      int n, long sl, long outer_stride, int nx, int TX, int NS, int last,
                                                      double *__restrict__ partials, const CgScalars *__restrict__ cg, int xcd, LineDict ld = LineDict())
 {
-    static_assert(!DICT || NT, "line tables: next to the streaming instantiations only");
-    static_assert(EARLY == 0 || DICT, "early loads: the table instantiations only (the streaming one would carry L and 1/d of chunk 1 too: beyond 128 registers)");
-    static_assert(EARLY >= 0 && EARLY <= 2, "early loads: levels 0, 1, 2");
+    static_assert(schur_c_legal(DIR, NT, DICT, EARLY), "not a variant of k_schur_c");
     extern __shared__ double sm[];
     if (cg && cg->done) return;
     constexpr int SEG = 8;
@@ -2063,7 +2075,7 @@ __device__ __forceinline__ void xcd_cg(const XcdArgs &A, XcdCtx &C, long offN, l
                     const unsigned tt = act ? t : 0;
                     if (NB == 0) {
                         ms.x[0] = pin;
-                        dot += schur_s_tile<8, 1, false, 0, true, false, NoMid, false, true>(ms, A.G, sL, sDR, sD0, C.sN, C.sSl, C.sOst, A.nx, C.sTX, C.sNSEG, tt % C.sGx, tt / C.sGx, 0, C.sGy,
+                        dot += schur_s_tile<8, 1, false, 0, SV_NT, NoMid, true>(ms, A.G, sL, sDR, sD0, C.sN, C.sSl, C.sOst, A.nx, C.sTX, C.sNSEG, tt % C.sGx, tt / C.sGx, 0, C.sGy,
                                                                                               C.sLtid, act, C.sSm, sa0, fz, false, fuse, alpha, beta, false);
                     } else {
                         const unsigned per = (unsigned)(C.sGx * C.sGy), bz = tt / per, rem = tt - bz * per;
@@ -2072,14 +2084,14 @@ __device__ __forceinline__ void xcd_cg(const XcdArgs &A, XcdCtx &C, long offN, l
 #pragma unroll
                             for (int q = 0; q <= NB; ++q) { m.x[q] = pin + (A.ma[1].x[q] - A.pA); m.Cd[q] = nullptr; }
                             m = select_mode(m, A.mt[1], bz, NB + 1);
-                            dot += schur_s_tile<SEG, 1, false, NB, true, false, NoMid, false, true>(m, A.G, sL, sDR, sD0, C.sN, C.sSl, C.sOst, A.nx, C.sTX, C.sNSEG, rem % C.sGx, rem / C.sGx, bz, C.sGy,
+                            dot += schur_s_tile<SEG, 1, false, NB, SV_NT, NoMid, true>(m, A.G, sL, sDR, sD0, C.sN, C.sSl, C.sOst, A.nx, C.sTX, C.sNSEG, rem % C.sGx, rem / C.sGx, bz, C.sGy,
                                                                                                     C.sLtid, act, C.sSm, sa0, fz, false, fuse, alpha, beta, false);
                         } else {
                             ModeArgs m = mz;
 #pragma unroll
                             for (int q = 0; q <= NB; ++q) { m.x[q] = pin + (A.ma[2].x[q] - A.pA); m.Cd[q] = nullptr; }
                             m = select_mode(m, A.mt[2], bz, NB + 1);
-                            dot += schur_s_tile<SEG, 2, false, NB, true, false, NoMid, false, true>(m, A.G, sL, sDR, sD0, C.sN, C.sSl, C.sOst, A.nx, C.sTX, C.sNSEG, rem % C.sGx, rem / C.sGx, bz, C.sGy,
+                            dot += schur_s_tile<SEG, 2, false, NB, SV_NT, NoMid, true>(m, A.G, sL, sDR, sD0, C.sN, C.sSl, C.sOst, A.nx, C.sTX, C.sNSEG, rem % C.sGx, rem / C.sGx, bz, C.sGy,
                                                                                                     C.sLtid, act, C.sSm, sa0, fz, false, fuse, alpha, beta, false);
                         }
                     }

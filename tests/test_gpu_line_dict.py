@@ -109,6 +109,8 @@ def _check_plan(s, want, counts=None, families=None):
         for d in "xyz":
             assert plan[d]["dict"] == want[d], (in_cg, d, plan[d], plan["line_dict"])
             assert plan[d]["nt"] == 1, (d, plan[d])
+            if plan[d]["family"] == "s":                            # the one-chunk kernel names its instantiation: the table next to the streaming loads
+                assert plan[d]["variant"] == "+".join(["nt"] + ["zw"] * plan[d]["zw"] + ["dict"] * want[d]), (in_cg, d, plan[d])
             assert (plan["line_dict"][d] > 0) == bool(want[d]), plan["line_dict"]
             if counts is not None and want[d]:
                 assert plan["line_dict"][d] == counts[d], (d, plan["line_dict"], counts)
@@ -160,6 +162,8 @@ def test_apply_and_solve(name):
     assert plan["x"]["NCH"] == (2 if name.startswith("A") else 1)
     if name in ("A_long", "A_split"):                                  # inside CG: per-pass shares of p.q in the z.w form
         assert plan["lean"] == 0 and plan["split_dot"] == 1 and plan["y"]["zw"] == 1 and plan["z"]["zw"] == 1, plan
+    if name == "A_split":
+        assert plan["y"]["variant"] == "nt+zw+dict" and plan["z"]["variant"] == "nt+zw+dict", plan
     assert 0 < s.info("line_dict_bytes") and s.info("line_dict_rejected") == 0
     on = _applies(s, ref["x"], ref["y"], name)
     k1, n1 = s.solve_keff(); h1 = s.history(); hk1, cg1, phi1 = h1["k"].copy(), h1["cg"].copy(), s.get_phi().copy()

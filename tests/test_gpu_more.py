@@ -111,6 +111,20 @@ def test_error_behaviour():
     t.close()
 
 
+def test_long_segments():
+    """s_seg = 16 / 32 (RT0-P0 only): the long-segment instantiations of the one-chunk kernel, base variant, against the oracle's apply"""
+    inp = synthetic_inputs(20, 40, 9, 2, seed=5)
+    o, s = make_oracle(inp), make_hip(inp)
+    x = np.random.default_rng(2).standard_normal(o.n_phi); y = o.schur_apply(1, x)
+    s.set_option("s_long", 0)                                      # the one-chunk kernel whatever the environment forces (the chunked one has no s_seg)
+    for seg in (16, 32):
+        s.set_option("s_seg", seg)
+        plan = s.apply_plan()
+        assert all(plan[d]["family"] == "s" and plan[d]["SEG"] == seg and plan[d]["variant"] == "" for d in "yz"), plan
+        assert rel_l2(s.schur_apply(1, x), y) < 1e-12
+    s.close()
+
+
 @pytest.mark.parametrize("nx,rt", [(1500, 0), (2100, 0), (3000, 0), (700, 1)])
 def test_long_x_lines(nx, rt):
     """x lines beyond 1024 cells (NCH = 16 / 32 chunks per lane; RT1 up to 1024): apply and group solve against the oracle"""

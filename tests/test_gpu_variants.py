@@ -167,6 +167,8 @@ def _expect_xcd(shape, rt, xcd, plan):
         tiles = p["grid"][0] if d == "x" else p["grid"][0] * p["grid"][1]
         assert p["family"] == ("x" if d == "x" else "s"), (d, p)
         assert p["nt"] == (1 if rt == 0 else 0), (d, p)              # streaming loads: RT0-P0 instantiations
+        if d != "x" and rt != 0:
+            assert p["variant"] == "", (d, p)                        # higher orders: the base kernel, whatever the options ask for
         assert p["xcd_order"] == int(want[d]), (d, xcd, p)
         assert p["xcd_permutes"] == int(want[d] and tiles % 8 == 0 and tiles > 8), (d, xcd, p)
     return want
@@ -280,6 +282,8 @@ def test_chunked_kernel_streaming_and_xcd(mesh, dirs):
         assert plan["lean"] == 0 and plan["split_dot"] == 1
         for d in "yz":
             assert plan[d]["family"] == fam[d] and plan[d]["zw"] == 1, (d, plan[d])
+            if fam[d] == "s":
+                assert plan[d]["variant"] == ("nt+zw+dict" if plan[d]["dict"] else "nt+zw"), (d, plan[d])
         res[xcd] = (ya, _solves(s, cg, "s_long_dirs=%d xcd=%d" % (dirs, xcd))[0])
     for xcd in (-1, 3):                                            # the tile order moves no partial: stored by position
         _same_bits(res[xcd][0], res[0][0], "apply xcd=%d" % xcd)
@@ -354,6 +358,8 @@ def test_slab_z_passes_and_endpoint_weights(planes, nt_min):
     ref = _ref_keff(SLAB_SHAPE, 0)
     opts = {} if nt_min is None else dict(nt_min_cells=nt_min)
     nt = 0 if nt_min is None else 1
+    def var(*bits):                                                # the k_schur_s variant: streaming loads ride along with whatever the pass carries
+        return "+".join(b for b in ("fuse", "nt", "sr") if b in bits or (b == "nt" and nt))
     # default options: the XCD order of the z passes of small slabs is on by itself and, with 3 x 8 tiles, really permutes
     t = _team(inp, planes, opts)
     y_def = _team_apply_matches(t, SLAB_SHAPE, "default")          # prepares the team: the report needs its separator sweeps and weights
@@ -364,6 +370,8 @@ def test_slab_z_passes_and_endpoint_weights(planes, nt_min):
             for m in ("z1", "z2") if not in_cg else ("z2",):        # inside CG the endpoint pass is k_endpoint_w by default: below
                 p = plan[m]
                 assert p["family"] == "s" and p["grid"] == [3, 8, 1] and p["nt"] == nt and p["xcd_order"] == 1 and p["xcd_permutes"] == 1, (m, p)
+                # outside CG both passes are the base kernel; inside, the accumulation pass leaves the three sums of the single-reduction CG
+                assert p["variant"] == (var("sr") if in_cg and plan["single_reduce"] else var()), (m, in_cg, p)
     t.head.set_option("xcd", 0)
     assert all(x.apply_plan()[m]["xcd_order"] == 0 for x in t.slabs for m in ("z1", "z2"))
     _same_bits(_team_apply_matches(t, SLAB_SHAPE, "xcd=0"), y_def, "team apply, natural tile order")
@@ -385,8 +393,8 @@ def test_slab_z_passes_and_endpoint_weights(planes, nt_min):
             assert plan["single_reduce"] == 1 and plan["fused"] == 1
             assert plan["z1"]["family"] == "endpoint_w" and plan["z1"]["grid"] == [3, 8, 1], plan["z1"]
             assert plan["z2"]["family"] == "s" and plan["z2"]["nt"] == nt and plan["z2"]["xcd_permutes"] == 1, plan["z2"]
-            assert plan["z2"]["fold"] == int(fold == 1 and sweeps == 0)
-            assert x.apply_plan(False)["z1"]["family"] == "s"         # outside CG: the chain solve
+            assert plan["z2"]["fold"] == int(fold == 1 and sweeps == 0) and plan["z2"]["variant"] == var("sr"), plan["z2"]
+            assert x.apply_plan(False)["z1"]["family"] == "s" and x.apply_plan(False)["z1"]["variant"] == var()   # outside CG: the chain solve, base kernel
         k, n = t.solve_keff()
         assert n == 6 and t.head.info("cg_reductions") == 1 and t.head.info("endpoint_weights") == 1
         h = t.history()
@@ -399,6 +407,23 @@ def test_slab_z_passes_and_endpoint_weights(planes, nt_min):
     (h1, p1, c1), (h0, p0, c0) = res[1], res[0]
     np.testing.assert_allclose(h1, h0, rtol=1e-11)
     assert rel_l2(p1, p0) < 1e-9 and abs(c1 - c0) <= 0.02 * c0
+    # the same CG with the endpoint pass as a chain solve: k_schur_s carries the fused update and r -= alpha q (fuse + sr), same bars
+    t = _team(inp, planes, dict(opts, cg_single_reduce=1, endpoint_weights=0)); t.set_tol(*FIXED)
+    _team_apply_matches(t, SLAB_SHAPE, "endpoint_weights=0")
+    for x in t.slabs:
+        plan = x.apply_plan(True)
+        assert plan["single_reduce"] == 1 and plan["fused"] == 1
+        assert plan["z1"]["family"] == "s" and plan["z1"]["variant"] == var("fuse", "sr") and plan["z1"]["nt"] == nt, plan["z1"]
+        assert plan["z2"]["family"] == "s" and plan["z2"]["variant"] == var("sr"), plan["z2"]
+        assert x.apply_plan(False)["z1"]["variant"] == var()
+    k, n = t.solve_keff()
+    assert n == 6 and t.head.info("cg_reductions") == 1 and t.head.info("endpoint_weights") == 0
+    h = t.history()
+    errs = (np.abs(h["k"] / ref["hk"] - 1).max(), rel_l2(t.get_phi_local().ravel(), ref["phi"].ravel()))
+    print(f"team fixed work endpoint_weights=0: k-history {errs[0]:.3e} (bar 1e-9), flux {errs[1]:.3e} (bar 1e-8)")
+    np.testing.assert_allclose(h["k"], ref["hk"], rtol=1e-9)
+    assert errs[1] < 1e-8
+    t.close()
 
 
 def test_slab_separator_fold_engages_on_thick_slabs():
