@@ -75,7 +75,9 @@ int nf_team_schur_apply(nf_handle h, int g, const double *const *x_dev, double *
 
 /* sizes: "dim","nx","ny","nz","ne","ng","n_phi","n_J","n_loc","last_outer","last_cg_total",
  * "coarse_outer","device","n_local_slabs","n_ranks","rank","cg_reductions" (cross-rank reductions per CG iteration of the last CG solve on a
- * team: 1 single-reduction CG, 2 reference recurrence, 0 undivided mesh),"vec_reduce","xchg_comm" ; returns -1 for an unknown key */
+ * team: 1 single-reduction CG, 2 reference recurrence, 0 undivided mesh),"vec_reduce","xchg_comm","cg_form" (the form of the CG iteration the last CG solve ran -- after a refused one-XCD start
+ * the form it continued with -- as an index into xcd, fuse3, lean, fused, classic, team_lean, team_vec, team_sr: the names nf_apply_plan
+ * reports as "form") ; returns -1 for an unknown key */
 long nf_info(nf_handle h, const char *key);
 
 /* NeutFEM::SetBC (src/NeutFEM.cpp:337-345): attr per BoundaryID (include/NeutFEM.hpp:73-91).
@@ -329,8 +331,11 @@ int nf_profile_reset(nf_handle h);
 /* the same counters, with the iteration counts of the last solve, as one JSON object */
 int nf_timers(nf_handle h, char *json_buf, size_t len);
 /* Read-only report of the launch plan: what the next Schur apply on this handle's mesh (or slab) would launch, as one JSON object
- * {"in_cg", "slab", "fused", "lean", "single_reduce", "split_dot", "xy_overlap", "passes": [...]}.  in_cg = 0: a plain nf_schur_apply /
- * nf_team_schur_apply; in_cg = 1: the apply inside an iteration of the launch-path CG (not the fused-direction or one-XCD solves).
+ * {"in_cg", "form", "slab", "fused", "lean", "single_reduce", "split_dot", "xy_overlap", "passes": [...]}.  in_cg = 0: a plain nf_schur_apply /
+ * nf_team_schur_apply; in_cg = 1: the apply inside an iteration of the launch-path CG.  "form": the form of the CG iteration the next
+ * CG solve is planned to run (xcd, fuse3, lean, fused, classic, team_lean, team_vec, team_sr; "" for in_cg = 0), from the one function
+ * the solve itself asks; "fused", "lean" and "single_reduce" follow from it.  The forms xcd and fuse3 launch no Schur pass of their own:
+ * for them the passes are those of the launch path (lean) the solve falls back to.
  * One entry of "passes" per direction that exists; the z direction of a slab has two (mode 1 = endpoint pass, mode 2 = accumulation
  * pass).  Per entry: "dir" (x / y / z), "mode", "family" (x = k_schur_x, s = k_schur_s, c = k_schur_c, endpoint_w = k_endpoint_w),
  * "SEG" (cells per segment), "NCH" (chunks per lane / block), "TX" (columns per block; lanes per line for x), "NSEG" (segments per

@@ -132,6 +132,7 @@ struct nf_team {
     // was limited to small slabs; with the weighted-sum endpoint pass (k_endpoint_w) it is FASTER than the two-reduction route in device time alone
     // at every size measured (256^3 as 2 / 4 / 8 slabs: -6.5 / -7.9 / -5.5 %, 512^3 as 8: -3.2 %; profiles/r04_d_*), so the limit is out of the way.
     int opt_cg1 = -1, last_cg_reductions = 0; long cg1_max_cells = 1L << 40, team_max_cells = 0;
+    int last_cg_form = 0;           // the CgForm the last cg_solve ran (nf_info "cg_form")
     int opt_endpoint_w = 1, last_endpoint_w = 0;   // its endpoint pass as two weighted sums per line (k_endpoint_w) instead of a chain solve
     bool rccl_reduce = false;       // scalar reductions go through ncclAllReduce (nproc > 1, or forced for testing)
     double *d_partials = nullptr; long partial_stride = 0, slab_cap = 0;
@@ -702,7 +703,7 @@ long nf_info(nf_handle S, const char *key)
     K("dim", S->dim); K("nx", S->nx); K("ny", S->ny); K("nz", S->nz); K("ne", S->N); K("ng", S->ng);
     K("n_phi", S->nphi); K("n_J", S->nJ); K("n_loc", S->nloc); K("rt_order", S->k); K("p_order", S->m); K("last_outer", T->last_outer);
     K("last_cg_total", T->last_cg_total); K("coarse_outer", T->coarse_outer); K("device", S->device);
-    K("last_path", T->last_path); K("last_resident_serial", T->last_resident_serial); K("last_direct", T->last_direct); K("direct_standin_unconverged", T->standin_unconverged); K("n_local_slabs", T->slabs.size()); K("n_ranks", T->nproc); K("rank", T->rank); K("vec_reduce", T->last_vec_reduce); K("cg_reductions", T->last_cg_reductions); K("endpoint_weights", T->last_endpoint_w); K("xchg_comm", T->comm_x ? 1 : 0); K("last_xcd", T->last_xcd); K("xcd_solves", T->xcd_solves); K("xcd_refused", T->xcd_refused);
+    K("last_path", T->last_path); K("last_resident_serial", T->last_resident_serial); K("last_direct", T->last_direct); K("direct_standin_unconverged", T->standin_unconverged); K("n_local_slabs", T->slabs.size()); K("n_ranks", T->nproc); K("rank", T->rank); K("vec_reduce", T->last_vec_reduce); K("cg_reductions", T->last_cg_reductions); K("cg_form", T->last_cg_form); K("endpoint_weights", T->last_endpoint_w); K("xchg_comm", T->comm_x ? 1 : 0); K("last_xcd", T->last_xcd); K("xcd_solves", T->xcd_solves); K("xcd_refused", T->xcd_refused);
     K("line_dict_rejected", S->ld_rejected); K("line_dict_bytes", S->ld_bytes);
 #undef K
     return -1;
@@ -1136,8 +1137,9 @@ static int team_finalize(nf_team *T, int op, const std::vector<int> &counts, int
 // iteration): the rank raises its flag and carries on with the schedule instead of returning -- its peers are about to enter the next
 // collective.  The flag travels in the reductions that exist anyway: the next CG solve ends on every rank at its first reduction
 // (cg_logic, FIN_RHS), the per-outer reduction hands the flags to the host (team_finalize, want_flag).  Returns true when the caller
-// must return `code` at once (single process).
-static bool team_poison(nf_team *T, int code)
+// must return `code` at once (single process).  Inside the CG loop (cg_solve) the rank likewise keeps issuing the collectives of the schedule
+// without the compute; vec_slots (the vector-reduce form): also the flag slots of the two partial vectors it sends from now on.
+static bool team_poison(nf_team *T, int code, bool vec_slots = false)
 {
     if (code == NF_OK) return false;
     if (T->nproc <= 1) return true;
@@ -1145,7 +1147,8 @@ static bool team_poison(nf_team *T, int code)
         T->poisoned = true; T->poison_rc = code; snprintf(T->poison_msg, sizeof T->poison_msg, "%s", nf_last_error());
         const double one = 1.0;
         (void)hipMemcpyAsync(T->d_errsrc, &one, sizeof one, hipMemcpyHostToDevice, T->stream);
-        (void)hipStreamSynchronize(T->stream);
+        if (vec_slots) for (double *slot : { T->d_partials + T->vec_cnt_pq, T->d_partials + T->partial_stride + T->vec_cnt_rr }) (void)hipMemcpyAsync(slot, &one, sizeof one, hipMemcpyHostToDevice, T->stream);
+        (void)hipStreamSynchronize(T->stream);                   // `one` lives on this stack frame; the stream may also have to recover from the failed call
         (void)hipGetLastError();
     }
     return false;
@@ -1632,19 +1635,6 @@ static int team_endpoint_phase(nf_team *T, int g, const std::vector<const double
 }
 
 static bool team_is_single(const nf_team *T) { return T->slabs.size() == 1 && !T->slabs[0]->if_lo && !T->slabs[0]->if_hi; }
-// The forms of the CG iteration (cg_solve), as far as they change what a Schur apply launches:
-// fused (RT0-P0, undivided mesh: x_sol / p updates ride in the next x pass, k_schur_x, CgFuse; slab teams: P0, in the endpoint pass of the z
-// lines, the first pass to read p); lean on top of it (undivided mesh, no RCCL: no k_finalize launches, see CgLean); the lean form of slab
-// teams; its single-reduction variant (Cg1: one reduction per iteration; needs the 8-cell-segment z passes on every local slab)
-static bool cg_fused(const nf_team *T) { return T->opt_fuse != 0 && (team_is_single(T) || T->slabs[0]->nloc == 1); }
-static bool cg_lean(const nf_team *T) { return cg_fused(T) && T->opt_lean && team_is_single(T) && !T->rccl_reduce && T->slabs[0]->N <= T->lean_max_cells; }
-static bool cg_tlean(const nf_team *T) { return cg_fused(T) && T->opt_lean && !team_is_single(T); }
-static bool cg_sr(const nf_team *T)
-{
-    bool sr = cg_tlean(T) && (T->opt_cg1 > 0 || (T->opt_cg1 < 0 && T->team_max_cells <= T->cg1_max_cells));
-    for (auto *S : T->slabs) sr = sr && S->dim == 3 && S->nb == 0 && (T->opt_s_seg == 0 || T->opt_s_seg == 8) && S->nz <= 1024;
-    return sr;
-}
 // Split dot product of an apply inside CG (see team_schur_apply): on undivided RT0-P0 meshes outside the lean path, where a chunked long-line
 // pass forms the last share (only the LAST pass forms the dot product otherwise) or on request (split_dot = 2)
 static bool split_dot(const nf_team *T, bool want_dot, bool lean)
@@ -1756,80 +1746,6 @@ int nf_team_schur_apply(nf_handle S, int g, const double *const *x_dev, double *
     return NF_OK;
 }
 
-// ---- read-only report of the launch plan -------------------------------------------------------
-// What the next Schur apply on this handle's mesh (or slab) would launch, per direction, as one JSON object.  It prints what
-// the launch functions execute (x_plan for the x pass, s_pass for a y / z pass) and calls the predicates they call (endpoint_w_taken, the cg_*
-// forms, split_dot, xy_overlap); apart from building the tables of distinct lines where the next
-// apply would (line_dict_prepare) it launches nothing and writes no state.  The one thing it cannot know is a device
-// that refuses the chunked kernel's LDS at launch time (launch_s then falls back to the one-chunk kernel).
-struct PlanPass { const char *dir, *family; int mode, SEG, NCH, TX, NSEG; dim3 grid; unsigned block; bool nt, p2, zw, order; unsigned tiles; bool fold = false, dict = false; int early = 0; unsigned V = 0; };
-static void plan_emit(std::string &js, const PlanPass &p)
-{
-    char tmp[416];
-    snprintf(tmp, sizeof tmp, "%s{\"dir\": \"%s\", \"mode\": %d, \"family\": \"%s\", \"SEG\": %d, \"NCH\": %d, \"TX\": %d, \"NSEG\": %d, \"grid\": [%u, %u, %u], "
-             "\"block\": %u, \"nt\": %d, \"p2\": %d, \"zw\": %d, \"xcd_order\": %d, \"xcd_permutes\": %d, \"fold\": %d, \"dict\": %d, \"early\": %d", js.back() == '[' ? "" : ", ", p.dir, p.mode, p.family,
-             p.SEG, p.NCH, p.TX, p.NSEG, p.grid.x, p.grid.y, p.grid.z, p.block, p.nt ? 1 : 0, p.p2 ? 1 : 0, p.zw ? 1 : 0, p.order ? 1 : 0, xcd_permutes(p.order, p.tiles) ? 1 : 0, p.fold ? 1 : 0, p.dict ? 1 : 0, p.early);
-    js += tmp;
-    if (!strcmp(p.family, "s")) js += ", \"variant\": \"" + variant_name(p.V) + "\"";   // which k_schur_s
-    js += "}";
-}
-static int plan_s(std::string &js, const nf_solver *S, int d, int zmode, bool want_dot, bool zw_dot, bool fuse, bool cg1)   // a launch_s call
-{
-    const SPass ps = s_pass(S, d, zmode, want_dot, zw_dot, fuse, cg1);
-    if (ps.rc != NF_OK) return ps.rc;
-    const dim3 gr = ps.chunked ? c_grid(S, d, ps.cp) : ps.seg.grid;
-    plan_emit(js, { d == 1 ? "y" : "z", ps.chunked ? "c" : "s", zmode, ps.chunked ? C_SEG : ps.seg.SEG, ps.chunked ? C_NCH : 1, ps.chunked ? ps.cp.TX : ps.seg.TX, ps.chunked ? ps.cp.NS : ps.seg.NSEG,
-                    gr, ps.chunked ? c_block(ps.cp) : ps.seg.block.x, (ps.V & SV_NT) != 0, false, (ps.V & SV_ZW) != 0, ps.xcd != 0, gr.x * gr.y, ps.fold, (ps.V & SV_DICT) != 0, ps.early, ps.V });
-    return NF_OK;
-}
-int nf_apply_plan(nf_handle S, int in_cg, char *json_buf, size_t len)
-{
-    if (!S || !json_buf || len < 2) return fail(NF_ERR_ARG, "nf_apply_plan: bad arguments");
-    if (!S->built) return fail(NF_ERR_STATE, "nf_apply_plan: call nf_build first");
-    // the tables of distinct lines are part of what the next apply does: it would build them first, so the report does (its only side effect)
-    HIPCHK(hipSetDevice(S->team->device));
-    NFCHK(line_dict_prepare(S->team));
-    const nf_team *T = S->team;
-    const bool slab = S->if_lo || S->if_hi;
-    // a team settles the separator sweeps, the endpoint weights and its largest slab when it is prepared (the first team apply or solve)
-    if (!team_is_single(T) && !T->linked_ready) return fail(NF_ERR_STATE, "nf_apply_plan: run a team apply or solve first (the team has not been prepared since its options changed)");
-    // How the CG forms reach a launch is taken from cg_solve and team_schur_apply, not shared with them: cg_solve applies S to d_p with
-    // CgFuse::p = d_p when fused (so `P.fuse.p == xs[i]` of team_endpoint_phase is `fused`), sets Cg1::red exactly when cg_sr() holds (so
-    // `P.cg1.red != nullptr` is `sr`), sets ApplyCg::lean exactly when cg_lean() holds, and asks for the dot product of every apply; the
-    // last pass, and every pass under the split dot product, then gets a partial buffer (`last && partials` of the launch functions).
-    const bool cg = in_cg != 0, fused = cg && cg_fused(T), lean = cg && cg_lean(T), sr = cg && cg_sr(T);
-    const bool split = split_dot(T, cg, lean);
-    bool any_if = false; for (auto *X : T->slabs) any_if |= X->if_lo || X->if_hi;
-    const bool xy_all = xy_overlap(T, any_if, false);
-    char tmp[256];
-    snprintf(tmp, sizeof tmp, "{\"in_cg\": %d, \"slab\": %d, \"fused\": %d, \"lean\": %d, \"single_reduce\": %d, \"split_dot\": %d, \"xy_overlap\": %d, \"passes\": [",
-             cg ? 1 : 0, slab ? 1 : 0, fused ? 1 : 0, lean ? 1 : 0, sr ? 1 : 0, split ? 1 : 0, xy_all ? 1 : 0);
-    std::string js = tmp;
-    for (int d = 0; d < S->dim; ++d) {
-        const bool last = d == S->dim - 1, want_dot = cg && (last || split);
-        if (d == 0) {
-            const XPlan xp = x_plan(S, fused);
-            if (!xp.NCH) return fail(NF_ERR_UNSUPPORTED, "nx = %d exceeds the x-line kernel limit (%d cells)", S->nx, S->nb == 0 ? 4096 : 1024);
-            plan_emit(js, { "x", "x", 0, 0, xp.NCH, 1 << xp.lpl_log2, 0, dim3(xp.grid, (unsigned)n_modes(S)), 256u, xp.nt, xp.p2, false, xp.xcd, xp.grid, false, xp.dict });
-        } else if (d == 2 && slab) {
-            // endpoint pass: inside the fused CG the update reads the vector the pass is applied to (cg_solve applies to d_p)
-            if (endpoint_w_taken(T, S, sr, fused)) { const dim3 gr = endpoint_w_grid(S); plan_emit(js, { "z", "endpoint_w", 1, 0, 0, 64, 0, gr, 256u, false, false, false, false, gr.x * gr.y }); }
-            else NFCHK(plan_s(js, S, 2, 1, false, false, fused, sr));
-            NFCHK(plan_s(js, S, 2, 2, want_dot, split, fused, sr));
-        } else if (d == 1 && xy_all) NFCHK(plan_s(js, S, 1, 0, false, split, fused, sr));
-        else NFCHK(plan_s(js, S, d, 0, want_dot, split, fused, sr));
-    }
-    {   // distinct lines of the largest group per direction, 0 where the direction does not use its table
-        int nd[3] = { 0, 0, 0 };
-        for (int d = 0; d < S->dim; ++d) if (dict_dir(S, d)) nd[d] = *std::max_element(S->ld_rows[d].begin(), S->ld_rows[d].end());
-        snprintf(tmp, sizeof tmp, "], \"line_dict\": {\"x\": %d, \"y\": %d, \"z\": %d}}", nd[0], nd[1], nd[2]);
-        js += tmp;
-    }
-    if (js.size() + 1 > len) return fail(NF_ERR_ARG, "nf_apply_plan: buffer of %zu bytes is too small (%zu needed)", len, js.size() + 1);
-    memcpy(json_buf, js.c_str(), js.size() + 1);
-    return NF_OK;
-}
-
 #ifdef NF_STAMPS
 static long long *g_stamps = nullptr;
 extern "C" int nf_debug_stamps(long long *out48) { if (!g_stamps) return -1; return hipMemcpy(out48, g_stamps, 48 * sizeof(long long), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2; }
@@ -1879,31 +1795,33 @@ static Fuse3Plan fuse3_plan(const nf_solver *S)
     P.ok = true;
     return P;
 }
+// The instantiations of k_apply3<NCH, VEC, NB, SEG>: up to four chunks per lane; 8-cell segments, and 4-cell ones for the bubble moments
+constexpr bool apply3_legal(int NCH, int NB, int SEG) { return NCH >= 1 && NCH <= 4 && NB >= 0 && NB <= 2 && (SEG == 8 || (SEG == 4 && NB > 0)); }
 // one k_apply3 launch: q_d = S_d p for every direction; pin = the vector the iteration reads, pout = where the new p goes
 static int launch_apply3(nf_solver *S, int g, const Fuse3Plan &P, const double *pin, double *pout, double *xsol, const CgLean &lean)
 {
     nf_team *T = S->team; hipStream_t st = T->stream;
     const long N = S->N;
     const Geom G = make_geom(S);
-    ModeArgs ma[3]; ModeTab mt[3];
+    ModeArgs ma[3]; ModeTab mt[3]; const double *L[3], *DR[3], *D0[3];
     double *qd[3] = { S->d_q, S->d_qy, S->d_qz };
     for (int d = 0; d < 3; ++d) {
         const int dd = d < S->dim ? d : 0;
-        ma[d] = mode_args(S, g, dd, 0, pin, qd[d < S->dim ? d : 0]); mt[d] = mode_tab(S, dd);
+        ma[d] = mode_args(S, g, dd, 0, pin, qd[dd]); mt[d] = mode_tab(S, dd);
+        L[d] = S->d_L[dd] + g * N; DR[d] = S->d_DR[dd] + g * N; D0[d] = S->d_D0[dd] + g * S->nlines[dd];
     }
-    const double *L[3], *DR[3], *D0[3];
-    for (int d = 0; d < 3; ++d) { const int dd = d < S->dim ? d : 0; L[d] = S->d_L[dd] + g * N; DR[d] = S->d_DR[dd] + g * N; D0[d] = S->d_D0[dd] + g * S->nlines[dd]; }
     const CgFuse fz = { const_cast<double *>(pin), S->d_r, xsol, pout };
-#define NF_A3(NCHV, VECV, NBV, SEGV) hipLaunchKernelGGL((k_apply3<NCHV, VECV, NBV, SEGV>), dim3((unsigned)P.nblocks), dim3((unsigned)P.B), P.lds, st, ma[0], ma[1], ma[2], mt[0], mt[1], mt[2], G, \
-        L[0], DR[0], D0[0], L[1], DR[1], D0[1], L[2], DR[2], D0[2], S->nx, S->ny, S->nlines[0], P.A, T->d_partials, T->d_cg, fz, lean)
-#define NF_A3_SEG(NCHV, VECV, NBV) do { if (NBV == 0 || P.seg == 8) NF_A3(NCHV, VECV, NBV, 8); else NF_A3(NCHV, VECV, NBV, (NBV == 0 ? 8 : 4)); } while (0)
-#define NF_A3_NB(NCHV, VECV) do { if (S->nb == 0) NF_A3_SEG(NCHV, VECV, 0); else if (S->nb == 1) NF_A3_SEG(NCHV, VECV, 1); else NF_A3_SEG(NCHV, VECV, 2); } while (0)
-#define NF_A3_VEC(NCHV) do { if (P.vec) NF_A3_NB(NCHV, true); else NF_A3_NB(NCHV, false); } while (0)
-    if (P.nch == 1) NF_A3_VEC(1); else if (P.nch == 2) NF_A3_VEC(2); else NF_A3_VEC(4);
-#undef NF_A3_VEC
-#undef NF_A3_NB
-#undef NF_A3_SEG
-#undef NF_A3
+    int lg = 0; while ((1 << lg) < P.nch) ++lg;
+    const unsigned key = (P.seg == 4 || P.seg == 8) ? ((((unsigned)lg * 2 + (P.vec ? 1u : 0u)) * 3 + (unsigned)S->nb) * 2 + (P.seg == 8 ? 1u : 0u)) : ~0u;
+    const bool hit = with_index<3 * 2 * 3 * 2>(key, [&](auto i) {
+        constexpr unsigned I = decltype(i)::value;
+        constexpr int NCH = 1 << (I / 12), NB = I / 2 % 3, SEG = (I & 1) ? 8 : 4; constexpr bool VEC = I / 6 % 2;
+        if constexpr (!apply3_legal(NCH, NB, SEG)) return false;
+        else hipLaunchKernelGGL((k_apply3<NCH, VEC, NB, SEG>), dim3((unsigned)P.nblocks), dim3((unsigned)P.B), P.lds, st, ma[0], ma[1], ma[2], mt[0], mt[1], mt[2], G,
+                                L[0], DR[0], D0[0], L[1], DR[1], D0[1], L[2], DR[2], D0[2], S->nx, S->ny, S->nlines[0], P.A, T->d_partials, T->d_cg, fz, lean);
+        return true;
+    });
+    if (!hit) return fail(NF_ERR_ARG, "k_apply3: no instantiation for NCH = %d, vec %d, NB = %d, SEG = %d", P.nch, P.vec, S->nb, P.seg);
     return NF_OK;
 }
 
@@ -1957,6 +1875,22 @@ static int xcd_fill(nf_solver *S, int g, const Fuse3Plan &P, XcdArgs &A, int *nc
     *nch_out = nch;
     return NF_OK;
 }
+// The instantiations of k_cg_xcd / k_keff_xcd<NCH, VEC, NB, SEG>: one or two chunks per lane; 8-cell segments for the P0 flux, 4-cell ones
+// for the bubble moments (xcd_eligible).  launch(XcdInst) opts the kernel of its family in to the LDS and launches it.
+constexpr bool xcd_legal(int NCH, int NB, int SEG) { return NCH >= 1 && NCH <= 2 && NB >= 0 && NB <= 2 && SEG == (NB == 0 ? 8 : 4); }
+template <int NCH_, bool VEC_, int NB_, int SEG_> struct XcdInst { static constexpr int NCH = NCH_, NB = NB_, SEG = SEG_; static constexpr bool VEC = VEC_; };
+template <class F> static int xcd_select(const char *name, const nf_solver *S, const Fuse3Plan &P, int nch, F &&launch)
+{
+    int rc = NF_OK;
+    const unsigned key = (P.seg == 4 || P.seg == 8) ? ((((unsigned)(nch - 1) * 2 + (P.vec ? 1u : 0u)) * 3 + (unsigned)S->nb) * 2 + (P.seg == 8 ? 1u : 0u)) : ~0u;
+    const bool hit = with_index<2 * 2 * 3 * 2>(key, [&](auto i) {
+        constexpr unsigned I = decltype(i)::value;
+        constexpr int NCH = 1 + I / 12, NB = I / 2 % 3, SEG = (I & 1) ? 8 : 4; constexpr bool VEC = I / 6 % 2;
+        if constexpr (!xcd_legal(NCH, NB, SEG)) return false;
+        else { rc = launch(XcdInst<NCH, VEC, NB, SEG>()); return true; }
+    });
+    return hit ? rc : fail(NF_ERR_ARG, "%s: no instantiation for NCH = %d, vec %d, NB = %d, SEG = %d", name, nch, P.vec, S->nb, P.seg);
+}
 static const size_t XCD_LDS = (size_t)(5 * 1024 + 64 + 32) * sizeof(double);
 static int launch_cg_xcd(nf_solver *S, int g, const Fuse3Plan &P, double *xsol, unsigned long long seq)
 {
@@ -1964,254 +1898,325 @@ static int launch_cg_xcd(nf_solver *S, int g, const Fuse3Plan &P, double *xsol, 
     XcdArgs A; int nch = 1;
     NFCHK(xcd_fill(S, g, P, A, &nch));
     A.xsol = xsol; A.cg = T->d_cg; A.hp = T->d_pub; A.seq = seq;
-    const size_t lds = XCD_LDS;
-    const unsigned G = 8u * (unsigned)T->xcd_groups;
-#define NF_XCD(NCHV, VECV, NBV, SEGV) do { if (!lds_opt_in((const void *)k_cg_xcd<NCHV, VECV, NBV, SEGV>, lds)) return fail(NF_ERR_HIP, "k_cg_xcd: %zu bytes of LDS refused", lds); \
-        hipLaunchKernelGGL((k_cg_xcd<NCHV, VECV, NBV, SEGV>), dim3(G), dim3(XCD_THREADS), lds, st, A); } while (0)
-#define NF_XCD_NB(NCHV, VECV) do { if (S->nb == 0) NF_XCD(NCHV, VECV, 0, 8); else if (S->nb == 1) NF_XCD(NCHV, VECV, 1, 4); else NF_XCD(NCHV, VECV, 2, 4); } while (0)
-    if (nch == 1) { if (P.vec) NF_XCD_NB(1, true); else NF_XCD_NB(1, false); }
-    else { if (P.vec) NF_XCD_NB(2, true); else NF_XCD_NB(2, false); }
-#undef NF_XCD_NB
-#undef NF_XCD
+    const size_t lds = XCD_LDS; const unsigned G = 8u * (unsigned)T->xcd_groups;
+    NFCHK(xcd_select("k_cg_xcd", S, P, nch, [&](auto t) -> int { using I = decltype(t);
+        if (!lds_opt_in((const void *)k_cg_xcd<I::NCH, I::VEC, I::NB, I::SEG>, lds)) return fail(NF_ERR_HIP, "k_cg_xcd: %zu bytes of LDS refused", lds);
+        hipLaunchKernelGGL((k_cg_xcd<I::NCH, I::VEC, I::NB, I::SEG>), dim3(G), dim3(XCD_THREADS), lds, st, A);
+        return NF_OK;
+    }));
     HIPCHK(hipGetLastError());
+    return NF_OK;
+}
+// ---- the forms of the CG iteration: cg_plan is the only place that chooses one.  cg_solve runs the plan, nf_apply_plan and nf_info report it, solve_keff_impl asks it whether
+// the one-XCD kernels apply.  What an iteration of each form launches: the table of DESIGN.md 3 and the cg_step functions.  fused: x_sol / p
+// updates ride in the next x pass (RT0-P0 undivided mesh; k_schur_x, CgFuse) or in the endpoint pass of the z lines, the first pass to read
+// p (slab teams, P0).  The order is nf_info "cg_form".
+enum CgForm { CG_XCD, CG_FUSE3, CG_LEAN, CG_FUSED, CG_CLASSIC, CG_TEAM_LEAN, CG_TEAM_VEC, CG_TEAM_SR };
+static const char *const CG_FORM_NAME[] = { "xcd", "fuse3", "lean", "fused", "classic", "team_lean", "team_vec", "team_sr" };
+struct CgPlan {
+    CgForm form = CG_CLASSIC; Fuse3Plan f3; int gru = 0;         // f3: xcd, fuse3; gru: those and lean (blocks of k_cg_rupdate / k_cg_rupdate3)
+    bool fused = false; int reductions = 0;                      // ApplyCg::fused (every form but classic); cross-rank reductions per iteration (nf_info "cg_reductions")
+    bool lean() const { return form == CG_XCD || form == CG_FUSE3 || form == CG_LEAN; }   // ApplyCg::lean is set
+};
+static CgPlan cg_plan(const nf_team *T)
+{
+    CgPlan P; const nf_solver *S0 = T->slabs[0]; const bool single = team_is_single(T);
+    P.fused = T->opt_fuse != 0 && (single || S0->nloc == 1);
+    P.reductions = single ? 0 : 2;
+    P.form = P.fused ? CG_FUSED : CG_CLASSIC;
+    if (!P.fused || !T->opt_lean) return P;
+    if (!single) {
+        bool sr = T->opt_cg1 > 0 || (T->opt_cg1 < 0 && T->team_max_cells <= T->cg1_max_cells);
+        for (auto *S : T->slabs) sr = sr && S->dim == 3 && S->nb == 0 && (T->opt_s_seg == 0 || T->opt_s_seg == 8) && S->nz <= 1024;
+        const bool vec = T->nproc > 1 && T->slabs.size() == 1 && T->vec_ok && T->opt_vec_reduce;
+        P.form = sr ? CG_TEAM_SR : vec ? CG_TEAM_VEC : CG_TEAM_LEAN; P.reductions = sr ? 1 : 2;
+        return P;
+    }
+    if (T->rccl_reduce || S0->N > T->lean_max_cells) return P;
+    P.form = CG_LEAN;
+    // every block of the next x pass sums the |r|^2 partials; fewer partials (cg_lean_grid) cost k_cg_rupdate more than they save (measured)
+    P.gru = grid_for(S0->nphi, 256, T->opt_lean_grid);
+    if (!T->opt_fuse3 || S0->N > T->fuse3_max_cells) return P;
+    P.f3 = fuse3_plan(S0);
+    if (P.f3.ok && P.f3.nblocks > T->slab_cap) P.f3.ok = false;  // cannot decide: slab_partial_need counts a partial per block of this launch
+    if (P.f3.ok) P.form = xcd_eligible(T, S0, P.f3) ? CG_XCD : CG_FUSE3;
+    return P;
+}
+
+// ---- read-only report of the launch plan -------------------------------------------------------
+// What the next Schur apply on this handle's mesh (or slab) would launch, per direction, as one JSON object.  It prints what
+// the launch functions execute (x_plan for the x pass, s_pass for a y / z pass) and calls the predicates they call (endpoint_w_taken, cg_plan,
+// split_dot, xy_overlap); apart from building the tables of distinct lines where the next
+// apply would (line_dict_prepare) it launches nothing and writes no state.  The one thing it cannot know is a device
+// that refuses the chunked kernel's LDS at launch time (launch_s then falls back to the one-chunk kernel).
+struct PlanPass { const char *dir, *family; int mode, SEG, NCH, TX, NSEG; dim3 grid; unsigned block; bool nt, p2, zw, order; unsigned tiles; bool fold = false, dict = false; int early = 0; unsigned V = 0; };
+static void plan_emit(std::string &js, const PlanPass &p)
+{
+    char tmp[416];
+    snprintf(tmp, sizeof tmp, "%s{\"dir\": \"%s\", \"mode\": %d, \"family\": \"%s\", \"SEG\": %d, \"NCH\": %d, \"TX\": %d, \"NSEG\": %d, \"grid\": [%u, %u, %u], "
+             "\"block\": %u, \"nt\": %d, \"p2\": %d, \"zw\": %d, \"xcd_order\": %d, \"xcd_permutes\": %d, \"fold\": %d, \"dict\": %d, \"early\": %d", js.back() == '[' ? "" : ", ", p.dir, p.mode, p.family,
+             p.SEG, p.NCH, p.TX, p.NSEG, p.grid.x, p.grid.y, p.grid.z, p.block, p.nt ? 1 : 0, p.p2 ? 1 : 0, p.zw ? 1 : 0, p.order ? 1 : 0, xcd_permutes(p.order, p.tiles) ? 1 : 0, p.fold ? 1 : 0, p.dict ? 1 : 0, p.early);
+    js += tmp;
+    if (!strcmp(p.family, "s")) js += ", \"variant\": \"" + variant_name(p.V) + "\"";   // which k_schur_s
+    js += "}";
+}
+static int plan_s(std::string &js, const nf_solver *S, int d, int zmode, bool want_dot, bool zw_dot, bool fuse, bool cg1)   // a launch_s call
+{
+    const SPass ps = s_pass(S, d, zmode, want_dot, zw_dot, fuse, cg1);
+    if (ps.rc != NF_OK) return ps.rc;
+    const dim3 gr = ps.chunked ? c_grid(S, d, ps.cp) : ps.seg.grid;
+    plan_emit(js, { d == 1 ? "y" : "z", ps.chunked ? "c" : "s", zmode, ps.chunked ? C_SEG : ps.seg.SEG, ps.chunked ? C_NCH : 1, ps.chunked ? ps.cp.TX : ps.seg.TX, ps.chunked ? ps.cp.NS : ps.seg.NSEG,
+                    gr, ps.chunked ? c_block(ps.cp) : ps.seg.block.x, (ps.V & SV_NT) != 0, false, (ps.V & SV_ZW) != 0, ps.xcd != 0, gr.x * gr.y, ps.fold, (ps.V & SV_DICT) != 0, ps.early, ps.V });
+    return NF_OK;
+}
+int nf_apply_plan(nf_handle S, int in_cg, char *json_buf, size_t len)
+{
+    if (!S || !json_buf || len < 2) return fail(NF_ERR_ARG, "nf_apply_plan: bad arguments");
+    if (!S->built) return fail(NF_ERR_STATE, "nf_apply_plan: call nf_build first");
+    // the tables of distinct lines are part of what the next apply does: it would build them first, so the report does (its only side effect)
+    HIPCHK(hipSetDevice(S->team->device));
+    NFCHK(line_dict_prepare(S->team));
+    const nf_team *T = S->team;
+    const bool slab = S->if_lo || S->if_hi;
+    // a team settles the separator sweeps, the endpoint weights and its largest slab when it is prepared (the first team apply or solve)
+    if (!team_is_single(T) && !T->linked_ready) return fail(NF_ERR_STATE, "nf_apply_plan: run a team apply or solve first (the team has not been prepared since its options changed)");
+    // cg_solve applies S to d_p with CgFuse::p = d_p when fused (`P.fuse.p == xs[i]` of team_endpoint_phase) and asks for the dot product of every
+    // apply: the last pass, and every pass under the split dot product, gets a partial buffer.  xcd and fuse3 launch no Schur pass: theirs
+    // are the passes of the launch path (lean) such a solve would fall back to.
+    const CgPlan cp = cg_plan(T);
+    const bool cg = in_cg != 0, fused = cg && cp.fused, lean = cg && cp.lean(), sr = cg && cp.form == CG_TEAM_SR;
+    const bool split = split_dot(T, cg, lean);
+    bool any_if = false; for (auto *X : T->slabs) any_if |= X->if_lo || X->if_hi;
+    const bool xy_all = xy_overlap(T, any_if, false);
+    char tmp[288];
+    snprintf(tmp, sizeof tmp, "{\"in_cg\": %d, \"form\": \"%s\", \"slab\": %d, \"fused\": %d, \"lean\": %d, \"single_reduce\": %d, \"split_dot\": %d, \"xy_overlap\": %d, \"passes\": [",
+             cg ? 1 : 0, cg ? CG_FORM_NAME[cp.form] : "", slab ? 1 : 0, fused ? 1 : 0, lean ? 1 : 0, sr ? 1 : 0, split ? 1 : 0, xy_all ? 1 : 0);
+    std::string js = tmp;
+    for (int d = 0; d < S->dim; ++d) {
+        const bool last = d == S->dim - 1, want_dot = cg && (last || split);
+        if (d == 0) {
+            const XPlan xp = x_plan(S, fused);
+            if (!xp.NCH) return fail(NF_ERR_UNSUPPORTED, "nx = %d exceeds the x-line kernel limit (%d cells)", S->nx, S->nb == 0 ? 4096 : 1024);
+            plan_emit(js, { "x", "x", 0, 0, xp.NCH, 1 << xp.lpl_log2, 0, dim3(xp.grid, (unsigned)n_modes(S)), 256u, xp.nt, xp.p2, false, xp.xcd, xp.grid, false, xp.dict });
+        } else if (d == 2 && slab) {
+            // endpoint pass: inside the fused CG the update reads the vector the pass is applied to (cg_solve applies to d_p)
+            if (endpoint_w_taken(T, S, sr, fused)) { const dim3 gr = endpoint_w_grid(S); plan_emit(js, { "z", "endpoint_w", 1, 0, 0, 64, 0, gr, 256u, false, false, false, false, gr.x * gr.y }); }
+            else NFCHK(plan_s(js, S, 2, 1, false, false, fused, sr));
+            NFCHK(plan_s(js, S, 2, 2, want_dot, split, fused, sr));
+        } else if (d == 1 && xy_all) NFCHK(plan_s(js, S, 1, 0, false, split, fused, sr));
+        else NFCHK(plan_s(js, S, d, 0, want_dot, split, fused, sr));
+    }
+    {   // distinct lines of the largest group per direction, 0 where the direction does not use its table
+        int nd[3] = { 0, 0, 0 };
+        for (int d = 0; d < S->dim; ++d) if (dict_dir(S, d)) nd[d] = *std::max_element(S->ld_rows[d].begin(), S->ld_rows[d].end());
+        snprintf(tmp, sizeof tmp, "], \"line_dict\": {\"x\": %d, \"y\": %d, \"z\": %d}}", nd[0], nd[1], nd[2]);
+        js += tmp;
+    }
+    if (js.size() + 1 > len) return fail(NF_ERR_ARG, "nf_apply_plan: buffer of %zu bytes is too small (%zu needed)", len, js.size() + 1);
+    memcpy(json_buf, js.c_str(), js.size() + 1);
     return NF_OK;
 }
 
 // ---- CG (SchurSolver::SolveSchurImplicit, src/solvers.cpp:577-636) -----------------------------
+// What the pieces of one cg_solve share.  form: the plan's, or fuse3 after a one-XCD start that was not to be (no mapped page, refused, timed out).
+// Lean, vector reduce: row 0 of the partial buffer holds the p.q partials of the last direction pass, row 1 the |r|^2 partials of k_cg_rupdate
+// (vector reduce: + a flag slot each; d_vec: the two rows all-reduced).
+struct CgRun {
+    nf_team *T; int g; const CgPlan &P; CgForm form; const std::vector<double *> &x;   // x: the solution, per slab
+    std::vector<const double *> ps; std::vector<double *> qs;     // p and q = S p, per slab
+    std::vector<int> gcnt, acnt, cnt3;                             // per slab: blocks of the vector kernels, p.q partials of the apply, |r|^2 partials of k_endpoint_w
+    bool any_if = false;                                           // some local slab has an interface
+    double *row1() const { return T->d_partials + T->partial_stride; }
+    double *vec_rr() const { return T->d_vec + T->vec_stride; }
+    // a failed call inside the iteration: NF_OK if the rank is poisoned and carries on with the schedule, the code if it must leave at once
+    int chk(int rc) const { return team_poison(T, rc, form == CG_TEAM_VEC) ? rc : NF_OK; }
+    template <class F> void each_slab(F &&launch) const { if (!T->poisoned) for (size_t i = 0; i < T->slabs.size(); ++i) launch(T->slabs[i], (int)i); }   // a poisoned rank launches no compute
+};
+// The CG state an apply of iteration `index` consumes, and with index = the iterations launched so far what the batch-end stop test reads
+static ApplyCg cg_apply_args(const CgRun &R, int index)
+{
+    nf_team *T = R.T; const int first = index == 0 ? 1 : 0;
+    ApplyCg A; A.cg = T->d_cg; A.fused = R.P.fused; A.xsol = &R.x;
+    if (R.form == CG_FUSE3 || R.form == CG_LEAN) A.lean = CgLean{ T->d_cg, R.row1(), R.P.gru, index & 1, first };
+    if (R.form == CG_TEAM_SR) A.cg1 = Cg1{ T->d_red, T->d_cg, index };
+    if (R.form == CG_TEAM_VEC) A.lean_z1 = CgLean{ T->d_cg, R.vec_rr(), T->vec_cnt_rr, index & 1, first, T->vec_cnt_rr };
+    if (R.form == CG_TEAM_LEAN) A.lean_z1 = CgLean{ T->d_cg, T->d_red + 2, -1, index & 1, first };
+    return A;
+}
+// fuse3: two launches.  p lives in a pair of buffers: iteration 0 reads A = d_p as k_cg_init left it; iteration i >= 1 reads the p of
+// iteration i-1 (A for odd i, B for even i) and writes r + beta p into the other one
+static int cg_step_fuse3(CgRun &R, int index)
+{
+    nf_team *T = R.T; nf_solver *S0 = T->slabs[0];
+    double *A = S0->d_p, *B = S0->d_p2;
+    double *pin = (index == 0 || (index & 1)) ? A : B, *pout = pin == A ? B : A;
+    hipEvent_t ta = nullptr, tb = nullptr;
+    const bool prof = T->profile && (T->prof_tick++ % T->prof_every == 0);
+    if (prof) prof_begin(T, 3, &ta, &tb);
+    const int rc = launch_apply3(S0, R.g, R.P.f3, pin, pout, R.x[0], cg_apply_args(R, index).lean);
+    if (prof) (void)hipEventRecord(tb, T->stream);
+    hipLaunchKernelGGL(k_cg_rupdate3, dim3(R.P.gru), dim3(256), 0, T->stream, S0->d_r, (const double *)S0->d_q, (const double *)(S0->dim >= 2 ? S0->d_qy : nullptr),
+                       (const double *)(S0->dim == 3 ? S0->d_qz : nullptr), S0->nphi, T->d_cg, R.row1(), CgLean{ T->d_cg, T->d_partials, R.P.f3.nblocks, index & 1, 0 });
+    return rc;
+}
+// every other form: q = S p with the form's CG state; on a poisoned rank, what the apply owes its neighbours instead
+static int cg_step_apply(CgRun &R, int index, long global_it)
+{
+    nf_team *T = R.T;
+    T->xchg_in_apply = 0;
+    int ra = NF_OK;
+    if (T->nproc > 1 && T->rank == T->inject_rank && global_it == T->inject_iter)
+        { ra = fail(NF_ERR_HIP, "injected failure on rank %d at CG iteration %ld (NEUTFEM_INJECT_FAIL)", T->rank, global_it); TRACE_COMM("rank %d INJECT at %ld", T->rank, global_it); }
+    else if (!T->poisoned) ra = team_schur_apply(T, R.g, R.ps, R.qs, true, cg_apply_args(R, index), &R.acnt, &R.cnt3);
+    NFCHK(R.chk(ra));
+    if (T->poisoned && R.any_if) {
+        // the interface exchanges this apply still owes its neighbours: one per apply + one per separator sweep (team_endpoint_phase)
+        // with the stream dependencies of team_endpoint_phase: the exchange waits for the solver's stream (ev_z1), the reductions
+        // wait for the exchange (ev_xchg).  Without the first one the comm stream runs iterations ahead, and a transport whose
+        // operations of one process share a progress thread (the stand-in does; RCCL's proxy has the same shape) deadlocks: this
+        // rank blocks in the NEXT iteration's receive while its peers still wait for it in THIS iteration's all-reduce.
+        if (T->xchg_in_apply == 0) { (void)hipEventRecord(T->ev_z1, T->stream); (void)hipStreamWaitEvent(T->comm_stream, T->ev_z1, 0); }
+        for (int k = T->xchg_in_apply; k < 1 + T->sep_sweeps; ++k) (void)exchange_planes(T, k == 0 ? 0 : 2, 0, T->comm_stream);
+        (void)hipEventRecord(T->ev_xchg, T->comm_stream); (void)hipStreamWaitEvent(T->stream, T->ev_xchg, 0);
+        // a poisoned rank skips the apply, so cnt3 still holds the counts of its last one: cleared with acnt.  team_reduce_sr reads
+        // cnt3[i] only where acnt[i] > 0, so the reduction sees no partials of this rank in any row either way
+        for (size_t i = 0; i < R.acnt.size(); ++i) R.acnt[i] = R.cnt3[i] = 0;
+    }
+    return NF_OK;
+}
+// what follows the apply, per form
+static int cg_step_team_sr(CgRun &R, int) { return R.chk(team_reduce_sr(R.T, R.acnt, R.cnt3)); }   // the one reduction of the iteration; its consumer is the next endpoint pass
+static int cg_step_team_vec(CgRun &R, int index)                   // the partial vectors themselves cross the ranks; their consumers sum them (CgLean with a count and a flag slot)
+{
+    nf_team *T = R.T; double *send_pq = T->d_partials, *send_rr = R.row1(), *vec_pq = T->d_vec;
+    auto allred = [&](double *send, double *recv, int cnt) -> int { NCCLCHK(g_rccl.AllReduce(send, recv, (size_t)cnt + 1, NCCL_DOUBLE, NCCL_SUM, T->comm, T->stream)); return NF_OK; };
+    if (!T->poisoned && R.acnt[0] != T->vec_cnt_pq) NFCHK(R.chk(fail(NF_ERR_STATE, "vector reduce: the accumulation pass left %d partials, %d were agreed", R.acnt[0], T->vec_cnt_pq)));
+    NFCHK(R.chk(allred(send_pq, vec_pq, T->vec_cnt_pq)));
+    R.each_slab([&](nf_solver *S, int i) { hipLaunchKernelGGL(k_cg_rupdate, dim3(R.gcnt[i]), dim3(256), 0, T->stream, S->d_r, S->d_q, S->nphi, T->d_cg, send_rr, CgLean{ T->d_cg, vec_pq, T->vec_cnt_pq, index & 1, 0, T->vec_cnt_pq }); });
+    return R.chk(allred(send_rr, R.vec_rr(), T->vec_cnt_rr));
+}
+static int cg_step_team_lean(CgRun &R, int index)
+{
+    nf_team *T = R.T;
+    NFCHK(R.chk(team_reduce(T, R.acnt, T->d_red)));               // d_red[0] = p.q, d_red[1] = error flags
+    R.each_slab([&](nf_solver *S, int i) { hipLaunchKernelGGL(k_cg_rupdate, dim3(R.gcnt[i]), dim3(256), 0, T->stream, S->d_r, S->d_q, S->nphi, T->d_cg, T->d_partials + i * T->slab_cap, CgLean{ T->d_cg, T->d_red, -1, index & 1, 0 }); });
+    return R.chk(team_reduce(T, R.gcnt, T->d_red + 2));           // d_red[2] = |r|^2, d_red[3] = error flags
+}
+static int cg_step_lean(CgRun &R, int index)
+{
+    R.each_slab([&](nf_solver *S, int) { hipLaunchKernelGGL(k_cg_rupdate, dim3(R.P.gru), dim3(256), 0, R.T->stream, S->d_r, S->d_q, S->nphi, R.T->d_cg, R.row1(), CgLean{ R.T->d_cg, R.T->d_partials, R.acnt[0], index & 1, 0 }); });
+    return NF_OK;
+}
+static int cg_step_scalar(CgRun &R, int)                           // fused, classic: the scalars behind k_finalize
+{
+    nf_team *T = R.T; const bool fused = R.form == CG_FUSED;
+    NFCHK(R.chk(team_finalize(T, FIN_PAP, R.acnt, 1, T->d_out, 0.0, 0)));
+    R.each_slab([&](nf_solver *S, int i) {
+        if (fused) hipLaunchKernelGGL(k_cg_rupdate, dim3(R.gcnt[i]), dim3(256), 0, T->stream, S->d_r, S->d_q, S->nphi, T->d_cg, T->d_partials + i * T->slab_cap, CgLean{});
+        else hipLaunchKernelGGL(k_cg_update, dim3(R.gcnt[i]), dim3(256), 0, T->stream, R.x[i], S->d_r, S->d_p, S->d_q, S->nphi, T->d_cg, T->d_partials + i * T->slab_cap); });
+    NFCHK(R.chk(team_finalize(T, FIN_RR, R.gcnt, 1, T->d_out, 0.0, 0)));
+    if (!fused) R.each_slab([&](nf_solver *S, int i) { hipLaunchKernelGGL(k_cg_pupdate, dim3(R.gcnt[i]), dim3(256), 0, T->stream, S->d_p, S->d_r, S->nphi, T->d_cg); });
+    return NF_OK;
+}
+static int cg_step(CgRun &R, int index, long global_it)           // iteration `index` of the solve in the run's form
+{
+    static int (*const after_apply[])(CgRun &, int) = { nullptr, nullptr, cg_step_lean, cg_step_scalar, cg_step_scalar, cg_step_team_lean, cg_step_team_vec, cg_step_team_sr };   // by CgForm
+    if (R.form == CG_FUSE3) return cg_step_fuse3(R, index);
+    NFCHK(cg_step_apply(R, index, global_it));
+    return after_apply[R.form](R, index);
+}
+// The stop test of a batch's last iteration where the form leaves it to the next pass that consumes |r|^2, and the scalars to the host
+static int cg_stop_test(CgRun &R, int launched, CgScalars *sc)
+{
+    nf_team *T = R.T; const ApplyCg A = cg_apply_args(R, launched);
+    if ((R.form == CG_FUSE3 || R.form == CG_LEAN) && pub_ready(T)) {
+        const unsigned long long seq = ++T->pub_seq;
+        hipLaunchKernelGGL(k_cg_lean_rr, dim3(1), dim3(256), 0, T->stream, A.lean, T->d_pub, seq);
+        return pub_wait(T, seq, sc, nullptr, 0);
+    }
+    if (R.form == CG_FUSE3 || R.form == CG_LEAN) hipLaunchKernelGGL(k_cg_lean_rr, dim3(1), dim3(256), 0, T->stream, A.lean, (HostPub *)nullptr, 0ULL);
+    if (R.form == CG_TEAM_SR) hipLaunchKernelGGL(k_cg1_logic, dim3(1), dim3(64), 0, T->stream, A.cg1, (HostPub *)nullptr, 0ULL);
+    if (R.form == CG_TEAM_VEC || R.form == CG_TEAM_LEAN) hipLaunchKernelGGL(k_cg_lean_rr, dim3(1), dim3(256), 0, T->stream, A.lean_z1, (HostPub *)nullptr, 0ULL);
+    return readback(T, T->d_cg, sc, nullptr, nullptr, 0);
+}
+static int cg_result(nf_team *T, int g, CgForm form, const CgScalars &sc, int *its_out, double *res_out)   // what a finished solve reports
+{
+    T->last_cg_form = form;
+    if (!std::isfinite(sc.rr)) return fail(NF_ERR_NUMERIC, "CG produced a non-finite residual (group %d)", g);
+    T->last_its[g] = sc.its;
+    if (its_out) *its_out = sc.its;
+    if (res_out) *res_out = sc.rhs_norm > 0 ? std::sqrt(sc.rr) / sc.rhs_norm : 0.0;
+    return NF_OK;
+}
 // rhs / x: per-slab pointers
 // inited: k_group_rhs has already written x = 0, r = p = rhs and the |rhs|^2 partials (one launch less per group solve)
 static int cg_solve(nf_team *T, int g, const std::vector<const double *> &rhs, const std::vector<double *> &x, double tol, int maxit,
                     int *its_out, double *res_out, bool inited = false)
 {
-    const int ns = (int)T->slabs.size();
-    std::vector<int> gcnt(ns), acnt(ns), cnt3(ns, 0);              // cnt3: |r|^2 partials of k_endpoint_w per slab (team_endpoint_phase)
-    std::vector<const double *> ps(ns); std::vector<double *> qs(ns);
-    for (int i = 0; i < ns; ++i) {
-        nf_solver *S = T->slabs[i];
-        gcnt[i] = grid_for(S->nphi); ps[i] = S->d_p; qs[i] = S->d_q;
-        if (!inited) hipLaunchKernelGGL(k_cg_init, dim3(gcnt[i]), dim3(256), 0, T->stream, rhs[i], x[i], S->d_r, S->d_p, S->nphi, T->d_partials + i * T->slab_cap);
-    }
-    NFCHK(team_finalize(T, FIN_RHS, gcnt, 1, T->d_out, tol, maxit));
+    const int ns = (int)T->slabs.size(); nf_solver *S0 = T->slabs[0];
+    const CgPlan P = cg_plan(T);
+    CgRun R{ T, g, P, P.form, x };
+    R.ps.resize(ns); R.qs.resize(ns); R.gcnt.resize(ns); R.acnt.resize(ns); R.cnt3.assign(ns, 0);
+    auto init = [&] { for (int i = 0; i < ns; ++i) hipLaunchKernelGGL(k_cg_init, dim3(R.gcnt[i]), dim3(256), 0, T->stream, rhs[i], x[i], T->slabs[i]->d_r, T->slabs[i]->d_p, T->slabs[i]->nphi, T->d_partials + i * T->slab_cap); };
+    for (int i = 0; i < ns; ++i) { nf_solver *S = T->slabs[i]; R.gcnt[i] = grid_for(S->nphi); R.ps[i] = S->d_p; R.qs[i] = S->d_q; R.any_if |= S->if_lo || S->if_hi; }
+    if (!inited) init();
+    NFCHK(team_finalize(T, FIN_RHS, R.gcnt, 1, T->d_out, tol, maxit));
     CgScalars sc; memset(&sc, 0, sizeof sc);
-    int launched = 0;
-    // first batch: what the previous solve of this group needed, plus two (an iteration launched past convergence costs five
-    // early-exit kernels, ~10 us; a second host check costs a D2H copy and a stream drain, ~50 us)
-    int batch = T->cg_batch > 0 ? T->cg_batch : (T->last_its[g] > 0 ? T->last_its[g] + 2 : 1), grow = 2;
-    // fused and lean variants (cg_fused / cg_lean).  Lean: row 0 of the partial buffer holds the p.q partials of the last direction pass,
-    // row 1 the |r|^2 partials of k_cg_rupdate.
-    const bool fused = cg_fused(T), lean = cg_lean(T);
-    // every block of the next x pass sums the |r|^2 partials; fewer partials (cg_lean_grid) cost k_cg_rupdate more than they save (measured)
-    const int gru = lean ? grid_for(T->slabs[0]->nphi, 256, T->opt_lean_grid) : 0;
-    double *row1 = T->d_partials + T->partial_stride;
-    int rc = NF_OK;
-    // lean variant for slab teams (fused, RT0-P0): the endpoint pass of the z lines and k_cg_rupdate consume the all-reduced
-    // totals (d_red[2] = |r|^2, d_red[0] = p.q, each followed by the ranks' error flags) and derive beta / alpha and the stop tests themselves: no k_cg_logic launches
-    const bool tlean = cg_tlean(T), sr = cg_sr(T);                // the single-reduction variant (Cg1) of the slab teams' lean form
-    T->last_cg_reductions = team_is_single(T) ? 0 : (sr ? 1 : 2); T->last_endpoint_w = 0;
-    // fused-direction variant on top of the lean one (small / medium meshes): two launches per iteration, see k_apply3
-    Fuse3Plan f3;
-    nf_solver *S0 = T->slabs[0];
-    if (lean && T->opt_fuse3 && S0->N <= T->fuse3_max_cells) f3 = fuse3_plan(S0);
-    if (f3.ok && f3.nblocks > T->slab_cap) f3.ok = false;
-    if (f3.ok) {
+    T->last_cg_reductions = P.reductions; T->last_endpoint_w = 0; T->last_vec_reduce = P.form == CG_TEAM_VEC ? 1 : 0; T->last_xcd = 0;
+    if (P.f3.ok) {
         if (!S0->d_p2) NFCHK(dalloc(&S0->d_p2, S0->nphi));
         if (S0->dim >= 2 && !S0->d_qy) NFCHK(dalloc(&S0->d_qy, S0->nphi));
         if (S0->dim == 3 && !S0->d_qz) NFCHK(dalloc(&S0->d_qz, S0->nphi));
     }
-    T->last_xcd = 0;
-    if (f3.ok && xcd_eligible(T, S0, f3) && pub_ready(T)) {
-        // the whole solve in one launch on one XCD (k_cg_xcd); the kernel hands the final scalars to the host itself
+    if (R.form == CG_XCD && !pub_ready(T)) R.form = CG_FUSE3;    // the kernel hands the final scalars to the host itself: no mapped page, no one-XCD solve
+    if (R.form == CG_XCD) {                                       // the whole solve in one launch on one XCD (k_cg_xcd)
         const unsigned long long seq = ++T->pub_seq;
-        NFCHK(launch_cg_xcd(S0, g, f3, x[0], seq));
+        NFCHK(launch_cg_xcd(S0, g, P.f3, x[0], seq));
         NFCHK(pub_wait(T, seq, &sc, nullptr, 0));
-        if (sc.err == 4) {
-            // a grid barrier timed out in the middle of the solve (a participant stalled for longer than the bound: another process on
-            // the GPU, a debugger): x, r and p are half-way, but the right-hand side is intact -- start the solve again on the launch
-            // path (the kernels have all left by now: the flag that ended one ended the others) and keep this solver off the one-XCD path
-            T->opt_cgx = 0; ++T->xcd_refused;
-            HIPCHK(hipStreamSynchronize(T->stream));
-            for (int i = 0; i < ns; ++i) {
-                nf_solver *S = T->slabs[i];
-                hipLaunchKernelGGL(k_cg_init, dim3(gcnt[i]), dim3(256), 0, T->stream, rhs[i], x[i], S->d_r, S->d_p, S->nphi, T->d_partials + i * T->slab_cap);
-            }
-        }
-        if (sc.err != 3 && sc.err != 4) {
-            T->last_xcd = 1; ++T->xcd_solves;
-            HIPCHK(hipGetLastError());
-            if (!std::isfinite(sc.rr)) return fail(NF_ERR_NUMERIC, "CG produced a non-finite residual (group %d)", g);
-            T->last_its[g] = sc.its;
-            if (its_out) *its_out = sc.its;
-            if (res_out) *res_out = sc.rhs_norm > 0 ? std::sqrt(sc.rr) / sc.rhs_norm : 0.0;
-            return NF_OK;
-        }
-        // the workgroups did not assemble (nothing placed on the XCD, or it is busy): no vector has been touched -- this solve and the
-        // following ones of this solver go through the launch path
-        if (sc.err == 3) { T->opt_cgx = 0; ++T->xcd_refused; }
-        NFCHK(team_finalize(T, FIN_RHS, gcnt, 1, T->d_out, tol, maxit));
+        if (sc.err != 3 && sc.err != 4) { T->last_xcd = 1; ++T->xcd_solves; HIPCHK(hipGetLastError()); return cg_result(T, g, CG_XCD, sc, its_out, res_out); }
+        // err 3: the workgroups did not assemble (nothing placed on the XCD, or it is busy): no vector has been touched.  err 4: a grid
+        // barrier timed out in the middle of the solve (a participant stalled for longer than the bound: another process on the GPU, a
+        // debugger): x, r and p are half-way, but the right-hand side is intact (the kernels have all left by now: the flag that ended
+        // one ended the others).  Either way this solve starts again on the launch path, and so do the following ones of this solver
+        T->opt_cgx = 0; ++T->xcd_refused; R.form = CG_FUSE3;
+        if (sc.err == 4) { HIPCHK(hipStreamSynchronize(T->stream)); init(); }
+        NFCHK(team_finalize(T, FIN_RHS, R.gcnt, 1, T->d_out, tol, maxit));
         memset(&sc, 0, sizeof sc);
     }
-    // A local failure on a multi-rank team (a refused launch, a failed HIP call) must not end this rank's part of the schedule: the
-    // other ranks are about to wait in the collectives of this batch.  The rank raises its error flag (it rides in every reduction
-    // that crosses ranks, CgScalars::err), stops launching compute, keeps issuing exactly the collectives the schedule holds, and
-    // returns when the flag has stopped every rank -- at the same iteration everywhere.
-    const bool multi = T->nproc > 1;
-    bool any_if = false; for (auto *S : T->slabs) any_if |= S->if_lo || S->if_hi;
-    // vector reduce (see nf_team::d_vec): row 0 of the partial buffer = this rank's p.q partials + flag slot, row 1 = |r|^2 partials + flag slot
-    const bool vred = tlean && !sr && multi && ns == 1 && T->vec_ok && T->opt_vec_reduce;
-    double *send_pq = T->d_partials, *send_rr = T->d_partials + T->partial_stride;
-    double *vec_pq = T->d_vec, *vec_rr = vred ? T->d_vec + T->vec_stride : nullptr;
-    T->last_vec_reduce = vred ? 1 : 0;
-    if (vred) {                                                   // other kernels use these rows between solves: clear the two flag slots
-        HIPCHK(hipMemsetAsync(send_pq + T->vec_cnt_pq, 0, sizeof(double), T->stream));
-        HIPCHK(hipMemsetAsync(send_rr + T->vec_cnt_rr, 0, sizeof(double), T->stream));
-    }
-    auto bad = [&](int code) -> bool {                            // true: leave the loop (single process); false: carry on (poisoned or fine)
-        if (code == NF_OK) return false;
-        if (!multi) { rc = code; return true; }
-        if (!T->poisoned) {
-            T->poisoned = true; T->poison_rc = code; snprintf(T->poison_msg, sizeof T->poison_msg, "%s", nf_last_error());
-            const double one = 1.0;
-            (void)hipMemcpyAsync(T->d_errsrc, &one, sizeof one, hipMemcpyHostToDevice, T->stream);
-            if (vred) {                                           // the flag slots of the two vectors this rank sends from now on
-                (void)hipMemcpyAsync(send_pq + T->vec_cnt_pq, &one, sizeof one, hipMemcpyHostToDevice, T->stream);
-                (void)hipMemcpyAsync(send_rr + T->vec_cnt_rr, &one, sizeof one, hipMemcpyHostToDevice, T->stream);
-            }
-            (void)hipStreamSynchronize(T->stream);               // `one` lives on this stack frame; the stream may also have to recover from the failed call
-            (void)hipGetLastError();
-        }
-        return false;
-    };
+    if (R.form == CG_TEAM_VEC)                                    // other kernels use these rows between solves: clear the two flag slots
+        for (double *slot : { T->d_partials + T->vec_cnt_pq, R.row1() + T->vec_cnt_rr }) HIPCHK(hipMemsetAsync(slot, 0, sizeof(double), T->stream));
+    int launched = 0, rc = NF_OK;
+    // first batch: what the previous solve of this group needed, plus two (an iteration launched past convergence costs five
+    // early-exit kernels, ~10 us; a second host check costs a D2H copy and a stream drain, ~50 us)
+    int batch = T->cg_batch > 0 ? T->cg_batch : (T->last_its[g] > 0 ? T->last_its[g] + 2 : 1), grow = 2;
     while (launched < maxit && rc == NF_OK) {
-        int nb = std::min(batch, maxit - launched);
-        for (int it = 0; it < nb && rc == NF_OK; ++it) {
-            const int index = launched + it;                      // iteration number within this solve
-            const long global_it = T->cg_iter_total++;
-            if (f3.ok) {
-                // p lives in a pair of buffers: iteration 0 reads A = d_p as k_cg_init left it; iteration i >= 1 reads the p of
-                // iteration i-1 (A for odd i, B for even i) and writes r + beta p into the other one
-                double *A = S0->d_p, *B = S0->d_p2;
-                double *pin = (index == 0 || (index & 1)) ? A : B, *pout = pin == A ? B : A;
-                hipEvent_t ta = nullptr, tb = nullptr;
-                const bool prof = T->profile && (T->prof_tick++ % T->prof_every == 0);
-                if (prof) prof_begin(T, 3, &ta, &tb);
-                rc = launch_apply3(S0, g, f3, pin, pout, x[0], CgLean{ T->d_cg, row1, gru, index & 1, index == 0 ? 1 : 0 });
-                if (prof) (void)hipEventRecord(tb, T->stream);
-                hipLaunchKernelGGL(k_cg_rupdate3, dim3(gru), dim3(256), 0, T->stream, S0->d_r, (const double *)S0->d_q, (const double *)(S0->dim >= 2 ? S0->d_qy : nullptr),
-                                   (const double *)(S0->dim == 3 ? S0->d_qz : nullptr), S0->nphi, T->d_cg, row1, CgLean{ T->d_cg, T->d_partials, f3.nblocks, index & 1, 0 });
-                continue;
-            }
-            ApplyCg A; A.cg = T->d_cg; A.fused = fused; A.xsol = &x;
-            if (lean) A.lean = CgLean{ T->d_cg, row1, gru, index & 1, index == 0 ? 1 : 0 };
-            if (sr) A.cg1 = Cg1{ T->d_red, T->d_cg, index };
-            else if (tlean) A.lean_z1 = vred ? CgLean{ T->d_cg, vec_rr, T->vec_cnt_rr, index & 1, index == 0 ? 1 : 0, T->vec_cnt_rr }
-                                             : CgLean{ T->d_cg, T->d_red + 2, -1, index & 1, index == 0 ? 1 : 0 };
-            T->xchg_in_apply = 0;
-            int ra = NF_OK;
-            if (multi && T->rank == T->inject_rank && global_it == T->inject_iter)
-                { ra = fail(NF_ERR_HIP, "injected failure on rank %d at CG iteration %ld (NEUTFEM_INJECT_FAIL)", T->rank, global_it); TRACE_COMM("rank %d INJECT at %ld", T->rank, global_it); }
-            else if (!T->poisoned) ra = team_schur_apply(T, g, ps, qs, true, A, &acnt, &cnt3);
-            if (bad(ra)) break;
-            if (T->poisoned && any_if) {
-                // the interface exchanges this apply still owes its neighbours: one per apply + one per separator sweep (team_endpoint_phase)
-                // with the stream dependencies of team_endpoint_phase: the exchange waits for the solver's stream (ev_z1), the reductions
-                // wait for the exchange (ev_xchg).  Without the first one the comm stream runs iterations ahead, and a transport whose
-                // operations of one process share a progress thread (the stand-in does; RCCL's proxy has the same shape) deadlocks: this
-                // rank blocks in the NEXT iteration's receive while its peers still wait for it in THIS iteration's all-reduce.
-                if (T->xchg_in_apply == 0) { (void)hipEventRecord(T->ev_z1, T->stream); (void)hipStreamWaitEvent(T->comm_stream, T->ev_z1, 0); }
-                for (int k = T->xchg_in_apply; k < 1 + T->sep_sweeps; ++k) (void)exchange_planes(T, k == 0 ? 0 : 2, 0, T->comm_stream);
-                (void)hipEventRecord(T->ev_xchg, T->comm_stream); (void)hipStreamWaitEvent(T->stream, T->ev_xchg, 0);
-                // a poisoned rank skips the apply, so cnt3 still holds the counts of its last one: cleared with acnt.  team_reduce_sr reads
-                // cnt3[i] only where acnt[i] > 0, so the reduction sees no partials of this rank in any row either way
-                for (int i = 0; i < ns; ++i) acnt[i] = cnt3[i] = 0;
-            }
-            if (sr) {                                             // the one reduction of this iteration; its consumer is the next endpoint pass
-                if (bad(team_reduce_sr(T, acnt, cnt3))) break;
-                continue;
-            }
-            if (vred) {
-                // the partial vectors themselves cross the ranks; their consumers sum them (CgLean with a count and a flag slot)
-                auto allred = [&](double *send, double *recv, int cnt) -> int { NCCLCHK(g_rccl.AllReduce(send, recv, (size_t)cnt + 1, NCCL_DOUBLE, NCCL_SUM, T->comm, T->stream)); return NF_OK; };
-                if (!T->poisoned && acnt[0] != T->vec_cnt_pq) { if (bad(fail(NF_ERR_STATE, "vector reduce: the accumulation pass left %d partials, %d were agreed", acnt[0], T->vec_cnt_pq))) break; }
-                if (bad(allred(send_pq, vec_pq, T->vec_cnt_pq))) break;
-                if (!T->poisoned)
-                    hipLaunchKernelGGL(k_cg_rupdate, dim3(gcnt[0]), dim3(256), 0, T->stream, T->slabs[0]->d_r, T->slabs[0]->d_q, T->slabs[0]->nphi, T->d_cg, send_rr,
-                                       CgLean{ T->d_cg, vec_pq, T->vec_cnt_pq, index & 1, 0, T->vec_cnt_pq });
-                if (bad(allred(send_rr, vec_rr, T->vec_cnt_rr))) break;
-                continue;
-            }
-            if (tlean) {
-                if (bad(team_reduce(T, acnt, T->d_red))) break;   // d_red[0] = p.q, d_red[1] = error flags
-                if (!T->poisoned)
-                    for (int i = 0; i < ns; ++i) {
-                        nf_solver *S = T->slabs[i];
-                        hipLaunchKernelGGL(k_cg_rupdate, dim3(gcnt[i]), dim3(256), 0, T->stream, S->d_r, S->d_q, S->nphi, T->d_cg, T->d_partials + i * T->slab_cap,
-                                           CgLean{ T->d_cg, T->d_red, -1, index & 1, 0 });
-                    }
-                if (bad(team_reduce(T, gcnt, T->d_red + 2))) break;   // d_red[2] = |r|^2, d_red[3] = error flags
-                continue;
-            }
-            if (!lean && bad(team_finalize(T, FIN_PAP, acnt, 1, T->d_out, 0.0, 0))) break;
-            if (!T->poisoned)
-                for (int i = 0; i < ns; ++i) {
-                    nf_solver *S = T->slabs[i];
-                    if (lean) hipLaunchKernelGGL(k_cg_rupdate, dim3(gru), dim3(256), 0, T->stream, S->d_r, S->d_q, S->nphi, T->d_cg, row1,
-                                                 CgLean{ T->d_cg, T->d_partials, acnt[0], index & 1, 0 });
-                    else if (fused) hipLaunchKernelGGL(k_cg_rupdate, dim3(gcnt[i]), dim3(256), 0, T->stream, S->d_r, S->d_q, S->nphi, T->d_cg, T->d_partials + i * T->slab_cap, CgLean{});
-                    else hipLaunchKernelGGL(k_cg_update, dim3(gcnt[i]), dim3(256), 0, T->stream, x[i], S->d_r, S->d_p, S->d_q, S->nphi, T->d_cg, T->d_partials + i * T->slab_cap);
-                }
-            if (lean) continue;
-            if (bad(team_finalize(T, FIN_RR, gcnt, 1, T->d_out, 0.0, 0))) break;
-            if (fused || T->poisoned) continue;
-            for (int i = 0; i < ns; ++i) {
-                nf_solver *S = T->slabs[i];
-                hipLaunchKernelGGL(k_cg_pupdate, dim3(gcnt[i]), dim3(256), 0, T->stream, S->d_p, S->d_r, S->nphi, T->d_cg);
-            }
-        }
+        const int nb = std::min(batch, maxit - launched);
+        for (int it = 0; it < nb && rc == NF_OK; ++it) rc = cg_step(R, launched + it, T->cg_iter_total++);
         if (rc != NF_OK) break;
         launched += nb;
-        // lean: the stop tests of the batch's last iteration have not been evaluated yet (the next x pass would do it)
-        if (lean && pub_ready(T)) {                               // the kernel that evaluates the stop tests hands the scalars to the host itself
-            const unsigned long long seq = ++T->pub_seq;
-            hipLaunchKernelGGL(k_cg_lean_rr, dim3(1), dim3(256), 0, T->stream, CgLean{ T->d_cg, row1, gru, launched & 1, 0 }, T->d_pub, seq);
-            { const int rw = pub_wait(T, seq, &sc, nullptr, 0); if (rw != NF_OK) { rc = rw; break; } }
-        } else {
-            if (lean) hipLaunchKernelGGL(k_cg_lean_rr, dim3(1), dim3(256), 0, T->stream, CgLean{ T->d_cg, row1, gru, launched & 1, 0 }, (HostPub *)nullptr, 0ULL);
-            if (sr) hipLaunchKernelGGL(k_cg1_logic, dim3(1), dim3(64), 0, T->stream, Cg1{ T->d_red, T->d_cg, launched }, (HostPub *)nullptr, 0ULL);
-            else if (tlean) hipLaunchKernelGGL(k_cg_lean_rr, dim3(1), dim3(256), 0, T->stream, vred ? CgLean{ T->d_cg, vec_rr, T->vec_cnt_rr, launched & 1, 0, T->vec_cnt_rr }
-                                                                                                 : CgLean{ T->d_cg, T->d_red + 2, -1, launched & 1, 0 }, (HostPub *)nullptr, 0ULL);
-            { const int rw = readback(T, T->d_cg, &sc, nullptr, nullptr, 0); if (rw != NF_OK) { rc = rw; break; } }
-        }
-        if (sc.done) break;
+        rc = cg_stop_test(R, launched, &sc);
+        if (rc != NF_OK || sc.done) break;
         // after the first (predicted) batch grow geometrically: an iteration launched past convergence is five early-exit
         // kernels (~10 us), a host check is a D2H copy + stream drain (~50 us)
         batch = T->cg_batch > 0 ? T->cg_batch : (launched < 8 ? 1 : grow);
         if (launched >= 8) grow = std::min(64, 2 * grow);
     }
     NFCHK(rc);
-    if (T->poisoned) {                                            // the flag has stopped every rank (or maxit did): this rank reports what hit it
-        const int code = T->poison_rc; char msg[256]; snprintf(msg, sizeof msg, "%s", T->poison_msg);
-        T->poisoned = false;
-        (void)hipMemsetAsync(T->d_errsrc, 0, sizeof(double), T->stream);
-        return fail(code, "%s", msg);
-    }
+    if (T->poisoned) return team_poison_result(T);               // the flag has stopped every rank (or maxit did): this rank reports what hit it
     if (sc.err == 2) return fail(NF_ERR_REMOTE, "another rank of the team reported an error during the CG solve of group %d; every rank stopped at iteration %d", g, sc.its);
     if (launched == 0) {
         HIPCHK(hipMemcpyAsync(&sc, T->d_cg, sizeof sc, hipMemcpyDeviceToHost, T->stream));
         HIPCHK(hipStreamSynchronize(T->stream));
     }
-    if (fused)
+    if (P.fused)
         for (int i = 0; i < ns; ++i) {
             const double *plast = T->slabs[i]->d_p;
-            if (f3.ok && sc.its >= 2 && ((sc.its - 1) & 1)) plast = T->slabs[i]->d_p2;   // the direction of the last iteration (see the buffer pair above)
-            hipLaunchKernelGGL(k_cg_flush, dim3(gcnt[i]), dim3(256), 0, T->stream, x[i], plast, T->slabs[i]->nphi, T->d_cg);
+            if (R.form == CG_FUSE3 && sc.its >= 2 && ((sc.its - 1) & 1)) plast = T->slabs[i]->d_p2;   // the direction of the last iteration (see cg_step_fuse3)
+            hipLaunchKernelGGL(k_cg_flush, dim3(R.gcnt[i]), dim3(256), 0, T->stream, x[i], plast, T->slabs[i]->nphi, T->d_cg);
         }
     HIPCHK(hipGetLastError());
     if (T->profile) prof_collect(T);
-    if (!std::isfinite(sc.rr)) return fail(NF_ERR_NUMERIC, "CG produced a non-finite residual (group %d)", g);
-    T->last_its[g] = sc.its;
-    if (its_out) *its_out = sc.its;
-    if (res_out) *res_out = sc.rhs_norm > 0 ? std::sqrt(sc.rr) / sc.rhs_norm : 0.0;
-    return NF_OK;
+    return cg_result(T, g, R.form, sc, its_out, res_out);
 }
 
 int nf_solve_group(nf_handle S, int g, const double *rhs_dev, double *phi_dev, double tol, int maxit, int *its, double *res)
@@ -3145,15 +3150,12 @@ static int solve_keff_xcd(nf_team *T, const nf_keff_opts *o, const Fuse3Plan &P,
     if (T->hist_cg_cap < o->max_outer * ng) { NFCHK(dalloc(&T->d_hist_cg, (size_t)o->max_outer * ng)); T->hist_cg_cap = o->max_outer * ng; }
     if (!T->d_rout) NFCHK(dalloc(&T->d_rout, 1));
     O.hist = T->d_hist; O.hist_cg = T->d_hist_cg; O.out = T->d_rout;
-    const size_t lds = XCD_LDS;
-    const unsigned G = 8u * (unsigned)T->xcd_groups;
-#define NF_XK(NCHV, VECV, NBV, SEGV) do { if (!lds_opt_in((const void *)k_keff_xcd<NCHV, VECV, NBV, SEGV>, lds)) return NF_RESIDENT_UNAVAILABLE; \
-        hipLaunchKernelGGL((k_keff_xcd<NCHV, VECV, NBV, SEGV>), dim3(G), dim3(XCD_THREADS), lds, st, A, O); } while (0)
-#define NF_XK_NB(NCHV, VECV) do { if (S->nb == 0) NF_XK(NCHV, VECV, 0, 8); else if (S->nb == 1) NF_XK(NCHV, VECV, 1, 4); else NF_XK(NCHV, VECV, 2, 4); } while (0)
-    if (nch == 1) { if (P.vec) NF_XK_NB(1, true); else NF_XK_NB(1, false); }
-    else { if (P.vec) NF_XK_NB(2, true); else NF_XK_NB(2, false); }
-#undef NF_XK_NB
-#undef NF_XK
+    const size_t lds = XCD_LDS; const unsigned G = 8u * (unsigned)T->xcd_groups;
+    NFCHK(xcd_select("k_keff_xcd", S, P, nch, [&](auto t) -> int { using I = decltype(t);
+        if (!lds_opt_in((const void *)k_keff_xcd<I::NCH, I::VEC, I::NB, I::SEG>, lds)) return NF_RESIDENT_UNAVAILABLE;
+        hipLaunchKernelGGL((k_keff_xcd<I::NCH, I::VEC, I::NB, I::SEG>), dim3(G), dim3(XCD_THREADS), lds, st, A, O);
+        return NF_OK;
+    }));
     HIPCHK(hipGetLastError());
     ResidentOut ro;
     HIPCHK(hipMemcpyAsync(&ro, T->d_rout, sizeof ro, hipMemcpyDeviceToHost, st));
@@ -3256,23 +3258,21 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
             T->last_path = 0; T->profile = prof_req;              // the device refused the LDS the resident kernel plans with: host-driven path
         }
     }
-    // mid-size meshes (2 k - 28 k unknowns per group, every order): the whole power iteration in one launch on one XCD (k_keff_xcd)
-    if (single && !use_diag && !use_cmfd && !direct && !dense && !T->rccl_reduce && o->max_outer > 0 && T->opt_keffx && T->opt_fuse && T->opt_lean && T->opt_fuse3 &&
-        S0->N <= T->fuse3_max_cells && S0->N <= T->lean_max_cells) {
-        const Fuse3Plan f3 = fuse3_plan(S0);
-        if (xcd_eligible(T, S0, f3)) {
-            T->last_path = 3;
-            const int rx = solve_keff_xcd(T, o, f3, keff, ca, cbv, sigma, cg_tol, cg_max, &keff);
-            if (rx != NF_RESIDENT_UNAVAILABLE) {
-                NFCHK(rx);
-                S0->raw_valid = T->last_outer > 0; S0->raw_is_diag = false; S0->jz_valid = false;
-                T->has_valid_keff = 1; T->last_keff = keff;
-                if (keff_out) *keff_out = keff;
-                if (n_outer) *n_outer = T->last_outer;
-                return NF_OK;
-            }
-            T->last_path = 0;
+    // mid-size meshes (2 k - 28 k unknowns per group, every order): the whole power iteration in one launch on one XCD (k_keff_xcd),
+    // where the group solves would take the one-XCD form of CG
+    const CgPlan cp = cg_plan(T);
+    if (!use_diag && !use_cmfd && !direct && o->max_outer > 0 && T->opt_keffx && cp.form == CG_XCD) {
+        T->last_path = 3;
+        const int rx = solve_keff_xcd(T, o, cp.f3, keff, ca, cbv, sigma, cg_tol, cg_max, &keff);
+        if (rx != NF_RESIDENT_UNAVAILABLE) {
+            NFCHK(rx);
+            S0->raw_valid = T->last_outer > 0; S0->raw_is_diag = false; S0->jz_valid = false;
+            T->has_valid_keff = 1; T->last_keff = keff;
+            if (keff_out) *keff_out = keff;
+            if (n_outer) *n_outer = T->last_outer;
+            return NF_OK;
         }
+        T->last_path = 0;
     }
     ScatterArgs sa; sa.ng = ng;
     double hout[5] = { 0, 0, 0, 0, 0 };

@@ -6,6 +6,8 @@ import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 TEST_TOL = (1e-5, 1e-4, 1e-4, 200, 1000)      # reference drivers: set_tol(1e-5,1e-4,1e-4,200,1000)
+# nf_info "cg_form": the form of the CG iteration the last CG solve ran, in the order of include/neutfem_hip.h (apply_plan names them)
+CG_FORMS = ("xcd", "fuse3", "lean", "fused", "classic", "team_lean", "team_vec", "team_sr")
 
 
 def load_inputs(name):

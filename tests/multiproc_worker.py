@@ -81,8 +81,9 @@ def main():
     ys = [None] * world; ps = [None] * world; ks = [None] * world; js = [None] * world
     vec = t.head.info("vec_reduce")                               # 1: the last CG solve all-reduced the partial vectors themselves (no k_finalize)
     red = t.head.info("cg_reductions")                            # cross-rank reductions per CG iteration of the last CG solve (1: single-reduction CG)
+    form = t.head.info("cg_form")                                 # the form of the CG iteration the last CG solve ran (helpers.CG_FORMS)
     xc = t.head.info("xchg_comm")
-    dist.gather_object(y, ys if rank == 0 else None); dist.gather_object(phi, ps if rank == 0 else None); dist.gather_object((k, n, vec, red, xc), ks if rank == 0 else None)
+    dist.gather_object(y, ys if rank == 0 else None); dist.gather_object(phi, ps if rank == 0 else None); dist.gather_object((k, n, vec, red, xc, form), ks if rank == 0 else None)
     dist.gather_object((J, k1 - k0), js if rank == 0 else None)
     if rank == 0:
         extra = {}
@@ -95,7 +96,7 @@ def main():
                 zs.append(z if r == world - 1 else z[:, :-1])
             extra["J"] = np.concatenate([np.concatenate(xs, axis=1), np.concatenate(ysf, axis=1), np.concatenate(zs, axis=1).reshape(2, -1)], axis=1)
         np.savez(out, y=np.concatenate(ys, axis=0), phi=np.concatenate(ps, axis=1), k=np.array([v[0] for v in ks]), n=np.array([v[1] for v in ks]),
-                 vec=np.array([v[2] for v in ks]), red=np.array([v[3] for v in ks]), xc=np.array([v[4] for v in ks]), x=xg, **extra)
+                 vec=np.array([v[2] for v in ks]), red=np.array([v[3] for v in ks]), xc=np.array([v[4] for v in ks]), form=np.array([v[5] for v in ks]), x=xg, **extra)
     dist.barrier()
     t.close()
     dist.destroy_process_group()

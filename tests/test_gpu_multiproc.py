@@ -12,7 +12,7 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import make_hip, make_oracle, rel_l2, synthetic_inputs
+from helpers import CG_FORMS, make_hip, make_oracle, rel_l2, synthetic_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -100,6 +100,8 @@ def test_reduction_routes_agree(tmp_path):
     a, b, c = outs
     assert (a["red"] == 1).all() and (a["vec"] == 0).all() and (a["xc"] == 1).all()
     assert (b["red"] == 2).all() and (b["vec"] == 1).all() and (b["xc"] == 0).all() and (c["red"] == 2).all() and (c["vec"] == 0).all()
+    for x, form in ((a, "team_sr"), (b, "team_vec"), (c, "team_lean")):   # every rank ran the same form of the CG iteration, the one asked for
+        assert [CG_FORMS[f] for f in x["form"]] == [form] * 3, (form, x["form"])
     for x in (a, b):
         assert int(x["n"][0]) == int(c["n"][0]) and abs(x["k"][0] - c["k"][0]) / c["k"][0] < 1e-11
         assert rel_l2(x["phi"].ravel(), c["phi"].ravel()) < 1e-9
