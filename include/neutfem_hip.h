@@ -304,6 +304,69 @@ int nf_get_mode(nf_handle h, int i, int adjoint, double *phi_host);
 int nf_block_gram(nf_handle h, int b, long n, const double *Q_dev, const double *Z_dev, double *QtZ_host, double *ZtZ_host);
 int nf_block_rotate(nf_handle h, int b, int m, long n, double *Q_dev, const double *Z_dev, const double *C_host, const double *H_host, double *res2_host);
 
+/* ---- space-time kinetics with delayed-neutron precursors (no counterpart in the reference) ----------------------------
+ * Implicit Euler in time on the discrete system of nf_solve_subcritical.  With S_g, Ms, Mf, tf(phi) = sum_g' Mf_g' phi_g' as there,
+ * W_p(e) = detJ(e) C-hat_pp the mass weight of a unit cross section (|e| at P0, no drop), velocities v_g, precursor families
+ * i = 1..I (beta_i, lambda_i, beta = sum beta_i < 1), a delayed spectrum chi_d,g (ng values, the same in every cell; NULL: the handle's
+ * Chi per cell) and the eigenvalue k0 given at begin, one step of length dt solves per group
+ *   (S_g + diag(W / (v_g dt))) phi_g^{n+1} = chi~_g tf(phi^{n+1}) / k0 + sum_{g' != g} Ms[g <- g'] phi_g'^{n+1} + q_g
+ *   q_g = W phi_g^n / (v_g dt) + chi_d,g sum_i lambda_i c_i^n / (1 + lambda_i dt),    chi~_g = chi_g - chi_d,g sum_i beta_i / (1 + lambda_i dt)
+ * and then advances c_i^{n+1} = (c_i^n + dt beta_i tf(phi^{n+1}) / k0) / (1 + lambda_i dt).  The handle's Chi is the TOTAL steady-state
+ * spectrum (the prompt part is what is left, (1 - beta) chi_p = chi - beta chi_d), so the state at begin is stationary for any chi_d.
+ * The precursors live in tf-space: one vector of n_phi doubles per family; c_i^0 = beta_i tf(phi^0) / (lambda_i k0).
+ * The left operator is the built operator of the cross sections with SigR_g + 1 / (v_g dt): a built twin of the handle (same mesh,
+ * boundary types, device copies of the cross sections), cached and rebuilt only when dt changes or the handle has been built again
+ * since (nf_info "transient_rebuilds" counts the builds).  The emission term is what k_group_rhs computes for the fixed-source solve
+ * with chi~ for chi and 1 / k0 for the fission scale, its |chi~ / k0| < 1e-14 drop at P >= 1 included. */
+#define NF_PRECURSORS_MAX 8
+typedef struct nf_kinetics {
+    int n_families;                     /* I, 0 .. NF_PRECURSORS_MAX; 0 = prompt neutrons only */
+    double beta[NF_PRECURSORS_MAX];     /* delayed fractions beta_i >= 0, sum < 1 */
+    double lambda[NF_PRECURSORS_MAX];   /* decay constants lambda_i > 0 */
+    const double *velocity_host;        /* ng neutron velocities v_g > 0 */
+    const double *chi_delayed_host;     /* ng values of the delayed spectrum, or NULL = the handle's Chi */
+} nf_kinetics;
+typedef struct nf_transient_result {
+    double time;                /* t after the call's last completed step */
+    double power;               /* P(t) / P(0) */
+    double production;          /* P(t) = sum over g, e of nuSigf_g(e) |e| phibar_g(e) (nf_subcrit_result::production) */
+    double phi_int;             /* sum over g, e of |e| phibar_g(e) */
+    double precursors;          /* the precursor population: sum over i, e of c_i[e, dof 0] */
+    double rebalance;           /* the factor f of the last outer (1 at the solution) */
+    long n_steps;               /* steps completed since begin */
+    int n_outer;                /* outers of this call, all steps */
+    int n_outer_max;            /* the most outers one step of this call took */
+    int cg_total;               /* inner iterations of this call */
+    int n_unconverged;          /* steps of this call accepted after max_outer outers */
+} nf_transient_result;
+/* Starts a transient on a BUILT handle (NF_ERR_STATE otherwise) from its current flux phi^0 and the eigenvalue keff: records
+ * P(0) (<= 0 or non-finite: NF_ERR_ARG), sets the equilibrium precursors and t = 0; a running transient is replaced.  Invalid data ->
+ * NF_ERR_ARG: a v <= 0, a lambda <= 0, a beta < 0, sum beta >= 1, n_families outside 0 .. NF_PRECURSORS_MAX, a non-finite value, keff <= 0.
+ * The transient owns a private copy of its flux (ng n_phi doubles) beside the precursors: every other solve on the handle changes the
+ * handle's current flux, never the transient's state, and the next step resumes from the transient's own flux.  It survives
+ * nf_upload_xs + nf_build on the handle -- that is how the caller perturbs the core; the next step uses the new cross sections.
+ * Undivided meshes of one process only (slab teams, multi-rank teams: NF_ERR_UNSUPPORTED before any collective). */
+int nf_transient_begin(nf_handle h, const nf_kinetics *kin, double keff);
+/* n_steps implicit-Euler steps of length dt.  Per step a source iteration from phi^n on the twin (the handle's current flux is
+ * untouched until the step completes): per outer k_fission, the Gauss-Seidel sweep of nf_solve_subcritical with the group solver
+ * nf_solve_keff picks on the twin, and one scalar rebalance -- with U the sum of the DOF-0 rows of the right-hand sides the sweep used,
+ * E the sum of the same rows of the emission + scatter terms the new iterate would produce and Q the sum of those rows of q, the iterate
+ * is scaled by f = Q / (U - E) (f = 1 where that is not finite; exactly 1 at the solution).  Without it the iteration contracts like
+ * 1 - beta per outer and is unusable (option "transient_rebalance" = 0, for measurements).  Stop test after the scaling:
+ * ||x - x_prev|| / ||x|| < tol_flux and |P - P_prev| / |P| < tol_keff; after max_outer outers the step is accepted and counted in
+ * n_unconverged.  On completion of a step the precursors advance, the new flux becomes the handle's current flux (nf_get_phi, nf_get_J,
+ * nf_project_* see time t) and the time advances; power_host (n_steps doubles, may be NULL) receives P / P(0) after every step.
+ * Reads tol_keff, tol_flux, max_outer, max_inner, solver_type, solver_type_pushed from opts; use_coarse_init, use_cmfd and
+ * use_diagonal_solver must be 0, dt > 0 (finite), n_steps >= 1, max_outer >= 1 (NF_ERR_ARG); NF_ERR_STATE without nf_transient_begin or
+ * with a handle that is not built.  A non-finite sum in any outer -> NF_ERR_NUMERIC: time, flux and precursors stay those of the last
+ * completed step (res reports them) and the handle stays usable.  The warm k-eff state and nf_get_history are untouched; nf_progress
+ * counts the outers of the call.  Deterministic.  nf_info "transient_steps": steps completed since begin. */
+int nf_transient_step(nf_handle h, const nf_keff_opts *opts, double dt, int n_steps, double *power_host, nf_transient_result *res);
+/* precursor family `family` (0-based) of the running transient in the host DOF layout of nf_get_phi, one group's length (n_phi) */
+int nf_get_precursors(nf_handle h, int family, double *c_host);
+/* ends the transient and releases the twin and the precursors (nf_destroy does the same); NF_OK without one */
+int nf_transient_end(nf_handle h);
+
 /* NeutFEM::SolveCoarse (src/NeutFEM.cpp:2380-2611): returns k_coarse and the prolonged flux
  * (ng*n_phi doubles, host) without touching the fine solution. */
 int nf_solve_coarse(nf_handle h, const nf_keff_opts *opts, double *k_coarse, double *phi_host);
@@ -418,10 +481,14 @@ int nf_time_device_copy(nf_handle h, size_t bytes, int reps, double *gbps);
  *   "c_early" (default -1): the chunked y / z pass on its table (family c with "dict") requests the vector loads of its tile ahead of the
  *   sweeps that hide them: 1 = x of both chunks in one round trip, 2 = also y of the upper chunk before that chunk's forward sweep and y of the
  *   lower chunk before the backward half, 0 = each load where it is used, -1 = the level that measurably gains.  Only loads
- *   move: the results are bit-identical at every level.  nf_apply_plan reports the level per pass as "early".
+ *   move: the results are bit-identical at every level.  nf_apply_plan reports the level per pass as "early";
+ *   "transient_rebalance" (default 1): nf_transient_step scales the iterate of every outer by the balance factor f; 0 = plain source
+ *   iteration (same fixed point, a contraction of about 1 - beta per outer: for measurements).
  * nf_info keys beyond the mesh sizes: "last_path" (0 host-driven outer loop, 1 diagonal device loop, 2 resident kernel, 3 one-XCD kernel),
  * "last_direct" (0 CG as configured, 1 dense S^-1, 2 CG to 1e-14 standing in), "line_dict_rejected" (mask of the directions whose table the
- * bit-for-bit verification refused: a fingerprint collision, not an error), "line_dict_bytes" (device memory of the tables and line ids). */
+ * bit-for-bit verification refused: a fingerprint collision, not an error), "line_dict_bytes" (device memory of the tables and line ids),
+ * "transient_steps" (steps completed since nf_transient_begin; 0 without a transient), "transient_rebuilds" (builds of the step operator
+ * since nf_transient_begin). */
 int nf_set_option(nf_handle h, const char *key, long value);
 
 /* raw device-memory helpers so callers without torch can drive the *_dev entry points */

@@ -16,6 +16,7 @@ SYMBOLS = [
     "nf_schur_apply", "nf_solve_group", "nf_build_diagonal_cache", "nf_get_diagonal_cache", "nf_solve_keff",
     "nf_upload_source", "nf_solve_subcritical", "nf_solve_modes", "nf_get_mode", "nf_block_gram", "nf_block_rotate", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_apply_plan", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_project_flux", "nf_project_power", "nf_refine", "nf_zoom_source", "nf_get_source", "nf_set_phi_adj", "nf_zoom_resolved", "nf_sensitivity", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
     "nf_get_warm_state", "nf_get_history", "nf_profile_get", "nf_profile_reset", "nf_time_schur_apply", "nf_time_device_copy", "nf_progress", "nf_set_progress_callback", "nf_local_matrices",
+    "nf_transient_begin", "nf_transient_step", "nf_get_precursors", "nf_transient_end",
     "nf_set_option", "nf_mem_info", "nf_dev_alloc", "nf_dev_free", "nf_memcpy_h2d", "nf_memcpy_d2h", "nf_synchronize", "nf_stream",
 ]
 
@@ -57,6 +58,22 @@ class ZoomResult(C.Structure):
 
 class SensResult(C.Structure):
     _fields_ = [("norm", C.c_double), ("keff", C.c_double), ("n_cells", C.c_long)]
+
+    def as_dict(self): return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+PRECURSORS_MAX = 8
+
+
+class KineticsArgs(C.Structure):
+    _fields_ = [("n_families", C.c_int), ("beta", C.c_double * PRECURSORS_MAX), ("lam", C.c_double * PRECURSORS_MAX),
+                ("velocity_host", C.POINTER(C.c_double)), ("chi_delayed_host", C.POINTER(C.c_double))]
+
+
+class TransientResult(C.Structure):
+    _fields_ = [("time", C.c_double), ("power", C.c_double), ("production", C.c_double), ("phi_int", C.c_double),
+                ("precursors", C.c_double), ("rebalance", C.c_double), ("n_steps", C.c_long),
+                ("n_outer", C.c_int), ("n_outer_max", C.c_int), ("cg_total", C.c_int), ("n_unconverged", C.c_int)]
 
     def as_dict(self): return {name: getattr(self, name) for name, _ in self._fields_}
 
@@ -111,6 +128,10 @@ def load():
     L.nf_set_phi_adj.argtypes = [vp, dp]
     L.nf_zoom_resolved.argtypes = [vp, C.POINTER(KeffOpts), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(vp), C.POINTER(ZoomResult)]
     L.nf_sensitivity.argtypes = [vp, C.c_double, vp, vp, vp, vp, vp, C.POINTER(SensResult)]
+    L.nf_transient_begin.argtypes = [vp, C.POINTER(KineticsArgs), C.c_double]
+    L.nf_transient_step.argtypes = [vp, C.POINTER(KeffOpts), C.c_double, C.c_int, dp, C.POINTER(TransientResult)]
+    L.nf_get_precursors.argtypes = [vp, C.c_int, dp]
+    L.nf_transient_end.argtypes = [vp]
     L.nf_set_phi.argtypes = [vp, dp]
     L.nf_get_phi.argtypes = [vp, dp]
     L.nf_get_J.argtypes = [vp, dp]
@@ -281,6 +302,34 @@ class HipSolver:
     def get_mode(self, i, adjoint=False):
         """mode i of the last solve_modes of that kind, (ng, n_phi) in the host DOF layout of get_phi; unit L2 norm"""
         out = np.empty(self.ng * self.n_phi); self._chk(self.L.nf_get_mode(self.h, int(i), int(adjoint), _dp(out))); return out.reshape(self.ng, self.n_phi)
+
+    def transient_begin(self, velocity, beta, lam, keff, chi_delayed=None):
+        """nf_transient_begin: a transient from the current flux and the eigenvalue keff; velocity (ng), beta / lam (one entry per
+        precursor family, at most PRECURSORS_MAX; empty = prompt neutrons only), chi_delayed (ng values, None = the handle's Chi)"""
+        v = np.ascontiguousarray(velocity, dtype=np.float64).ravel(); assert v.size == self.ng
+        b, l = (np.asarray(a, dtype=np.float64).ravel() for a in (beta, lam)); assert b.size == l.size
+        k = KineticsArgs(); k.n_families = int(b.size)
+        for i in range(min(b.size, PRECURSORS_MAX)):
+            k.beta[i], k.lam[i] = b[i], l[i]
+        k.velocity_host = _dp(v)
+        cd = None if chi_delayed is None else np.ascontiguousarray(chi_delayed, dtype=np.float64).ravel()
+        if cd is not None:
+            assert cd.size == self.ng
+            k.chi_delayed_host = _dp(cd)
+        self._chk(self.L.nf_transient_begin(self.h, C.byref(k), float(keff)))
+
+    def transient_step(self, dt, n_steps=1):
+        """nf_transient_step with the tolerances / linear solver of this object: (result dict, relative power after every step)"""
+        o = self.opts()
+        r = TransientResult(); power = np.zeros(max(int(n_steps), 1))
+        self._chk(self.L.nf_transient_step(self.h, C.byref(o), float(dt), int(n_steps), _dp(power), C.byref(r)))
+        return r.as_dict(), power
+
+    def get_precursors(self, i):
+        """precursor family i of the running transient, n_phi values in the host DOF layout of get_phi"""
+        out = np.empty(self.n_phi); self._chk(self.L.nf_get_precursors(self.h, int(i), _dp(out))); return out
+
+    def transient_end(self): self._chk(self.L.nf_transient_end(self.h))
 
     def block_gram(self, Q, Z):
         """nf_block_gram on two host blocks of shape (n, b): (Q^T Z, Z^T Z), both (b, b)"""

@@ -3,7 +3,7 @@
 //
 // The class keeps what the reference keeps on the host -- cross-section arrays, flux, tolerances,
 // BC map, warm-start flags -- and hands the hot path (BuildMatrices, SolveKeff, SolveCoarse,
-// build_diagonal_cache, SolveSubcritical, SolveModes, project_flux, project_power, zoom_resolved, sensitivity_maps) to the HIP library.  There is NO CPU fallback:
+// build_diagonal_cache, SolveSubcritical, SolveModes, step_transient, project_flux, project_power, zoom_resolved, sensitivity_maps) to the HIP library.  There is NO CPU fallback:
 // without a HIP device those methods raise RuntimeError.  The reflector methods the reference binds are accepted and ignored.
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -198,6 +198,69 @@ public:
         d["M"] = r.M; d["k_source"] = r.k_source; d["ratio"] = r.ratio; d["phi_int"] = r.phi_int; d["phi_int_nofission"] = r.phi_int_nofission;
         d["production"] = r.production; d["source"] = r.source; d["n_outer"] = r.n_outer; d["n_outer_nofission"] = r.n_outer_nofission;
         d["cg_total"] = r.cg_total; d["converged"] = r.converged;
+        return d;
+    }
+    // Space-time kinetics (extension; include/neutfem_hip.h, nf_transient_*).  begin_transient pushes the host flux mirror and
+    // starts from it with keff (default: GetLastKeff()); a perturbation is an edit of a get_SigR() .. view followed by BuildMatrices();
+    // step_transient advances n_steps implicit-Euler steps with the tolerances and the linear solver of this object, returns P / P(0) per
+    // step and pulls the new flux into the mirror (get_flux(), ExportVTK see time t).  GetLastKeff stays as it is.
+    void BeginTransient(arr_t velocity, arr_t beta, arr_t decay, py::object chi_delayed, py::object keff)
+    {
+        need_built("begin_transient");
+        if (velocity.size() != ng_) throw std::runtime_error("begin_transient: velocity needs one entry per group");
+        if (beta.size() != decay.size()) throw std::runtime_error("begin_transient: beta and decay need one entry per precursor family each");
+        if (beta.size() > NF_PRECURSORS_MAX) throw std::runtime_error("begin_transient: at most " + std::to_string(NF_PRECURSORS_MAX) + " precursor families");
+        nf_kinetics kin{};
+        kin.n_families = (int)beta.size();
+        for (int i = 0; i < kin.n_families; ++i) { kin.beta[i] = beta.data()[i]; kin.lambda[i] = decay.data()[i]; }
+        kin.velocity_host = velocity.data();
+        arr_t cd;
+        if (!chi_delayed.is_none()) {
+            cd = chi_delayed.cast<arr_t>();
+            if (cd.size() != ng_) throw std::runtime_error("begin_transient: chi_delayed needs one entry per group");
+            kin.chi_delayed_host = cd.data();
+        }
+        chk(nf_set_phi(h_, Phi_.data()));
+        chk(nf_transient_begin(h_, &kin, keff.is_none() ? last_keff_ : keff.cast<double>()));
+        transient_ = nf_transient_result{}; transient_.power = 1.0; has_transient_ = true;
+    }
+    py::array_t<double> StepTransient(double dt, int n_steps)
+    {
+        need_built("step_transient");
+        Log(VerbosityLevel::NORMAL, "\n=== CINETIQUE ESPACE-TEMPS (EULER IMPLICITE) ===");
+        nf_keff_opts o = make_opts(false, {}, false);
+        py::array_t<double> power((py::ssize_t)std::max(n_steps, 0));
+        nf_transient_result r{};
+        const int rc = nf_transient_step(h_, &o, dt, n_steps, n_steps > 0 ? power.mutable_data() : nullptr, &r);
+        if (has_transient_ && (rc == NF_OK || rc == NF_ERR_NUMERIC)) { transient_ = r; if (r.n_steps > 0 && h_) (void)nf_get_phi(h_, Phi_.data()); }
+        chk(rc);
+        if (verb_ >= VerbosityLevel::NORMAL)
+            std::cout << "  t = " << r.time << " : P/P0 = " << std::fixed << std::setprecision(8) << r.power << std::defaultfloat << "  (" << r.n_outer
+                      << " iterations externes, max " << r.n_outer_max << " par pas" << (r.n_unconverged ? ", non converge" : "") << ")" << std::endl;
+        return power;
+    }
+    py::array_t<double> GetPrecursors(int i)
+    {
+        need_built("get_precursors");
+        std::vector<double> full((size_t)nphi_);
+        chk(nf_get_precursors(h_, i, full.data()));
+        std::vector<py::ssize_t> shape;
+        if (dim_ >= 3) shape.push_back(nz_);
+        if (dim_ >= 2) shape.push_back(ny_);
+        shape.push_back(nx_);
+        py::array_t<double> out(shape);                           // DOF 0 of every cell, shaped like one group of get_flux()
+        double *po = out.mutable_data();
+        for (long e = 0; e < ne_; ++e) po[e] = full[(size_t)e * nloc_];
+        return out;
+    }
+    py::dict GetTransientInfo() const
+    {
+        if (!has_transient_) throw std::runtime_error("get_transient_info: call begin_transient() first");
+        const nf_transient_result &r = transient_;
+        py::dict d;
+        d["time"] = r.time; d["power"] = r.power; d["production"] = r.production; d["phi_int"] = r.phi_int; d["precursors"] = r.precursors;
+        d["rebalance"] = r.rebalance; d["n_steps"] = r.n_steps; d["n_outer"] = r.n_outer; d["n_outer_max"] = r.n_outer_max;
+        d["cg_total"] = r.cg_total; d["n_unconverged"] = r.n_unconverged;
         return d;
     }
     // SolveModes (extension; include/neutfem_hip.h, nf_solve_modes): the n_modes leading lambda-modes by block power iteration with the
@@ -499,6 +562,7 @@ private:
     nf_modes_result modes_[2]{}; bool has_modes_[2] = {false, false}; int last_modes_ = -1;   // the last SolveModes, direct / adjoint (get_modes_info)
     nf_zoom_result zoom_{}; bool has_zoom_ = false;               // the last zoom_resolved (get_zoom_info)
     nf_sens_result sens_{}; bool has_sens_ = false;               // the last sensitivity_maps (get_sensitivity_info)
+    nf_transient_result transient_{}; bool has_transient_ = false;   // the last step_transient (get_transient_info)
 };
 
 PYBIND11_MODULE(_neutfem_eigen, m)
@@ -589,5 +653,13 @@ PYBIND11_MODULE(_neutfem_eigen, m)
              "extension: the last zoom_resolved's nf_zoom_result as a dict (source, phi_int, production, n_outer, cg_total, converged, n_cells)")
         .def("sensitivity_maps", &NeutFEM::SensitivityMaps,
              "extension: dk/dXS per cell from the solved flux, the solved adjoint flux and GetLastKeff(): {'D', 'SigR', 'NSF', 'Chi', 'SigS'} shaped like get_D() .. get_SigS()")
-        .def("get_sensitivity_info", &NeutFEM::GetSensitivityInfo, "extension: the last sensitivity_maps' nf_sens_result as a dict (norm, keff, n_cells)");
+        .def("get_sensitivity_info", &NeutFEM::GetSensitivityInfo, "extension: the last sensitivity_maps' nf_sens_result as a dict (norm, keff, n_cells)")
+        .def("begin_transient", &NeutFEM::BeginTransient, py::arg("velocity"), py::arg("beta"), py::arg("decay"), py::arg("chi_delayed") = py::none(),
+             py::arg("keff") = py::none(),
+             "extension: start a transient from the current flux: velocity per group, beta / decay per precursor family, chi_delayed per group (None: Chi), keff (None: GetLastKeff())")
+        .def("step_transient", &NeutFEM::StepTransient, py::arg("dt"), py::arg("n_steps") = 1,
+             "extension: n_steps implicit-Euler steps of length dt; returns P / P(0) after every step; get_flux() then holds the flux at time t")
+        .def("get_precursors", &NeutFEM::GetPrecursors, py::arg("i"), "extension: precursor family i of the running transient, cell values shaped like one group of get_flux()")
+        .def("get_transient_info", &NeutFEM::GetTransientInfo,
+             "extension: the last step_transient's nf_transient_result as a dict (time, power, production, phi_int, precursors, rebalance, step and outer counts)");
 }

@@ -111,6 +111,7 @@ static int rccl_load()
 }
 
 struct nf_solver;
+struct Transient;                                                 // the running transient of a handle (nf_transient_begin), defined with its code
 struct nf_team {
     std::vector<nf_solver *> slabs;
     int device = 0;
@@ -255,6 +256,9 @@ struct nf_solver {
     bool raw_valid = false, raw_is_diag = false;
     double *d_qsrc = nullptr;                           // external source as a load vector, ng * nphi (nf_upload_source, k_source_q)
     double src_total = 0.0; bool src_any = false;       // sum of Q |e| over the slab's cells, some Q != 0
+    Transient *tr = nullptr; long build_gen = 0;        // nf_transient_begin's state; nf_build calls so far (the step operator follows them)
+    long tr_rebuilds = 0;                               // builds of the step operator since the handle was created (nf_info "transient_rebuilds")
+    int opt_tr_rebalance = 1;                           // option "transient_rebalance"
     double *d_Jz = nullptr; bool jz_valid = false;      // slabs: z currents of the last solve, ng * nJz face DOFs (nf_get_J)
     double *d_Jzb = nullptr;                            // slabs, RT1+: z bubbles of the local cells, ng * N * ni
     // CMFD (include/NeutFEM.hpp:119-143): D~ / D^ per direction (ng * faces), PCG work vectors, scalars
@@ -301,6 +305,8 @@ static void line_dict_drop(nf_solver *S)
 }
 
 static void modes_drop(nf_solver *S);
+static void transient_drop(nf_solver *S);
+static long transient_steps(const nf_solver *S);
 
 static const char *SLOT_NAMES[5] = { "schur_x", "schur_y", "schur_z", "schur_apply", "schur_z1" };
 
@@ -561,6 +567,7 @@ int nf_destroy(nf_handle S)
         return NF_OK;
     }
     coarse_cache_drop(T);
+    transient_drop(S);
     if (T && T->stream) (void)hipStreamSynchronize(T->stream);
     for (int d = 0; d < 3; ++d) { dfree(S->d_Dt[d]); dfree(S->d_Dh[d]); }
     dfree(S->d_cm); dfree(S->d_cmJ); dfree(S->d_cmsc);
@@ -705,6 +712,7 @@ long nf_info(nf_handle S, const char *key)
     K("last_cg_total", T->last_cg_total); K("coarse_outer", T->coarse_outer); K("device", S->device);
     K("last_path", T->last_path); K("last_resident_serial", T->last_resident_serial); K("last_direct", T->last_direct); K("direct_standin_unconverged", T->standin_unconverged); K("n_local_slabs", T->slabs.size()); K("n_ranks", T->nproc); K("rank", T->rank); K("vec_reduce", T->last_vec_reduce); K("cg_reductions", T->last_cg_reductions); K("cg_form", T->last_cg_form); K("endpoint_weights", T->last_endpoint_w); K("xchg_comm", T->comm_x ? 1 : 0); K("last_xcd", T->last_xcd); K("xcd_solves", T->xcd_solves); K("xcd_refused", T->xcd_refused);
     K("line_dict_rejected", S->ld_rejected); K("line_dict_bytes", S->ld_bytes);
+    K("transient_steps", transient_steps(S)); K("transient_rebuilds", S->tr_rebuilds);
 #undef K
     return -1;
 }
@@ -825,6 +833,7 @@ int nf_build(nf_handle S)
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     S->built = true; S->diag_valid = false; S->cmfd_init = false; S->cmfd_iface = false; S->dense_valid = false;   // src/NeutFEM.cpp:454-456
+    ++S->build_gen;
     S->team->linked_ready = false;
     return NF_OK;
 }
@@ -3595,6 +3604,304 @@ int nf_solve_subcritical(nf_handle S, const nf_keff_opts *o, nf_subcrit_result *
     return solve_subcritical_impl(S->team, o, res);
 }
 
+// ---- space-time kinetics (no counterpart in the reference) -------------------------------------------------------------
+// Implicit Euler on the system of nf_solve_subcritical: a step is a fixed-source solve with fission on the operator whose removal cross
+// section is shifted by 1 / (v dt) -- a built twin of the handle, made the way refine_impl makes one.  Host-driven like
+// solve_subcritical_impl, with one scalar rebalance per outer (without it the iteration contracts like 1 - beta).
+struct Transient {
+    int nfam = 0; double beta[NF_PRECURSORS_MAX], lambda[NF_PRECURSORS_MAX];
+    std::vector<double> v, chid; bool has_chid = false;          // ng velocities; ng values of the delayed spectrum (else the handle's Chi)
+    double k0 = 1.0, P0 = 0.0;
+    double time = 0.0, production = 0.0, phi_int = 0.0, precursors = 0.0, rebalance = 1.0; long n_steps = 0;   // after the last completed step
+    nf_solver *twin = nullptr; double twin_dt = 0.0; long twin_gen = -1;   // the step operator and what it was built for
+    double *d_phi = nullptr;        // the transient's own flux, ng * nphi: other solves on the handle change the handle's, not this one
+    double *d_c = nullptr;          // precursors, nfam * nphi (tf-space, device DOF order)
+    double *d_q = nullptr, *d_W = nullptr;                        // the step's source, ng * nphi; mass weights, nphi
+    double *d_part = nullptr, *d_sums = nullptr;                  // TR_ROWS rows of RED_GRID block partials; their sums (layout below)
+};
+static const int TR_ROWS = 8, TR_ROW_U = 4, TR_ROW_E = 5, TR_ROW_Q = 6;   // rows 0..3: the balance pass (the precursor pass: 0, 1)
+enum { TR_U = 0, TR_E = 1, TR_Q = 2, TR_F = 3, TR_PHI = 4, TR_P = 5, TR_NSQ = 6, TR_DSQ = 7, TR_C = 8, TR_P0 = 9, TR_NSUMS = 10 };   // d_sums: 0..7 are read back every outer
+
+static void transient_drop(nf_solver *S)
+{
+    Transient *R = S->tr;
+    if (!R) return;
+    std::string keep = g_err;
+    if (R->twin) nf_destroy(R->twin);
+    (void)hipSetDevice(S->device);
+    if (S->team && S->team->stream) (void)hipStreamSynchronize(S->team->stream);
+    dfree(R->d_phi); dfree(R->d_c); dfree(R->d_q); dfree(R->d_W); dfree(R->d_part); dfree(R->d_sums);
+    delete R; S->tr = nullptr;
+    g_err = keep;
+}
+static long transient_steps(const nf_solver *S) { return S->tr ? S->tr->n_steps : 0; }
+
+// sums of nq rows of block partials (cnt per row, stride RED_GRID) into out, on the team's stream: k_finalize as team_finalize launches it
+static void tr_finalize(nf_team *T, const double *part, int cnt, int nq, double *out)
+{
+    PartSegs ps; memset(&ps, 0, sizeof ps); ps.n = 1; ps.cnt[0] = cnt;
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(256), 0, T->stream, (int)FIN_SUM, part, ps, (long)RED_GRID, nq, T->d_cg, out, 0.0, 0, 0, T->d_red, (const double *)nullptr);
+}
+static TrGroups tr_chid(const Transient *R) { TrGroups c; memset(&c, 0, sizeof c); for (size_t g = 0; g < R->chid.size(); ++g) c.v[g] = R->chid[g]; return c; }
+
+int nf_transient_end(nf_handle S)
+{
+    if (!S) return fail(NF_ERR_ARG, "null handle");
+    transient_drop(S);
+    return NF_OK;
+}
+
+int nf_transient_begin(nf_handle S, const nf_kinetics *kin, double keff)
+{
+    if (!S || !kin) return fail(NF_ERR_ARG, "nf_transient_begin: bad arguments");
+    nf_team *T = S->team;
+    if (T->nproc > 1 || !team_is_single(T)) return fail(NF_ERR_UNSUPPORTED, "nf_transient_begin works on an undivided mesh of one process (not on slab or multi-rank teams)");
+    if (!S->built) return fail(NF_ERR_STATE, "nf_transient_begin: call nf_build first");
+    const int ng = S->ng, I = kin->n_families;
+    if (!(keff > 0.0) || !std::isfinite(keff)) return fail(NF_ERR_ARG, "nf_transient_begin: keff must be finite and > 0 (got %g)", keff);
+    if (I < 0 || I > NF_PRECURSORS_MAX) return fail(NF_ERR_ARG, "nf_transient_begin: n_families must be 0 .. %d (got %d)", NF_PRECURSORS_MAX, I);
+    if (!kin->velocity_host) return fail(NF_ERR_ARG, "nf_transient_begin: velocity_host is NULL");
+    for (int g = 0; g < ng; ++g) {
+        if (!(kin->velocity_host[g] > 0.0) || !std::isfinite(kin->velocity_host[g])) return fail(NF_ERR_ARG, "nf_transient_begin: velocity of group %d must be finite and > 0 (got %g)", g, kin->velocity_host[g]);
+        if (kin->chi_delayed_host && !std::isfinite(kin->chi_delayed_host[g])) return fail(NF_ERR_ARG, "nf_transient_begin: non-finite delayed spectrum in group %d", g);
+    }
+    double bsum = 0.0;
+    for (int i = 0; i < I; ++i) {
+        if (!(kin->beta[i] >= 0.0) || !std::isfinite(kin->beta[i])) return fail(NF_ERR_ARG, "nf_transient_begin: beta of family %d must be finite and >= 0 (got %g)", i, kin->beta[i]);
+        if (!(kin->lambda[i] > 0.0) || !std::isfinite(kin->lambda[i])) return fail(NF_ERR_ARG, "nf_transient_begin: lambda of family %d must be finite and > 0 (got %g)", i, kin->lambda[i]);
+        bsum += kin->beta[i];
+    }
+    if (!(bsum < 1.0)) return fail(NF_ERR_ARG, "nf_transient_begin: the delayed fractions sum to %g (must be < 1)", bsum);
+    HIPCHK(hipSetDevice(S->device));
+    transient_drop(S);
+    Transient *R = new Transient();
+    S->tr = R; S->tr_rebuilds = 0;
+    R->nfam = I; R->k0 = keff;
+    for (int i = 0; i < I; ++i) { R->beta[i] = kin->beta[i]; R->lambda[i] = kin->lambda[i]; }
+    R->v.assign(kin->velocity_host, kin->velocity_host + ng);
+    R->has_chid = kin->chi_delayed_host != nullptr;
+    if (R->has_chid) R->chid.assign(kin->chi_delayed_host, kin->chi_delayed_host + ng);
+    const long N = S->N, NP = S->nphi; const size_t NN = (size_t)NP * ng;
+    hipStream_t st = T->stream;
+    auto body = [&]() -> int {
+        NFCHK(dalloc(&R->d_phi, NN)); NFCHK(dalloc(&R->d_c, (size_t)NP * I)); NFCHK(dalloc(&R->d_q, NN)); NFCHK(dalloc(&R->d_W, (size_t)NP));
+        NFCHK(dalloc(&R->d_part, (size_t)TR_ROWS * RED_GRID)); NFCHK(dalloc(&R->d_sums, (size_t)TR_NSUMS));
+        HIPCHK(hipMemsetAsync(R->d_sums, 0, TR_NSUMS * sizeof(double), st));
+        HIPCHK(hipMemcpyAsync(R->d_phi, S->d_phi, NN * sizeof(double), hipMemcpyDeviceToDevice, st));
+        ChatArgs ch; ch.nloc = S->nloc;                           // C-hat_pp as nf_build forms it
+        for (int p = 0; p < S->nloc; ++p) {
+            int q = p; double c = 1.0;
+            for (int t = 0; t < S->dim; ++t) { c *= 2.0 / (2.0 * (q % S->n1) + 1.0); q /= S->n1; }
+            ch.c[p] = c;
+        }
+        hipLaunchKernelGGL(k_tr_weights, dim3(grid_for(N)), dim3(256), 0, st, R->d_W, S->d_hx, S->d_hy, S->d_hz, S->nx, S->ny, N, S->dim, ch);
+        TrFamilies fam; memset(&fam, 0, sizeof fam); fam.n = I;   // equilibrium: c_i = beta_i tf / (lambda_i k0)
+        for (int i = 0; i < I; ++i) fam.b[i] = R->beta[i] / (R->lambda[i] * keff);
+        const int gP = grid_for(NP);
+        hipLaunchKernelGGL(k_tr_precursors, dim3(gP), dim3(256), 0, st, S->d_Mf, (const double *)R->d_phi, R->d_c, N, NP, ng, fam, 1, R->d_part, (long)RED_GRID);
+        tr_finalize(T, R->d_part, gP, 2, R->d_sums + TR_C);
+        double h[2] = { 0, 0 };
+        NFCHK(readback(T, nullptr, nullptr, R->d_sums + TR_C, h, 2));
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        if (!(h[1] > 0.0) || !std::isfinite(h[1]) || !std::isfinite(h[0]))
+            return fail(NF_ERR_ARG, "nf_transient_begin: the production of the current flux, P(0) = %g, must be finite and > 0 (precursor population %g)", h[1], h[0]);
+        R->precursors = h[0]; R->P0 = R->production = h[1];
+        return NF_OK;
+    };
+    const int rc = body();
+    if (rc != NF_OK) transient_drop(S);
+    return rc;
+}
+
+// the step operator for dt: a built twin with SigR_g + 1 / (v_g dt) and chi~ in the place of Chi, kept until dt or the handle's build changes
+static int transient_twin(nf_solver *S, double dt)
+{
+    Transient *R = S->tr;
+    if (R->twin && R->twin_dt == dt && R->twin_gen == S->build_gen) return NF_OK;
+    if (R->twin) { nf_destroy(R->twin); R->twin = nullptr; }
+    const int ng = S->ng; const long N = S->N; const size_t NN = (size_t)N * ng;
+    nf_handle F = nullptr;
+    NFCHK(create_impl(S->k, S->m, ng, (int)S->xb.size(), S->xb.data(), (int)S->yb.size(), S->yb.data(), (int)S->zb.size(), S->zb.data(), 0, 0, S->device, &F));
+    auto body = [&]() -> int {
+        if (F->dim != S->dim || F->N != N || F->nphi != S->nphi) return fail(NF_ERR_ARG, "nf_transient_step: the step operator's mesh differs from the handle's");
+        for (int a = 0; a < 8; ++a) if (S->bc_set[a]) nf_set_bc(F, a, S->bc_type[a]);
+        hipStream_t st = S->team->stream;
+        NFCHK(dalloc(&F->d_D, NN)); NFCHK(dalloc(&F->d_SigR, NN)); NFCHK(dalloc(&F->d_NSF, NN)); NFCHK(dalloc(&F->d_Chi, NN));
+        HIPCHK(hipMemcpyAsync(F->d_D, S->d_D, NN * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(F->d_NSF, S->d_NSF, NN * sizeof(double), hipMemcpyDeviceToDevice, st));
+        TrGroups shift; memset(&shift, 0, sizeof shift);
+        double a = 0.0;
+        for (int g = 0; g < ng; ++g) shift.v[g] = 1.0 / (R->v[g] * dt);
+        for (int i = 0; i < R->nfam; ++i) a += R->beta[i] / (1.0 + R->lambda[i] * dt);
+        const int gN = grid_for((long)NN);
+        hipLaunchKernelGGL(k_tr_shift, dim3(gN), dim3(256), 0, st, (const double *)S->d_SigR, F->d_SigR, N, (long)NN, shift);
+        hipLaunchKernelGGL(k_tr_chi, dim3(gN), dim3(256), 0, st, (const double *)S->d_Chi, F->d_Chi, N, (long)NN, tr_chid(R), R->has_chid ? 0 : 1, a);
+        for (int b = 0; b < ng * ng; ++b)
+            if (S->d_SigS[b]) {
+                NFCHK(dalloc(&F->d_SigS[b], (size_t)N));
+                HIPCHK(hipMemcpyAsync(F->d_SigS[b], S->d_SigS[b], (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, st));
+            }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));                         // the copies ran on the handle's stream; nf_build uses the twin's
+        F->xs_uploaded = true;
+        return nf_build(F);
+    };
+    const int rc = body();
+    if (rc != NF_OK) { std::string keep = g_err; nf_destroy(F); g_err = keep; (void)hipGetLastError(); return rc; }
+    R->twin = F; R->twin_dt = dt; R->twin_gen = S->build_gen; ++S->tr_rebuilds;
+    return NF_OK;
+}
+
+// one step on the twin F: the rebalanced source iteration from the transient's flux.  hout = the sums of the last outer (d_sums 0..7)
+static int transient_iterate(nf_solver *S, nf_solver *F, const nf_keff_opts *o, const InnerPlan &ip, double dt, nf_transient_result *r,
+                             long *outers, bool *conv, double *hout)
+{
+    Transient *R = S->tr; nf_team *TT = F->team; hipStream_t st = TT->stream;
+    const int ng = S->ng; const long N = S->N, NP = S->nphi, NT = NP * ng;
+    const int gP = grid_for(NP), gC = grid_for(N), gT = grid_for(NT);
+    double *part = R->d_part, *sums = R->d_sums;
+    HIPCHK(hipMemcpyAsync(F->d_phi, R->d_phi, (size_t)NT * sizeof(double), hipMemcpyDeviceToDevice, st));
+    TrGroups ivdt; memset(&ivdt, 0, sizeof ivdt);
+    for (int g = 0; g < ng; ++g) ivdt.v[g] = 1.0 / (R->v[g] * dt);
+    TrFamilies fam; memset(&fam, 0, sizeof fam); fam.n = R->nfam;
+    for (int i = 0; i < R->nfam; ++i) fam.a[i] = R->lambda[i] / (1.0 + R->lambda[i] * dt);
+    hipLaunchKernelGGL(k_tr_source, dim3(gP), dim3(256), 0, st, (const double *)R->d_phi, (const double *)R->d_c, (const double *)R->d_W,
+                       (const double *)S->d_Chi, R->d_q, N, NP, ng, ivdt, tr_chid(R), R->has_chid ? 0 : 1, fam, part + TR_ROW_Q * RED_GRID);
+    tr_finalize(TT, part + TR_ROW_Q * RED_GRID, gP, 1, sums + TR_Q);
+    ScatterArgs sa; sa.ng = ng;
+    const double inv_k = 1.0 / R->k0;
+    double P_old = R->production;
+    int n = 0;
+    *conv = false;
+    for (int it = 0; it < o->max_outer; ++it) {
+        hipLaunchKernelGGL(k_fission, dim3(gP), dim3(256), 0, st, F->d_Mf, F->d_phi, ng, NP, F->d_tf, TT->d_partials, (const double *)nullptr, 0L);
+        for (int g = 0; g < ng; ++g) {
+            for (int gp = 0; gp < 64; ++gp) sa.M[gp] = gp < ng ? F->d_Ms[g * ng + gp] : nullptr;
+            const bool cgi = !ip.dense;                           // CG start rides in the same launch (cg_solve(..., inited))
+            hipLaunchKernelGGL(k_group_rhs<true>, dim3(gP), dim3(256), 0, st, sa, g, F->d_Chi + g * N, F->d_tf, inv_k, F->d_raw, F->d_phi,
+                               (const double *)nullptr, F->d_rhs, NP, N,
+                               cgi ? F->d_raw + g * NP : (double *)nullptr, cgi ? F->d_r : (double *)nullptr, cgi ? F->d_p : (double *)nullptr,
+                               cgi ? TT->d_partials : (double *)nullptr, (const double *)(R->d_q + g * NP));
+            hipLaunchKernelGGL(k_tr_rhs_sum, dim3(gC), dim3(256), 0, st, (const double *)F->d_rhs, N, part + TR_ROW_U * RED_GRID, g == 0 ? 1 : 0);
+            int its = 0; double cres = 0.0;
+            if (ip.dense) { dense_solve(TT, g, F->d_rhs, F->d_raw + g * NP); its = 1; }
+            else {
+                NFCHK(cg_solve(TT, g, { F->d_rhs }, { F->d_raw + g * NP }, ip.cg_tol, ip.cg_max, &its, &cres, true));
+                if (ip.direct && !(cres <= 1e-14)) ++S->team->standin_unconverged;
+            }
+            r->cg_total += its;
+        }
+        tr_finalize(TT, part + TR_ROW_U * RED_GRID, gC, 1, sums + TR_U);
+        hipLaunchKernelGGL(k_tr_emission, dim3(gC), dim3(256), 0, st, F->d_Mf, (const double *)F->d_raw, (const double *)F->d_Chi,
+                           (const double *const *)F->d_Ms_tab, inv_k, N, NP, ng, part + TR_ROW_E * RED_GRID);
+        tr_finalize(TT, part + TR_ROW_E * RED_GRID, gC, 1, sums + TR_E);
+        hipLaunchKernelGGL(k_tr_balance, dim3(gT), dim3(256), 0, st, F->d_Mf, (const double *)F->d_raw, F->d_phi, F->d_hx, F->d_hy, F->d_hz,
+                           F->nx, F->ny, N, NP, NT, sums, S->opt_tr_rebalance, part, (long)RED_GRID);
+        tr_finalize(TT, part, gT, 4, sums + TR_PHI);
+        NFCHK(readback(TT, nullptr, nullptr, sums, hout, 8));
+        n = it + 1; ++r->n_outer; ++*outers;
+        __atomic_store_n(&S->team->outers_done, *outers, __ATOMIC_RELEASE);
+        const double Phi = hout[TR_PHI], P = hout[TR_P], dphi = std::sqrt(hout[TR_DSQ] / hout[TR_NSQ]);
+        if (!std::isfinite(hout[TR_U]) || !std::isfinite(hout[TR_E]) || !std::isfinite(hout[TR_Q]) || !std::isfinite(Phi) || !std::isfinite(P) || !std::isfinite(dphi))
+            return fail(NF_ERR_NUMERIC, "nf_transient_step: the step's source iteration produced non-finite sums (step %ld, outer %d: U=%g E=%g Q=%g Phi=%g P=%g)",
+                        R->n_steps + 1, it, hout[TR_U], hout[TR_E], hout[TR_Q], Phi, P);
+        const double dq = P - P_old;
+        const double rel = dq == 0.0 ? 0.0 : std::fabs(dq) / std::fabs(P);
+        P_old = P;
+        if (rel < o->tol_keff && dphi < o->tol_flux) { *conv = true; break; }
+    }
+    r->n_outer_max = std::max(r->n_outer_max, n);
+    return NF_OK;
+}
+
+int nf_transient_step(nf_handle S, const nf_keff_opts *o, double dt, int n_steps, double *power_host, nf_transient_result *res)
+{
+    if (!S || !o) return fail(NF_ERR_ARG, "nf_transient_step: bad arguments");
+    nf_team *T = S->team;
+    if (T->nproc > 1 || !team_is_single(T)) return fail(NF_ERR_UNSUPPORTED, "nf_transient_step works on an undivided mesh of one process (not on slab or multi-rank teams)");
+    if (o->use_coarse_init || o->use_cmfd || o->use_diagonal_solver) return fail(NF_ERR_ARG, "nf_transient_step: coarse start, CMFD and the diagonal solver do not apply to a time step");
+    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(NF_ERR_ARG, "nf_transient_step: dt must be finite and > 0 (got %g)", dt);
+    if (n_steps < 1) return fail(NF_ERR_ARG, "nf_transient_step: n_steps must be at least 1 (got %d)", n_steps);
+    if (o->max_outer < 1) return fail(NF_ERR_ARG, "nf_transient_step: max_outer must be at least 1");
+    Transient *R = S->tr;
+    if (!R) return fail(NF_ERR_STATE, "nf_transient_step: call nf_transient_begin first");
+    if (!S->built) return fail(NF_ERR_STATE, "nf_transient_step: call nf_build first (the cross sections were uploaded again)");
+    HIPCHK(hipSetDevice(S->device));
+    HIPCHK(hipStreamSynchronize(T->stream));                      // the twin's stream reads what the handle's wrote
+    __atomic_store_n(&T->outers_done, 0L, __ATOMIC_RELEASE);
+    nf_transient_result r; memset(&r, 0, sizeof r);
+    auto report = [&] {
+        r.time = R->time; r.production = R->production; r.power = R->production / R->P0; r.phi_int = R->phi_int; r.precursors = R->precursors;
+        r.rebalance = R->rebalance; r.n_steps = R->n_steps;
+        if (res) *res = r;
+    };
+    const int ng = S->ng; const long N = S->N, NP = S->nphi; const size_t B = (size_t)NP * ng * sizeof(double);
+    long outers = 0;
+    auto body = [&]() -> int {
+        NFCHK(transient_twin(S, dt));
+        nf_solver *F = R->twin; nf_team *TT = F->team; hipStream_t st = TT->stream;
+        const long xcd0 = TT->xcd_solves;
+        NFCHK(team_prepare(TT));
+        const InnerPlan ip = inner_plan(TT, o);
+        T->last_direct = ip.dense ? 1 : ip.direct ? 2 : 0;
+        if (ip.dense) NFCHK(dense_prepare(TT));
+        TT->last_path = 0; TT->profile = false;
+        TrFamilies fam; memset(&fam, 0, sizeof fam); fam.n = R->nfam;   // c_i <- (c_i + dt beta_i tf / k0) / (1 + lambda_i dt)
+        for (int i = 0; i < R->nfam; ++i) { fam.a[i] = 1.0 / (1.0 + R->lambda[i] * dt); fam.b[i] = dt * R->beta[i] / (R->k0 * (1.0 + R->lambda[i] * dt)); }
+        const int gP = grid_for(NP);
+        int rc = NF_OK;
+        for (int s = 0; s < n_steps && rc == NF_OK; ++s) {
+            double hout[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }; bool conv = false;
+            if ((rc = transient_iterate(S, F, o, ip, dt, &r, &outers, &conv, hout)) != NF_OK) break;
+            // completion: precursors from tf(phi^{n+1}), the new flux becomes the transient's and the handle's, time advances
+            hipLaunchKernelGGL(k_tr_precursors, dim3(gP), dim3(256), 0, st, F->d_Mf, (const double *)F->d_phi, R->d_c, N, NP, ng, fam, 0, R->d_part, (long)RED_GRID);
+            tr_finalize(TT, R->d_part, gP, 2, R->d_sums + TR_C);
+            double hc[2] = { 0, 0 };
+            if ((rc = readback(TT, nullptr, nullptr, R->d_sums + TR_C, hc, 2)) != NF_OK) break;
+            for (double *dst : { R->d_phi, S->d_phi, S->d_raw })
+                if (hipMemcpyAsync(dst, F->d_phi, B, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = fail(NF_ERR_HIP, "nf_transient_step: copy of the new flux failed");
+            if (rc == NF_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(NF_ERR_HIP, "nf_transient_step: %s", hipGetErrorString(hipGetLastError()));
+            if (rc != NF_OK) break;
+            S->raw_valid = true; S->raw_is_diag = false; S->jz_valid = false;
+            R->time += dt; ++R->n_steps;
+            R->phi_int = hout[TR_PHI]; R->production = hout[TR_P]; R->rebalance = hout[TR_F]; R->precursors = hc[0];
+            if (!conv) ++r.n_unconverged;
+            if (power_host) power_host[s] = R->production / R->P0;
+        }
+        T->xcd_solves += TT->xcd_solves - xcd0;
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipGetLastError());
+        return rc;
+    };
+    const int rc = body();
+    if (rc != NF_OK && R->twin) {                                 // the twin may hold a half-done solve: the next step builds a fresh one
+        std::string keep = g_err; nf_destroy(R->twin); R->twin = nullptr; g_err = keep; (void)hipGetLastError();
+    }
+    report();
+    return rc;
+}
+
+int nf_get_precursors(nf_handle S, int family, double *c_host)
+{
+    if (!S || !c_host) return fail(NF_ERR_ARG, "nf_get_precursors: bad arguments");
+    Transient *R = S->tr;
+    if (!R) return fail(NF_ERR_STATE, "nf_get_precursors: call nf_transient_begin first");
+    if (family < 0 || family >= R->nfam) return fail(NF_ERR_ARG, "nf_get_precursors: family %d out of range (%d families)", family, R->nfam);
+    HIPCHK(hipSetDevice(S->device));
+    hipStream_t st = S->team->stream;
+    const double *src = R->d_c + (size_t)family * S->nphi;
+    DevTmp<double> tmp;
+    if (S->nloc > 1) {
+        NFCHK(dalloc(&tmp.p, (size_t)S->nphi));
+        hipLaunchKernelGGL(k_transpose_dofs, dim3(grid_for(S->nphi)), dim3(256), 0, st, src, tmp.p, S->N, S->nloc, 0);
+        src = tmp.p;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(c_host, src, (size_t)S->nphi * sizeof(double), hipMemcpyDeviceToHost));
+    return NF_OK;
+}
+
 // ---- SolveAdjoint (src/NeutFEM.cpp:1877-2082) -----------------------------------------------------
 // Literal control flow of the reference, including what makes it fragile (forward-ordered sweep on the transposed scatter,
 // Chebyshev from outer 5 when k is free).  Works on slab teams (collective).
@@ -4579,6 +4886,7 @@ int nf_set_option(nf_handle S, const char *key, long value)
     else if (!strcmp(key, "cg_fuse3_max_cells")) T->fuse3_max_cells = value;
     else if (!strcmp(key, "cg_lean_grid")) T->opt_lean_grid = (int)std::max(1L, std::min(1024L, value));
     else if (!strcmp(key, "sens_grid")) T->opt_sens_grid = (int)std::max(1L, std::min(65536L, value));
+    else if (!strcmp(key, "transient_rebalance")) S->opt_tr_rebalance = value != 0;
     else return fail(NF_ERR_ARG, "nf_set_option: unknown key %s", key);
     // options that move a mesh into or out of the streaming kernels: look again at the next apply (a mesh whose lines do not repeat pays the
     // fingerprints and the host sort once per build, not once per option)

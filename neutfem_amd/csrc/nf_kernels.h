@@ -2477,6 +2477,148 @@ __global__ __launch_bounds__(256) void k_subcrit_reduce(const double *__restrict
         partials[2 * stride + blockIdx.x] = sn; partials[3 * stride + blockIdx.x] = sd;
     }
 }
+
+// ---- space-time kinetics, nf_transient_step ---------------------------------------------------------------------------
+// All streaming grid-stride kernels in the style of k_subcrit_reduce: block partials in a fixed order (rows of `stride` doubles), summed
+// by k_finalize.  Vectors are SoA [g*n + p*N + e] (n = DOFs per group), per-cell arrays [g*N + e].
+struct TrGroups { double v[64]; };                               // one value per group
+struct TrFamilies { int n; double a[NF_PRECURSORS_MAX], b[NF_PRECURSORS_MAX]; };   // two coefficients per precursor family
+// SigR of the step operator: SigR_g + 1 / (v_g dt) (shift.v[g]), all groups
+__global__ __launch_bounds__(256) void k_tr_shift(const double *__restrict__ sigr, double *__restrict__ out, long N, long ntot, TrGroups shift)
+{
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < ntot; i += gridDim.x * 256L) out[i] = sigr[i] + shift.v[i / N];
+}
+// chi~_g(e) = chi_g(e) - chi_d,g(e) a: chi_d the ng values of `chid`, or chi itself (per_cell)
+__global__ __launch_bounds__(256) void k_tr_chi(const double *__restrict__ chi, double *__restrict__ out, long N, long ntot, TrGroups chid,
+                                                int per_cell, double a)
+{
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < ntot; i += gridDim.x * 256L) {
+        const double c = chi[i];
+        out[i] = c - (per_cell ? c : chid.v[i / N]) * a;
+    }
+}
+// W_p(e) = detJ(e) C-hat_pp, the mass weight of a unit cross section (|e| at P0): k_cell_coef's values for xs = 1 without its drop
+__global__ __launch_bounds__(256) void k_tr_weights(double *__restrict__ W, const double *__restrict__ hx, const double *__restrict__ hy,
+                                                    const double *__restrict__ hz, int nx, int ny, long N, int dim, ChatArgs ch)
+{
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < N; e += gridDim.x * 256L) {
+        const int ix = (int)(e % nx); const long r = e / nx; const int iy = (int)(r % ny); const int iz = (int)(r / ny);
+        if (ch.nloc == 1) { W[e] = hx[ix] * hy[iy] * hz[iz]; continue; }
+        double detJ = hx[ix] / 2.0;
+        if (dim >= 2) detJ *= hy[iy] / 2.0;
+        if (dim == 3) detJ *= hz[iz] / 2.0;
+        for (int p = 0; p < ch.nloc; ++p) W[(long)p * N + e] = detJ * ch.c[p];
+    }
+}
+// step source of all groups in one pass: q_g = W phi_g ivdt_g + chi_d,g sum_i fam.a[i] c_i with fam.a[i] = lambda_i / (1 + lambda_i dt),
+// ivdt_g = 1 / (v_g dt); chi_d as in k_tr_chi.  Row 0 of the partials: Q = the sum of q over the DOF-0 rows (j < N) of all groups
+__global__ __launch_bounds__(256) void k_tr_source(const double *__restrict__ phi, const double *__restrict__ c, const double *__restrict__ W,
+                                                   const double *__restrict__ chi, double *__restrict__ q, long N, long n, int ng,
+                                                   TrGroups ivdt, TrGroups chid, int per_cell, TrFamilies fam, double *__restrict__ partials)
+{
+    __shared__ double sred[4];
+    double sq = 0.0;
+    for (long j = blockIdx.x * 256L + threadIdx.x; j < n; j += gridDim.x * 256L) {
+        double d = 0.0;
+        for (int i = 0; i < fam.n; ++i) d += fam.a[i] * c[i * n + j];
+        const double w = W[j]; const long e = j % N;
+        for (int g = 0; g < ng; ++g) {
+            const double v = w * phi[g * n + j] * ivdt.v[g] + (per_cell ? chi[g * N + e] : chid.v[g]) * d;
+            q[g * n + j] = v;
+            if (j < N) sq += v;
+        }
+    }
+    sq = block_sum(sq, sred);
+    if (threadIdx.x == 0) partials[blockIdx.x] = sq;
+}
+// U of the rebalance: the sum of the DOF-0 rows of the right-hand side the group solve is about to use (its first N entries), added to
+// the partial of the groups before it (first = 1: the row starts here).  k_group_rhs itself stays as it is.
+__global__ __launch_bounds__(256) void k_tr_rhs_sum(const double *__restrict__ rhs, long N, double *__restrict__ partials, int first)
+{
+    __shared__ double sred[4];
+    double s = 0.0;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < N; i += gridDim.x * 256L) s += rhs[i];
+    s = block_sum(s, sred);
+    if (threadIdx.x == 0) partials[blockIdx.x] = first ? s : partials[blockIdx.x] + s;
+}
+// E of the rebalance: what the DOF-0 rows of k_group_rhs<true> would hold for the NEW iterate y without q, summed over all groups -- tf as
+// k_fission forms it, the emission and the scatter terms by k_group_rhs's own expressions and drop rule (a mismatch would move the fixed
+// point of the iteration).  Ms: the ng*ng device pointers [g*ng + gp] (nullptr: empty block).
+__global__ __launch_bounds__(256) void k_tr_emission(const double *__restrict__ Mf, const double *__restrict__ y, const double *__restrict__ chi,
+                                                     const double *const *__restrict__ Ms, double inv_k, long N, long n, int ng,
+                                                     double *__restrict__ partials)
+{
+    __shared__ double sred[4];
+    double se = 0.0;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < N; i += gridDim.x * 256L) {
+        double tf = 0.0;
+        for (int g = 0; g < ng; ++g) tf += Mf[g * n + i] * y[g * n + i];
+        for (int g = 0; g < ng; ++g) {
+            double v;
+            if (n == N) v = inv_k * (chi[g * N + i] * tf);
+            else { const double cv = chi[g * N + i] * inv_k; v = fabs(cv) < 1e-14 ? 0.0 : cv * tf; }
+            for (int gp = 0; gp < ng; ++gp) {
+                const double *M = Ms[g * ng + gp];
+                if (gp == g || !M) continue;
+                v += M[i] * y[gp * n + i];
+            }
+            se += v;
+        }
+    }
+    se = block_sum(se, sred);
+    if (threadIdx.x == 0) partials[blockIdx.x] = se;
+}
+// the balance pass, once per outer over all groups: x = f y with f = Q / (U - E) from sums = { U, E, Q } (f = 1 where that is not finite,
+// U = E, or rebalance = 0), old <- x, and the block partials of Phi, P, ||x||^2, ||x - old||^2 (rows 0..3, as k_subcrit_reduce).  Every
+// thread forms the same f; block 0 stores it in sums[3].
+__global__ __launch_bounds__(256) void k_tr_balance(const double *__restrict__ Mf, const double *__restrict__ y, double *__restrict__ old,
+                                                    const double *__restrict__ hx, const double *__restrict__ hy, const double *__restrict__ hz,
+                                                    int nx, int ny, long N, long n, long ntot, double *sums, int rebalance,
+                                                    double *__restrict__ partials, long stride)
+{
+    __shared__ double sred[4];
+    double f = 1.0;
+    if (rebalance) {
+        const double U = sums[0], E = sums[1], Q = sums[2];
+        const double t = Q / (U - E);
+        if (U != E && (t - t) == 0.0) f = t;
+    }
+    double sf = 0.0, sp = 0.0, sn = 0.0, sd = 0.0;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < ntot; i += gridDim.x * 256L) {
+        const double v = f * y[i], d = v - old[i];
+        sn += v * v; sd += d * d;
+        old[i] = v;
+        const long j = i - (i / n) * n;
+        if (j < N) { sf += cell_measure(hx, hy, hz, nx, ny, j) * v; sp += Mf[i] * v; }
+    }
+    sf = block_sum(sf, sred); sp = block_sum(sp, sred); sn = block_sum(sn, sred); sd = block_sum(sd, sred);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = sf; partials[stride + blockIdx.x] = sp;
+        partials[2 * stride + blockIdx.x] = sn; partials[3 * stride + blockIdx.x] = sd;
+        if (blockIdx.x == 0) sums[3] = f;
+    }
+}
+// all precursor families in one pass, tf = sum_g Mf_g phi_g formed on the fly: c_i <- fam.a[i] c_i + fam.b[i] tf (a step: a = 1 / (1 +
+// lambda_i dt), b = dt beta_i / (k0 (1 + lambda_i dt)); init = 1, the equilibrium at begin: c_i = fam.b[i] tf, c is not read).
+// Row 0 of the partials: the precursor population, the sum of the DOF-0 rows of all c_i; row 1: P = the sum of the DOF-0 rows of tf.
+__global__ __launch_bounds__(256) void k_tr_precursors(const double *__restrict__ Mf, const double *__restrict__ phi, double *__restrict__ c,
+                                                       long N, long n, int ng, TrFamilies fam, int init, double *__restrict__ partials, long stride)
+{
+    __shared__ double sred[4];
+    double sc = 0.0, sp = 0.0;
+    for (long j = blockIdx.x * 256L + threadIdx.x; j < n; j += gridDim.x * 256L) {
+        double tf = 0.0;
+        for (int g = 0; g < ng; ++g) tf += Mf[g * n + j] * phi[g * n + j];
+        if (j < N) sp += tf;
+        for (int i = 0; i < fam.n; ++i) {
+            const double v = init ? fam.b[i] * tf : fam.a[i] * c[i * n + j] + fam.b[i] * tf;
+            c[i * n + j] = v;
+            if (j < N) sc += v;
+        }
+    }
+    sc = block_sum(sc, sred); sp = block_sum(sp, sred);
+    if (threadIdx.x == 0) { partials[blockIdx.x] = sc; partials[stride + blockIdx.x] = sp; }
+}
 // phi /= norm, then ChebyshevAccel::operator() (src/solvers.cpp:720-756).  mode 0: no acceleration,
 // 1: store phi0, 2: phi1 = phi0 + a1 (phi - phi0), 3: three-term.  cur <- result.
 __global__ __launch_bounds__(256) void k_normalize_cheb(const double *__restrict__ raw, double *__restrict__ cur,
