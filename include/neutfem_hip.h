@@ -74,7 +74,7 @@ int nf_comm_selftest(nf_handle h);
 int nf_team_schur_apply(nf_handle h, int g, const double *const *x_dev, double *const *y_dev);
 
 /* sizes: "dim","nx","ny","nz","ne","ng","n_phi","n_J","n_loc","last_outer","last_cg_total",
- * "coarse_outer","device","n_local_slabs","n_ranks","rank","cg_reductions" (cross-rank reductions per CG iteration of the last CG solve on a
+ * "coarse_outer","device","void_cells","n_local_slabs","n_ranks","rank","cg_reductions" (cross-rank reductions per CG iteration of the last CG solve on a
  * team: 1 single-reduction CG, 2 reference recurrence, 0 undivided mesh),"vec_reduce","xchg_comm","cg_form" (the form of the CG iteration the last CG solve ran -- after a refused one-XCD start
  * the form it continued with -- as an index into xcd, fuse3, lean, fused, classic, team_lean, team_vec, team_sr: the names nf_apply_plan
  * reports as "form") ; returns -1 for an unknown key */
@@ -83,6 +83,32 @@ long nf_info(nf_handle h, const char *key);
 /* NeutFEM::SetBC (src/NeutFEM.cpp:337-345): attr per BoundaryID (include/NeutFEM.hpp:73-91).
  * Only DIRICHLET changes the operator (src/NeutFEM.cpp:1328-1456); the rest is natural/ignored. */
 int nf_set_bc(nf_handle h, int attr, int bc_type);
+
+/* ---- cut-out cells with a vacuum (albedo) condition (no counterpart in the reference) ---------------------------------
+ * Cells marked void are cut out of the domain, and every face a kept cell shares with a void one carries J.n = gamma phi, n pointing
+ * out of the kept cell (ANL-7416: gamma = 0.4692 on the stepped outline of the core).  In the built operator a void cell adds nothing
+ * to A and B; a kept|void face gets A_ff += I_f(a) / gamma, I_f(a) the face integral of the Dirichlet term with the area of the kept
+ * cell's face; every current DOF no kept cell touches (void|void faces, natural domain faces and bubbles of void cells) gets the identity;
+ * a Dirichlet domain face of a void cell keeps its 2 D I term (it is decoupled).  C keeps the void cells (SigR as uploaded), while nuSigf,
+ * chi and every scatter block count as zero there whatever was uploaded; D and SigR of void cells must still pass nf_upload_xs's checks.
+ * The flux is exactly zero in void cells, and so are their bubble currents.  Domain faces keep their meaning: NF_BC_DIRICHLET gets the
+ * reference's term, every other type is natural -- a vacuum condition on a domain face is posed with one plane of void cells outside it.
+ * mask_host: N bytes in cell order, non-zero = void; NULL removes the mask (gamma is then ignored); a mask without a set byte is the
+ * same as NULL.  The call takes effect at the next nf_build and marks the handle un-built (solves return NF_ERR_STATE until then); it
+ * drops the coarse cache, the tables of distinct lines, the dense S^-1 and the modes, as nf_upload_xs does.  nf_info "void_cells" = the
+ * number of void cells (0: no mask).  Errors: gamma non-finite or <= 0, or every cell void -> NF_ERR_ARG; a slab (nf_create_slab, linked
+ * or multi-rank) -> NF_ERR_UNSUPPORTED.
+ * With a mask: nf_build, nf_schur_apply (y = C x in void cells), nf_solve_group (the right-hand side is taken as 0 in void cells),
+ * nf_solve_keff, nf_solve_adjoint, nf_get_phi / nf_get_phi_adj / nf_get_J, nf_set_phi, nf_project_flux / nf_project_power, history, timers
+ * and plan reports work.  The CG runs the forms fuse3, lean, fused or classic, never xcd, and the in-kernel paths (resident, one-XCD,
+ * diagonal device loop) are not taken: nf_info "last_path" is 0; a direct solver type runs CG to 1e-14 ("last_direct" 2), never the dense
+ * S^-1.  NF_ERR_UNSUPPORTED (the text names nf_set_void; before any launch) with a mask for the calls that form A_ff themselves or build
+ * a twin handle without the mask -- nf_solve_keff / nf_solve_adjoint with use_diagonal_solver (RT0-P0), use_cmfd or use_coarse_init,
+ * nf_build_diagonal_cache, nf_initialize_cmfd, nf_solve_coarse, nf_coarsen, nf_refine, nf_zoom_source, nf_zoom_resolved, nf_sensitivity,
+ * nf_transient_begin / nf_transient_step -- and for nf_solve_subcritical and nf_solve_modes. */
+int nf_set_void(nf_handle h, const unsigned char *mask_host, double gamma);
+/* the mask (N bytes, 0 / 1; may be NULL) and gamma (may be NULL) as set; NF_ERR_STATE without a mask */
+int nf_get_void(nf_handle h, unsigned char *mask_host, double *gamma);
 
 /* Public XS members D_data_, SigR_data_, NSF_data_, Chi_data_, SigS_data_
  * (include/NeutFEM.hpp:373-388) -> device.  Host arrays in the reference layouts. */

@@ -12,7 +12,7 @@ from . import lib_path
 
 SYMBOLS = [
     "nf_last_error", "nf_device_count", "nf_create", "nf_destroy", "nf_create_slab", "nf_link_slabs", "nf_comm_unique_id",
-    "nf_comm_init", "nf_comm_info", "nf_comm_selftest", "nf_team_schur_apply", "nf_info", "nf_set_bc", "nf_upload_xs", "nf_build",
+    "nf_comm_init", "nf_comm_info", "nf_comm_selftest", "nf_team_schur_apply", "nf_info", "nf_set_bc", "nf_set_void", "nf_get_void", "nf_upload_xs", "nf_build",
     "nf_schur_apply", "nf_solve_group", "nf_build_diagonal_cache", "nf_get_diagonal_cache", "nf_solve_keff",
     "nf_upload_source", "nf_solve_subcritical", "nf_solve_modes", "nf_get_mode", "nf_block_gram", "nf_block_rotate", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_apply_plan", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_project_flux", "nf_project_power", "nf_refine", "nf_zoom_source", "nf_get_source", "nf_set_phi_adj", "nf_zoom_resolved", "nf_sensitivity", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
     "nf_get_warm_state", "nf_get_history", "nf_profile_get", "nf_profile_reset", "nf_time_schur_apply", "nf_time_device_copy", "nf_progress", "nf_set_progress_callback", "nf_local_matrices",
@@ -104,6 +104,8 @@ def load():
     L.nf_info.restype = C.c_long
     L.nf_info.argtypes = [vp, C.c_char_p]
     L.nf_set_bc.argtypes = [vp, C.c_int, C.c_int]
+    L.nf_set_void.argtypes = [vp, C.POINTER(C.c_ubyte), C.c_double]
+    L.nf_get_void.argtypes = [vp, C.POINTER(C.c_ubyte), dp]
     L.nf_upload_xs.argtypes = [vp, dp, dp, dp, dp, dp]
     L.nf_build.argtypes = [vp]
     L.nf_schur_apply.argtypes = [vp, C.c_int, vp, vp]
@@ -234,6 +236,20 @@ class HipSolver:
     def set_bc(self, attr, bctype): self._chk(self.L.nf_set_bc(self.h, int(attr), int(bctype)))
     def set_tol(self, tk, tf, tl, mo, mi): self.tol = (tk, tf, tl, mo, mi)
     def set_linear_solver(self, t): self.solver_type, self.solver_pushed = int(t), 1
+
+    def set_void(self, mask, gamma=0.0):
+        """nf_set_void: cells with a non-zero mask entry (any shape of ne entries, any integer or bool dtype) are cut out of the domain,
+        J.n = gamma phi on every face a kept cell shares with one; None removes the mask.  Takes effect at the next build()"""
+        if mask is None:
+            self._chk(self.L.nf_set_void(self.h, None, float(gamma))); return
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).ravel(); assert m.size == self.ne
+        self._chk(self.L.nf_set_void(self.h, m.ctypes.data_as(C.POINTER(C.c_ubyte)), float(gamma)))
+
+    def get_void(self):
+        """(mask as ne bytes, gamma) as set through set_void; RuntimeError without a mask"""
+        m, g = np.empty(self.ne, dtype=np.uint8), C.c_double()
+        self._chk(self.L.nf_get_void(self.h, m.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(g)))
+        return m, g.value
 
     def upload_xs(self, D, SigR, NSF, Chi, SigS):
         arrs = [np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (D, SigR, NSF, Chi, SigS)]

@@ -3,7 +3,7 @@
 //
 // The class keeps what the reference keeps on the host -- cross-section arrays, flux, tolerances,
 // BC map, warm-start flags -- and hands the hot path (BuildMatrices, SolveKeff, SolveCoarse,
-// build_diagonal_cache, SolveSubcritical, SolveModes, step_transient, project_flux, project_power, zoom_resolved, sensitivity_maps) to the HIP library.  There is NO CPU fallback:
+// build_diagonal_cache, SolveSubcritical, SolveModes, step_transient, set_void (handed over at BuildMatrices), project_flux, project_power, zoom_resolved, sensitivity_maps) to the HIP library.  There is NO CPU fallback:
 // without a HIP device those methods raise RuntimeError.  The reflector methods the reference binds are accepted and ignored.
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -108,12 +108,48 @@ public:
         int i = (int)solver_; return i >= 0 && i < 10 ? n[i] : "Unknown";
     }
 
+    // Cut-out cells (extension; include/neutfem_hip.h, nf_set_void): cells with a non-zero mask entry leave the domain and
+    // every face a kept cell shares with one carries J.n = gamma phi.  mask is shaped like one group of get_D(), any integer or bool
+    // dtype.  Kept on the object and handed to the handle at BuildMatrices(), the way the boundary types are.
+    std::vector<py::ssize_t> cell_shape() const
+    {
+        std::vector<py::ssize_t> shape;
+        if (dim_ >= 3) shape.push_back(nz_);
+        if (dim_ >= 2) shape.push_back(ny_);
+        shape.push_back(nx_);
+        return shape;
+    }
+    void SetVoid(py::array mask, double gamma)
+    {
+        const std::vector<py::ssize_t> shape = cell_shape();
+        bool ok = mask.ndim() == (py::ssize_t)shape.size();
+        for (size_t i = 0; ok && i < shape.size(); ++i) ok = mask.shape((py::ssize_t)i) == shape[i];
+        if (!ok) throw std::invalid_argument("set_void: the mask must be shaped like one group of get_D()");
+        if (!std::isfinite(gamma) || !(gamma > 0.0)) throw std::invalid_argument("set_void: gamma must be finite and positive");
+        auto nz = py::array_t<bool, py::array::c_style | py::array::forcecast>::ensure(py::module_::import("numpy").attr("not_equal")(mask, 0));
+        if (!nz) throw std::invalid_argument("set_void: the mask must be an integer or bool array");
+        std::vector<unsigned char> v((size_t)ne_);
+        long cnt = 0;
+        for (long e = 0; e < ne_; ++e) { v[e] = nz.data()[e] ? 1 : 0; cnt += v[e]; }
+        if (cnt == ne_) throw std::invalid_argument("set_void: every cell is void");
+        void_.swap(v); void_gamma_ = gamma;
+    }
+    void ClearVoid() { void_.clear(); void_gamma_ = 0.0; }
+    py::object GetVoid() const
+    {
+        if (void_.empty()) return py::none();
+        py::array_t<bool> m(cell_shape());
+        for (long e = 0; e < ne_; ++e) m.mutable_data()[e] = void_[e] != 0;
+        return py::make_tuple(m, void_gamma_);
+    }
+
     // ---- hot path ---------------------------------------------------------------------------------
     void BuildMatrices()
     {
         Log(VerbosityLevel::NORMAL, "Assemblage des matrices...");
         ensure_handle();
         for (auto &kv : bc_types_) if (kv.first >= 0 && kv.first < 8) chk(nf_set_bc(h_, kv.first, (int)kv.second));
+        if (!void_.empty() || void_on_handle_) { chk(nf_set_void(h_, void_.empty() ? nullptr : void_.data(), void_gamma_)); void_on_handle_ = !void_.empty(); }
         chk(nf_upload_xs(h_, D_.data(), SigR_.data(), NSF_.data(), Chi_.data(), SigS_.data()));
         chk(nf_build(h_));
         Log(VerbosityLevel::NORMAL, "  Assemblage termine (coefficients + factorisation par lignes sur GPU)");
@@ -553,6 +589,7 @@ private:
     }
 
     nf_handle h_ = nullptr;
+    std::vector<unsigned char> void_; double void_gamma_ = 0.0; bool void_on_handle_ = false;   // set_void: the mask (empty = none), on the handle since the last BuildMatrices
     std::map<int, BCType> bc_types_; std::map<int, double> bc_values_; std::map<int, std::pair<double, double>> robin_;
     LinearSolverType solver_ = LinearSolverType::BICGSTAB; bool solver_pushed_ = false;   // src/NeutFEM.cpp:126 vs solvers.cpp:68
     double tol_keff_ = 1e-5, tol_flux_ = 1e-5, tol_L2_ = 1e-5; int max_outer_ = 200, max_inner_ = 1000;
@@ -633,6 +670,10 @@ PYBIND11_MODULE(_neutfem_eigen, m)
         .def("get_flux", [](NeutFEM &s) { return s.flux(s.Phi_, s.fluxP0_); })
         .def("get_flux_adj", [](NeutFEM &s) { return s.flux(s.PhiAdj_, s.fluxAdjP0_); })
         .def("get_current", &NeutFEM::GetCurrent, "extension: Sol_J_ as a flat (ng*n_J) array in the reference DOF order")
+        .def("set_void", &NeutFEM::SetVoid, py::arg("mask"), py::arg("gamma"),
+             "extension: cut the cells with a non-zero mask entry (shaped like one group of get_D()) out of the domain, J.n = gamma phi on their faces to kept cells; takes effect at BuildMatrices()")
+        .def("clear_void", &NeutFEM::ClearVoid, "extension: remove the set_void mask; takes effect at BuildMatrices()")
+        .def("get_void", &NeutFEM::GetVoid, "extension: (mask as a bool array shaped like one group of get_D(), gamma) as set through set_void, None without a mask")
         .def("get_bc_map", &NeutFEM::GetBCMap, "extension: {attr: BCType value} as set through set_bc")
         .def("get_subcritical_info", &NeutFEM::GetSubcriticalInfo,
              "extension: the last SolveSubcritical's nf_subcrit_result as a dict (M, k_source, ratio, integrals, outer counts, converged)")

@@ -226,6 +226,8 @@ struct nf_solver {
     double *d_D = nullptr, *d_SigR = nullptr, *d_NSF = nullptr, *d_Chi = nullptr;
     std::vector<double *> d_SigS;          // ng*ng blocks [g_to*ng+g_from], nullptr when all |s| <= 1e-14
     bool xs_uploaded = false, built = false, diag_valid = false;
+    // nf_set_void: cells cut out of the domain (device bytes, nullptr = no mask; the host copy for nf_get_void), J.n = void_gamma phi on kept|void faces
+    unsigned char *d_void = nullptr; std::vector<unsigned char> void_host; double void_gamma = 0.0; long void_cells = 0;
     // operators
     double *d_Cd = nullptr, *d_Mf = nullptr, *d_Mchi = nullptr;   // ng*nphi diagonals: C, fission, chi-weighted mass (adjoint)
     double *d_phi_adj = nullptr;                        // adjoint flux, ng*nphi (allocated by the first adjoint solve)
@@ -306,6 +308,21 @@ static void line_dict_drop(nf_solver *S)
 
 static void modes_drop(nf_solver *S);
 static void transient_drop(nf_solver *S);
+static bool team_is_single(const nf_team *T);
+
+// nf_set_void.  The vector kernels of the CG come in two instantiations: launch(std::true_type, mask) on a masked handle, else
+// launch(std::false_type, {}) -- the code without a mask.
+template <class F> static void with_void(const nf_solver *S, F &&launch)
+{
+    if (S->d_void) launch(std::true_type{}, VoidMask{ S->d_void, S->N }); else launch(std::false_type{}, VoidMask{ nullptr, 0 });
+}
+// The calls that form A_ff themselves or build a twin handle that would not carry the mask, and the solves whose exact twins know no mask
+static int void_refuse(const nf_solver *S, const char *who)
+{
+    if (S) for (const nf_solver *X : S->team->slabs) if (X->d_void)
+        return fail(NF_ERR_UNSUPPORTED, "%s: not supported on a handle with cut-out cells (nf_set_void); remove the mask with nf_set_void(h, NULL, 0) and build again", who);
+    return NF_OK;
+}
 static long transient_steps(const nf_solver *S);
 
 static const char *SLOT_NAMES[5] = { "schur_x", "schur_y", "schur_z", "schur_apply", "schur_z1" };
@@ -572,7 +589,7 @@ int nf_destroy(nf_handle S)
     for (int d = 0; d < 3; ++d) { dfree(S->d_Dt[d]); dfree(S->d_Dh[d]); }
     dfree(S->d_cm); dfree(S->d_cmJ); dfree(S->d_cmsc);
     dfree(S->d_hx); dfree(S->d_hy); dfree(S->d_hz); dfree(S->d_xb); dfree(S->d_yb); dfree(S->d_zb);
-    dfree(S->d_D); dfree(S->d_SigR); dfree(S->d_NSF); dfree(S->d_Chi);
+    dfree(S->d_D); dfree(S->d_SigR); dfree(S->d_NSF); dfree(S->d_Chi); dfree(S->d_void);
     for (auto &p : S->d_SigS) dfree(p);
     for (auto &p : S->d_Ms) dfree(p);
     dfree(S->d_Ms_tab);
@@ -711,6 +728,7 @@ long nf_info(nf_handle S, const char *key)
     K("n_phi", S->nphi); K("n_J", S->nJ); K("n_loc", S->nloc); K("rt_order", S->k); K("p_order", S->m); K("last_outer", T->last_outer);
     K("last_cg_total", T->last_cg_total); K("coarse_outer", T->coarse_outer); K("device", S->device);
     K("last_path", T->last_path); K("last_resident_serial", T->last_resident_serial); K("last_direct", T->last_direct); K("direct_standin_unconverged", T->standin_unconverged); K("n_local_slabs", T->slabs.size()); K("n_ranks", T->nproc); K("rank", T->rank); K("vec_reduce", T->last_vec_reduce); K("cg_reductions", T->last_cg_reductions); K("cg_form", T->last_cg_form); K("endpoint_weights", T->last_endpoint_w); K("xchg_comm", T->comm_x ? 1 : 0); K("last_xcd", T->last_xcd); K("xcd_solves", T->xcd_solves); K("xcd_refused", T->xcd_refused);
+    K("void_cells", S->void_cells);
     K("line_dict_rejected", S->ld_rejected); K("line_dict_bytes", S->ld_bytes);
     K("transient_steps", transient_steps(S)); K("transient_rebuilds", S->tr_rebuilds);
 #undef K
@@ -722,6 +740,41 @@ int nf_set_bc(nf_handle S, int attr, int bc_type)
     if (!S || attr < 0 || attr >= 8) return fail(NF_ERR_ARG, "nf_set_bc: bad attribute %d", attr);
     S->bc_set[attr] = 1; S->bc_type[attr] = bc_type; S->dense_valid = false;
     coarse_cache_drop(S->team); line_dict_drop(S);
+    return NF_OK;
+}
+
+int nf_set_void(nf_handle S, const unsigned char *mask, double gamma)
+{
+    if (!S) return fail(NF_ERR_ARG, "nf_set_void: null handle");
+    if (S->if_lo || S->if_hi || !team_is_single(S->team)) return fail(NF_ERR_UNSUPPORTED, "nf_set_void: slabs and slab teams know no cut-out cells (undivided meshes only)");
+    long cnt = 0;
+    if (mask) {
+        if (!std::isfinite(gamma) || !(gamma > 0.0)) return fail(NF_ERR_ARG, "nf_set_void: gamma must be finite and positive (got %g)", gamma);
+        for (long e = 0; e < S->N; ++e) cnt += mask[e] != 0;
+        if (cnt == S->N) return fail(NF_ERR_ARG, "nf_set_void: every cell is void");
+    }
+    HIPCHK(hipSetDevice(S->device));
+    hipStream_t st = S->team->stream;
+    // the operator, and whatever was derived from it, is stale until the next nf_build (as after nf_upload_xs)
+    S->built = false; S->diag_valid = false; S->cmfd_init = false; S->cmfd_iface = false; S->dense_valid = false;
+    coarse_cache_drop(S->team); line_dict_drop(S); modes_drop(S);
+    HIPCHK(hipStreamSynchronize(st));
+    dfree(S->d_void); S->void_host.clear(); S->void_cells = 0; S->void_gamma = 0.0;
+    if (cnt == 0) return NF_OK;                                   // a mask without a set byte is no mask
+    S->void_host.resize((size_t)S->N);
+    for (long e = 0; e < S->N; ++e) S->void_host[e] = mask[e] ? 1 : 0;
+    NFCHK(dalloc(&S->d_void, (size_t)S->N));
+    HIPCHK(hipMemcpyAsync(S->d_void, S->void_host.data(), (size_t)S->N, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    S->void_cells = cnt; S->void_gamma = gamma;
+    return NF_OK;
+}
+int nf_get_void(nf_handle S, unsigned char *mask, double *gamma)
+{
+    if (!S) return fail(NF_ERR_ARG, "nf_get_void: null handle");
+    if (!S->d_void) return fail(NF_ERR_STATE, "nf_get_void: no mask is set (nf_set_void)");
+    if (mask) memcpy(mask, S->void_host.data(), (size_t)S->N);
+    if (gamma) *gamma = S->void_gamma;
     return NF_OK;
 }
 
@@ -778,6 +831,7 @@ int nf_build(nf_handle S)
 {
     if (!S) return fail(NF_ERR_ARG, "nf_build: null handle");
     if (!S->xs_uploaded) return fail(NF_ERR_STATE, "nf_build: call nf_upload_xs first");
+    if (S->d_void && !team_is_single(S->team)) return fail(NF_ERR_UNSUPPORTED, "nf_build: a slab team knows no cut-out cells (nf_set_void)");
     HIPCHK(hipSetDevice(S->device));
     coarse_cache_drop(S->team); line_dict_drop(S); modes_drop(S);
     hipStream_t st = S->team->stream;
@@ -800,15 +854,17 @@ int nf_build(nf_handle S)
     }
     Geom G = make_geom(S);
     const int gN = grid_for(N, 256, 65535);
+    const unsigned char *vmask = S->d_void;
     for (int g = 0; g < ng; ++g) {
         hipLaunchKernelGGL(k_cell_coef, dim3(gN), dim3(256), 0, st, S->d_SigR + g * N, S->d_Cd + g * NP, S->d_hx, S->d_hy, S->d_hz, S->nx, S->ny, N, 0, S->dim, ch);
-        hipLaunchKernelGGL(k_cell_coef, dim3(gN), dim3(256), 0, st, S->d_NSF + g * N, S->d_Mf + g * NP, S->d_hx, S->d_hy, S->d_hz, S->nx, S->ny, N, 1, S->dim, ch);
-        hipLaunchKernelGGL(k_cell_coef, dim3(gN), dim3(256), 0, st, S->d_Chi + g * N, S->d_Mchi + g * NP, S->d_hx, S->d_hy, S->d_hz, S->nx, S->ny, N, 2, S->dim, ch);   // M_chi (:432-439)
+        // nf_set_void: the flux is zero in the void cells, so Mf, M_chi and Ms are zero there whatever was uploaded; C keeps them
+        hipLaunchKernelGGL(k_cell_coef, dim3(gN), dim3(256), 0, st, S->d_NSF + g * N, S->d_Mf + g * NP, S->d_hx, S->d_hy, S->d_hz, S->nx, S->ny, N, 1, S->dim, ch, vmask);
+        hipLaunchKernelGGL(k_cell_coef, dim3(gN), dim3(256), 0, st, S->d_Chi + g * N, S->d_Mchi + g * NP, S->d_hx, S->d_hy, S->d_hz, S->nx, S->ny, N, 2, S->dim, ch, vmask);   // M_chi (:432-439)
         for (int gp = 0; gp < ng; ++gp) {
             const int i = g * ng + gp;
             if (!S->d_SigS[i]) { dfree(S->d_Ms[i]); continue; }
             NFCHK(dalloc(&S->d_Ms[i], NP));
-            hipLaunchKernelGGL(k_cell_coef, dim3(gN), dim3(256), 0, st, S->d_SigS[i], S->d_Ms[i], S->d_hx, S->d_hy, S->d_hz, S->nx, S->ny, N, 1, S->dim, ch);
+            hipLaunchKernelGGL(k_cell_coef, dim3(gN), dim3(256), 0, st, S->d_SigS[i], S->d_Ms[i], S->d_hx, S->d_hy, S->d_hz, S->nx, S->ny, N, 1, S->dim, ch, vmask);
         }
         for (int d = 0; d < S->dim; ++d) {
             const long nl = S->nlines[d];
@@ -818,8 +874,10 @@ int nf_build(nf_handle S)
                 lo = S->if_lo; hi = S->if_hi;
                 so.alo = S->d_alo + g * nl; so.ahi = S->d_ahi + g * nl; so.hlo = S->d_hlo + g * nl; so.hhi = S->d_hhi + g * nl; so.gfl = S->d_gfl + g * nl;
             }
-            hipLaunchKernelGGL(k_factor_lines, dim3((unsigned)((nl + 63) / 64)), dim3(64), 0, st, G, d, S->d_D + g * N,
-                               S->d_L[d] + g * N, S->d_DR[d] + g * N, S->d_D0[d] + g * nl, nl, lo, hi, so);
+            if (vmask) hipLaunchKernelGGL(k_factor_lines<true>, dim3((unsigned)((nl + 63) / 64)), dim3(64), 0, st, G, d, S->d_D + g * N,
+                                          S->d_L[d] + g * N, S->d_DR[d] + g * N, S->d_D0[d] + g * nl, nl, lo, hi, so, VoidArgs{ vmask, 1.0 / S->void_gamma });
+            else hipLaunchKernelGGL(k_factor_lines<false>, dim3((unsigned)((nl + 63) / 64)), dim3(64), 0, st, G, d, S->d_D + g * N,
+                                    S->d_L[d] + g * N, S->d_DR[d] + g * N, S->d_D0[d] + g * nl, nl, lo, hi, so, VoidArgs{ nullptr, 0.0 });
         }
     }
     {
@@ -1733,6 +1791,8 @@ int nf_schur_apply(nf_handle S, int g, const double *x_dev, double *y_dev)
     HIPCHK(hipSetDevice(S->device));
     NFCHK(line_dict_prepare(T));                                 // an undivided mesh needs nothing else of team_prepare
     NFCHK(team_schur_apply(T, g, { x_dev }, { y_dev }, false, ApplyCg()));
+    // nf_set_void: the passes know no mask; the void cells' own entries are set to what the masked operator gives there, C x
+    if (S->d_void) hipLaunchKernelGGL(k_void_apply_fix, dim3(grid_for(S->nphi)), dim3(256), 0, T->stream, x_dev, y_dev, (const double *)(S->d_Cd + (size_t)g * S->nphi), S->nphi, VoidMask{ S->d_void, S->N });
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(T->stream));
     if (T->profile) prof_collect(T);
@@ -1838,7 +1898,7 @@ static int launch_apply3(nf_solver *S, int g, const Fuse3Plan &P, const double *
 // CgScalars hold the outcome of FIN_RHS, r = p = rhs, x = 0.  One launch; the kernel publishes the final scalars to the host itself.
 static bool xcd_eligible(const nf_team *T, const nf_solver *S, const Fuse3Plan &P)
 {
-    if (!T->opt_cgx || !P.ok || T->profile) return false;
+    if (!T->opt_cgx || !P.ok || T->profile || S->d_void) return false;   // nf_set_void: the one-launch kernels keep their CG vectors to themselves and know no mask
     if (S->nb == 0 ? (S->nloc != 1 || n_modes(S) != 1) : (P.seg != 4 || n_modes(S) > 9 || S->nb > 2)) return false;   // P0 flux: one unknown per cell; bubble moments: the SEG = 4 tiles
     if (S->nphi < T->xcd_min_cells || S->nphi > T->xcd_max_cells) return false;                                      // the window counts unknowns per group
     for (int r = 0; r < 2; ++r) if (S->dim >= r + 2 && (P.A.NSEG[r] >= 64 || P.A.TX[r] * P.A.NSEG[r] > 448)) return false;   // no wavefront scan in the packed tiles; a tile fits beside the other roles
@@ -2064,8 +2124,9 @@ static int cg_step_fuse3(CgRun &R, int index)
     if (prof) prof_begin(T, 3, &ta, &tb);
     const int rc = launch_apply3(S0, R.g, R.P.f3, pin, pout, R.x[0], cg_apply_args(R, index).lean);
     if (prof) (void)hipEventRecord(tb, T->stream);
-    hipLaunchKernelGGL(k_cg_rupdate3, dim3(R.P.gru), dim3(256), 0, T->stream, S0->d_r, (const double *)S0->d_q, (const double *)(S0->dim >= 2 ? S0->d_qy : nullptr),
-                       (const double *)(S0->dim == 3 ? S0->d_qz : nullptr), S0->nphi, T->d_cg, R.row1(), CgLean{ T->d_cg, T->d_partials, R.P.f3.nblocks, index & 1, 0 });
+    with_void(S0, [&](auto M, VoidMask vm) {
+        hipLaunchKernelGGL(k_cg_rupdate3<decltype(M)::value>, dim3(R.P.gru), dim3(256), 0, T->stream, S0->d_r, (const double *)S0->d_q, (const double *)(S0->dim >= 2 ? S0->d_qy : nullptr),
+                           (const double *)(S0->dim == 3 ? S0->d_qz : nullptr), S0->nphi, T->d_cg, R.row1(), CgLean{ T->d_cg, T->d_partials, R.P.f3.nblocks, index & 1, 0 }, vm); });
     return rc;
 }
 // every other form: q = S p with the form's CG state; on a poisoned rank, what the apply owes its neighbours instead
@@ -2101,28 +2162,29 @@ static int cg_step_team_vec(CgRun &R, int index)                   // the partia
     auto allred = [&](double *send, double *recv, int cnt) -> int { NCCLCHK(g_rccl.AllReduce(send, recv, (size_t)cnt + 1, NCCL_DOUBLE, NCCL_SUM, T->comm, T->stream)); return NF_OK; };
     if (!T->poisoned && R.acnt[0] != T->vec_cnt_pq) NFCHK(R.chk(fail(NF_ERR_STATE, "vector reduce: the accumulation pass left %d partials, %d were agreed", R.acnt[0], T->vec_cnt_pq)));
     NFCHK(R.chk(allred(send_pq, vec_pq, T->vec_cnt_pq)));
-    R.each_slab([&](nf_solver *S, int i) { hipLaunchKernelGGL(k_cg_rupdate, dim3(R.gcnt[i]), dim3(256), 0, T->stream, S->d_r, S->d_q, S->nphi, T->d_cg, send_rr, CgLean{ T->d_cg, vec_pq, T->vec_cnt_pq, index & 1, 0, T->vec_cnt_pq }); });
+    R.each_slab([&](nf_solver *S, int i) { hipLaunchKernelGGL(k_cg_rupdate<false>, dim3(R.gcnt[i]), dim3(256), 0, T->stream, S->d_r, S->d_q, S->nphi, T->d_cg, send_rr, CgLean{ T->d_cg, vec_pq, T->vec_cnt_pq, index & 1, 0, T->vec_cnt_pq }, VoidMask{ nullptr, 0 }); });
     return R.chk(allred(send_rr, R.vec_rr(), T->vec_cnt_rr));
 }
 static int cg_step_team_lean(CgRun &R, int index)
 {
     nf_team *T = R.T;
     NFCHK(R.chk(team_reduce(T, R.acnt, T->d_red)));               // d_red[0] = p.q, d_red[1] = error flags
-    R.each_slab([&](nf_solver *S, int i) { hipLaunchKernelGGL(k_cg_rupdate, dim3(R.gcnt[i]), dim3(256), 0, T->stream, S->d_r, S->d_q, S->nphi, T->d_cg, T->d_partials + i * T->slab_cap, CgLean{ T->d_cg, T->d_red, -1, index & 1, 0 }); });
+    R.each_slab([&](nf_solver *S, int i) { hipLaunchKernelGGL(k_cg_rupdate<false>, dim3(R.gcnt[i]), dim3(256), 0, T->stream, S->d_r, S->d_q, S->nphi, T->d_cg, T->d_partials + i * T->slab_cap, CgLean{ T->d_cg, T->d_red, -1, index & 1, 0 }, VoidMask{ nullptr, 0 }); });
     return R.chk(team_reduce(T, R.gcnt, T->d_red + 2));           // d_red[2] = |r|^2, d_red[3] = error flags
 }
 static int cg_step_lean(CgRun &R, int index)
 {
-    R.each_slab([&](nf_solver *S, int) { hipLaunchKernelGGL(k_cg_rupdate, dim3(R.P.gru), dim3(256), 0, R.T->stream, S->d_r, S->d_q, S->nphi, R.T->d_cg, R.row1(), CgLean{ R.T->d_cg, R.T->d_partials, R.acnt[0], index & 1, 0 }); });
+    R.each_slab([&](nf_solver *S, int) { with_void(S, [&](auto M, VoidMask vm) {
+        hipLaunchKernelGGL(k_cg_rupdate<decltype(M)::value>, dim3(R.P.gru), dim3(256), 0, R.T->stream, S->d_r, S->d_q, S->nphi, R.T->d_cg, R.row1(), CgLean{ R.T->d_cg, R.T->d_partials, R.acnt[0], index & 1, 0 }, vm); }); });
     return NF_OK;
 }
 static int cg_step_scalar(CgRun &R, int)                           // fused, classic: the scalars behind k_finalize
 {
     nf_team *T = R.T; const bool fused = R.form == CG_FUSED;
     NFCHK(R.chk(team_finalize(T, FIN_PAP, R.acnt, 1, T->d_out, 0.0, 0)));
-    R.each_slab([&](nf_solver *S, int i) {
-        if (fused) hipLaunchKernelGGL(k_cg_rupdate, dim3(R.gcnt[i]), dim3(256), 0, T->stream, S->d_r, S->d_q, S->nphi, T->d_cg, T->d_partials + i * T->slab_cap, CgLean{});
-        else hipLaunchKernelGGL(k_cg_update, dim3(R.gcnt[i]), dim3(256), 0, T->stream, R.x[i], S->d_r, S->d_p, S->d_q, S->nphi, T->d_cg, T->d_partials + i * T->slab_cap); });
+    R.each_slab([&](nf_solver *S, int i) { with_void(S, [&](auto M, VoidMask vm) {
+        if (fused) hipLaunchKernelGGL(k_cg_rupdate<decltype(M)::value>, dim3(R.gcnt[i]), dim3(256), 0, T->stream, S->d_r, S->d_q, S->nphi, T->d_cg, T->d_partials + i * T->slab_cap, CgLean{}, vm);
+        else hipLaunchKernelGGL(k_cg_update<decltype(M)::value>, dim3(R.gcnt[i]), dim3(256), 0, T->stream, R.x[i], S->d_r, S->d_p, S->d_q, S->nphi, T->d_cg, T->d_partials + i * T->slab_cap, vm); }); });
     NFCHK(R.chk(team_finalize(T, FIN_RR, R.gcnt, 1, T->d_out, 0.0, 0)));
     if (!fused) R.each_slab([&](nf_solver *S, int i) { hipLaunchKernelGGL(k_cg_pupdate, dim3(R.gcnt[i]), dim3(256), 0, T->stream, S->d_p, S->d_r, S->nphi, T->d_cg); });
     return NF_OK;
@@ -2166,7 +2228,8 @@ static int cg_solve(nf_team *T, int g, const std::vector<const double *> &rhs, c
     const CgPlan P = cg_plan(T);
     CgRun R{ T, g, P, P.form, x };
     R.ps.resize(ns); R.qs.resize(ns); R.gcnt.resize(ns); R.acnt.resize(ns); R.cnt3.assign(ns, 0);
-    auto init = [&] { for (int i = 0; i < ns; ++i) hipLaunchKernelGGL(k_cg_init, dim3(R.gcnt[i]), dim3(256), 0, T->stream, rhs[i], x[i], T->slabs[i]->d_r, T->slabs[i]->d_p, T->slabs[i]->nphi, T->d_partials + i * T->slab_cap); };
+    auto init = [&] { for (int i = 0; i < ns; ++i) with_void(T->slabs[i], [&](auto M, VoidMask vm) {
+        hipLaunchKernelGGL(k_cg_init<decltype(M)::value>, dim3(R.gcnt[i]), dim3(256), 0, T->stream, rhs[i], x[i], T->slabs[i]->d_r, T->slabs[i]->d_p, T->slabs[i]->nphi, T->d_partials + i * T->slab_cap, vm); }); };
     for (int i = 0; i < ns; ++i) { nf_solver *S = T->slabs[i]; R.gcnt[i] = grid_for(S->nphi); R.ps[i] = S->d_p; R.qs[i] = S->d_q; R.any_if |= S->if_lo || S->if_hi; }
     if (!inited) init();
     NFCHK(team_finalize(T, FIN_RHS, R.gcnt, 1, T->d_out, tol, maxit));
@@ -2245,6 +2308,7 @@ int nf_build_diagonal_cache(nf_handle S)
     if (!S) return fail(NF_ERR_ARG, "null handle");
     nf_team *T = S->team;
     for (auto *X : T->slabs) if (!X->built) return fail(NF_ERR_STATE, "nf_build_diagonal_cache: call nf_build first");
+    NFCHK(void_refuse(S, "nf_build_diagonal_cache"));
     if (S->k != 0 || S->m != 0) return NF_OK;                     // "non applicable (ordre > 0)", src/NeutFEM.cpp:484-487
     bool valid = true, any_if = false;
     for (auto *X : T->slabs) { valid &= X->diag_valid; any_if |= X->if_lo || X->if_hi; }
@@ -2434,7 +2498,7 @@ static int flux_to_J(nf_solver *S, int g, const double *field_g, double *dJ, int
             for (int t = 0; t < S->dim; ++t) { if (t == d) continue; amode += (q % S->n1) * mul; q /= S->n1; mul *= S->k + 1; }
             hipLaunchKernelGGL(k_flux_to_J, dim3((unsigned)((S->nlines[d] + 63) / 64)), dim3(64), 0, st, G, ma, S->nb, amode, nfa, ni,
                                S->d_D + g * N, S->d_L[d] + g * N, S->d_DR[d] + g * N, S->d_D0[d] + g * S->nlines[d],
-                               dJ + foff[d], dJ + nJface + (long)d * N * ni, S->nlines[d], diag);
+                               dJ + foff[d], dJ + nJface + (long)d * N * ni, S->nlines[d], diag, (const unsigned char *)S->d_void);
         }
     return NF_OK;
 }
@@ -2625,6 +2689,7 @@ static int coarse_init(nf_team *T, const nf_keff_opts *o, double *k_coarse, cons
 int nf_solve_coarse(nf_handle S, const nf_keff_opts *o, double *k_coarse, double *phi_host)
 {
     if (!S || !o || !k_coarse || !phi_host) return fail(NF_ERR_ARG, "nf_solve_coarse: bad arguments");
+    NFCHK(void_refuse(S, "nf_solve_coarse"));
     if (!S->built) return fail(NF_ERR_STATE, "nf_solve_coarse: call nf_build first");
     if (!team_is_single(S->team)) return fail(NF_ERR_UNSUPPORTED, "coarse-mesh initialisation is not available on a slab-decomposed mesh");
     HIPCHK(hipSetDevice(S->device));
@@ -2668,6 +2733,7 @@ int nf_initialize_cmfd(nf_handle S)
 {
     if (!S) return fail(NF_ERR_ARG, "null handle");
     if (!S->built) return fail(NF_ERR_STATE, "nf_initialize_cmfd: call nf_build first");
+    NFCHK(void_refuse(S, "nf_initialize_cmfd"));
     HIPCHK(hipSetDevice(S->device));
     for (auto *X : S->team->slabs) if (!X->built) return fail(NF_ERR_STATE, "nf_initialize_cmfd: every slab of the team must be built first");
     NFCHK(cmfd_initialize_team(S->team));                        // collective on a multi-rank team (interface D-tilde)
@@ -2869,6 +2935,7 @@ static int cmfd_step_team(nf_team *T, double keff, int use_diag)
 int nf_coarsen(nf_handle S, int rx, int ry, int rz, nf_handle *coarse)
 {
     if (!S || !coarse || rx < 1 || ry < 1 || rz < 1) return fail(NF_ERR_ARG, "nf_coarsen: bad arguments");
+    NFCHK(void_refuse(S, "nf_coarsen"));
     if (!S->xs_uploaded) return fail(NF_ERR_STATE, "nf_coarsen: call nf_upload_xs first");
     if (!team_is_single(S->team)) return fail(NF_ERR_UNSUPPORTED, "nf_coarsen works on an undivided mesh (slab teams coarsen inside nf_solve_keff)");
     if (S->dim < 2) ry = 1;
@@ -3199,7 +3266,7 @@ static InnerPlan inner_plan(const nf_team *T, const nf_keff_opts *o)
     long Ntot = 0; for (auto *S : T->slabs) Ntot += S->nphi;
     InnerPlan p;
     p.direct = !o->solver_type_pushed || o->solver_type <= 2 || (single && Ntot < 200);
-    p.dense = p.direct && single && !T->rccl_reduce && Ntot <= T->direct_max_dofs;
+    p.dense = p.direct && single && !T->rccl_reduce && Ntot <= T->direct_max_dofs && !T->slabs[0]->d_void;   // nf_set_void: the dense S^-1 is formed without the mask; CG to 1e-14 stands in
     p.cg_tol = p.direct ? 1e-14 : o->tol_flux;                    // SetTolerance forwards tol_flux (:334)
     p.cg_max = p.direct ? (int)std::min<long>(20 * Ntot + 50, 200000L) : o->max_inner;   // CG ends in <= n steps in exact arithmetic
     return p;
@@ -3251,7 +3318,7 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
     T->last_path = 0;
     {
         ResidentArgs probe;
-        if (single && !use_diag && !use_cmfd && !direct && !T->rccl_reduce && T->opt_resident && o->max_outer > 0 &&
+        if (single && !use_diag && !use_cmfd && !direct && !T->rccl_reduce && T->opt_resident && o->max_outer > 0 && !S0->d_void &&   // nf_set_void: the resident kernel knows no mask
             ((S0->nphi <= T->resident_max_dofs && resident_plan(S0, &probe)) || (S0->nphi <= T->resident_serial_max_dofs && resident_serial_fits(T, S0)))) {
             const bool prof_req = T->profile;
             T->last_path = 2; T->profile = false;
@@ -3388,6 +3455,7 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
 int nf_solve_keff(nf_handle S, const nf_keff_opts *o, double *keff, int *n_outer)
 {
     if (!S || !o) return fail(NF_ERR_ARG, "nf_solve_keff: bad arguments");
+    if ((o->use_diagonal_solver && S->k == 0 && S->m == 0) || o->use_cmfd || o->use_coarse_init) NFCHK(void_refuse(S, "nf_solve_keff with use_diagonal_solver, use_cmfd or use_coarse_init"));
     if (S->team->dead) return fail(NF_ERR_COMM, "this team lost a collective (NF_ERR_COMM) and is unusable: destroy the handles and end the process with a non-zero code (never re-exec)");
     for (auto *X : S->team->slabs) if (!X->built) return fail(NF_ERR_STATE, "nf_solve_keff: call nf_build first");
     HIPCHK(hipSetDevice(S->device));
@@ -3597,6 +3665,7 @@ static int solve_subcritical_impl(nf_team *T, const nf_keff_opts *o, nf_subcrit_
 int nf_solve_subcritical(nf_handle S, const nf_keff_opts *o, nf_subcrit_result *res)
 {
     if (!S || !o) return fail(NF_ERR_ARG, "nf_solve_subcritical: bad arguments");
+    NFCHK(void_refuse(S, "nf_solve_subcritical"));
     if (S->team->dead) return fail(NF_ERR_COMM, "this team lost a collective (NF_ERR_COMM) and is unusable: destroy the handles and end the process with a non-zero code (never re-exec)");
     for (auto *X : S->team->slabs) if (!X->built) return fail(NF_ERR_STATE, "nf_solve_subcritical: call nf_build first");
     HIPCHK(hipSetDevice(S->device));
@@ -3654,6 +3723,7 @@ int nf_transient_end(nf_handle S)
 int nf_transient_begin(nf_handle S, const nf_kinetics *kin, double keff)
 {
     if (!S || !kin) return fail(NF_ERR_ARG, "nf_transient_begin: bad arguments");
+    NFCHK(void_refuse(S, "nf_transient_begin"));
     nf_team *T = S->team;
     if (T->nproc > 1 || !team_is_single(T)) return fail(NF_ERR_UNSUPPORTED, "nf_transient_begin works on an undivided mesh of one process (not on slab or multi-rank teams)");
     if (!S->built) return fail(NF_ERR_STATE, "nf_transient_begin: call nf_build first");
@@ -3818,6 +3888,7 @@ static int transient_iterate(nf_solver *S, nf_solver *F, const nf_keff_opts *o, 
 int nf_transient_step(nf_handle S, const nf_keff_opts *o, double dt, int n_steps, double *power_host, nf_transient_result *res)
 {
     if (!S || !o) return fail(NF_ERR_ARG, "nf_transient_step: bad arguments");
+    NFCHK(void_refuse(S, "nf_transient_step"));
     nf_team *T = S->team;
     if (T->nproc > 1 || !team_is_single(T)) return fail(NF_ERR_UNSUPPORTED, "nf_transient_step works on an undivided mesh of one process (not on slab or multi-rank teams)");
     if (o->use_coarse_init || o->use_cmfd || o->use_diagonal_solver) return fail(NF_ERR_ARG, "nf_transient_step: coarse start, CMFD and the diagonal solver do not apply to a time step");
@@ -3908,6 +3979,7 @@ int nf_get_precursors(nf_handle S, int family, double *c_host)
 int nf_solve_adjoint(nf_handle S, const nf_keff_opts *o, int normalize_to_direct, int use_direct_keff, double *keff_adj, int *n_outer)
 {
     if (!S || !o) return fail(NF_ERR_ARG, "nf_solve_adjoint: bad arguments");
+    if ((o->use_diagonal_solver && S->k == 0 && S->m == 0) || o->use_cmfd || o->use_coarse_init) NFCHK(void_refuse(S, "nf_solve_adjoint with use_diagonal_solver, use_cmfd or use_coarse_init"));
     if (S->team->dead) return fail(NF_ERR_COMM, "this team lost a collective (NF_ERR_COMM) and is unusable: destroy the handles and end the process with a non-zero code (never re-exec)");
     nf_team *T = S->team;
     for (auto *X : T->slabs) if (!X->built) return fail(NF_ERR_STATE, "nf_solve_adjoint: call nf_build first");
@@ -3920,8 +3992,8 @@ int nf_solve_adjoint(nf_handle S, const nf_keff_opts *o, int normalize_to_direct
     double keff = 1.0;
     if (use_direct_keff && T->has_valid_keff) keff = T->last_keff;          // :1885-1889
     // global number of flux DOFs (the start vector is 1 / ||1||, :1891-1892): local sum, all-reduced on a multi-rank team
-    double ntot = 0.0; long NPtot = 0;
-    for (auto *X : T->slabs) { ntot += (double)X->nphi * ng; NPtot += X->nphi; }
+    double ntot = 0.0;
+    for (auto *X : T->slabs) ntot += (double)X->nphi * ng;
     if (T->rccl_reduce && T->nproc > 1) {
         HIPCHK(hipMemcpyAsync(T->d_red, &ntot, sizeof(double), hipMemcpyHostToDevice, st));
         NCCLCHK(g_rccl.AllReduce(T->d_red, T->d_red, 1, NCCL_DOUBLE, NCCL_SUM, T->comm, st));
@@ -3940,10 +4012,10 @@ int nf_solve_adjoint(nf_handle S, const nf_keff_opts *o, int normalize_to_direct
         NFCHK(dalloc(&nsft[i].p, (size_t)X->N));
         hipLaunchKernelGGL(k_sum_groups, dim3(grid_for(X->N)), dim3(256), 0, st, X->d_NSF, nsft[i].p, X->N, ng);    // :1898-1905
     }
-    const bool direct = !o->solver_type_pushed || o->solver_type <= 2 || (team_is_single(T) && NPtot < 200);
-    const bool dense = direct && team_is_single(T) && !T->rccl_reduce && NPtot <= T->direct_max_dofs;   // S is symmetric: the same S^-1
-    const double cg_tol = direct ? 1e-14 : o->tol_flux;
-    const int cg_max = direct ? (int)std::min<long>(20 * NPtot + 50, 200000L) : o->max_inner;
+    const InnerPlan ip = inner_plan(T, o);                       // S is symmetric: the same group solver, the same S^-1
+    const bool dense = ip.dense;
+    const double cg_tol = ip.cg_tol;
+    const int cg_max = ip.cg_max;
     if (dense) NFCHK(dense_prepare(T));
     const int nmax = CHEB_NMAX; const double sigma = CHEB_SIGMA;
     double ca[16], cbv[16];
@@ -4208,6 +4280,7 @@ int nf_refine(nf_handle S, int rx, int ry, int rz, nf_handle *fine)
 {
     if (!S || !fine) return fail(NF_ERR_ARG, "nf_refine: bad arguments");
     *fine = nullptr;
+    NFCHK(void_refuse(S, "nf_refine"));
     NFCHK(refine_args(S, rx, ry, rz, "nf_refine"));
     if (!team_is_single(S->team)) return fail(NF_ERR_UNSUPPORTED, "nf_refine works on an undivided mesh (not on the slabs of a team)");
     if (!S->xs_uploaded) return fail(NF_ERR_STATE, "nf_refine: call nf_upload_xs first");
@@ -4231,6 +4304,7 @@ static void launch_zoom_d(int m, const RefinePlan &P, hipStream_t st, const doub
 int nf_zoom_source(nf_handle C, nf_handle F, int adjoint, double keff)
 {
     if (!C || !F || C == F) return fail(NF_ERR_ARG, "nf_zoom_source: bad arguments");
+    NFCHK(void_refuse(C, "nf_zoom_source")); NFCHK(void_refuse(F, "nf_zoom_source"));
     if (!team_is_single(C->team) || !team_is_single(F->team)) return fail(NF_ERR_UNSUPPORTED, "nf_zoom_source works on undivided meshes (not on the slabs of a team)");
     if (C->device != F->device || C->ng != F->ng || C->dim != F->dim || C->k != F->k || C->m != F->m ||
         F->nx % C->nx || F->ny % C->ny || F->nz % C->nz)
@@ -4307,6 +4381,7 @@ int nf_zoom_resolved(nf_handle S, const nf_keff_opts *o, int rx, int ry, int rz,
 {
     if (!S || !o || !fine) return fail(NF_ERR_ARG, "nf_zoom_resolved: bad arguments");
     *fine = nullptr;
+    NFCHK(void_refuse(S, "nf_zoom_resolved"));
     if (o->use_coarse_init || o->use_cmfd || o->use_diagonal_solver)
         return fail(NF_ERR_ARG, "nf_zoom_resolved: coarse start, CMFD and the diagonal solver do not apply to the zoom's fixed-source iteration");
     if (o->max_outer < 1) return fail(NF_ERR_ARG, "nf_zoom_resolved: max_outer must be at least 1");
@@ -4352,6 +4427,7 @@ static void launch_sens_current_d(const nf_solver *S, int grid, hipStream_t st, 
 int nf_sensitivity(nf_handle S, double keff, double *dD, double *dSigR, double *dNSF, double *dChi, double *dSigS, nf_sens_result *res)
 {
     if (!S) return fail(NF_ERR_ARG, "nf_sensitivity: bad arguments");
+    NFCHK(void_refuse(S, "nf_sensitivity"));
     if (!std::isfinite(keff) || !(keff > 0.0)) return fail(NF_ERR_ARG, "nf_sensitivity: keff must be finite and positive (got %g)", keff);
     if (!team_is_single(S->team)) return fail(NF_ERR_UNSUPPORTED, "nf_sensitivity works on an undivided mesh (the z currents cross slabs: slab teams and multi-rank teams are not supported)");
     if (S->N > 0xFFFFFFFFL) return fail(NF_ERR_UNSUPPORTED, "nf_sensitivity: %ld cells (the kernels index cells with 32 bits)", S->N);
@@ -4630,6 +4706,7 @@ static int solve_modes_impl(nf_solver *S, const nf_keff_opts *o, int m, int b, i
 int nf_solve_modes(nf_handle S, const nf_keff_opts *o, int n_modes, int n_guard, int adjoint, nf_modes_result *res)
 {
     if (!S || !o) return fail(NF_ERR_ARG, "nf_solve_modes: bad arguments");
+    NFCHK(void_refuse(S, "nf_solve_modes"));
     nf_team *T = S->team;
     if (T->dead) return fail(NF_ERR_COMM, "this team lost a collective (NF_ERR_COMM) and is unusable: destroy the handles and end the process with a non-zero code (never re-exec)");
     if (n_modes < 1 || n_guard < 0 || n_modes + n_guard > NF_MODES_MAX)

@@ -416,11 +416,12 @@ __global__ void k_cg1_logic(Cg1 c, HostPub *hp, unsigned long long seq)
 struct ChatArgs { int nloc; double c[27]; };
 __global__ void k_cell_coef(const double *__restrict__ xs, double *__restrict__ out, const double *__restrict__ hx,
                             const double *__restrict__ hy, const double *__restrict__ hz, int nx, int ny, long N,
-                            int mode, int dim, ChatArgs ch)
+                            int mode, int dim, ChatArgs ch, const unsigned char *__restrict__ voidm = nullptr)
 {
+    // voidm (nf_set_void; fission, chi and scatter matrices only): the cross section of a void cell counts as zero, whatever was uploaded
     for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < N; e += (long)gridDim.x * blockDim.x) {
         const int ix = (int)(e % nx); const long r = e / nx; const int iy = (int)(r % ny); const int iz = (int)(r / ny);
-        const double s = xs[e];
+        const double s = voidm && voidm[e] ? 0.0 : xs[e];
         if (ch.nloc == 1 && mode != 2) {
             const double V = hx[ix] * hy[iy] * hz[iz];
             double v = s * V;
@@ -528,9 +529,28 @@ __device__ __forceinline__ ModeArgs select_mode(ModeArgs ma, const ModeTab &mt, 
 // hlo/hhi = this slab's half of the separator diagonal, a2_edge - a1_edge^2 (T_II^-1)[end,end].
 // gfl = a1_lo a1_hi (T_II^-1)[first,last] measures the separator-to-separator coupling through the slab.
 struct SlabOut { double *alo, *ahi, *hlo, *hhi, *gfl; };
+// Cut-out cells (nf_set_void): voidm = one byte per cell, non-zero = void; inv_gamma = 1 / gamma of J.n = gamma phi on every face a kept
+// cell shares with a void one.  A void cell adds nothing to the chain (cell_a gives (0, 0)), a kept|void face adds I_f / gamma to its
+// diagonal -- I_f = dirichlet_term / (2 D) in the unit transverse scaling, with the area of the kept cell's face -- and a diagonal no kept
+// cell and no Dirichlet term touches becomes 1 (identity row: void|void faces, natural domain faces of void cells).  A Dirichlet domain face
+// of a void cell keeps its 2 D I term; it is decoupled (L = 0 on both sides of a void cell).  MASK = false is the code without any of this.
+struct VoidArgs { const unsigned char *voidm; double inv_gamma; };
+// The same mask for the vector kernels of the CG (DOF order [p][e]: the cell of entry i is i % ncell).  The direction passes know no mask:
+// on a vector that is zero in the void cells B^T x is what the masked B gives and the line solves decouple by the factors, so only the
+// void cells' own entries of S x come out wrong -- and p.q never sees them while p is zero there.  It is enough that r stays zero in the
+// void cells (then p = r + beta p and x do): the MASK = true instantiations of the residual updates write 0 there and keep it out of |r|^2.
+struct VoidMask { const unsigned char *m; long ncell; };
+__device__ __forceinline__ bool void_entry(const VoidMask &vm, long i, long n) { return vm.m[n == vm.ncell ? i : i % vm.ncell] != 0; }
+// y = Cd x in the void cells: what a plain Schur apply (nf_schur_apply) owes the caller there (C keeps the void cells; 0 for an x that vanishes there)
+__global__ void k_void_apply_fix(const double *__restrict__ x, double *__restrict__ y, const double *__restrict__ Cd, long n, VoidMask vm)
+{
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L)
+        if (void_entry(vm, i, n)) y[i] = Cd[i] * x[i];
+}
+template <bool MASK>
 __global__ void k_factor_lines(Geom G, int d, const double *__restrict__ D, double *__restrict__ L,
                                double *__restrict__ DR, double *__restrict__ D0, long nlines, int if_lo, int if_hi,
-                               SlabOut so)
+                               SlabOut so, VoidArgs va)
 {
     const long line = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (line >= nlines) return;
@@ -542,38 +562,48 @@ __global__ void k_factor_lines(Geom G, int d, const double *__restrict__ D, doub
     int *ci = d == 0 ? &ix : d == 1 ? &iy : &iz;
     const int fs = if_lo ? 1 : 0, ce = if_hi ? n - 1 : n;       // chain cells [fs, ce)
     double a2, a1, ea2, ea1;
+    // MASK (undivided meshes only): is cell c of the line void; the Robin term of the face between a void cell and kept cell c
+    auto isv = [&](int c) -> bool { if constexpr (MASK) return va.voidm[base + (long)c * sl] != 0; else return false; };
+    auto robin = [&](int c) -> double { *ci = c; return 0.5 * dirichlet_term(G, d, ix, iy, iz, 1.0) * va.inv_gamma; };
     // first chain face: lower contribution = Dirichlet term or the edge cell below
     *ci = fs;
     double Dc = D[base + (long)fs * sl];
+    bool vc = isv(fs);
     cell_a(G, d, ix, iy, iz, Dc, a2, a1);
+    if (MASK && vc) a2 = a1 = 0.0;
     double dprev;
     double alo = 0.0, a2lo = 0.0;
     if (if_lo) { *ci = 0; cell_a(G, d, ix, iy, iz, D[base], ea2, ea1); alo = ea1; a2lo = ea2; dprev = ea2 + a2; }
     else { *ci = fs; dprev = a2 + (G.dir_lo[d] ? dirichlet_term(G, d, ix, iy, iz, Dc) : 0.0); }
+    if (MASK && dprev == 0.0) dprev = 1.0;
     double ahi = 0.0, a2hi = 0.0;
     if (if_hi) { *ci = n - 1; cell_a(G, d, ix, iy, iz, D[base + (long)(n - 1) * sl], ea2, ea1); ahi = ea1; a2hi = ea2; }
     D0[line] = 1.0 / dprev;
     double prodl = 1.0, g00 = 1.0 / dprev;                      // (T^-1)[0,0] = sum_k (prod_{j<k} l_j)^2 / d'_k
     for (int c = fs; c < ce; ++c) {
         double diag_next, na2 = 0.0, na1 = 0.0;
+        bool vn = false;
         if (c + 1 < ce) {
             *ci = c + 1;
             const double Dn = D[base + (long)(c + 1) * sl];
             cell_a(G, d, ix, iy, iz, Dn, na2, na1);
+            if constexpr (MASK) { vn = isv(c + 1); if (vn) na2 = na1 = 0.0; }
             diag_next = a2 + na2;
+            if constexpr (MASK) if (vc != vn) diag_next += robin(vc ? c + 1 : c);
         } else if (if_hi) {
             diag_next = a2 + a2hi;
         } else {
             *ci = c;
             diag_next = a2 + (G.dir_hi[d] ? dirichlet_term(G, d, ix, iy, iz, Dc) : 0.0);
         }
+        if (MASK && diag_next == 0.0) diag_next = 1.0;
         const double l = a1 / dprev;
         const double dn = diag_next - l * a1;
         L[base + (long)c * sl] = l;
         DR[base + (long)c * sl] = 1.0 / dn;
         prodl *= -l; g00 += prodl * prodl / dn;
         dprev = dn;
-        if (c + 1 < ce) { Dc = D[base + (long)(c + 1) * sl]; a2 = na2; a1 = na1; }
+        if (c + 1 < ce) { Dc = D[base + (long)(c + 1) * sl]; a2 = na2; a1 = na1; vc = vn; }
     }
     if (if_lo) { L[base] = 0.0; DR[base] = 0.0; }
     if (if_hi) { L[base + (long)(n - 1) * sl] = 0.0; DR[base + (long)(n - 1) * sl] = 0.0; }
@@ -1848,9 +1878,10 @@ __global__ __launch_bounds__(512) void k_apply3(ModeArgs max0, ModeArgs may0, Mo
 #endif
 }
 // r -= alpha ((qx + qy) + qz), |r|^2 partials; consumes the x.y partials of k_apply3 (FIN_PAP).  qy / qz may be null (1D / 2D).
+template <bool MASK>
 __global__ __launch_bounds__(256) void k_cg_rupdate3(double *__restrict__ r, const double *__restrict__ qx, const double *__restrict__ qy,
                                                      const double *__restrict__ qz, long n, const CgScalars *__restrict__ cg,
-                                                     double *__restrict__ partials, CgLean lean)
+                                                     double *__restrict__ partials, CgLean lean, VoidMask vm)
 {
     __shared__ double sred[4];
     // flags, |r|^2 of this iteration and the first trip's vector entries are requested before the reduction of the p.q partials
@@ -1859,7 +1890,8 @@ __global__ __launch_bounds__(256) void k_cg_rupdate3(double *__restrict__ r, con
     const double rr_cur = lean.st->rr2[lean.par];
     const long i0 = blockIdx.x * 256L + threadIdx.x;
     double r0 = 0.0, q0 = 0.0;
-    if (i0 < n) { r0 = r[i0]; q0 = qx[i0]; if (qy) q0 += qy[i0]; if (qz) q0 += qz[i0]; }
+    bool v0 = false;
+    if (i0 < n) { r0 = r[i0]; q0 = qx[i0]; if (qy) q0 += qy[i0]; if (qz) q0 += qz[i0]; if constexpr (MASK) v0 = void_entry(vm, i0, n); }
     if (done0) return;
     const double pq = strided_total(lean.partials, lean.count, sred);
     const bool brk = fabs(pq) < 1e-30;
@@ -1867,12 +1899,13 @@ __global__ __launch_bounds__(256) void k_cg_rupdate3(double *__restrict__ r, con
     if (blockIdx.x == 0 && threadIdx.x == 0) { lean.st->pAp = pq; lean.st->pend = 0; if (brk) lean.st->done = 1; else lean.st->alpha = alpha; }
     if (brk) return;
     double s = 0.0;
-    if (i0 < n) { const double rn = r0 - alpha * q0; r[i0] = rn; s += rn * rn; }
+    if (i0 < n) { double rn = r0 - alpha * q0; if (MASK && v0) rn = 0.0; r[i0] = rn; s += rn * rn; }
     for (long i = i0 + gridDim.x * 256L; i < n; i += gridDim.x * 256L) {
         double q = qx[i];
         if (qy) q += qy[i];
         if (qz) q += qz[i];
-        const double rn = r[i] - alpha * q;
+        double rn = r[i] - alpha * q;
+        if constexpr (MASK) if (void_entry(vm, i, n)) rn = 0.0;
         r[i] = rn; s += rn * rn;
     }
     s = block_sum(s, sred);
@@ -2298,22 +2331,26 @@ __global__ __launch_bounds__(XCD_THREADS) void k_keff_xcd(XcdArgs A, XcdOuter O)
 
 // ---------------------------------------------------------------------------------------------
 // CG vector kernels (src/solvers.cpp:577-631).  Fixed grids, grid-stride loops.
+// MASK (nf_set_void, VoidMask above): the residual is written as 0 in the void cells and stays out of |r|^2; the right-hand side counts as 0 there
+template <bool MASK>
 __global__ __launch_bounds__(256) void k_cg_init(const double *__restrict__ rhs, double *__restrict__ x,
                                                  double *__restrict__ r, double *__restrict__ p, long n,
-                                                 double *__restrict__ partials)
+                                                 double *__restrict__ partials, VoidMask vm)
 {
     __shared__ double sred[4];
     double s = 0.0;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) {
-        const double b = rhs[i];
+        double b = rhs[i];
+        if constexpr (MASK) if (void_entry(vm, i, n)) b = 0.0;
         x[i] = 0.0; r[i] = b; p[i] = b; s += b * b;
     }
     s = block_sum(s, sred);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
+template <bool MASK>
 __global__ __launch_bounds__(256) void k_cg_update(double *__restrict__ x, double *__restrict__ r,
                                                    const double *__restrict__ p, const double *__restrict__ q, long n,
-                                                   const CgScalars *__restrict__ cg, double *__restrict__ partials)
+                                                   const CgScalars *__restrict__ cg, double *__restrict__ partials, VoidMask vm)
 {
     __shared__ double sred[4];
     if (cg->done) return;
@@ -2321,15 +2358,17 @@ __global__ __launch_bounds__(256) void k_cg_update(double *__restrict__ x, doubl
     double s = 0.0;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) {
         x[i] = fma(alpha, p[i], x[i]);
-        const double rn = r[i] - alpha * q[i];
+        double rn = r[i] - alpha * q[i];
+        if constexpr (MASK) if (void_entry(vm, i, n)) rn = 0.0;
         r[i] = rn; s += rn * rn;
     }
     s = block_sum(s, sred);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 // fused CG: r -= alpha q and |r|^2 only (x_sol and p are updated by the next x pass)
+template <bool MASK>
 __global__ __launch_bounds__(256) void k_cg_rupdate(double *__restrict__ r, const double *__restrict__ q, long n,
-                                                    const CgScalars *__restrict__ cg, double *__restrict__ partials, CgLean lean)
+                                                    const CgScalars *__restrict__ cg, double *__restrict__ partials, CgLean lean, VoidMask vm)
 {
     __shared__ double sred[4];
     if (cg->done) return;
@@ -2345,7 +2384,8 @@ __global__ __launch_bounds__(256) void k_cg_rupdate(double *__restrict__ r, cons
     } else alpha = cg->alpha;
     double s = 0.0;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) {
-        const double rn = r[i] - alpha * q[i];                   // (streaming loads change nothing here: 102.3 vs 102.9 us of non-pass time per iteration)
+        double rn = r[i] - alpha * q[i];                         // (streaming loads change nothing here: 102.3 vs 102.9 us of non-pass time per iteration)
+        if constexpr (MASK) if (void_entry(vm, i, n)) rn = 0.0;
         r[i] = rn; s += rn * rn;
     }
     s = block_sum(s, sred);
@@ -3639,7 +3679,8 @@ __global__ void k_prolong(const double *__restrict__ coarse, double *__restrict_
 // faces (src/FEM.cpp:264-334, 377-397).  jface / jbub point at this direction's face / bubble block; nfa = (k+1)^(dim-1).
 __global__ void k_flux_to_J(Geom G, ModeArgs ma, int nb, int amode, int nfa, int ni, const double *__restrict__ D,
                             const double *__restrict__ L, const double *__restrict__ DR, const double *__restrict__ D0,
-                            double *__restrict__ jface, double *__restrict__ jbub, long nlines, int diag)
+                            double *__restrict__ jface, double *__restrict__ jbub, long nlines, int diag,
+                            const unsigned char *__restrict__ voidm = nullptr)
 {
     const long line = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (line >= nlines) return;
@@ -3683,7 +3724,7 @@ __global__ void k_flux_to_J(Geom G, ModeArgs ma, int nb, int amode, int nfa, int
                 for (int l = 0; l < G.k; ++l) {
                     const double tb = l < nb ? ma.Gc[l] * ma.x[l + 1][a] * ma.iM[l] * ic : 0.0;
                     const double v = tb - (ma.eL[l] * u + ma.eR[l] * uhi);
-                    jbub[a * ni + l + G.k * amode] = -v;
+                    jbub[a * ni + l + G.k * amode] = voidm && voidm[a] ? 0.0 : -v;   // nf_set_void: identity rows with a zero load
                 }
             }
         }

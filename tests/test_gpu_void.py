@@ -1,0 +1,529 @@
+"""Cut-out cells with a vacuum (albedo) condition, nf_set_void, against the CPU oracle's nfo_set_void.
+
+Cells marked void leave the domain and every face a kept cell shares with one carries J.n = gamma phi.  The device side is the factor
+builder (k_factor_lines with the mask), the masked residual updates of the CG and a few cell-wise kernels; the direction passes know no
+mask.  The mask used here holds every case the factor builder can get wrong:
+
+  stepped cut    for y rows j < ny // 3, c = (ny // 3 - j) max(1, nx // 12) cells at both ends of the x lines: kept|void faces in x and y at
+                 varying positions, lines that start and end void (and, where 2 c >= nx, lines that are void over their whole length)
+  hole           3 cells of one x line at the mesh centre: two kept segments in one line, void|void faces
+  void line      row ny - 1 of plane 0, void over its whole length
+  top plane      void except one kept cell: an isolated cell whose six faces are all boundary faces, z lines that end in a void cell on a
+                 natural domain face (the inputs keep three domain faces natural: dirichlet = (1, 3, 5))
+
+Bars, as in tests/test_gpu_variants.py (shapes, option sets and bars imported from there):
+  apply        max |y - y_oracle| <= 1e-12 max |y_oracle| on every group, input with 10 % of its entries scaled by 1e-12 and zero in void cells;
+               y exactly 0 in void cells
+  fixed work   solve_keff, tol (0, 1e-11, 1e-11, 6, 3000) (RT1 / RT2: 5000 inner): k-history 1e-9, flux 1e-8, currents 1e-7 against the oracle;
+               flux and bubble currents of void cells exactly 0
+  inside CG    solve_group on the conditioned twin against the oracle's: equal iteration counts, rel_l2 < 1e-10.  Two builds of the oracle,
+               with and without FMA contraction (the procedure of tests/test_rounding_sensitivity.py), on the same masked inputs: B 39 / 38
+               and R 115 / 108 iterations (group 0 / 1, seed 5) in both builds, solutions 2.0e-16 / 9.3e-15 apart -- no spread in the counts,
+               so the bar stays equality; which right-hand sides can carry that bar at all is settled on the oracle alone (CG_SEED below)
+The oracle's k of the three masked shapes after the six outers is 0.17214 / 0.25363 / 0.21386, and 0.16988 on B at gamma = 0.5 (1.3 % away:
+a wrong gamma cannot pass the 1e-9 bar, test_other_gamma asserts the distance); test_python_class asserts that the unmasked problem has
+another k."""
+import ctypes
+import functools
+import json
+import os
+import time
+
+import numpy as np
+import pytest
+
+from helpers import CG_FORMS, GOLDEN, load_inputs, rel_l2, synthetic_inputs
+from test_gpu_variants import B, CG_MAX, CG_TOL, CLASSIC, FIXED, R, WINDOW, _set
+
+pytestmark = pytest.mark.gpu
+
+GAMMA = 0.4692
+Q = ((20, 6, 5), 2)                                               # RT2-P2
+FIXED_HI = FIXED[:4] + (5000,)                                    # RT1 / RT2: 5000 inner
+LAUNCH_FORMS = ("fuse3", "lean", "fused", "classic")             # what cg_plan may choose under a mask
+
+
+def void_mask(nx, ny, nz):
+    """the mask of the module docstring, shaped like one group of the cross sections"""
+    m = np.zeros((nz, ny, nx), bool)
+    step = max(1, nx // 12)
+    if ny == 1:                                                   # 1D: the end cuts and the hole
+        m[:, :, :step] = True; m[:, :, nx - step:] = True
+    for j in range(ny // 3):
+        c = min((ny // 3 - j) * step, nx)
+        m[:, j, :c] = True; m[:, j, nx - c:] = True
+    m[nz // 2, ny // 2, nx // 2 - 1:nx // 2 + 2] = True
+    if ny > 1:
+        m[0, ny - 1, :] = True
+    if nz > 1:
+        m[nz - 1] = True; m[nz - 1, ny // 2, nx // 2] = False
+    return m.reshape(tuple(n for n in (nz, ny, nx) if n > 1) or (nx,))
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs(shape, conditioned=False):
+    """inputs and mask of a shape; nuSigf, chi and the scatter blocks are zero in void cells (the oracle relies on its caller for that)"""
+    nx, ny, nz = shape
+    kw = dict(nonuniform=False, void_frac=0.0) if conditioned else {}
+    inp = synthetic_inputs(nx, ny, nz, 2, seed=nx + 7 * ny + 13 * nz, dirichlet=(1, 3, 5), **kw)
+    if conditioned:
+        inp["SigR"] = 50.0 * inp["SigR"]
+    mask = void_mask(nx, ny, nz)
+    inp["NSF"][:, mask] = 0.0; inp["Chi"][:, mask] = 0.0; inp["SigS"][:, :, mask] = 0.0
+    return inp, mask
+
+
+def _oracle(inp, rt, mask, gamma):
+    """make_oracle's steps with set_void before BuildMatrices"""
+    from oracle.oracle import OracleNeutFEM
+    o = OracleNeutFEM(rt, rt, int(inp["ng"]), inp["x_breaks"], inp["y_breaks"], inp["z_breaks"])
+    o.set_linear_solver(6)
+    for a, t in zip(inp["bc_attr"], inp["bc_type"]):
+        o.set_bc(int(a), int(t), 0.0)
+    o.get_D()[...] = inp["D"]; o.get_SigR()[...] = inp["SigR"]; o.get_NSF()[...] = inp["NSF"]
+    o.get_Chi()[...] = inp["Chi"]; o.get_SigS()[...] = inp["SigS"]
+    if mask is not None:
+        o.set_void(mask, 1.0 / gamma)
+    o.BuildMatrices()
+    return o
+
+
+def _hip(inp, rt, mask, gamma=GAMMA, opts=None, build=True):
+    """make_hip's steps with set_void before build"""
+    from neutfem_amd.capi import HipSolver
+    s = HipSolver(rt, rt, int(inp["ng"]), inp["x_breaks"], inp["y_breaks"], inp["z_breaks"])
+    s.set_linear_solver(6)
+    for a, t in zip(inp["bc_attr"], inp["bc_type"]):
+        s.set_bc(int(a), int(t))
+    s.upload_xs(inp["D"], inp["SigR"], inp["NSF"], inp["Chi"], inp["SigS"])
+    if mask is not None:
+        s.set_void(mask, gamma)
+    _set(s, opts or {})
+    if build:
+        s.build()
+    return s
+
+
+def _dof_mask(mask, n_loc):
+    """the mask per flux DOF, host layout [e * n_loc + p]"""
+    return np.repeat(mask.ravel(), n_loc)
+
+
+@functools.lru_cache(maxsize=None)
+def _ref(shape, rt, gamma=GAMMA, tol=None):
+    """the oracle side of a masked mesh, computed once: apply inputs / outputs per group, then the fixed-work solve"""
+    inp, mask = _inputs(shape)
+    o = _oracle(inp, rt, mask, gamma)
+    dm = _dof_mask(mask, o.nloc)
+    rng = np.random.default_rng(3)
+    xs, ys = [], []
+    for g in range(2):
+        x = rng.standard_normal(o.n_phi)
+        x[rng.random(o.n_phi) < 0.1] *= 1e-12
+        x[dm] = 0.0
+        xs.append(x); ys.append(o.schur_apply(g, x))
+    tol = tol or (FIXED if rt == 0 else FIXED_HI)
+    o.set_tol(*tol)
+    o.SolveKeff(); h = o.history()
+    assert h["n_outer"] == tol[3] and h["cg"].max() < tol[4], (h["n_outer"], h["cg"].max())
+    out = dict(x=xs, y=ys, hk=h["k"].copy(), phi=o.phi_dofs().copy(), J=o.J_dofs().copy(), dm=dm, nvoid=int(mask.sum()),
+               nface=o.n_J - o.ne * o.dim * o.ni, ni=o.ni, dim=o.dim)
+    assert (out["phi"][:, dm] == 0).all()                          # the oracle's flux is exactly 0 in void cells
+    for a in xs + ys + [out["hk"], out["phi"], out["J"]]:
+        a.setflags(write=False)
+    return out
+
+
+def _check_apply(s, ref, label):
+    for g in range(2):
+        y = s.schur_apply(g, ref["x"][g])
+        err = np.abs(y - ref["y"][g]).max() / np.abs(ref["y"][g]).max()
+        print(f"apply {label} g={g}: max-abs error / max|y| = {err:.3e} (bar 1e-12)")
+        assert np.isfinite(y).all() and err <= 1e-12, (label, g, err)
+        assert (y[ref["dm"]] == 0).all(), (label, g)
+
+
+def _check_fixed(s, ref, label, tol, want_form=None):
+    """plan, fixed-work solve, reports; k-history 1e-9, flux 1e-8, currents 1e-7; zeros in void cells"""
+    plan = s.apply_plan(True)["form"]
+    assert plan in LAUNCH_FORMS and (want_form is None or plan == want_form), (label, plan, want_form)
+    s.set_tol(*tol); s.reset_flux(); s.set_warm_state(0, 1.0)
+    k, n = s.solve_keff(); h = s.history()
+    assert n == tol[3]
+    assert CG_FORMS[s.info("cg_form")] == plan and s.info("last_path") == 0 and s.info("xcd_solves") == 0, (label, s.info("cg_form"), s.info("last_path"))
+    assert s.info("void_cells") == ref["nvoid"]
+    phi, J = s.get_phi(), s.get_J()
+    errs = (np.abs(h["k"] / ref["hk"] - 1).max(), rel_l2(phi.ravel(), ref["phi"].ravel()), rel_l2(J.ravel(), ref["J"].ravel()))
+    print(f"fixed work {label} ({plan}): k = {k:.8f}, k-history {errs[0]:.3e} (1e-9), flux {errs[1]:.3e} (1e-8), currents {errs[2]:.3e} (1e-7)")
+    np.testing.assert_allclose(h["k"], ref["hk"], rtol=1e-9)
+    assert errs[1] < 1e-8 and errs[2] < 1e-7
+    assert (phi[:, ref["dm"]] == 0).all()
+    if ref["ni"]:                                                 # bubble currents [d][e][ni] behind the faces: exactly 0 in void cells
+        bub = J[:, ref["nface"]:].reshape(2, ref["dim"], -1, ref["ni"])
+        assert (bub[:, :, ref["dm"][::len(ref["dm"]) // bub.shape[2]], :] == 0).all()
+    return h["k"].copy(), phi.copy()
+
+
+# ---- apply ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mesh", [B, R, Q], ids=["B", "R", "rt2"])
+def test_apply(mesh):
+    shape, rt = mesh
+    ref = _ref(shape, rt)
+    inp, mask = _inputs(shape)
+    s = _hip(inp, rt, mask)
+    assert s.info("void_cells") == mask.sum() and s.apply_plan()["form"] == ""
+    _check_apply(s, ref, f"{shape} RT{rt}")
+    m, g = s.get_void()
+    assert np.array_equal(m.astype(bool), mask.ravel()) and g == GAMMA
+    s.close()
+
+
+# ---- fixed work, every allowed form of the CG ----------------------------------------------------------------------------------------
+FORMS_B = [("default", {}, "fuse3"), ("classic_opts", CLASSIC, "lean"), ("no_lean", dict(CLASSIC, cg_lean=0), "fused"), ("no_fuse", dict(CLASSIC, cg_fuse=0), "classic")]
+
+
+@pytest.mark.parametrize("label,opts,form", FORMS_B, ids=[f[0] for f in FORMS_B])
+def test_fixed_work_B_every_form(label, opts, form):
+    shape, rt = B
+    inp, mask = _inputs(shape)
+    s = _hip(inp, rt, mask, opts=opts)
+    _check_fixed(s, _ref(shape, rt), f"B {label}", FIXED, form)
+    s.close()
+
+
+@pytest.mark.parametrize("opts", [{}, CLASSIC], ids=["default", "classic_opts"])
+@pytest.mark.parametrize("mesh", [R, Q], ids=["R", "rt2"])
+def test_fixed_work_higher_orders(mesh, opts):
+    shape, rt = mesh
+    inp, mask = _inputs(shape)
+    s = _hip(inp, rt, mask, opts=opts)
+    _check_fixed(s, _ref(shape, rt), f"{shape} RT{rt}", FIXED_HI)
+    s.close()
+
+
+def test_other_gamma():
+    """gamma = 0.5 on B: the factor of the Robin term is the argument, not a constant"""
+    shape, rt = B
+    inp, mask = _inputs(shape)
+    ref = _ref(shape, rt, 0.5)
+    assert abs(ref["hk"][-1] / _ref(shape, rt)["hk"][-1] - 1) > 1e-3
+    s = _hip(inp, rt, mask, 0.5)
+    _check_apply(s, ref, "B gamma=0.5")
+    _check_fixed(s, ref, "B gamma=0.5", FIXED)
+    s.close()
+
+
+# ---- inside CG -----------------------------------------------------------------------------------------------------------------------
+# Equal iteration counts can only be asked where the oracle's own stop is not marginal.  The CG residual is known to about n u kappa of
+# |b|: n iterations, u = 1.1e-16, kappa the condition number.  On R the oracle's residual falls by 0.79 per iteration, so sqrt(kappa) =
+# (1 + 0.79) / (1 - 0.79), kappa = 73, and with n = 115 that is 9e-13: 9 % of the tolerance 1e-11, where one iteration changes the residual by
+# 21 %.  (B: 39 iterations, 0.49 per iteration, kappa = 9: 4e-14.)  So a right-hand side qualifies when the oracle's TRUE residual |b - S x| / |b| is
+# above 1.1 tol one iteration before its stop and below tol / 1.1 at it, in both groups -- a property of the oracle alone, asserted below.
+# Seeds are tried from 5 (the seed of tests/test_gpu_variants.py) upwards: B qualifies at once (1.29 / 0.62 and 1.72 / 0.85 of tol), on R the
+# first that does is 68 (1.13 / 0.89 and 1.11 / 0.87; seed 5 gives 1.02 / 0.81 and 1.09 / 0.85: the stop of group 0 hangs on 2 %).
+CG_SEED = {B: 5, R: 68}
+
+
+@functools.lru_cache(maxsize=None)
+def _ref_cg(mesh):
+    shape, rt = mesh
+    inp, mask = _inputs(shape, True)
+    o = _oracle(inp, rt, mask, GAMMA)
+    dm = _dof_mask(mask, o.nloc)
+    rng = np.random.default_rng(CG_SEED[mesh])
+    rhs, sol, its = [], [], []
+    for g in range(2):
+        b = np.abs(rng.standard_normal(o.n_phi)); b[dm] = 0.0
+        o.set_tol(1e-5, CG_TOL, CG_TOL, 200, CG_MAX)
+        x, _, n = o.solve_group(g, b, with_J=False)
+        margin = []
+        for it in (n - 1, n):                                     # the oracle's true residual one iteration before its stop and at it
+            o.set_tol(1e-5, 1e-30, 1e-30, 200, it)
+            xi = o.solve_group(g, b, with_J=False)[0]
+            margin.append(np.linalg.norm(b - o.schur_apply(g, xi)) / np.linalg.norm(b) / CG_TOL)
+        print(f"oracle CG {shape} RT{rt} g={g}: {n} iterations, true residual / tol = {margin[0]:.3f} before the stop, {margin[1]:.3f} at it")
+        assert margin[0] > 1.1 and margin[1] < 1 / 1.1, (mesh, g, margin)
+        rhs.append(b); sol.append(x); its.append(n)
+    return dict(rhs=rhs, sol=sol, its=its, dm=dm)
+
+
+@pytest.mark.parametrize("opts", [{}, CLASSIC], ids=["default", "classic_opts"])
+@pytest.mark.parametrize("mesh", [B, R], ids=["B", "R"])
+def test_solve_group(mesh, opts):
+    shape, rt = mesh
+    ref = _ref_cg(mesh)
+    inp, mask = _inputs(shape, True)
+    s = _hip(inp, rt, mask, opts=opts)
+    for g in range(2):
+        x, n, res = s.solve_group(g, ref["rhs"][g], CG_TOL, CG_MAX)
+        err = rel_l2(x, ref["sol"][g])
+        print(f"solve_group {shape} RT{rt} g={g}: its {n} (oracle {ref['its'][g]}), rel_l2 = {err:.3e} (bar 1e-10), form {CG_FORMS[s.info('cg_form')]}")
+        assert res < CG_TOL and n == ref["its"][g], (g, n, ref["its"][g])
+        assert err < 1e-10 and (x[ref["dm"]] == 0).all()
+    assert CG_FORMS[s.info("cg_form")] in LAUNCH_FORMS and s.info("xcd_solves") == 0
+    # a right-hand side that does not vanish in void cells is taken as 0 there
+    b = ref["rhs"][0].copy(); b[ref["dm"]] = 3.0
+    x, n, _ = s.solve_group(0, b, CG_TOL, CG_MAX)
+    assert n == ref["its"][0] and rel_l2(x, ref["sol"][0]) < 1e-10 and (x[ref["dm"]] == 0).all()
+    s.close()
+
+
+# ---- small meshes: the in-kernel paths must step aside -------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", [(12, 10, 8), WINDOW[0][0]], ids=["resident_window", "one_xcd_window"])
+def test_small_meshes_take_the_launch_path(shape):
+    inp, mask = _inputs(shape)
+    plain = _hip(inp, 0, None)                                    # without a mask these meshes run inside one kernel
+    plain.set_tol(*FIXED); plain.solve_keff()
+    assert plain.info("last_path") in (2, 3), plain.info("last_path")
+    plain.close()
+    s = _hip(inp, 0, mask)
+    _check_apply(s, _ref(shape, 0), str(shape))
+    _check_fixed(s, _ref(shape, 0), str(shape), FIXED)
+    s.close()
+
+
+# ---- 2D and 1D -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mesh", [((70, 24, 1), 0), ((40, 1, 1), 1)], ids=["2d_rt0", "1d_rt1"])
+def test_lower_dimensions(mesh):
+    shape, rt = mesh
+    tol = FIXED if rt == 0 else FIXED_HI
+    inp, mask = _inputs(shape)
+    ref = _ref(shape, rt, GAMMA, tol)
+    s = _hip(inp, rt, mask)
+    _check_apply(s, ref, f"{shape} RT{rt}")
+    _check_fixed(s, ref, f"{shape} RT{rt}", tol)
+    s.close()
+
+
+# ---- no mask: the code as it stands --------------------------------------------------------------------------------------------------
+def test_no_mask_is_identity():
+    shape, rt = B
+    inp, mask = _inputs(shape)
+    x = np.random.default_rng(11).standard_normal(int(np.prod(shape)))
+
+    def run(s):
+        assert s.info("void_cells") == 0
+        with pytest.raises(RuntimeError, match="-5"):
+            s.get_void()
+        plans = [json.dumps(s.apply_plan(c), sort_keys=True) for c in (False, True)]
+        y = s.schur_apply(0, x)
+        s.set_tol(*FIXED); s.solve_keff(); h = s.history()
+        out = (plans, y, h["k"].copy(), s.get_phi().copy(), s.info("last_path"), s.info("cg_form"), s.info("xcd_solves"))
+        s.close()
+        return out
+
+    never = run(_hip(inp, rt, None))
+    zeros = run(_hip(inp, rt, np.zeros_like(mask)))
+    s = _hip(inp, rt, mask, build=False); s.set_void(None); s.build()
+    removed = run(s)
+    for other in (zeros, removed):
+        assert other[0] == never[0]
+        for a, b in zip(other[1:4], never[1:4]):
+            assert np.array_equal(a, b)
+        assert other[4:] == never[4:]
+    assert never[4] == 3                                          # B sits in the one-XCD window: the unmasked handle still takes it
+
+
+# ---- junk in void cells ----------------------------------------------------------------------------------------------------------------
+def test_junk_in_void_cells_is_ignored():
+    shape, rt = B
+    inp, mask = _inputs(shape)
+    junk = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in inp.items()}
+    rng = np.random.default_rng(17)
+    n = int(mask.sum())
+    junk["NSF"][:, mask] = rng.uniform(0.1, 5.0, (2, n)); junk["Chi"][:, mask] = rng.uniform(0.1, 1.0, (2, n))
+    junk["SigS"][:, :, mask] = rng.uniform(0.1, 5.0, (2, 2, n))
+    res = []
+    for i in (inp, junk):
+        s = _hip(i, rt, mask)
+        s.set_tol(*FIXED); s.solve_keff()
+        res.append((s.history()["k"].copy(), s.get_phi().copy())); s.close()
+    assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][1], res[1][1])
+
+
+# ---- the benchmarks as specified -----------------------------------------------------------------------------------------------------
+def test_iaea2d_as_specified():
+    """ANL-7416 11-A2 with the vacuum condition on the stepped outline: RT2-P2 at 2 x 2 cells per assembly lands +0.40 pcm from the literature
+    k on the oracle (tests/test_oracle.py); the GPU within the project's parity of 0.11 pcm plus the rounding of that figure.  13 k unknowns per
+    group: inside the one-XCD window, so this is also a check of the predicate"""
+    from test_oracle import _IAEA2D_FIRST
+    base = load_inputs("iaea2d")
+    kref = float(base["kref"])
+    assert kref == 1.029585
+    blank = np.ones((19, 19), bool)
+    for r, f in enumerate(_IAEA2D_FIRST):
+        if f is not None:
+            blank[r, f:19 - f] = False
+    blank = np.repeat(np.repeat(blank, 2, 0), 2, 1)
+    s = _hip(base, 2, blank)
+    assert s.apply_plan(True)["form"] in LAUNCH_FORMS
+    s.set_tol(1e-9, 1e-8, 1e-8, 2000, 5000)
+    t0 = time.time(); k, n = s.solve_keff(); dt = time.time() - t0
+    pcm = 1e5 * (1.0 / kref - 1.0 / k)
+    print(f"IAEA-2D as specified RT2-P2: k = {k:.8f}, {pcm:+.3f} pcm vs k_ref (oracle +0.40), {n} outers, {dt:.2f} s")
+    assert s.info("last_path") == 0 and s.info("xcd_solves") == 0 and CG_FORMS[s.info("cg_form")] in LAUNCH_FORMS
+    assert abs(pcm - 0.40) < 0.12, pcm
+    assert (s.get_phi()[:, _dof_mask(blank, s.n_loc)] == 0).all()
+    s.close()
+
+
+def _iaea3d_spec(m):
+    """inputs of oracle/iaea3d_as_specified.py, mode spec: m cells per assembly and axis, one void plane below and one above"""
+    base = load_inputs("iaea3d")
+    per_assembly = lambda a: a[..., :, ::2, ::2]
+    refine = lambda a: np.repeat(np.repeat(np.repeat(a, m, axis=-1), m, axis=-2), m, axis=-3)
+    inp = dict(base)
+    for k in ("D", "SigR", "NSF", "Chi", "SigS"):
+        inp[k] = np.ascontiguousarray(refine(per_assembly(base[k])))
+    xb = np.linspace(0.0, 380.0, 19 * m + 1); zb = np.linspace(0.0, 380.0, 19 * m + 1)
+    blank = inp["D"][0] == 1e-3
+    pad = lambda a: np.concatenate([a[..., :1, :, :], a, a[..., -1:, :, :]], axis=-3)
+    for k in ("D", "SigR", "NSF", "Chi", "SigS"):
+        inp[k] = np.ascontiguousarray(pad(inp[k]))
+    blank = np.concatenate([np.ones_like(blank[:1]), blank, np.ones_like(blank[:1])], axis=0)
+    inp["D"][:, blank] = 1.0; inp["SigR"][:, blank] = 1.0; inp["NSF"][:, blank] = 0.0; inp["Chi"][:, blank] = 0.0; inp["SigS"][:, :, blank] = 0.0
+    inp["x_breaks"], inp["y_breaks"], inp["z_breaks"] = xb, xb.copy(), np.concatenate([[-1.0], zb, [381.0]])
+    return inp, blank
+
+
+@pytest.mark.parametrize("rt,m", [(0, 1), (0, 2), (1, 1)])
+def test_iaea3d_as_specified(rt, m):
+    """ANL-7416 11-A1 as specified against the oracle's table (tests/golden/iaea3d_as_specified.json): k within 0.11 pcm, equal outer counts"""
+    with open(os.path.join(GOLDEN, "iaea3d_as_specified.json")) as f:
+        row = [r for r in json.load(f)["runs"] if r["mode"] == "spec" and r["rt"] == rt and r["m"] == m][0]
+    inp, blank = _iaea3d_spec(m)
+    s = _hip(inp, rt, blank)
+    s.set_tol(1e-8, 1e-7, 1e-7, 1000, 5000)
+    t0 = time.time(); k, n = s.solve_keff(); dt = time.time() - t0
+    print(f"IAEA-3D as specified RT{rt}-P{rt} m={m}: k = {k:.7f} (oracle {row['keff']:.7f}), {n} outers (oracle {row['outers']}), "
+          f"{s.info('last_cg_total')} CG (oracle {row['cg']}), {dt:.2f} s (oracle {row['seconds']} s)")
+    assert abs(k - row["keff"]) < 1.1e-6, (k, row["keff"])
+    assert n == row["outers"]
+    assert s.info("last_path") == 0 and CG_FORMS[s.info("cg_form")] in LAUNCH_FORMS
+    s.close()
+
+
+# ---- adjoint ---------------------------------------------------------------------------------------------------------------------------
+def test_adjoint():
+    """solve_adjoint under the mask against the oracle's SolveAdjoint, at the bars of tests/test_gpu_parity.py::test_solve_adjoint (equal k and
+    outer counts, adjoint flux 1e-7; free k: k-history 1e-8 over the 5 outers before the Chebyshev step).  Fixed work like the solves above
+    (6 outers, inner CG to 1e-11): at the drivers' inner tolerance of 1e-4 a single group solve that stops one iteration apart moves the
+    iterate by more than the bar"""
+    shape, rt = B
+    inp, mask = _inputs(shape)
+    o, s = _oracle(inp, rt, mask, GAMMA), _hip(inp, rt, mask)
+    o.set_tol(*FIXED); s.set_tol(*FIXED)
+    ko = o.SolveKeff(); ks, _ = s.solve_keff()
+    ka_o = o.SolveAdjoint(True, True); ka_s, n = s.solve_adjoint(True, True)
+    assert ka_o == ko and ka_s == ks
+    assert n == o.info("last_outer") == FIXED[3]
+    assert CG_FORMS[s.info("cg_form")] in LAUNCH_FORMS and s.info("xcd_solves") == 0
+    err = rel_l2(s.get_phi_adj().ravel(), o.phi_adj_dofs().ravel())
+    print(f"adjoint, fixed k: {n} outers, CG {s.history()['cg'].sum()} (oracle {o.history()['cg'].sum()}), rel_l2 = {err:.3e} (bar 1e-7)")
+    assert err < 1e-7
+    assert (s.get_phi_adj()[:, mask.ravel()] == 0).all() and (o.phi_adj_dofs()[:, mask.ravel()] == 0).all()
+    tol5 = FIXED[:3] + (5,) + FIXED[4:]                           # 5 outers: before the Chebyshev step
+    o.set_tol(*tol5); s.set_tol(*tol5)
+    o.SolveAdjoint(False, False); s.solve_adjoint(False, False)
+    errs = (np.abs(s.history()["k"] / o.history()["k"] - 1).max(), rel_l2(s.get_phi_adj().ravel(), o.phi_adj_dofs().ravel()))
+    print(f"adjoint, free k: k-history {errs[0]:.3e} (bar 1e-8), rel_l2 = {errs[1]:.3e} (bar 1e-7)")
+    np.testing.assert_allclose(s.history()["k"], o.history()["k"], rtol=1e-8)
+    assert errs[1] < 1e-7
+    s.close()
+
+
+# ---- Python class ----------------------------------------------------------------------------------------------------------------------
+def test_python_class():
+    import neutfem_amd
+    neutfem_amd.install_compat()
+    import neutfem._neutfem_eigen as m
+    shape, rt = B
+    inp, mask = _inputs(shape)
+    s = _hip(inp, rt, mask)
+    s.set_tol(*FIXED); k_ref, _ = s.solve_keff(); phi_ref = s.get_phi().copy(); s.close()
+    p = m.NeutFEM(rt, rt, 2, inp["x_breaks"], inp["y_breaks"], inp["z_breaks"])
+    p.set_verbosity(m.VerbosityLevel.SILENT); p.set_linear_solver(m.LinearSolverType.BICGSTAB)
+    for a in inp["bc_attr"]:
+        p.set_bc(int(a), m.BCType.DIRICHLET)
+    p.get_D()[...] = inp["D"]; p.get_SigR()[...] = inp["SigR"]; p.get_NSF()[...] = inp["NSF"]; p.get_Chi()[...] = inp["Chi"]; p.get_SigS()[...] = inp["SigS"]
+    p.set_tol(*FIXED)
+    p.set_void(mask.astype(np.int32), GAMMA)
+    p.BuildMatrices()
+    k = p.SolveKeff()
+    assert k == k_ref
+    flux = p.get_flux()
+    assert np.array_equal(flux.ravel(), phi_ref.ravel()) and (flux[:, mask] == 0).all() and (flux[:, ~mask] != 0).all()
+    p.clear_void(); p.BuildMatrices(); p.reset_flux()
+    assert abs(p.SolveKeff() / k_ref - 1) > 1e-3                  # without the mask it is another problem
+
+
+# ---- refusals --------------------------------------------------------------------------------------------------------------------------
+def _refused(call, code):
+    with pytest.raises(RuntimeError) as e:
+        call()
+    msg = str(e.value)
+    assert msg.startswith(f"neutfem_hip error {code}:"), msg
+    return msg
+
+
+def test_refusals():
+    shape, rt = B
+    inp, mask = _inputs(shape)
+    loose = (1e-4, 1e-4, 1e-4, 30, 500)
+    s = _hip(inp, rt, mask); s.set_tol(*loose)
+    other = _hip(inp, rt, None); fine = other.refine(1, 1, 1)     # a twin without a mask, for zoom_source
+    src = np.ones((2,) + mask.shape)
+
+    def adjoint(**kw):
+        o = s.opts(**kw); k, n = ctypes.c_double(), ctypes.c_int()
+        s._chk(s.L.nf_solve_adjoint(s.h, ctypes.byref(o), 1, 1, ctypes.byref(k), ctypes.byref(n)))
+
+    calls = {
+        "keff_diag": lambda: s.solve_keff(use_diag=True), "keff_cmfd": lambda: s.solve_keff(use_cmfd=True),
+        "keff_coarse": lambda: s.solve_keff(True, (2, 2, 1)),
+        "adjoint_diag": lambda: adjoint(use_diag=True), "adjoint_cmfd": lambda: adjoint(use_cmfd=True), "adjoint_coarse": lambda: adjoint(use_coarse=True, factors=(2, 2, 1)),
+        "diag_cache": lambda: s._chk(s.L.nf_build_diagonal_cache(s.h)), "init_cmfd": s.initialize_cmfd,
+        "solve_coarse": lambda: s.solve_coarse((2, 2, 1)), "coarsen": lambda: s.coarsen(2, 2, 1).close(), "refine": lambda: s.refine(1, 1, 1).close(),
+        "zoom_source": lambda: s.zoom_source(fine, 1.0), "zoom_resolved": lambda: s.zoom_resolved((1, 1, 1), 1.0)[0].close(),
+        "sensitivity": lambda: s.sensitivity(1.0, ("D",)), "transient_begin": lambda: s.transient_begin([1e7, 1e5], [0.005], [0.1], 1.0),
+        "subcritical": lambda: s.solve_subcritical(), "modes": lambda: s.solve_modes(1, 1),
+    }
+    s.upload_source(src)
+    for name, call in calls.items():
+        msg = _refused(call, -4)
+        assert "nf_set_void" in msg, (name, msg)
+    # the same handle without the mask: every one of them works
+    s.set_void(None)
+    _refused(s.solve_keff, -5)                                    # between set_void and build
+    _refused(lambda: s.schur_apply(0, np.zeros(s.n_phi)), -5)
+    s.build()
+    k, _ = s.solve_keff(); s.solve_adjoint(True, True)            # a flux, an adjoint flux and k for the calls that need them
+    for name, call in calls.items():
+        call()
+    s.transient_end()
+    other.close(); fine.close()
+    # arguments and state
+    for gamma in (0.0, -1.0, float("inf"), float("nan")):
+        _refused(lambda: s.set_void(mask, gamma), -1)
+    _refused(lambda: s.set_void(np.ones_like(mask), GAMMA), -1)
+    s.solve_keff()                                                # refused calls leave the handle built and unmasked
+    assert s.info("void_cells") == 0
+    s.set_void(mask, GAMMA)
+    assert s.info("void_cells") == mask.sum()
+    _refused(s.solve_keff, -5); _refused(lambda: s.solve_adjoint(True, True), -5)
+    _refused(lambda: s.solve_group(0, np.zeros(s.n_phi), 1e-8, 10), -5)
+    s.build(); s.solve_keff()
+    assert s.info("last_path") == 0
+    s.close()
+
+
+def test_slabs_are_refused():
+    from neutfem_amd.capi import HipTeam
+    inp = synthetic_inputs(8, 6, 8, 2, seed=4)
+    t = HipTeam(0, 0, 2, inp["x_breaks"], inp["y_breaks"], inp["z_breaks"], [(0, 4), (4, 8)])
+    for sl in t.slabs:
+        m = np.zeros(sl.ne, bool); m[0] = True
+        msg = _refused(lambda: sl.set_void(m, GAMMA), -4)
+        assert "nf_set_void" in msg
+        _refused(lambda: sl.set_void(None), -4)
+    t.close()
