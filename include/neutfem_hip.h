@@ -234,7 +234,8 @@ int nf_project_power(nf_handle h, int rx, int ry, int rz, int adjoint, const dou
  * cell is cut into rx x ry x rz equal parts (breaks xb[i] + a (xb[i+1] - xb[i]) / rx, every coarse break kept exactly; cell order of
  * nf_project_flux); a fine cell has the cross sections of its parent.  The factors are taken literally, as nf_project_flux takes them.
  * Undivided meshes only (slab teams: NF_ERR_UNSUPPORTED); needs nf_upload_xs.  On a failure the partial handle is destroyed, *fine is
- * NULL and h stays usable.  The caller destroys the twin. */
+ * NULL and h stays usable.  The caller destroys the twin.  The fine handle starts with the options (nf_set_option) h has at this call
+ * and reports its own solves (nf_info "cg_form", "xcd_solves", "last_direct" ... on the fine handle). */
 int nf_refine(nf_handle h, int rx, int ry, int rz, nf_handle *fine);
 /* Fills the load vector of `fine` (what nf_upload_source fills) from the coarse handle's current flux (adjoint = 1: its adjoint flux):
  * the fission source chi_g(e) / keff sum_g' nuSigf_g'(e) phi_g'(x) of every coarse cell e, a polynomial, restricted exactly to every
@@ -386,7 +387,9 @@ int nf_transient_begin(nf_handle h, const nf_kinetics *kin, double keff);
  * use_diagonal_solver must be 0, dt > 0 (finite), n_steps >= 1, max_outer >= 1 (NF_ERR_ARG); NF_ERR_STATE without nf_transient_begin or
  * with a handle that is not built.  A non-finite sum in any outer -> NF_ERR_NUMERIC: time, flux and precursors stay those of the last
  * completed step (res reports them) and the handle stays usable.  The warm k-eff state and nf_get_history are untouched; nf_progress
- * counts the outers of the call.  Deterministic.  nf_info "transient_steps": steps completed since begin. */
+ * counts the outers of the call.  Deterministic.  nf_info "transient_steps": steps completed since begin.  The step operator takes
+ * the options (nf_set_option) of h at every call, and nf_info on h reports its last CG solve ("cg_form", "cg_reductions", "last_xcd",
+ * "xcd_solves", "xcd_refused", "last_direct"). */
 int nf_transient_step(nf_handle h, const nf_keff_opts *opts, double dt, int n_steps, double *power_host, nf_transient_result *res);
 /* precursor family `family` (0-based) of the running transient in the host DOF layout of nf_get_phi, one group's length (n_phi) */
 int nf_get_precursors(nf_handle h, int family, double *c_host);
@@ -510,6 +513,8 @@ int nf_time_device_copy(nf_handle h, size_t bytes, int reps, double *gbps);
  *   move: the results are bit-identical at every level.  nf_apply_plan reports the level per pass as "early";
  *   "transient_rebalance" (default 1): nf_transient_step scales the iterate of every outer by the balance factor f; 0 = plain source
  *   iteration (same fixed point, a contraction of about 1 - beta per outer: for measurements).
+ * The handles the library derives from h solve under h's options: the step operator of nf_transient_step (at every call), the fine
+ * handle of nf_refine / nf_zoom_resolved (as they are when it is made) and, for the options that choose its solve, the coarse twin of SolveCoarse.
  * nf_info keys beyond the mesh sizes: "last_path" (0 host-driven outer loop, 1 diagonal device loop, 2 resident kernel, 3 one-XCD kernel),
  * "last_direct" (0 CG as configured, 1 dense S^-1, 2 CG to 1e-14 standing in), "line_dict_rejected" (mask of the directions whose table the
  * bit-for-bit verification refused: a fingerprint collision, not an error), "line_dict_bytes" (device memory of the tables and line ids),

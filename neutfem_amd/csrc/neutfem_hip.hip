@@ -2581,6 +2581,37 @@ static void dense_solve(nf_team *T, int g, const double *rhs, double *sol)
     hipLaunchKernelGGL(k_dense_matvec, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, T->stream, (const double *)(S->d_Sdense + (size_t)g * n * n), rhs, sol, n);
 }
 
+// ---- twin handles take the caller's options (nf_set_option) --------------------------------------
+// The one place that hands a team's options to the team of a handle the library derives from it.  Every twin gets what chooses its solve:
+// the form of the CG iteration (cg_plan, xcd_eligible), the group solver (inner_plan), the SolveKeff path, cg_batch.  same_mesh_kind: the
+// twin has the caller's orders and runs its passes at the caller's scale (the step operator of a transient, nf_refine's fine handle), so
+// it also gets what the launch plans of an apply and the scalar readback (pub_ready) read.  The coarse twin of SolveCoarse is RT0-P0 on a
+// mesh many times smaller: pass tuning meant for the caller's mesh stays off it.
+static void team_copy_options(nf_team *C, const nf_team *T, bool same_mesh_kind)
+{
+    C->opt_cg1 = T->opt_cg1; C->cg1_max_cells = T->cg1_max_cells; C->opt_endpoint_w = T->opt_endpoint_w; C->opt_fuse = T->opt_fuse; C->opt_lean = T->opt_lean;
+    C->opt_sepfold = T->opt_sepfold; C->opt_lean_grid = T->opt_lean_grid; C->lean_max_cells = T->lean_max_cells;
+    C->opt_fuse3 = T->opt_fuse3; C->fuse3_max_cells = T->fuse3_max_cells; C->opt_cgx = T->opt_cgx; C->opt_keffx = T->opt_keffx;
+    C->xcd_min_cells = T->xcd_min_cells; C->xcd_max_cells = T->xcd_max_cells; C->xcd_id = T->xcd_id; C->xcd_groups = T->xcd_groups;
+    C->opt_resident = T->opt_resident; C->opt_resident_lds = T->opt_resident_lds; C->opt_resident_serial = T->opt_resident_serial;
+    C->opt_resident_two_sided = T->opt_resident_two_sided; C->resident_max_dofs = T->resident_max_dofs; C->resident_serial_max_dofs = T->resident_serial_max_dofs;
+    C->cg_batch = T->cg_batch; C->opt_outer_dev = T->opt_outer_dev; C->direct_max_dofs = T->direct_max_dofs;
+    if (!same_mesh_kind) return;
+    // the tables of distinct lines are built under these: a cached twin whose values change drops its tables (as nf_set_option does)
+    const bool dict_moved = C->opt_line_dict != T->opt_line_dict || C->line_dict_dirs != T->line_dict_dirs || C->line_dict_fp_bits != T->line_dict_fp_bits ||
+                            C->line_dict_max_bytes != T->line_dict_max_bytes;
+    const bool regime_moved = C->opt_nt_loads != T->opt_nt_loads || C->nt_min_cells != T->nt_min_cells || C->opt_s_long != T->opt_s_long || C->opt_s_long_dirs != T->opt_s_long_dirs ||
+                              C->s_long_min != T->s_long_min || C->s_long_min_y != T->s_long_min_y || C->opt_s_seg != T->opt_s_seg || C->opt_s_tx != T->opt_s_tx;
+    C->opt_line_dict = T->opt_line_dict; C->line_dict_dirs = T->line_dict_dirs; C->line_dict_fp_bits = T->line_dict_fp_bits; C->line_dict_max_bytes = T->line_dict_max_bytes;
+    C->opt_nt_loads = T->opt_nt_loads; C->nt_min_cells = T->nt_min_cells; C->opt_s_long = T->opt_s_long; C->opt_s_long_dirs = T->opt_s_long_dirs;
+    C->s_long_min = T->s_long_min; C->s_long_min_y = T->s_long_min_y; C->opt_s_seg = T->opt_s_seg; C->opt_s_tx = T->opt_s_tx;
+    C->opt_wsmin = T->opt_wsmin; C->opt_c_early = T->opt_c_early; C->opt_x_p2 = T->opt_x_p2; C->opt_split_dot = T->opt_split_dot; C->opt_xcd = T->opt_xcd;
+    C->opt_xy_overlap = T->opt_xy_overlap; C->xy_overlap_max_cells = T->xy_overlap_max_cells; C->opt_vec_reduce = T->opt_vec_reduce;
+    C->opt_pub = T->opt_pub; C->opt_sens_grid = T->opt_sens_grid; C->prof_every = T->prof_every;
+    if (dict_moved) { (void)hipSetDevice(C->device); for (auto *X : C->slabs) line_dict_drop(X); }
+    else if (regime_moved) for (auto *X : C->slabs) if (!X->d_lid[0] && !X->d_lid[1] && !X->d_lid[2]) X->ld_tried = false;
+}
+
 // ---- SolveCoarse (src/NeutFEM.cpp:2380-2611) ---------------------------------------------------
 static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff, int *n_outer);
 
@@ -2659,9 +2690,7 @@ static int coarse_init(nf_team *T, const nf_keff_opts *o, double *k_coarse, cons
     if (CT) {
         CT->comm = T->comm; CT->nproc = T->nproc; CT->rank = T->rank; CT->rccl_reduce = T->rccl_reduce; CT->linked_ready = false;
         // tuning options (nf_set_option) apply to the coarse solve as well
-        CT->opt_cg1 = T->opt_cg1; CT->cg1_max_cells = T->cg1_max_cells; CT->opt_endpoint_w = T->opt_endpoint_w; CT->comm_x = T->comm_x; CT->opt_fuse = T->opt_fuse; CT->opt_lean = T->opt_lean; CT->opt_sepfold = T->opt_sepfold; CT->opt_lean_grid = T->opt_lean_grid; CT->lean_max_cells = T->lean_max_cells;
-        CT->opt_fuse3 = T->opt_fuse3; CT->fuse3_max_cells = T->fuse3_max_cells; CT->opt_cgx = T->opt_cgx; CT->opt_keffx = T->opt_keffx; CT->xcd_min_cells = T->xcd_min_cells; CT->xcd_max_cells = T->xcd_max_cells; CT->xcd_id = T->xcd_id; CT->xcd_groups = T->xcd_groups; CT->opt_resident = T->opt_resident; CT->opt_resident_lds = T->opt_resident_lds; CT->opt_resident_serial = T->opt_resident_serial; CT->opt_resident_two_sided = T->opt_resident_two_sided; CT->resident_max_dofs = T->resident_max_dofs; CT->resident_serial_max_dofs = T->resident_serial_max_dofs;
-        CT->cg_batch = T->cg_batch; CT->opt_outer_dev = T->opt_outer_dev; CT->direct_max_dofs = T->direct_max_dofs;
+        CT->comm_x = T->comm_x; team_copy_options(CT, T, false);
     }
     double kc = 1.0; int nout = 0;
     if (rc == NF_OK) {
@@ -3796,6 +3825,7 @@ static int transient_twin(nf_solver *S, double dt)
     auto body = [&]() -> int {
         if (F->dim != S->dim || F->N != N || F->nphi != S->nphi) return fail(NF_ERR_ARG, "nf_transient_step: the step operator's mesh differs from the handle's");
         for (int a = 0; a < 8; ++a) if (S->bc_set[a]) nf_set_bc(F, a, S->bc_type[a]);
+        team_copy_options(F->team, S->team, true);
         hipStream_t st = S->team->stream;
         NFCHK(dalloc(&F->d_D, NN)); NFCHK(dalloc(&F->d_SigR, NN)); NFCHK(dalloc(&F->d_NSF, NN)); NFCHK(dalloc(&F->d_Chi, NN));
         HIPCHK(hipMemcpyAsync(F->d_D, S->d_D, NN * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -3912,7 +3942,8 @@ int nf_transient_step(nf_handle S, const nf_keff_opts *o, double dt, int n_steps
     auto body = [&]() -> int {
         NFCHK(transient_twin(S, dt));
         nf_solver *F = R->twin; nf_team *TT = F->team; hipStream_t st = TT->stream;
-        const long xcd0 = TT->xcd_solves;
+        team_copy_options(TT, T, true);                           // the twin is kept across steps: an option set since the last one holds for this one
+        const long xcd0 = TT->xcd_solves, refused0 = TT->xcd_refused;
         NFCHK(team_prepare(TT));
         const InnerPlan ip = inner_plan(TT, o);
         T->last_direct = ip.dense ? 1 : ip.direct ? 2 : 0;
@@ -3940,7 +3971,10 @@ int nf_transient_step(nf_handle S, const nf_keff_opts *o, double dt, int n_steps
             if (!conv) ++r.n_unconverged;
             if (power_host) power_host[s] = R->production / R->P0;
         }
-        T->xcd_solves += TT->xcd_solves - xcd0;
+        // nf_info on the handle reports the step's solves; a one-XCD start the device refused switches the path off for the handle as well
+        T->xcd_solves += TT->xcd_solves - xcd0; T->xcd_refused += TT->xcd_refused - refused0;
+        if (TT->xcd_refused != refused0) { T->opt_cgx = TT->opt_cgx; T->opt_keffx = TT->opt_keffx; }
+        if (!ip.dense && r.n_outer > 0) { T->last_cg_form = TT->last_cg_form; T->last_cg_reductions = TT->last_cg_reductions; T->last_xcd = TT->last_xcd; }
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipGetLastError());
         return rc;
@@ -4016,6 +4050,7 @@ int nf_solve_adjoint(nf_handle S, const nf_keff_opts *o, int normalize_to_direct
     const bool dense = ip.dense;
     const double cg_tol = ip.cg_tol;
     const int cg_max = ip.cg_max;
+    T->last_direct = dense ? 1 : ip.direct ? 2 : 0;
     if (dense) NFCHK(dense_prepare(T));
     const int nmax = CHEB_NMAX; const double sigma = CHEB_SIGMA;
     double ca[16], cbv[16];
@@ -4265,6 +4300,7 @@ static int refine_impl(nf_solver *S, int rx, int ry, int rz, nf_handle *out)
     *out = F;
     if (F->dim != dim || F->N != P.NE) return fail(NF_ERR_ARG, "nf_refine: the refined mesh lost a dimension");
     for (int a = 0; a < 8; ++a) if (S->bc_set[a]) nf_set_bc(F, a, S->bc_type[a]);
+    team_copy_options(F->team, S->team, true);
     const size_t NN = (size_t)P.NE * ng;
     NFCHK(dalloc(&F->d_D, NN)); NFCHK(dalloc(&F->d_SigR, NN)); NFCHK(dalloc(&F->d_NSF, NN)); NFCHK(dalloc(&F->d_Chi, NN));
     refine_replicate(S, P, rx, ry, rz, S->d_D, F->d_D, ng); refine_replicate(S, P, rx, ry, rz, S->d_SigR, F->d_SigR, ng);
@@ -4576,6 +4612,7 @@ static int solve_modes_impl(nf_solver *S, const nf_keff_opts *o, int m, int b, i
     const int use_diag = (o->use_diagonal_solver && S->k == 0 && S->m == 0) ? 1 : 0;
     if (use_diag) NFCHK(nf_build_diagonal_cache(S));
     const InnerPlan ip = inner_plan(T, o);
+    T->last_direct = ip.dense ? 1 : ip.direct ? 2 : 0;
     if (!use_diag && ip.dense) NFCHK(dense_prepare(T));
     T->profile = false;
     DevTmp<double> Qb, Zb;

@@ -41,6 +41,7 @@ GAMMA = 0.4692
 Q = ((20, 6, 5), 2)                                               # RT2-P2
 FIXED_HI = FIXED[:4] + (5000,)                                    # RT1 / RT2: 5000 inner
 LAUNCH_FORMS = ("fuse3", "lean", "fused", "classic")             # what cg_plan may choose under a mask
+ADJOINT_BAR = 1e-7                                                # test_adjoint: adjoint flux against the oracle's (tests/test_gpu_driver_forms.py imports it)
 
 
 def void_mask(nx, ny, nz):
@@ -420,7 +421,7 @@ def test_adjoint():
     assert CG_FORMS[s.info("cg_form")] in LAUNCH_FORMS and s.info("xcd_solves") == 0
     err = rel_l2(s.get_phi_adj().ravel(), o.phi_adj_dofs().ravel())
     print(f"adjoint, fixed k: {n} outers, CG {s.history()['cg'].sum()} (oracle {o.history()['cg'].sum()}), rel_l2 = {err:.3e} (bar 1e-7)")
-    assert err < 1e-7
+    assert err < ADJOINT_BAR
     assert (s.get_phi_adj()[:, mask.ravel()] == 0).all() and (o.phi_adj_dofs()[:, mask.ravel()] == 0).all()
     tol5 = FIXED[:3] + (5,) + FIXED[4:]                           # 5 outers: before the Chebyshev step
     o.set_tol(*tol5); s.set_tol(*tol5)
@@ -428,7 +429,7 @@ def test_adjoint():
     errs = (np.abs(s.history()["k"] / o.history()["k"] - 1).max(), rel_l2(s.get_phi_adj().ravel(), o.phi_adj_dofs().ravel()))
     print(f"adjoint, free k: k-history {errs[0]:.3e} (bar 1e-8), rel_l2 = {errs[1]:.3e} (bar 1e-7)")
     np.testing.assert_allclose(s.history()["k"], o.history()["k"], rtol=1e-8)
-    assert errs[1] < 1e-7
+    assert errs[1] < ADJOINT_BAR
     s.close()
 
 
