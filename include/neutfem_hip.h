@@ -105,7 +105,7 @@ int nf_set_bc(nf_handle h, int attr, int bc_type);
  * S^-1.  NF_ERR_UNSUPPORTED (the text names nf_set_void; before any launch) with a mask for the calls that form A_ff themselves or build
  * a twin handle without the mask -- nf_solve_keff / nf_solve_adjoint with use_diagonal_solver (RT0-P0), use_cmfd or use_coarse_init,
  * nf_build_diagonal_cache, nf_initialize_cmfd, nf_solve_coarse, nf_coarsen, nf_refine, nf_zoom_source, nf_zoom_resolved, nf_sensitivity,
- * nf_transient_begin / nf_transient_step -- and for nf_solve_subcritical and nf_solve_modes. */
+ * nf_transient_begin / nf_transient_step -- and for nf_solve_subcritical, nf_solve_modes, nf_solve_gpt, nf_gpt_source and nf_gpt_sensitivity. */
 int nf_set_void(nf_handle h, const unsigned char *mask_host, double gamma);
 /* the mask (N bytes, 0 / 1; may be NULL) and gamma (may be NULL) as set; NF_ERR_STATE without a mask */
 int nf_get_void(nf_handle h, unsigned char *mask_host, double *gamma);
@@ -294,6 +294,56 @@ typedef struct nf_sens_result {
 } nf_sens_result;
 int nf_sensitivity(nf_handle h, double keff, double *dD_dev, double *dSigR_dev, double *dNSF_dev, double *dChi_dev, double *dSigS_dev,
                    nf_sens_result *res);
+
+/* ---- generalized adjoint and response-ratio sensitivity maps (no counterpart in the reference) -------------------------
+ * Generalized perturbation theory for a ratio of linear functionals of the flux.  With M phi = (1/k) F phi as in DESIGN.md 14, two weight
+ * fields w_a, w_b (ng N doubles [g*N + e], the layout of nf_upload_source; any finite values, fixed data),
+ *   <w, phi> = sum_g sum_e w[g,e] |e| phibar_g(e)   (phibar = DOF 0, |e| the cell measure),        R = <w_a, phi> / <w_b, phi>,
+ *   S+ = w_a |e| / <w_a, phi> - w_b |e| / <w_b, phi> on the DOF-0 rows, 0 on the higher moments (<S+, phi> = 0 by construction),
+ * the generalized adjoint solves (M - F/k)^T Gamma+ = S+ with <Gamma+, F phi> = 0, and for a parameter p the weights do not depend on
+ *   (1/R) dR/dp = -Gamma+^T (dM/dp - (1/k) dF/dp) phi:
+ * the bilinear forms of nf_sensitivity with Gamma+ in place of phi+ and c = -1 in place of -k^2 / Nrm (so -c/k = 1/k).
+ * nf_solve_gpt iterates from Gamma = 0 with the current flux, the adjoint flux and keff: per outer the adjoint fission term of the
+ * previous iterate, one Gauss-Seidel group sweep from the LAST group to the first on the transposed scatter blocks, in place (exact for
+ * downscatter-only data; nf_solve_adjoint's forward order is the reference's and stays), with the group solver nf_solve_keff picks, then
+ * the deflation Gamma -= (<Gamma, F phi> / <phi+, F phi>) phi+.  Stops when ||Gamma_n - Gamma_n-1|| / ||Gamma_n|| < tol_flux or after
+ * max_outer outers (NF_OK, converged = 0).  No normalisation, no acceleration: it contracts like the dominance ratio of the core.
+ * Reads tol_flux, max_outer, max_inner, solver_type, solver_type_pushed from opts; use_coarse_init, use_cmfd and use_diagonal_solver
+ * must be 0 and max_outer >= 1 (NF_ERR_ARG).  Gamma+, the weights and the two sums live on the handle until the next nf_upload_xs,
+ * nf_build, nf_set_bc, nf_set_void or nf_destroy; a failed solve leaves no Gamma+.  The current flux, the adjoint flux, nf_get_J, the
+ * warm k-eff state and the history are not touched; nf_info "last_direct" / "cg_form" report what ran.  Deterministic.
+ * Errors: not built, no adjoint flux (nf_solve_adjoint or nf_set_phi_adj first; the current flux always exists, all ones before a
+ * solve) -> NF_ERR_STATE; keff non-finite or <= 0, non-finite
+ * weights, w_a a multiple of w_b (S+ identically zero) -> NF_ERR_ARG; <w_a, phi>, <w_b, phi> or phi+^T F phi zero or non-finite, a
+ * non-finite iterate -> NF_ERR_NUMERIC; slabs and multi-rank teams, a handle with cut-out cells (nf_set_void) -> NF_ERR_UNSUPPORTED.
+ * After any error the handle stays usable. */
+typedef struct nf_gpt_result {
+    double R;                   /* <w_a, phi> / <w_b, phi> */
+    double wa_phi, wb_phi;      /* the two sums */
+    double dgamma;              /* ||Gamma_n - Gamma_n-1|| / ||Gamma_n|| of the last outer */
+    double ratio;               /* contraction: that change over the one of the outer before (0 after a single outer) */
+    double deflation;           /* |<Gamma+, F phi>| / (||Gamma+|| ||F phi||) after the last deflation */
+    double norm;                /* phi+^T F phi, the denominator of the deflation */
+    int n_outer, cg_total, converged;
+} nf_gpt_result;
+int nf_solve_gpt(nf_handle h, const nf_keff_opts *opts, double keff, const double *wa_host, const double *wb_host, nf_gpt_result *res);
+/* Gamma+ in the host DOF layout of nf_get_phi_adj / nf_set_phi_adj (ng n_phi doubles).  nf_get_gamma: NF_ERR_STATE without one;
+ * nf_set_gamma allocates it if needed and keeps the weights the handle holds */
+int nf_get_gamma(nf_handle h, double *gamma_host);
+int nf_set_gamma(nf_handle h, const double *gamma_host);
+/* The response and source kernels on their own: puts the weights on the handle (as nf_solve_gpt does; a Gamma+ solved for other weights
+ * is dropped), sums_host[0..1] = <w_a, phi>, <w_b, phi> of the current flux (may be NULL) and S+ in the host DOF layout of nf_get_phi
+ * (src_host, may be NULL).  Errors as nf_solve_gpt's for the state, the weights and the sums (the sums are stored before they are judged). */
+int nf_gpt_source(nf_handle h, const double *wa_host, const double *wb_host, double *src_host, double *sums_host);
+/* The maps (1/R) dR/dp per cell from the current flux, Gamma+ and keff: dD .. dSigS as nf_sensitivity defines them with (phi, Gamma+) and
+ * c = -1; dWa[g,e] = |e| phibar_g(e) / <w_a, phi> and dWb[g,e] = -|e| phibar_g(e) / <w_b, phi> (ng N doubles each), the direct maps of the
+ * weights themselves, with the sums taken from the current flux -- a caller whose weights are cross sections adds them to the indirect
+ * maps.  DEVICE buffers; any may be NULL and is then skipped (the others come out bit-identical).  res: norm = <Gamma+, F phi> as
+ * measured (0 up to rounding for a solved Gamma+; the maps do not divide by it), the keff used and the cell count.  Changes no state.
+ * Errors: not built, no Gamma+ (nf_solve_gpt or nf_set_gamma first), dWa / dWb without weights on the handle -> NF_ERR_STATE; keff
+ * non-finite or <= 0 -> NF_ERR_ARG; the rest as nf_sensitivity.  Option "sens_grid" caps the blocks of every GPT kernel too. */
+int nf_gpt_sensitivity(nf_handle h, double keff, double *dD_dev, double *dSigR_dev, double *dNSF_dev, double *dChi_dev, double *dSigS_dev,
+                       double *dWa_dev, double *dWb_dev, nf_sens_result *res);
 
 /* ---- lambda-modes: the leading eigenpairs by block power iteration (no counterpart in the reference) -------------------
  * With K0 = blockdiag(S_g) - Ms and F = chi (x) Mf (the matrices of nf_solve_subcritical): the n_modes largest eigenvalues

@@ -14,7 +14,7 @@ SYMBOLS = [
     "nf_last_error", "nf_device_count", "nf_create", "nf_destroy", "nf_create_slab", "nf_link_slabs", "nf_comm_unique_id",
     "nf_comm_init", "nf_comm_info", "nf_comm_selftest", "nf_team_schur_apply", "nf_info", "nf_set_bc", "nf_set_void", "nf_get_void", "nf_upload_xs", "nf_build",
     "nf_schur_apply", "nf_solve_group", "nf_build_diagonal_cache", "nf_get_diagonal_cache", "nf_solve_keff",
-    "nf_upload_source", "nf_solve_subcritical", "nf_solve_modes", "nf_get_mode", "nf_block_gram", "nf_block_rotate", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_apply_plan", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_project_flux", "nf_project_power", "nf_refine", "nf_zoom_source", "nf_get_source", "nf_set_phi_adj", "nf_zoom_resolved", "nf_sensitivity", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
+    "nf_upload_source", "nf_solve_subcritical", "nf_solve_modes", "nf_get_mode", "nf_block_gram", "nf_block_rotate", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_apply_plan", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_project_flux", "nf_project_power", "nf_refine", "nf_zoom_source", "nf_get_source", "nf_set_phi_adj", "nf_zoom_resolved", "nf_sensitivity", "nf_solve_gpt", "nf_get_gamma", "nf_set_gamma", "nf_gpt_source", "nf_gpt_sensitivity", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
     "nf_get_warm_state", "nf_get_history", "nf_profile_get", "nf_profile_reset", "nf_time_schur_apply", "nf_time_device_copy", "nf_progress", "nf_set_progress_callback", "nf_local_matrices",
     "nf_transient_begin", "nf_transient_step", "nf_get_precursors", "nf_transient_end",
     "nf_set_option", "nf_mem_info", "nf_dev_alloc", "nf_dev_free", "nf_memcpy_h2d", "nf_memcpy_d2h", "nf_synchronize", "nf_stream",
@@ -58,6 +58,13 @@ class ZoomResult(C.Structure):
 
 class SensResult(C.Structure):
     _fields_ = [("norm", C.c_double), ("keff", C.c_double), ("n_cells", C.c_long)]
+
+    def as_dict(self): return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class GptResult(C.Structure):
+    _fields_ = [("R", C.c_double), ("wa_phi", C.c_double), ("wb_phi", C.c_double), ("dgamma", C.c_double), ("ratio", C.c_double),
+                ("deflation", C.c_double), ("norm", C.c_double), ("n_outer", C.c_int), ("cg_total", C.c_int), ("converged", C.c_int)]
 
     def as_dict(self): return {name: getattr(self, name) for name, _ in self._fields_}
 
@@ -130,6 +137,11 @@ def load():
     L.nf_set_phi_adj.argtypes = [vp, dp]
     L.nf_zoom_resolved.argtypes = [vp, C.POINTER(KeffOpts), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(vp), C.POINTER(ZoomResult)]
     L.nf_sensitivity.argtypes = [vp, C.c_double, vp, vp, vp, vp, vp, C.POINTER(SensResult)]
+    L.nf_solve_gpt.argtypes = [vp, C.POINTER(KeffOpts), C.c_double, dp, dp, C.POINTER(GptResult)]
+    L.nf_get_gamma.argtypes = [vp, dp]
+    L.nf_set_gamma.argtypes = [vp, dp]
+    L.nf_gpt_source.argtypes = [vp, dp, dp, dp, dp]
+    L.nf_gpt_sensitivity.argtypes = [vp, C.c_double, vp, vp, vp, vp, vp, vp, vp, C.POINTER(SensResult)]
     L.nf_transient_begin.argtypes = [vp, C.POINTER(KineticsArgs), C.c_double]
     L.nf_transient_step.argtypes = [vp, C.POINTER(KeffOpts), C.c_double, C.c_int, dp, C.POINTER(TransientResult)]
     L.nf_get_precursors.argtypes = [vp, C.c_int, dp]
@@ -428,6 +440,56 @@ class HipSolver:
         res = SensResult()
         try:
             self._chk(self.L.nf_sensitivity(self.h, float(keff), *[bufs[w].ptr if w in bufs else None for w in self.SENS_MAPS], C.byref(res)))
+            out = {w: b.download().reshape((self.ng, self.ng, self.ne) if w == "SigS" else (self.ng, self.ne)) for w, b in bufs.items()}
+        finally:
+            for b in bufs.values(): b.free()
+        out["result"] = res.as_dict()
+        return out
+
+    GPT_MAPS = SENS_MAPS + ("Wa", "Wb")
+
+    def _weights(self, w):
+        a = np.ascontiguousarray(w, dtype=np.float64).ravel(); assert a.size == self.ng * self.ne
+        return a
+
+    def solve_gpt(self, wa, wb, keff=None, use_diag=False, use_coarse=False, factors=(), use_cmfd=False):
+        """nf_solve_gpt with the tolerances / linear solver of this object: the generalized adjoint of R = <wa, phi> / <wb, phi> (weights
+        (ng, cells), the layout of upload_source) at keff (None: the warm state's k); the result struct as a dict"""
+        if keff is None:
+            v, k = C.c_int(), C.c_double()
+            self._chk(self.L.nf_get_warm_state(self.h, C.byref(v), C.byref(k)))
+            keff = k.value
+        a, b = self._weights(wa), self._weights(wb)
+        o = self.opts(use_coarse, factors, use_diag, False, use_cmfd)
+        r = GptResult()
+        self._chk(self.L.nf_solve_gpt(self.h, C.byref(o), float(keff), _dp(a), _dp(b), C.byref(r)))
+        return r.as_dict()
+
+    def get_gamma(self):
+        """the generalized adjoint of the last solve_gpt (or set_gamma), (ng, n_phi) in the host DOF layout of get_phi_adj"""
+        out = np.empty(self.ng * self.n_phi); self._chk(self.L.nf_get_gamma(self.h, _dp(out))); return out.reshape(self.ng, self.n_phi)
+
+    def set_gamma(self, gamma):
+        a = np.ascontiguousarray(gamma, dtype=np.float64).ravel(); assert a.size == self.ng * self.n_phi
+        self._chk(self.L.nf_set_gamma(self.h, _dp(a)))
+
+    def gpt_source(self, wa, wb, want_source=True):
+        """nf_gpt_source: puts the weights on the handle; (S+ as (ng, n_phi) in the host DOF layout or None, (<wa, phi>, <wb, phi>))"""
+        a, b = self._weights(wa), self._weights(wb)
+        src = np.empty(self.ng * self.n_phi) if want_source else None
+        sums = np.zeros(2)
+        self._chk(self.L.nf_gpt_source(self.h, _dp(a), _dp(b), _dp(src) if want_source else None, _dp(sums)))
+        return (src.reshape(self.ng, self.n_phi) if want_source else None), (float(sums[0]), float(sums[1]))
+
+    def gpt_sensitivity(self, keff, which=GPT_MAPS):
+        """nf_gpt_sensitivity: the maps (1/R) dR/dp per cell named in `which` as host arrays -- "D", "SigR", "NSF", "Chi", "Wa", "Wb":
+        (ng, cells), "SigS": (ng, ng, cells) [g_to, g_from] -- plus "result": the nf_sens_result as a dict.  Maps not asked for are not computed"""
+        bad = [w for w in which if w not in self.GPT_MAPS]
+        if bad: raise ValueError(f"gpt_sensitivity: unknown map {bad[0]!r} (known: {self.GPT_MAPS})")
+        bufs = {w: DeviceVector(self, self.ng * self.ne * (self.ng if w == "SigS" else 1)) for w in self.GPT_MAPS if w in which}
+        res = SensResult()
+        try:
+            self._chk(self.L.nf_gpt_sensitivity(self.h, float(keff), *[bufs[w].ptr if w in bufs else None for w in self.GPT_MAPS], C.byref(res)))
             out = {w: b.download().reshape((self.ng, self.ng, self.ne) if w == "SigS" else (self.ng, self.ne)) for w, b in bufs.items()}
         finally:
             for b in bufs.values(): b.free()

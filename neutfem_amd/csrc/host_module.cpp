@@ -3,7 +3,7 @@
 //
 // The class keeps what the reference keeps on the host -- cross-section arrays, flux, tolerances,
 // BC map, warm-start flags -- and hands the hot path (BuildMatrices, SolveKeff, SolveCoarse,
-// build_diagonal_cache, SolveSubcritical, SolveModes, step_transient, set_void (handed over at BuildMatrices), project_flux, project_power, zoom_resolved, sensitivity_maps) to the HIP library.  There is NO CPU fallback:
+// build_diagonal_cache, SolveSubcritical, SolveModes, step_transient, set_void (handed over at BuildMatrices), project_flux, project_power, zoom_resolved, sensitivity_maps, SolveGPT, gpt_sensitivity_maps) to the HIP library.  There is NO CPU fallback:
 // without a HIP device those methods raise RuntimeError.  The reflector methods the reference binds are accepted and ignored.
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -521,6 +521,71 @@ public:
         return d;
     }
 
+    // SolveGPT (extension): the generalized adjoint of R = <numerator, phi> / <denominator, phi> (nf_solve_gpt) with
+    // k = last_keff_ and the fields of the host mirrors, pushed the way sensitivity_maps pushes them.  The weights are shaped like get_D().
+    double SolveGPT(py::array_t<double, py::array::c_style | py::array::forcecast> numerator,
+                    py::array_t<double, py::array::c_style | py::array::forcecast> denominator)
+    {
+        if (!h_) throw std::runtime_error("SolveGPT: call BuildMatrices() first (there is no CPU fallback)");
+        if (!has_valid_keff_ || !has_valid_adjoint_)
+            throw std::runtime_error(std::string("SolveGPT: call ") + (!has_valid_keff_ ? "SolveKeff()" : "SolveAdjoint()") +
+                                     " first (the generalized adjoint needs a solved flux, a solved adjoint flux and k-eff)");
+        if ((long)numerator.size() != (long)ng_ * ne_ || (long)denominator.size() != (long)ng_ * ne_)
+            throw std::runtime_error("SolveGPT: the weights must be shaped like get_D()");
+        Log(VerbosityLevel::NORMAL, "\n=== ADJOINT GENERALISE (GPT) ===");
+        chk(nf_set_phi(h_, Phi_.data())); chk(nf_set_phi_adj(h_, PhiAdj_.data()));
+        nf_keff_opts o = make_opts(false, {}, false);
+        nf_gpt_result r{};
+        has_gpt_ = false;
+        chk(nf_solve_gpt(h_, &o, last_keff_, numerator.data(), denominator.data(), &r));
+        Gamma_.resize((size_t)ng_ * nphi_);
+        chk(nf_get_gamma(h_, Gamma_.data()));
+        gpt_ = r; has_gpt_ = true;
+        return r.R;
+    }
+    py::array_t<double> GetGamma()
+    {
+        if (!has_gpt_) throw std::runtime_error("get_gamma: call SolveGPT() first");
+        return flux(Gamma_, gammaP0_);
+    }
+    // (1/R) dR/dp per cell from the solved flux, the generalized adjoint on the handle and last_keff_ (nf_gpt_sensitivity): a dict of
+    // arrays shaped like get_D() .. get_SigS(), plus the direct maps "Wa" / "Wb" of the weights, shaped like get_D()
+    py::dict GptSensitivityMaps()
+    {
+        if (!h_) throw std::runtime_error("gpt_sensitivity_maps: call BuildMatrices() first (there is no CPU fallback)");
+        if (!has_gpt_) throw std::runtime_error("gpt_sensitivity_maps: call SolveGPT() first");
+        chk(nf_set_phi(h_, Phi_.data()));
+        const size_t n1 = (size_t)ng_ * ne_, n2 = n1 * ng_;
+        struct DevBuf { nf_handle h; void *p = nullptr; ~DevBuf() { if (p) nf_dev_free(h, p); } } buf{h_};
+        chk(nf_dev_alloc(h_, (6 * n1 + n2) * sizeof(double), &buf.p));
+        double *d = static_cast<double *>(buf.p);
+        nf_sens_result r{};
+        chk(nf_gpt_sensitivity(h_, last_keff_, d, d + n1, d + 2 * n1, d + 3 * n1, d + 6 * n1, d + 4 * n1, d + 5 * n1, &r));
+        std::vector<py::ssize_t> shape; shape.push_back(ng_);
+        if (dim_ >= 3) shape.push_back(nz_);
+        if (dim_ >= 2) shape.push_back(ny_);
+        shape.push_back(nx_);
+        std::vector<py::ssize_t> shape2(shape); shape2.insert(shape2.begin(), ng_);
+        py::dict out;
+        const char *names[7] = { "D", "SigR", "NSF", "Chi", "Wa", "Wb", "SigS" };
+        for (int i = 0; i < 7; ++i) {
+            py::array_t<double> a(i == 6 ? shape2 : shape);
+            chk(nf_memcpy_d2h(h_, a.mutable_data(), d + (size_t)i * n1, (i == 6 ? n2 : n1) * sizeof(double)));
+            out[names[i]] = a;
+        }
+        gpt_norm_ = r.norm;
+        return out;
+    }
+    py::dict GetGptInfo() const
+    {
+        if (!has_gpt_) throw std::runtime_error("get_gpt_info: call SolveGPT() first");
+        py::dict d;
+        d["R"] = gpt_.R; d["wa_phi"] = gpt_.wa_phi; d["wb_phi"] = gpt_.wb_phi; d["dgamma"] = gpt_.dgamma; d["ratio"] = gpt_.ratio;
+        d["deflation"] = gpt_.deflation; d["norm"] = gpt_.norm; d["n_outer"] = gpt_.n_outer; d["cg_total"] = gpt_.cg_total;
+        d["converged"] = gpt_.converged; d["keff"] = last_keff_; d["gamma_F_phi"] = gpt_norm_;
+        return d;
+    }
+
     // ---- numpy views (src/NeutFEM.cpp:2626-2730) ---------------------------------------------------
     py::array_t<double> view(std::vector<double> &v, bool sigs = false)
     {
@@ -542,7 +607,7 @@ public:
 
     int dim_, nx_, ny_, nz_, ng_, rt_, p_, nloc_;
     long ne_, nphi_, nJ_, nJface_;
-    std::vector<double> xb_, yb_, zb_, D_, SRC_, SigR_, NSF_, KSF_, Chi_, SigS_, Phi_, PhiAdj_, fluxP0_, fluxAdjP0_;
+    std::vector<double> xb_, yb_, zb_, D_, SRC_, SigR_, NSF_, KSF_, Chi_, SigS_, Phi_, PhiAdj_, fluxP0_, fluxAdjP0_, Gamma_, gammaP0_;
     double last_keff_ = 1.0, last_keff_adj_ = 1.0;
 
 private:
@@ -599,6 +664,7 @@ private:
     nf_modes_result modes_[2]{}; bool has_modes_[2] = {false, false}; int last_modes_ = -1;   // the last SolveModes, direct / adjoint (get_modes_info)
     nf_zoom_result zoom_{}; bool has_zoom_ = false;               // the last zoom_resolved (get_zoom_info)
     nf_sens_result sens_{}; bool has_sens_ = false;               // the last sensitivity_maps (get_sensitivity_info)
+    nf_gpt_result gpt_{}; bool has_gpt_ = false; double gpt_norm_ = 0.0;   // the last SolveGPT (get_gpt_info); <Gamma+, F phi> of the last gpt_sensitivity_maps
     nf_transient_result transient_{}; bool has_transient_ = false;   // the last step_transient (get_transient_info)
 };
 
@@ -695,6 +761,12 @@ PYBIND11_MODULE(_neutfem_eigen, m)
         .def("sensitivity_maps", &NeutFEM::SensitivityMaps,
              "extension: dk/dXS per cell from the solved flux, the solved adjoint flux and GetLastKeff(): {'D', 'SigR', 'NSF', 'Chi', 'SigS'} shaped like get_D() .. get_SigS()")
         .def("get_sensitivity_info", &NeutFEM::GetSensitivityInfo, "extension: the last sensitivity_maps' nf_sens_result as a dict (norm, keff, n_cells)")
+        .def("SolveGPT", &NeutFEM::SolveGPT, py::arg("numerator"), py::arg("denominator"),
+             "extension: the generalized adjoint of R = <numerator, phi> / <denominator, phi> (weights shaped like get_D()) at GetLastKeff(); returns R")
+        .def("get_gamma", &NeutFEM::GetGamma, "extension: the generalized adjoint of the last SolveGPT, shaped like get_flux_adj()")
+        .def("gpt_sensitivity_maps", &NeutFEM::GptSensitivityMaps,
+             "extension: (1/R) dR/dp per cell: {'D', 'SigR', 'NSF', 'Chi', 'SigS'} shaped like get_D() .. get_SigS() and the direct maps 'Wa', 'Wb' of the weights")
+        .def("get_gpt_info", &NeutFEM::GetGptInfo, "extension: the last SolveGPT's nf_gpt_result as a dict (R, sums, outers, converged, contraction, deflation residual)")
         .def("begin_transient", &NeutFEM::BeginTransient, py::arg("velocity"), py::arg("beta"), py::arg("decay"), py::arg("chi_delayed") = py::none(),
              py::arg("keff") = py::none(),
              "extension: start a transient from the current flux: velocity per group, beta / decay per precursor family, chi_delayed per group (None: Chi), keff (None: GetLastKeff())")

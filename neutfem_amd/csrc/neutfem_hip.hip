@@ -233,6 +233,9 @@ struct nf_solver {
     double *d_phi_adj = nullptr;                        // adjoint flux, ng*nphi (allocated by the first adjoint solve)
     double *d_modes[2] = {nullptr, nullptr}; int modes_n[2] = {0, 0}, modes_cap[2] = {0, 0};   // lambda-modes of the last nf_solve_modes (direct / adjoint), modes_n * ng*nphi
     int has_valid_adjoint = 0; double last_keff_adj = 1.0;
+    // nf_solve_gpt: the generalized adjoint Gamma+ (ng*nphi; gpt_valid: it holds a finished solve or an nf_set_gamma), the two weight fields
+    // (2 * ng*N, [w_a | w_b]; nullptr before the first solve) and the device scalars of the last solve (GPT_SLOTS; <w_a,phi>, <w_b,phi> first)
+    double *d_gamma = nullptr, *d_gpt_w = nullptr, *d_gpt_sc = nullptr; bool gpt_valid = false;
     std::vector<double *> d_Ms;                          // ng*ng
     const double **d_Ms_tab = nullptr;                   // the same ng*ng pointers on the device (resident kernel)
     double *d_L[3] = {nullptr, nullptr, nullptr}, *d_DR[3] = {nullptr, nullptr, nullptr}, *d_D0[3] = {nullptr, nullptr, nullptr};
@@ -307,6 +310,7 @@ static void line_dict_drop(nf_solver *S)
 }
 
 static void modes_drop(nf_solver *S);
+static void gpt_drop(nf_solver *S);
 static void transient_drop(nf_solver *S);
 static bool team_is_single(const nf_team *T);
 
@@ -602,6 +606,7 @@ int nf_destroy(nf_handle S)
     dfree(S->d_phi); dfree(S->d_raw); dfree(S->d_p0); dfree(S->d_p1);
     dfree(S->d_tf); dfree(S->d_rhs); dfree(S->d_r); dfree(S->d_p); dfree(S->d_q); dfree(S->d_p2); dfree(S->d_qy); dfree(S->d_qz);
     dfree(S->d_qsrc); dfree(S->d_modes[0]); dfree(S->d_modes[1]);
+    dfree(S->d_gamma); dfree(S->d_gpt_w); dfree(S->d_gpt_sc);
     if (T) {
         T->slabs.erase(std::remove(T->slabs.begin(), T->slabs.end(), S), T->slabs.end());
         for (size_t i = 0; i < T->slabs.size(); ++i) T->slabs[i]->slab_index = (int)i;
@@ -739,7 +744,7 @@ int nf_set_bc(nf_handle S, int attr, int bc_type)
 {
     if (!S || attr < 0 || attr >= 8) return fail(NF_ERR_ARG, "nf_set_bc: bad attribute %d", attr);
     S->bc_set[attr] = 1; S->bc_type[attr] = bc_type; S->dense_valid = false;
-    coarse_cache_drop(S->team); line_dict_drop(S);
+    coarse_cache_drop(S->team); line_dict_drop(S); gpt_drop(S);
     return NF_OK;
 }
 
@@ -757,7 +762,7 @@ int nf_set_void(nf_handle S, const unsigned char *mask, double gamma)
     hipStream_t st = S->team->stream;
     // the operator, and whatever was derived from it, is stale until the next nf_build (as after nf_upload_xs)
     S->built = false; S->diag_valid = false; S->cmfd_init = false; S->cmfd_iface = false; S->dense_valid = false;
-    coarse_cache_drop(S->team); line_dict_drop(S); modes_drop(S);
+    coarse_cache_drop(S->team); line_dict_drop(S); modes_drop(S); gpt_drop(S);
     HIPCHK(hipStreamSynchronize(st));
     dfree(S->d_void); S->void_host.clear(); S->void_cells = 0; S->void_gamma = 0.0;
     if (cnt == 0) return NF_OK;                                   // a mask without a set byte is no mask
@@ -787,7 +792,7 @@ int nf_upload_xs(nf_handle S, const double *D, const double *SigR, const double 
     // the device copies are overwritten from here on: whatever was built from the old ones is stale until the next nf_build,
     // also when this upload is refused below (a refused upload leaves the handle un-built, never half-valid)
     S->xs_uploaded = false; S->built = false; S->diag_valid = false; S->cmfd_init = false; S->cmfd_iface = false; S->dense_valid = false;
-    coarse_cache_drop(S->team); line_dict_drop(S); modes_drop(S);
+    coarse_cache_drop(S->team); line_dict_drop(S); modes_drop(S); gpt_drop(S);
     NFCHK(dalloc(&S->d_D, NN)); NFCHK(dalloc(&S->d_SigR, NN)); NFCHK(dalloc(&S->d_NSF, NN)); NFCHK(dalloc(&S->d_Chi, NN));
     HIPCHK(hipMemcpyAsync(S->d_D, D, B, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(S->d_SigR, SigR, B, hipMemcpyHostToDevice, st));
@@ -833,7 +838,7 @@ int nf_build(nf_handle S)
     if (!S->xs_uploaded) return fail(NF_ERR_STATE, "nf_build: call nf_upload_xs first");
     if (S->d_void && !team_is_single(S->team)) return fail(NF_ERR_UNSUPPORTED, "nf_build: a slab team knows no cut-out cells (nf_set_void)");
     HIPCHK(hipSetDevice(S->device));
-    coarse_cache_drop(S->team); line_dict_drop(S); modes_drop(S);
+    coarse_cache_drop(S->team); line_dict_drop(S); modes_drop(S); gpt_drop(S);
     hipStream_t st = S->team->stream;
     const int ng = S->ng; const long N = S->N, NP = S->nphi; const size_t NN = (size_t)N * ng;
     NFCHK(dalloc(&S->d_Cd, (size_t)NP * ng)); NFCHK(dalloc(&S->d_Mf, (size_t)NP * ng)); NFCHK(dalloc(&S->d_Mchi, (size_t)NP * ng));
@@ -4436,7 +4441,7 @@ int nf_zoom_resolved(nf_handle S, const nf_keff_opts *o, int rx, int ry, int rz,
 
 // ---- sensitivity maps: dk/dXS per cell from the current flux, the adjoint flux and an eigenvalue -----------------------
 // one launch of a kernel template <DIM, M> over the handle's order: NF_SENS_DM(k_sens_norm, part) / NF_SENS_DM(k_sens_mass, sc, maps...)
-#define NF_SENS_FIELDS(S) (const double *)(S)->d_phi, (const double *)(S)->d_phi_adj, (const double *)(S)->d_Chi, (const double *)(S)->d_NSF, \
+#define NF_SENS_FIELDS(S) (const double *)(S)->d_phi, adj, (const double *)(S)->d_Chi, (const double *)(S)->d_NSF, \
                           (const double *)(S)->d_hx, (const double *)(S)->d_hy, (const double *)(S)->d_hz, (S)->nx, (S)->ny, (S)->N, (S)->nphi, (S)->ng
 #define NF_SENS_M(KERNEL, DIM, ...) do { \
         if (S->m == 0) hipLaunchKernelGGL((KERNEL<DIM, 0>), dim3(grid), dim3(256), 0, st, NF_SENS_FIELDS(S), __VA_ARGS__); \
@@ -4444,8 +4449,9 @@ int nf_zoom_resolved(nf_handle S, const nf_keff_opts *o, int rx, int ry, int rz,
         else hipLaunchKernelGGL((KERNEL<DIM, 2>), dim3(grid), dim3(256), 0, st, NF_SENS_FIELDS(S), __VA_ARGS__); } while (0)
 #define NF_SENS_DM(KERNEL, ...) do { \
         if (S->dim == 1) NF_SENS_M(KERNEL, 1, __VA_ARGS__); else if (S->dim == 2) NF_SENS_M(KERNEL, 2, __VA_ARGS__); else NF_SENS_M(KERNEL, 3, __VA_ARGS__); } while (0)
-static void launch_sens_norm(const nf_solver *S, int grid, hipStream_t st, double *part) { NF_SENS_DM(k_sens_norm, part); }
-static void launch_sens_mass(const nf_solver *S, int grid, hipStream_t st, const double *sc, double *dSigR, double *dNSF, double *dChi, double *dSigS)
+// adj: the adjoint-side field of the bilinear forms (phi+ for nf_sensitivity, Gamma+ for nf_gpt_sensitivity)
+static void launch_sens_norm(const nf_solver *S, const double *adj, int grid, hipStream_t st, double *part) { NF_SENS_DM(k_sens_norm, part); }
+static void launch_sens_mass(const nf_solver *S, const double *adj, int grid, hipStream_t st, const double *sc, double *dSigR, double *dNSF, double *dChi, double *dSigS)
 {
     NF_SENS_DM(k_sens_mass, sc, dSigR, dNSF, dChi, dSigS);
 }
@@ -4460,31 +4466,39 @@ static void launch_sens_current_d(const nf_solver *S, int grid, hipStream_t st, 
     else if (S->k == 1) hipLaunchKernelGGL((k_sens_current<DIM, 1>), dim3(grid), dim3(256), 0, st, G, O, j, ja, D, sc, S->N, dD);
     else hipLaunchKernelGGL((k_sens_current<DIM, 2>), dim3(grid), dim3(256), 0, st, G, O, j, ja, D, sc, S->N, dD);
 }
-int nf_sensitivity(nf_handle S, double keff, double *dD, double *dSigR, double *dNSF, double *dChi, double *dSigS, nf_sens_result *res)
+static int gpt_grid(const nf_solver *S, long n) { return grid_for(n, 256, S->team->opt_sens_grid); }
+// The bilinear forms of DESIGN.md 14 on (phi, adj) with the three device scalars (Nrm, c, -c / k) of one of two scalar kernels:
+// gpt = false: k_sens_norm + k_sens_scalars (c = -k^2 / Nrm; Nrm zero or non-finite is an error) -- nf_sensitivity, launch for launch what
+// it always issued; gpt = true: k_fission + k_gpt_defl_dot + k_gpt_scalars (Nrm = <adj, F phi> as measured, c = -1) -- nf_gpt_sensitivity.
+// The caller has checked the state; who names it in the messages.
+static int sens_body(nf_solver *S, const double *adj, bool gpt, const char *who, double keff, double *dD, double *dSigR, double *dNSF, double *dChi,
+                     double *dSigS, double *nrm_out)
 {
-    if (!S) return fail(NF_ERR_ARG, "nf_sensitivity: bad arguments");
-    NFCHK(void_refuse(S, "nf_sensitivity"));
-    if (!std::isfinite(keff) || !(keff > 0.0)) return fail(NF_ERR_ARG, "nf_sensitivity: keff must be finite and positive (got %g)", keff);
-    if (!team_is_single(S->team)) return fail(NF_ERR_UNSUPPORTED, "nf_sensitivity works on an undivided mesh (the z currents cross slabs: slab teams and multi-rank teams are not supported)");
-    if (S->N > 0xFFFFFFFFL) return fail(NF_ERR_UNSUPPORTED, "nf_sensitivity: %ld cells (the kernels index cells with 32 bits)", S->N);
-    if (!S->built) return fail(NF_ERR_STATE, "nf_sensitivity: call nf_build first");
-    if (!S->d_phi_adj) return fail(NF_ERR_STATE, "nf_sensitivity: no adjoint flux (nf_solve_adjoint or nf_set_phi_adj first)");
-    HIPCHK(hipSetDevice(S->device));
-    (void)hipGetLastError();
     hipStream_t st = S->team->stream;
     const long N = S->N;
     const int ng = S->ng, grid = grid_for(N, 256, S->team->opt_sens_grid);
-    DevTmp<double> part; NFCHK(dalloc(&part.p, (size_t)grid + 3));     // the blocks' shares of Nrm, then Nrm, c, -c / k
-    double *sc = part.p + grid;
-    launch_sens_norm(S, grid, st, part.p);
-    hipLaunchKernelGGL(k_sens_scalars, dim3(1), dim3(256), 0, st, (const double *)part.p, grid, keff, sc);
+    const int gx = gpt_grid(S, S->nphi), npart = gpt ? std::max(2 * gx * ng, grid) : grid;
+    DevTmp<double> part; NFCHK(dalloc(&part.p, (size_t)npart + 3));    // the blocks' shares of Nrm, then Nrm, c, -c / k
+    double *sc = part.p + npart;
+    DevTmp<double> tf;
+    if (gpt) {
+        NFCHK(dalloc(&tf.p, (size_t)S->nphi));
+        hipLaunchKernelGGL(k_fission, dim3(grid_for(S->nphi)), dim3(256), 0, st, S->d_Mf, S->d_phi, ng, S->nphi, tf.p, S->team->d_partials, (const double *)nullptr, 0L);
+        hipLaunchKernelGGL(k_gpt_defl_dot, dim3(gx, ng), dim3(256), 0, st, adj, (const double *)S->d_Chi, (const double *)tf.p, N, S->nphi, part.p, (long)gx * ng);
+        hipLaunchKernelGGL(k_gpt_scalars, dim3(1), dim3(256), 0, st, (const double *)part.p, gx * ng, keff, sc);
+    } else {
+        launch_sens_norm(S, adj, grid, st, part.p);
+        hipLaunchKernelGGL(k_sens_scalars, dim3(1), dim3(256), 0, st, (const double *)part.p, grid, keff, sc);
+    }
     double nrm = 0.0;
     HIPCHK(hipMemcpyAsync(&nrm, sc, sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipGetLastError());
-    if (!std::isfinite(nrm) || nrm == 0.0)
-        return fail(NF_ERR_NUMERIC, "nf_sensitivity: the normalisation phi+^T F phi = %g is not usable (orthogonal, zero or non-finite fields, or no fission)", nrm);
-    if (dSigR || dNSF || dChi || dSigS) launch_sens_mass(S, grid, st, sc, dSigR, dNSF, dChi, dSigS);
+    if (!gpt && (!std::isfinite(nrm) || nrm == 0.0))
+        return fail(NF_ERR_NUMERIC, "%s: the normalisation phi+^T F phi = %g is not usable (orthogonal, zero or non-finite fields, or no fission)", who, nrm);
+    if (gpt && !std::isfinite(nrm))
+        return fail(NF_ERR_NUMERIC, "%s: Gamma+^T F phi = %g is not finite (non-finite fields)", who, nrm);
+    if (dSigR || dNSF || dChi || dSigS) launch_sens_mass(S, adj, grid, st, sc, dSigR, dNSF, dChi, dSigS);
     DevTmp<double> J, Ja;
     if (dD) {
         NFCHK(dalloc(&J.p, (size_t)S->nJ)); NFCHK(dalloc(&Ja.p, (size_t)S->nJ));
@@ -4495,7 +4509,7 @@ int nf_sensitivity(nf_handle S, double keff, double *dD, double *dSigR, double *
         for (int d = 0; d < 3; ++d) O.boff[d] = nJface + (long)d * N * ni;
         for (int g = 0; g < ng; ++g) {                            // group by group: two temporaries of nJ doubles
             NFCHK(flux_to_J(S, g, S->d_phi + (size_t)g * S->nphi, J.p, S->dim, 0, st));
-            NFCHK(flux_to_J(S, g, S->d_phi_adj + (size_t)g * S->nphi, Ja.p, S->dim, 0, st));
+            NFCHK(flux_to_J(S, g, adj + (size_t)g * S->nphi, Ja.p, S->dim, 0, st));
             const double *Dg = S->d_D + (size_t)g * N; double *out = dD + (size_t)g * N;
             if (S->dim == 1) launch_sens_current_d<1>(S, grid, st, G, O, J.p, Ja.p, Dg, sc, out);
             else if (S->dim == 2) launch_sens_current_d<2>(S, grid, st, G, O, J.p, Ja.p, Dg, sc, out);
@@ -4504,7 +4518,28 @@ int nf_sensitivity(nf_handle S, double keff, double *dD, double *dSigR, double *
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));                             // the temporaries are freed on return
-    if (res) { res->norm = nrm; res->keff = keff; res->n_cells = N; }
+    *nrm_out = nrm;
+    return NF_OK;
+}
+static int sens_args(nf_handle S, double keff, const char *who)
+{
+    if (!S) return fail(NF_ERR_ARG, "%s: bad arguments", who);
+    NFCHK(void_refuse(S, who));
+    if (!std::isfinite(keff) || !(keff > 0.0)) return fail(NF_ERR_ARG, "%s: keff must be finite and positive (got %g)", who, keff);
+    if (!team_is_single(S->team)) return fail(NF_ERR_UNSUPPORTED, "%s works on an undivided mesh (the z currents cross slabs: slab teams and multi-rank teams are not supported)", who);
+    if (S->N > 0xFFFFFFFFL) return fail(NF_ERR_UNSUPPORTED, "%s: %ld cells (the kernels index cells with 32 bits)", who, S->N);
+    if (!S->built) return fail(NF_ERR_STATE, "%s: call nf_build first", who);
+    return NF_OK;
+}
+int nf_sensitivity(nf_handle S, double keff, double *dD, double *dSigR, double *dNSF, double *dChi, double *dSigS, nf_sens_result *res)
+{
+    NFCHK(sens_args(S, keff, "nf_sensitivity"));
+    if (!S->d_phi_adj) return fail(NF_ERR_STATE, "nf_sensitivity: no adjoint flux (nf_solve_adjoint or nf_set_phi_adj first)");
+    HIPCHK(hipSetDevice(S->device));
+    (void)hipGetLastError();
+    double nrm = 0.0;
+    NFCHK(sens_body(S, S->d_phi_adj, false, "nf_sensitivity", keff, dD, dSigR, dNSF, dChi, dSigS, &nrm));
+    if (res) { res->norm = nrm; res->keff = keff; res->n_cells = S->N; }
     return NF_OK;
 }
 
@@ -4771,6 +4806,261 @@ int nf_get_mode(nf_handle S, int i, int adjoint, double *phi_host)
     if (!S->modes_n[a]) return fail(NF_ERR_STATE, "nf_get_mode: no %s modes on this handle (nf_solve_modes first; nf_build and nf_upload_xs drop them)", a ? "adjoint" : "direct");
     if (i < 0 || i >= S->modes_n[a]) return fail(NF_ERR_ARG, "nf_get_mode: mode %d of %d", i, S->modes_n[a]);
     return phi_transfer(S, phi_host, false, S->d_modes[a] + (size_t)i * S->nphi * S->ng);
+}
+
+// ---- SolveGPT: the generalized adjoint of a response ratio and its sensitivity maps (no counterpart in the reference) ----
+// R = <w_a, phi> / <w_b, phi>; (M - F / k)^T Gamma+ = S+ with <Gamma+, F phi> = 0, by the fixed-source adjoint iteration at criticality with
+// the fundamental mode deflated after every outer.  Host-driven like solve_modes_impl, on vectors of its own: phi, phi+, d_raw, the warm
+// state and the history are not touched.
+static void gpt_drop(nf_solver *S)
+{
+    if (S->team && S->team->stream && (S->d_gamma || S->d_gpt_w)) (void)hipStreamSynchronize(S->team->stream);
+    dfree(S->d_gamma); dfree(S->d_gpt_w); dfree(S->d_gpt_sc); S->gpt_valid = false;
+}
+// partial rows of the GPT kernels (2 rows of `stride` doubles) and their sums into the device slots sc[slot0], sc[slot0 + 1]
+struct GptWork { DevTmp<double> part; long stride = 0; };
+static void gpt_finalize(nf_team *T, GptWork &W, int cnt, double *sc, int slot0)
+{
+    hipLaunchKernelGGL(k_block_finalize, dim3(2), dim3(256), 0, T->stream, (const double *)W.part.p, W.stride, cnt, sc + slot0);
+}
+// the weights on the device ([w_a | w_b], kept on the handle), <w_a, phi> and <w_b, phi> of the current flux into sc[GPT_WA], sc[GPT_WB]
+// and on the host
+static int gpt_response(nf_solver *S, GptWork &W, double *sc, double *sums)
+{
+    nf_team *T = S->team; hipStream_t st = T->stream;
+    const long N = S->N; const int ng = S->ng, gc = gpt_grid(S, N);
+    hipLaunchKernelGGL(k_gpt_response, dim3(gc, ng), dim3(256), 0, st, (const double *)S->d_phi, (const double *)S->d_gpt_w, (const double *)(S->d_gpt_w + (size_t)ng * N),
+                       (const double *)S->d_hx, (const double *)S->d_hy, (const double *)S->d_hz, S->nx, S->ny, N, S->nphi, W.part.p, W.stride);
+    gpt_finalize(T, W, gc * ng, sc, GPT_WA);
+    HIPCHK(hipMemcpyAsync(sums, sc + GPT_WA, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(stream_wait(st));
+    return NF_OK;
+}
+static int gpt_work(nf_solver *S, GptWork &W)
+{
+    W.stride = (long)S->team->opt_sens_grid * S->ng;
+    return dalloc(&W.part.p, (size_t)2 * W.stride);
+}
+// the checks every GPT entry shares, before any launch
+static int gpt_args(nf_handle S, double keff, const char *who)
+{
+    if (!S) return fail(NF_ERR_ARG, "%s: bad arguments", who);
+    NFCHK(void_refuse(S, who));
+    if (S->team->dead) return fail(NF_ERR_COMM, "this team lost a collective (NF_ERR_COMM) and is unusable: destroy the handles and end the process with a non-zero code (never re-exec)");
+    if (!std::isfinite(keff) || !(keff > 0.0)) return fail(NF_ERR_ARG, "%s: keff must be finite and positive (got %g)", who, keff);
+    if (!team_is_single(S->team) || S->team->nproc > 1)
+        return fail(NF_ERR_UNSUPPORTED, "%s works on an undivided mesh (slab teams and multi-rank teams are not supported)", who);
+    if (!S->built) return fail(NF_ERR_STATE, "%s: call nf_build first", who);
+    if (!S->d_phi_adj) return fail(NF_ERR_STATE, "%s: no adjoint flux (nf_solve_adjoint or nf_set_phi_adj first)", who);
+    return NF_OK;
+}
+// non-finite weights, and weights that make S+ vanish identically (w_a = lambda w_b: R does not depend on phi)
+static int gpt_check_weights(const nf_solver *S, const double *wa, const double *wb, const char *who)
+{
+    const long n = (long)S->ng * S->N;
+    long ja = -1, jb = -1;
+    for (long i = 0; i < n; ++i) {
+        if (!std::isfinite(wa[i]) || !std::isfinite(wb[i]))
+            return fail(NF_ERR_ARG, "%s: non-finite weight in group %ld, cell %ld", who, i / S->N, i % S->N);
+        if (ja < 0 && wa[i] != 0.0) ja = i;
+        if (jb < 0 && wb[i] != 0.0) jb = i;
+    }
+    if (ja < 0 || jb < 0) return NF_OK;                           // a zero field: its sum is zero, reported as such (NF_ERR_NUMERIC)
+    bool prop = true;
+    for (long i = 0; i < n && prop; ++i) prop = wa[i] * wb[jb] == wb[i] * wa[jb];
+    if (prop) return fail(NF_ERR_ARG, "%s: the source S+ is identically zero (w_a is a multiple of w_b: the ratio does not depend on the flux)", who);
+    return NF_OK;
+}
+static int gpt_upload_weights(nf_solver *S, const double *wa, const double *wb)
+{
+    const size_t n = (size_t)S->ng * S->N;
+    hipStream_t st = S->team->stream;
+    if (!S->d_gpt_w) NFCHK(dalloc(&S->d_gpt_w, 2 * n));
+    if (!S->d_gpt_sc) NFCHK(dalloc(&S->d_gpt_sc, (size_t)GPT_SLOTS));
+    HIPCHK(hipMemsetAsync(S->d_gpt_sc, 0, GPT_SLOTS * sizeof(double), st));
+    HIPCHK(hipMemcpyAsync(S->d_gpt_w, wa, n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(S->d_gpt_w + n, wb, n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));                             // the host arrays are the caller's
+    return NF_OK;
+}
+static int gpt_check_sums(const double *sums, const char *who)
+{
+    if (!std::isfinite(sums[0]) || sums[0] == 0.0) return fail(NF_ERR_NUMERIC, "%s: the numerator <w_a, phi> = %g is not usable (zero or non-finite)", who, sums[0]);
+    if (!std::isfinite(sums[1]) || sums[1] == 0.0) return fail(NF_ERR_NUMERIC, "%s: the denominator <w_b, phi> = %g is not usable (zero or non-finite)", who, sums[1]);
+    return NF_OK;
+}
+
+static int solve_gpt_impl(nf_solver *S, const nf_keff_opts *o, double keff, nf_gpt_result *res)
+{
+    nf_team *T = S->team;
+    const int ng = S->ng; const long N = S->N, NP = S->nphi, NT = NP * ng;
+    hipStream_t st = T->stream;
+    NFCHK(team_prepare(T));
+    const InnerPlan ip = inner_plan(T, o);
+    T->last_direct = ip.dense ? 1 : ip.direct ? 2 : 0;
+    if (ip.dense) NFCHK(dense_prepare(T));
+    T->profile = false;
+    GptWork W; NFCHK(gpt_work(S, W));
+    double *sc = S->d_gpt_sc;
+    const int gN = grid_for(NP), gx = gpt_grid(S, NP);
+    nf_gpt_result r; memset(&r, 0, sizeof r);
+    double sums[2];
+    NFCHK(gpt_response(S, W, sc, sums));
+    NFCHK(gpt_check_sums(sums, "nf_solve_gpt"));
+    r.wa_phi = sums[0]; r.wb_phi = sums[1]; r.R = sums[0] / sums[1];
+    // tf = sum_g' Mf_g' phi_g', once per call: F phi = chi (x) tf is never stored; the denominator <phi+, F phi> and ||F phi||^2
+    DevTmp<double> tfphi, src, old;
+    NFCHK(dalloc(&tfphi.p, (size_t)NP)); NFCHK(dalloc(&src.p, (size_t)NT)); NFCHK(dalloc(&old.p, (size_t)NT));
+    hipLaunchKernelGGL(k_fission, dim3(gN), dim3(256), 0, st, S->d_Mf, S->d_phi, ng, NP, tfphi.p, T->d_partials, (const double *)nullptr, 0L);
+    hipLaunchKernelGGL(k_gpt_defl_dot, dim3(gx, ng), dim3(256), 0, st, (const double *)S->d_phi_adj, (const double *)S->d_Chi, (const double *)tfphi.p, N, NP, W.part.p, W.stride);
+    gpt_finalize(T, W, gx * ng, sc, GPT_DEN);
+    double den[2];
+    HIPCHK(hipMemcpyAsync(den, sc + GPT_DEN, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(stream_wait(st));
+    if (!std::isfinite(den[0]) || den[0] == 0.0)
+        return fail(NF_ERR_NUMERIC, "nf_solve_gpt: the normalisation phi+^T F phi = %g is not usable (orthogonal, zero or non-finite fields, or no fission)", den[0]);
+    const double *wa = S->d_gpt_w, *wb = S->d_gpt_w + (size_t)ng * N;
+    hipLaunchKernelGGL(k_gpt_source, dim3(gx, ng), dim3(256), 0, st, (const double *)S->d_phi, wa, wb, (const double *)sc, (const double *)S->d_hx, (const double *)S->d_hy,
+                       (const double *)S->d_hz, S->nx, S->ny, N, NP, src.p, (double *)nullptr, (double *)nullptr);
+    if (!S->d_gamma) NFCHK(dalloc(&S->d_gamma, (size_t)NT));
+    S->gpt_valid = false;                                         // until the iteration has finished
+    double *G = S->d_gamma;
+    HIPCHK(hipMemsetAsync(G, 0, (size_t)NT * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(old.p, 0, (size_t)NT * sizeof(double), st));
+    ScatterArgs sa; sa.ng = ng;
+    const double inv_k = 1.0 / keff;
+    double dprev = 0.0, h[3];
+    bool conv = false;
+    for (int it = 0; it < o->max_outer; ++it) {
+        // the adjoint fission term of the previous iterate, then the group sweep from the last group to the first on the transposed
+        // scatter blocks, in place: with downscatter only every scatter term reads a group this sweep has already solved
+        hipLaunchKernelGGL(k_fission, dim3(gN), dim3(256), 0, st, S->d_Mchi, (const double *)G, ng, NP, S->d_tf, T->d_partials, (const double *)nullptr, 0L);
+        for (int s = 0; s < ng; ++s) {
+            const int g = ng - 1 - s;
+            for (int gp = 0; gp < 64; ++gp) sa.M[gp] = gp < ng ? S->d_Ms[gp * ng + g] : nullptr;
+            // in the descending sweep the groups above g are the new ones: k_group_rhs reads both from the one array
+            double *sol = G + (size_t)g * NP;
+            const bool cgi = !ip.dense;
+            hipLaunchKernelGGL(k_group_rhs<true>, dim3(gN), dim3(256), 0, st, sa, g, S->d_NSF + g * N, S->d_tf, inv_k, (const double *)G, (const double *)G,
+                               (const double *)nullptr, S->d_rhs, NP, N,
+                               cgi ? sol : (double *)nullptr, cgi ? S->d_r : (double *)nullptr, cgi ? S->d_p : (double *)nullptr,
+                               cgi ? T->d_partials : (double *)nullptr, (const double *)(src.p + (size_t)g * NP));
+            int its = 0; double cres = 0.0;
+            if (ip.dense) { dense_solve(T, g, S->d_rhs, sol); its = 1; }
+            else {
+                NFCHK(cg_solve(T, g, { (const double *)S->d_rhs }, { sol }, ip.cg_tol, ip.cg_max, &its, &cres, true));
+                if (ip.direct && !(cres <= 1e-14)) ++T->standin_unconverged;
+            }
+            r.cg_total += its;
+        }
+        // deflation: Gamma -= (<Gamma, F phi> / <phi+, F phi>) phi+, beta formed on the device; norms and old <- Gamma in the same sweep
+        hipLaunchKernelGGL(k_gpt_defl_dot, dim3(gx, ng), dim3(256), 0, st, (const double *)G, (const double *)S->d_Chi, (const double *)tfphi.p, N, NP, W.part.p, W.stride);
+        hipLaunchKernelGGL(k_block_finalize, dim3(1), dim3(256), 0, st, (const double *)W.part.p, W.stride, gx * ng, sc + GPT_NUM);
+        hipLaunchKernelGGL(k_gpt_defl_update, dim3(gx, ng), dim3(256), 0, st, G, (const double *)S->d_phi_adj, old.p, (const double *)sc, NP, W.part.p, W.stride);
+        gpt_finalize(T, W, gx * ng, sc, GPT_NN);
+        HIPCHK(hipMemcpyAsync(h, sc + GPT_NUM, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(stream_wait(st));
+        const double nsq = h[1], dsq = h[2], dg = std::sqrt(dsq / nsq);
+        r.n_outer = it + 1;
+        __atomic_store_n(&T->outers_done, (long)(it + 1), __ATOMIC_RELEASE);
+        if (!std::isfinite(h[0]) || !std::isfinite(nsq) || !std::isfinite(dg))
+            return fail(NF_ERR_NUMERIC, "nf_solve_gpt: the iteration produced a non-finite iterate (outer %d: <Gamma, F phi> = %g, ||Gamma||^2 = %g, ||dGamma||^2 = %g)", it, h[0], nsq, dsq);
+        r.ratio = dprev > 0.0 ? dg / dprev : 0.0;
+        r.dgamma = dg; dprev = dg;
+        if (dg < o->tol_flux) { conv = true; break; }
+    }
+    // what the last deflation left of the fundamental mode: |<Gamma, F phi>| / (||Gamma|| ||F phi||)
+    hipLaunchKernelGGL(k_gpt_defl_dot, dim3(gx, ng), dim3(256), 0, st, (const double *)G, (const double *)S->d_Chi, (const double *)tfphi.p, N, NP, W.part.p, W.stride);
+    hipLaunchKernelGGL(k_block_finalize, dim3(1), dim3(256), 0, st, (const double *)W.part.p, W.stride, gx * ng, sc + GPT_NUM);
+    HIPCHK(hipMemcpyAsync(h, sc + GPT_NUM, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    r.deflation = std::fabs(h[0]) / (std::sqrt(h[1]) * std::sqrt(den[1]));
+    if (!std::isfinite(r.deflation)) return fail(NF_ERR_NUMERIC, "nf_solve_gpt: the iterate came out zero or non-finite (<Gamma, F phi> = %g, ||Gamma||^2 = %g)", h[0], h[1]);
+    r.norm = den[0];
+    r.converged = conv ? 1 : 0;
+    S->gpt_valid = true;
+    if (res) *res = r;
+    return NF_OK;
+}
+
+int nf_solve_gpt(nf_handle S, const nf_keff_opts *o, double keff, const double *wa_host, const double *wb_host, nf_gpt_result *res)
+{
+    if (!S || !o || !wa_host || !wb_host) return fail(NF_ERR_ARG, "nf_solve_gpt: bad arguments");
+    NFCHK(gpt_args(S, keff, "nf_solve_gpt"));
+    if (o->use_coarse_init || o->use_cmfd || o->use_diagonal_solver)
+        return fail(NF_ERR_ARG, "nf_solve_gpt: coarse start, CMFD and the diagonal model do not apply to the generalized adjoint (use_coarse_init, use_cmfd and use_diagonal_solver must be 0)");
+    if (o->max_outer < 1) return fail(NF_ERR_ARG, "nf_solve_gpt: max_outer must be at least 1");
+    NFCHK(gpt_check_weights(S, wa_host, wb_host, "nf_solve_gpt"));
+    HIPCHK(hipSetDevice(S->device));
+    (void)hipGetLastError();
+    S->gpt_valid = false;                                         // the weights below replace those Gamma+ was solved for
+    int rc = gpt_upload_weights(S, wa_host, wb_host);
+    if (rc == NF_OK) rc = solve_gpt_impl(S, o, keff, res);
+    if (rc != NF_OK) { (void)hipStreamSynchronize(S->team->stream); (void)hipGetLastError(); }
+    return rc;
+}
+int nf_get_gamma(nf_handle S, double *gamma_host)
+{
+    if (!S || !gamma_host) return fail(NF_ERR_ARG, "nf_get_gamma: bad arguments");
+    if (!S->gpt_valid) return fail(NF_ERR_STATE, "nf_get_gamma: no generalized adjoint on this handle (nf_solve_gpt or nf_set_gamma first; nf_upload_xs, nf_build, nf_set_bc and nf_set_void drop it)");
+    return phi_transfer(S, gamma_host, false, S->d_gamma);
+}
+int nf_set_gamma(nf_handle S, const double *gamma_host)
+{
+    if (!S || !gamma_host) return fail(NF_ERR_ARG, "nf_set_gamma: bad arguments");
+    HIPCHK(hipSetDevice(S->device));
+    if (!S->d_gamma) NFCHK(dalloc(&S->d_gamma, (size_t)S->nphi * S->ng));
+    NFCHK(phi_transfer(S, const_cast<double *>(gamma_host), true, S->d_gamma));
+    S->gpt_valid = true;
+    return NF_OK;
+}
+int nf_gpt_source(nf_handle S, const double *wa_host, const double *wb_host, double *src_host, double *sums_host)
+{
+    if (!S || !wa_host || !wb_host) return fail(NF_ERR_ARG, "nf_gpt_source: bad arguments");
+    NFCHK(gpt_args(S, 1.0, "nf_gpt_source"));
+    NFCHK(gpt_check_weights(S, wa_host, wb_host, "nf_gpt_source"));
+    HIPCHK(hipSetDevice(S->device));
+    (void)hipGetLastError();
+    hipStream_t st = S->team->stream;
+    const int ng = S->ng; const long N = S->N, NP = S->nphi;
+    S->gpt_valid = false;
+    NFCHK(gpt_upload_weights(S, wa_host, wb_host));
+    GptWork W; NFCHK(gpt_work(S, W));
+    double sums[2];
+    NFCHK(gpt_response(S, W, S->d_gpt_sc, sums));
+    if (sums_host) { sums_host[0] = sums[0]; sums_host[1] = sums[1]; }
+    NFCHK(gpt_check_sums(sums, "nf_gpt_source"));
+    if (!src_host) return NF_OK;
+    DevTmp<double> src; NFCHK(dalloc(&src.p, (size_t)NP * ng));
+    hipLaunchKernelGGL(k_gpt_source, dim3(gpt_grid(S, NP), ng), dim3(256), 0, st, (const double *)S->d_phi, (const double *)S->d_gpt_w, (const double *)(S->d_gpt_w + (size_t)ng * N),
+                       (const double *)S->d_gpt_sc, (const double *)S->d_hx, (const double *)S->d_hy, (const double *)S->d_hz, S->nx, S->ny, N, NP, src.p,
+                       (double *)nullptr, (double *)nullptr);
+    HIPCHK(hipGetLastError());
+    return phi_transfer(S, src_host, false, src.p);
+}
+int nf_gpt_sensitivity(nf_handle S, double keff, double *dD, double *dSigR, double *dNSF, double *dChi, double *dSigS, double *dWa, double *dWb, nf_sens_result *res)
+{
+    NFCHK(sens_args(S, keff, "nf_gpt_sensitivity"));
+    if (!S->gpt_valid) return fail(NF_ERR_STATE, "nf_gpt_sensitivity: no generalized adjoint on this handle (nf_solve_gpt or nf_set_gamma first)");
+    if ((dWa || dWb) && !S->d_gpt_w) return fail(NF_ERR_STATE, "nf_gpt_sensitivity: the maps of the weights need the weights of an nf_solve_gpt (or nf_gpt_source) on this handle");
+    HIPCHK(hipSetDevice(S->device));
+    (void)hipGetLastError();
+    if (dWa || dWb) {                                             // the sums of the flux the maps are taken at, then the two direct maps
+        hipStream_t st = S->team->stream;
+        const int ng = S->ng; const long N = S->N;
+        GptWork W; NFCHK(gpt_work(S, W));
+        double sums[2];
+        NFCHK(gpt_response(S, W, S->d_gpt_sc, sums));
+        NFCHK(gpt_check_sums(sums, "nf_gpt_sensitivity"));
+        hipLaunchKernelGGL(k_gpt_source, dim3(gpt_grid(S, N), ng), dim3(256), 0, st, (const double *)S->d_phi, (const double *)S->d_gpt_w, (const double *)(S->d_gpt_w + (size_t)ng * N),
+                           (const double *)S->d_gpt_sc, (const double *)S->d_hx, (const double *)S->d_hy, (const double *)S->d_hz, S->nx, S->ny, N, S->nphi, (double *)nullptr, dWa, dWb);
+        HIPCHK(hipGetLastError());
+    }
+    double nrm = 0.0;
+    NFCHK(sens_body(S, S->d_gamma, true, "nf_gpt_sensitivity", keff, dD, dSigR, dNSF, dChi, dSigS, &nrm));
+    if (res) { res->norm = nrm; res->keff = keff; res->n_cells = S->N; }
+    return NF_OK;
 }
 
 int nf_get_history(nf_handle S, double *k, double *dk, double *dphi, int *cg, int cap)

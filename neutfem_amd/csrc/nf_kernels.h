@@ -4570,6 +4570,93 @@ __global__ __launch_bounds__(256) void k_modes_extract(const double *__restrict_
         }
 }
 
+// ---- generalized adjoint and response-ratio maps (nf_solve_gpt / nf_gpt_sensitivity) ------------------------------------
+// Streaming grid-stride kernels over the device SoA layout [g*n + p*N + e] (n = DOFs per group): blockIdx.y is the group, blockIdx.x walks
+// the group's n DOFs (no division by n per element), block (x, y) writes its partial at y * gridDim.x + x of a row of `stride` doubles;
+// k_block_finalize adds a row's gridDim.x * gridDim.y partials in a fixed order and the totals stay on the device in the slots below.
+enum { GPT_WA = 0, GPT_WB = 1, GPT_DEN = 2, GPT_FF = 3, GPT_NUM = 4, GPT_NN = 5, GPT_DD = 6, GPT_SLOTS = 8 };
+// <w_a, phi> (row 0) and <w_b, phi> (row 1), <w, phi> = sum_g sum_e w[g,e] |e| phibar_g(e): one pass over the DOF-0 rows of all groups
+__global__ __launch_bounds__(256) void k_gpt_response(const double *__restrict__ phi, const double *__restrict__ wa, const double *__restrict__ wb,
+                                                      const double *__restrict__ hx, const double *__restrict__ hy, const double *__restrict__ hz,
+                                                      int nx, int ny, long N, long n, double *__restrict__ partials, long stride)
+{
+    __shared__ double sred[4];
+    const long g = blockIdx.y;
+    double sa = 0.0, sb = 0.0;
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < N; e += gridDim.x * 256L) {
+        const double v = cell_measure(hx, hy, hz, nx, ny, e) * phi[g * n + e];
+        sa = fma(wa[g * N + e], v, sa); sb = fma(wb[g * N + e], v, sb);
+    }
+    sa = block_sum(sa, sred); sb = block_sum(sb, sred);
+    if (threadIdx.x == 0) { const long b = (long)blockIdx.y * gridDim.x + blockIdx.x; partials[b] = sa; partials[stride + b] = sb; }
+}
+// S+ = w_a |e| / <w_a, phi> - w_b |e| / <w_b, phi> on the DOF-0 rows, 0 on the higher moments (src; may be NULL), from the device-resident
+// sums sc[GPT_WA], sc[GPT_WB]; with dWa / dWb (may be NULL) the direct maps (1/R) dR/dw_a = |e| phibar / <w_a, phi> and
+// (1/R) dR/dw_b = -|e| phibar / <w_b, phi>, [g*N + e]
+__global__ __launch_bounds__(256) void k_gpt_source(const double *__restrict__ phi, const double *__restrict__ wa, const double *__restrict__ wb,
+                                                    const double *__restrict__ sc, const double *__restrict__ hx, const double *__restrict__ hy,
+                                                    const double *__restrict__ hz, int nx, int ny, long N, long n, double *__restrict__ src,
+                                                    double *__restrict__ dWa, double *__restrict__ dWb)
+{
+    const long g = blockIdx.y;
+    const double A = sc[GPT_WA], B = sc[GPT_WB];
+    for (long j = blockIdx.x * 256L + threadIdx.x; j < n; j += gridDim.x * 256L) {
+        if (j >= N) { if (src) src[g * n + j] = 0.0; continue; }
+        const double vol = cell_measure(hx, hy, hz, nx, ny, j);
+        if (src) src[g * n + j] = wa[g * N + j] * vol / A - wb[g * N + j] * vol / B;
+        if (dWa || dWb) {
+            const double v = vol * phi[g * n + j];
+            if (dWa) __builtin_nontemporal_store(v / A, dWa + g * N + j);
+            if (dWb) __builtin_nontemporal_store(-(v / B), dWb + g * N + j);
+        }
+    }
+}
+// <x, F phi> (row 0) and ||F phi||^2 (row 1) in one pass over x: (F phi)_g[p, e] = chi_g(e) tf[p, e] with tf = sum_g' Mf_g' phi_g' (k_fission),
+// formed on the fly -- F phi is never stored.  x = Gamma: the numerator of the deflation; x = phi+: its denominator, once per call.
+__global__ __launch_bounds__(256) void k_gpt_defl_dot(const double *__restrict__ x, const double *__restrict__ chi, const double *__restrict__ tf,
+                                                      long N, long n, double *__restrict__ partials, long stride)
+{
+    __shared__ double sred[4];
+    const long g = blockIdx.y;
+    double s = 0.0, ff = 0.0;
+    for (long j = blockIdx.x * 256L + threadIdx.x; j < n; j += gridDim.x * 256L) {
+        const long e = n == N ? j : j % N;
+        const double f = chi[g * N + e] * tf[j];
+        s = fma(x[g * n + j], f, s); ff = fma(f, f, ff);
+    }
+    s = block_sum(s, sred); ff = block_sum(ff, sred);
+    if (threadIdx.x == 0) { const long b = (long)blockIdx.y * gridDim.x + blockIdx.x; partials[b] = s; partials[stride + b] = ff; }
+}
+// Gamma -= beta phi+ with beta = sc[GPT_NUM] / sc[GPT_DEN] read from the device (no host round trip), the block partials of ||Gamma||^2
+// (row 0) and ||Gamma - old||^2 (row 1) of the deflated iterate, and old <- Gamma, all in one sweep (the shape of k_subcrit_reduce):
+// three loads and two stores per DOF
+__global__ __launch_bounds__(256) void k_gpt_defl_update(double *__restrict__ gamma, const double *__restrict__ adj, double *__restrict__ old,
+                                                         const double *__restrict__ sc, long n, double *__restrict__ partials, long stride)
+{
+    __shared__ double sred[4];
+    const long g = blockIdx.y;
+    const double beta = sc[GPT_NUM] / sc[GPT_DEN];
+    double sn = 0.0, sd = 0.0;
+    for (long j = blockIdx.x * 256L + threadIdx.x; j < n; j += gridDim.x * 256L) {
+        const long i = g * n + j;
+        const double v = fma(-beta, adj[i], gamma[i]), d = v - old[i];
+        gamma[i] = v; old[i] = v;
+        sn = fma(v, v, sn); sd = fma(d, d, sd);
+    }
+    sn = block_sum(sn, sred); sd = block_sum(sd, sred);
+    if (threadIdx.x == 0) { const long b = (long)blockIdx.y * gridDim.x + blockIdx.x; partials[b] = sn; partials[stride + b] = sd; }
+}
+// one block, the counterpart of k_sens_scalars for the response ratio: sc[0] = <Gamma+, F phi> as measured (the n partials of a
+// k_gpt_defl_dot row added in k_block_finalize's order; it is reported, the maps do not divide by it), sc[1] = c = -1, sc[2] = -c / k = 1 / k.
+// k_sens_mass and k_sens_current then run unchanged on (phi, Gamma+).
+__global__ __launch_bounds__(256) void k_gpt_scalars(const double *__restrict__ part, int n, double keff, double *__restrict__ sc)
+{
+    __shared__ double sred[4];
+    double s = strided_sum256(part, n);
+    s = block_sum(s, sred);
+    if (threadIdx.x == 0) { sc[0] = s; sc[1] = -1.0; sc[2] = 1.0 / keff; }
+}
+
 // fill with a deterministic pseudo-random pattern (profiling helper)
 __global__ void k_fill_pattern(double *__restrict__ v, long n)
 {
