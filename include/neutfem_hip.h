@@ -485,7 +485,9 @@ int nf_timers(nf_handle h, char *json_buf, size_t len);
  * of x.y in the z.w form), "xcd_order" (the XCD-contiguous tile order is requested) and "xcd_permutes" (requested, and the tile count
  * is a multiple of 8 beyond 8: tiles really move), "fold" (accumulation pass of a slab: it forms the separator values
  * itself), "dict" (the pass reads its line factors from the table of distinct lines, see "line_dict") and "early" (level of early vector
- * loads of a table-backed chunked pass, option "c_early"; 0 for every other pass); at the top level "line_dict":
+ * loads of a table-backed chunked pass, option "c_early"; 0 for every other pass); y / z passes also "stage" (the staged form of
+ * k_schur_s, option "s_stage"; "variant" then ends in "stage") and "blocks" (workgroups launched: the tiles of "grid", or the
+ * persistent blocks of a staged pass -- "grid" stays the tile grid); at the top level "line_dict":
  * {"x", "y", "z"}, the distinct lines of the largest group per direction (0: no table in use).  Built from the predicates the launch functions
  * themselves call.  The one thing it does besides reporting: where the next apply would first build the tables of distinct lines
  * (once per build), the report builds them, since whether a direction verifies is part of the plan; otherwise it launches nothing
@@ -561,6 +563,10 @@ int nf_time_device_copy(nf_handle h, size_t bytes, int reps, double *gbps);
  *   sweeps that hide them: 1 = x of both chunks in one round trip, 2 = also y of the upper chunk before that chunk's forward sweep and y of the
  *   lower chunk before the backward half, 0 = each load where it is used, -1 = the level that measurably gains.  Only loads
  *   move: the results are bit-identical at every level.  nf_apply_plan reports the level per pass as "early";
+ *   "s_stage" (default -1): staged form of the table-backed y / z passes on k_schur_s (plain RT0-P0 lines, nx a multiple of the tile width): a
+ *   launch of "s_stage_grid" blocks (default 0 = one per compute unit) walks the tiles, and the next tile's vector is copied into LDS while
+ *   the current one is scanned.  -1 = the directions that measurably gain, where a block has at least two tiles, 0 = off,
+ *   1 = wherever eligible.  Only loads move: the results are bit-identical.  nf_apply_plan reports "stage" and "blocks" per pass;
  *   "transient_rebalance" (default 1): nf_transient_step scales the iterate of every outer by the balance factor f; 0 = plain source
  *   iteration (same fixed point, a contraction of about 1 - beta per outer: for measurements).
  * The handles the library derives from h solve under h's options: the step operator of nf_transient_step (at every call), the fine

@@ -190,6 +190,10 @@ struct nf_team {
     int opt_line_dict = -1, line_dict_dirs = 7, line_dict_fp_bits = 128; long line_dict_max_bytes = 512L * 1024;
     int opt_s_long = -1, s_long_min = 256;                // chunked long-line pass (k_schur_c): -1 auto (lines longer than s_long_min), 0 off, 1 always
     int opt_c_early = -1;                                 // its table-backed form: vector loads of both chunks issued up front (k_schur_c EARLY): -1 auto (C_EARLY_AUTO), 0, 1, 2
+    // staged form of the table-backed y / z passes (k_schur_s SV_STAGE: persistent blocks, the next tile's x copied into LDS under the scans).
+    // s_stage: -1 = the directions of S_STAGE_AUTO_DIRS where a block has a next tile to fetch, 0 = off, 1 = wherever eligible;
+    // s_stage_grid: blocks of such a launch, 0 = one per compute unit
+    int opt_s_stage = -1, opt_s_stage_grid = 0, ncu = 256;
     size_t lds_limit = 160 * 1024;                        // dynamic LDS a block may ask for (hipDeviceAttributeMaxSharedMemoryPerBlock at team creation)
     // fused-direction CG (two launches per iteration) up to this many cells.  Measured crossover against the four-launch lean path after
     // the round-2 latency work: 64^3 19.1 vs 27.2 us per CG iteration, 80^3 39.1 vs 34.5, 128^3 77.7 vs 70.9, 160^3 221 vs 150
@@ -514,6 +518,8 @@ static int create_impl(int rt_order, int p_order, int ng, int nxb, const double 
         if (hipDeviceGetAttribute(&b, hipDeviceAttributeSharedMemPerBlockOptin, device) != hipSuccess) b = 0;
         (void)hipGetLastError();
         T->lds_limit = (size_t)std::max(std::max(a, b), 64 * 1024);
+        if (hipDeviceGetAttribute(&a, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && a > 0) T->ncu = a;
+        (void)hipGetLastError();
     }
     const char *cb = getenv("NEUTFEM_CG_BATCH"); T->cg_batch = cb ? atoi(cb) : 0;
     *out = S;
@@ -1431,6 +1437,25 @@ static int s_xcd(const nf_solver *S, int d, int zmode)
 static bool s_nt(const nf_solver *S, int zmode, int SEG) { return zmode != 3 && S->nb == 0 && SEG == 8 && nt_regime(S); }   // plain lines and the z passes of a slab
 static bool s_dict(const nf_solver *S, int d, int zmode, int SEG) { return zmode == 0 && s_nt(S, zmode, SEG) && dict_dir(S, d); }
 static bool s_zw(const nf_solver *S, int zmode, bool zw_dot, bool want_dot) { return zmode == 0 && S->nb == 0 && zw_dot && want_dot; }     // z.w form of the pass's share of x.y
+// Staged form (SV_STAGE): plain table-backed lines in full-width tiles (16-byte aligned rows of TX doubles, a whole number of them per
+// 1-KiB copy instruction), the staged tile next to the summaries within the device's LDS.  Automatic: the directions that measurably
+// gain, and only where a block has a next tile to fetch (tiles >= 2 blocks).
+static const int S_STAGE_AUTO_DIRS = 2;                          // bit 0 = y, bit 1 = z
+static size_t s_stage_bytes(int n, int TX) { const int rpp = 1024 / (8 * TX); return (size_t)((n + rpp - 1) / rpp) * 1024; }
+static unsigned s_stage_blocks(const nf_solver *S, const SegPlan &sp)
+{
+    const unsigned tiles = sp.grid.x * sp.grid.y, want = (unsigned)(S->team->opt_s_stage_grid > 0 ? S->team->opt_s_stage_grid : S->team->ncu);
+    return std::min(tiles, want);
+}
+static bool s_stage(const nf_solver *S, int d, int zmode, const SegPlan &sp, unsigned V)
+{
+    const nf_team *T = S->team;
+    if (zmode != 0 || T->opt_s_stage == 0 || !(V & SV_NT) || !(V & SV_DICT) || (V & ~(SV_NT | SV_DICT | SV_ZW))) return false;
+    if (sp.TX < 8 || sp.TX > 64 || (sp.TX & (sp.TX - 1)) || S->nx % sp.TX != 0) return false;
+    if (sp.lds + s_stage_bytes(d == 1 ? S->ny : S->nz, sp.TX) > T->lds_limit) return false;
+    if (T->opt_s_stage > 0) return true;
+    return ((S_STAGE_AUTO_DIRS >> (d - 1)) & 1) && sp.grid.x * sp.grid.y >= 2 * s_stage_blocks(S, sp);
+}
 static bool s_fold(const nf_team *T, int zmode) { return zmode == 2 && T->sep_sweeps == 0 && T->opt_sepfold; }   // thick slabs: the accumulation pass forms the separator values itself
 // tiles of a (gx, gy) launch move under the XCD-contiguous order only when their count is a multiple of 8 (the kernels' own test) beyond 8 (the identity)
 static bool xcd_permutes(bool order, unsigned tiles) { return order && tiles % 8 == 0 && tiles > 8; }
@@ -1535,9 +1560,9 @@ static int line_dict_prepare(nf_team *T)
 struct SPass { int rc = NF_OK; bool chunked = false; ChunkPlan cp; SegPlan seg; unsigned V = 0; int xcd = 0, early = 0; bool fold = false, fuse = false; };
 static std::string variant_name(unsigned V)                      // "fuse+nt+sr"; "" for the base kernel
 {
-    static const char *const bit[] = { "fuse", "nt", "zw", "sr", "dict" };
+    static const char *const bit[] = { "fuse", "nt", "zw", "sr", "dict", "stage" };
     std::string r;
-    for (int i = 0; i < 5; ++i) if (V >> i & 1) r += (r.empty() ? "" : "+") + std::string(bit[i]);
+    for (int i = 0; i < 6; ++i) if (V >> i & 1) r += (r.empty() ? "" : "+") + std::string(bit[i]);
     return r;
 }
 // want_dot: the pass leaves its share of x.y (zw_dot: in the z.w form); fuse / cg1: a fused CG update / the single-reduction state (Cg1) ride along;
@@ -1563,6 +1588,7 @@ static SPass s_pass(const nf_solver *S, int d, int zmode, bool want_dot, bool zw
     const bool sr = cg1 && p0 && SEG == 8 && d == 2 && ((zmode == 1 && R.fuse) || (zmode == 2 && want_dot));
     R.V = (R.fuse && p0 ? SV_FUSE : 0) | (s_nt(S, zmode, SEG) ? SV_NT : 0) | (s_zw(S, zmode, zw_dot, want_dot) ? SV_ZW : 0)
         | (sr ? SV_SR : 0) | (s_dict(S, d, zmode, SEG) ? SV_DICT : 0);
+    if (s_stage(S, d, zmode, R.seg, R.V)) R.V |= SV_STAGE;
     R.xcd = s_xcd(S, d, zmode); R.fold = s_fold(S->team, zmode);
     return R;
 }
@@ -1631,17 +1657,34 @@ static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const 
             sa.fold = 1; sa.rlo = S->d_rlo; sa.rhi = S->d_rhi; sa.sinv_lo = S->d_sinv_lo + g * nl; sa.sinv_hi = S->d_sinv_hi + g * nl;
         }
     }
+    // staged form: persistent blocks over the same tile grid, the staged tile behind the summaries.  A vector that is not 16-byte aligned, a
+    // refused LDS opt-in or a refused launch leave the pass to the unstaged variant (as the chunked kernel steps back above)
+    if ((ps.V & SV_STAGE) && ((uintptr_t)ma.x[0] & 15)) ps.V &= ~SV_STAGE;
     int lg = 0; while ((4 << lg) < ps.seg.SEG) ++lg;
-    const unsigned key = (4 << lg) == ps.seg.SEG ? ((ps.V * 3 + (zmode != 0 ? 2u : d - 1u)) * 3 + (unsigned)S->nb) * 4 + (unsigned)lg : ~0u;   // shapes: y lines, z lines, z lines of a slab
-    const bool hit = with_index<(SV_ALL + 1) * 3 * 3 * 4>(key, [&](auto i) {
-        constexpr unsigned I = decltype(i)::value, V = I / 36;
-        constexpr int SEG = 4 << (I & 3), NB = I / 4 % 3, DIR = I / 12 % 3 == 0 ? 1 : 2; constexpr bool SLAB = I / 12 % 3 == 2;
-        if constexpr (!schur_s_legal(SEG, DIR, SLAB, NB, V)) return false;
-        else hipLaunchKernelGGL((k_schur_s<SEG, DIR, SLAB, NB, V>), ps.seg.grid, ps.seg.block, ps.seg.lds, st, ma, mt, G, da.on ? da.L : L, da.on ? da.DR : DR, D0, n, sl, ostride, S->nx,
-                                ps.seg.TX, ps.seg.NSEG, last, partials, cg, sa, fz, lz, da.ld);
-        return true;
-    });
-    return hit ? NF_OK : fail(NF_ERR_ARG, "k_schur_s: no instantiation for SEG = %d (s_seg), direction %d, zmode %d, NB = %d, variant \"%s\"", ps.seg.SEG, d, zmode, S->nb, variant_name(ps.V).c_str());
+    for (;;) {
+        bool staged = true;
+        const unsigned key = (4 << lg) == ps.seg.SEG ? ((ps.V * 3 + (zmode != 0 ? 2u : d - 1u)) * 3 + (unsigned)S->nb) * 4 + (unsigned)lg : ~0u;   // shapes: y lines, z lines, z lines of a slab
+        const bool hit = with_index<(SV_ALL + 1) * 3 * 3 * 4>(key, [&](auto i) {
+            constexpr unsigned I = decltype(i)::value, V = I / 36;
+            constexpr int SEG = 4 << (I & 3), NB = I / 4 % 3, DIR = I / 12 % 3 == 0 ? 1 : 2; constexpr bool SLAB = I / 12 % 3 == 2;
+            if constexpr (!schur_s_legal(SEG, DIR, SLAB, NB, V)) return false;
+            else if constexpr ((V & SV_STAGE) != 0) {
+                const size_t lds = ps.seg.lds + s_stage_bytes(n, ps.seg.TX);
+                const StageGrid sgr{ ps.seg.grid.x, ps.seg.grid.y };
+                staged = false;
+                if (lds_opt_in((const void *)k_schur_s<SEG, DIR, SLAB, NB, V>, lds)) {
+                    hipLaunchKernelGGL((k_schur_s<SEG, DIR, SLAB, NB, V>), dim3(s_stage_blocks(S, ps.seg), 1, ps.seg.grid.z), ps.seg.block, lds, st, ma, mt, G, da.on ? da.L : L, da.on ? da.DR : DR,
+                                       D0, n, sl, ostride, S->nx, ps.seg.TX, ps.seg.NSEG, last, partials, cg, sa, fz, lz, da.ld, sgr);
+                    staged = hipGetLastError() == hipSuccess;
+                }
+            }
+            else hipLaunchKernelGGL((k_schur_s<SEG, DIR, SLAB, NB, V>), ps.seg.grid, ps.seg.block, ps.seg.lds, st, ma, mt, G, da.on ? da.L : L, da.on ? da.DR : DR, D0, n, sl, ostride, S->nx,
+                                    ps.seg.TX, ps.seg.NSEG, last, partials, cg, sa, fz, lz, da.ld);
+            return true;
+        });
+        if (hit && (ps.V & SV_STAGE) && !staged) { ps.V &= ~SV_STAGE; continue; }   // refused: the unstaged variant
+        return hit ? NF_OK : fail(NF_ERR_ARG, "k_schur_s: no instantiation for SEG = %d (s_seg), direction %d, zmode %d, NB = %d, variant \"%s\"", ps.seg.SEG, d, zmode, S->nb, variant_name(ps.V).c_str());
+    }
 }
 
 // the endpoint pass of a slab as weighted sums (k_endpoint_w) instead of a chain solve: inside the single-reduction CG (sr), weights measured,
@@ -2023,7 +2066,7 @@ static CgPlan cg_plan(const nf_team *T)
 // split_dot, xy_overlap); apart from building the tables of distinct lines where the next
 // apply would (line_dict_prepare) it launches nothing and writes no state.  The one thing it cannot know is a device
 // that refuses the chunked kernel's LDS at launch time (launch_s then falls back to the one-chunk kernel).
-struct PlanPass { const char *dir, *family; int mode, SEG, NCH, TX, NSEG; dim3 grid; unsigned block; bool nt, p2, zw, order; unsigned tiles; bool fold = false, dict = false; int early = 0; unsigned V = 0; };
+struct PlanPass { const char *dir, *family; int mode, SEG, NCH, TX, NSEG; dim3 grid; unsigned block; bool nt, p2, zw, order; unsigned tiles; bool fold = false, dict = false; int early = 0; unsigned V = 0, blocks = 0; };
 static void plan_emit(std::string &js, const PlanPass &p)
 {
     char tmp[416];
@@ -2032,6 +2075,7 @@ static void plan_emit(std::string &js, const PlanPass &p)
              p.SEG, p.NCH, p.TX, p.NSEG, p.grid.x, p.grid.y, p.grid.z, p.block, p.nt ? 1 : 0, p.p2 ? 1 : 0, p.zw ? 1 : 0, p.order ? 1 : 0, xcd_permutes(p.order, p.tiles) ? 1 : 0, p.fold ? 1 : 0, p.dict ? 1 : 0, p.early);
     js += tmp;
     if (!strcmp(p.family, "s")) js += ", \"variant\": \"" + variant_name(p.V) + "\"";   // which k_schur_s
+    if (p.dir[0] != 'x') js += ", \"stage\": " + std::to_string((p.V & SV_STAGE) && !strcmp(p.family, "s") ? 1 : 0) + ", \"blocks\": " + std::to_string(p.blocks);   // launched blocks (staged: persistent)
     js += "}";
 }
 static int plan_s(std::string &js, const nf_solver *S, int d, int zmode, bool want_dot, bool zw_dot, bool fuse, bool cg1)   // a launch_s call
@@ -2040,7 +2084,8 @@ static int plan_s(std::string &js, const nf_solver *S, int d, int zmode, bool wa
     if (ps.rc != NF_OK) return ps.rc;
     const dim3 gr = ps.chunked ? c_grid(S, d, ps.cp) : ps.seg.grid;
     plan_emit(js, { d == 1 ? "y" : "z", ps.chunked ? "c" : "s", zmode, ps.chunked ? C_SEG : ps.seg.SEG, ps.chunked ? C_NCH : 1, ps.chunked ? ps.cp.TX : ps.seg.TX, ps.chunked ? ps.cp.NS : ps.seg.NSEG,
-                    gr, ps.chunked ? c_block(ps.cp) : ps.seg.block.x, (ps.V & SV_NT) != 0, false, (ps.V & SV_ZW) != 0, ps.xcd != 0, gr.x * gr.y, ps.fold, (ps.V & SV_DICT) != 0, ps.early, ps.V });
+                    gr, ps.chunked ? c_block(ps.cp) : ps.seg.block.x, (ps.V & SV_NT) != 0, false, (ps.V & SV_ZW) != 0, ps.xcd != 0, gr.x * gr.y, ps.fold, (ps.V & SV_DICT) != 0, ps.early, ps.V,
+                    !ps.chunked && (ps.V & SV_STAGE) ? s_stage_blocks(S, ps.seg) * gr.z : gr.x * gr.y * gr.z });
     return NF_OK;
 }
 int nf_apply_plan(nf_handle S, int in_cg, char *json_buf, size_t len)
@@ -2610,7 +2655,7 @@ static void team_copy_options(nf_team *C, const nf_team *T, bool same_mesh_kind)
     C->opt_line_dict = T->opt_line_dict; C->line_dict_dirs = T->line_dict_dirs; C->line_dict_fp_bits = T->line_dict_fp_bits; C->line_dict_max_bytes = T->line_dict_max_bytes;
     C->opt_nt_loads = T->opt_nt_loads; C->nt_min_cells = T->nt_min_cells; C->opt_s_long = T->opt_s_long; C->opt_s_long_dirs = T->opt_s_long_dirs;
     C->s_long_min = T->s_long_min; C->s_long_min_y = T->s_long_min_y; C->opt_s_seg = T->opt_s_seg; C->opt_s_tx = T->opt_s_tx;
-    C->opt_wsmin = T->opt_wsmin; C->opt_c_early = T->opt_c_early; C->opt_x_p2 = T->opt_x_p2; C->opt_split_dot = T->opt_split_dot; C->opt_xcd = T->opt_xcd;
+    C->opt_wsmin = T->opt_wsmin; C->opt_c_early = T->opt_c_early; C->opt_s_stage = T->opt_s_stage; C->opt_s_stage_grid = T->opt_s_stage_grid; C->opt_x_p2 = T->opt_x_p2; C->opt_split_dot = T->opt_split_dot; C->opt_xcd = T->opt_xcd;
     C->opt_xy_overlap = T->opt_xy_overlap; C->xy_overlap_max_cells = T->xy_overlap_max_cells; C->opt_vec_reduce = T->opt_vec_reduce;
     C->opt_pub = T->opt_pub; C->opt_sens_grid = T->opt_sens_grid; C->prof_every = T->prof_every;
     if (dict_moved) { (void)hipSetDevice(C->device); for (auto *X : C->slabs) line_dict_drop(X); }
@@ -5254,6 +5299,8 @@ int nf_set_option(nf_handle S, const char *key, long value)
     else if (!strcmp(key, "s_long_min_y")) T->s_long_min_y = (int)std::max(1L, std::min(1000000L, value));
     else if (!strcmp(key, "s_long_min")) T->s_long_min = (int)std::max(1L, std::min(1000000L, value));
     else if (!strcmp(key, "c_early")) T->opt_c_early = value < 0 ? -1 : (int)std::min(2L, value);
+    else if (!strcmp(key, "s_stage")) T->opt_s_stage = value < 0 ? -1 : (value > 0 ? 1 : 0);
+    else if (!strcmp(key, "s_stage_grid")) T->opt_s_stage_grid = (int)std::max(0L, std::min(1L << 20, value));
     else if (!strcmp(key, "line_dict") || !strcmp(key, "line_dict_dirs") || !strcmp(key, "line_dict_max_bytes") || !strcmp(key, "line_dict_fp_bits")) {
         if (!strcmp(key, "line_dict")) T->opt_line_dict = value < 0 ? -1 : (value > 0 ? 1 : 0);
         else if (!strcmp(key, "line_dict_dirs")) T->line_dict_dirs = (int)(value & 7);

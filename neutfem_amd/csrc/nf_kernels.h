@@ -28,6 +28,10 @@
 #ifndef NF_SR_Z2_WAVES
 #define NF_SR_Z2_WAVES 4
 #endif
+// where the staged y / z pass (k_schur_s, SV_STAGE) issues the next tile's copy: 0 = behind the first barrier, 1 = behind this tile's y loads (A/B builds)
+#ifndef NF_STAGE_PLACE
+#define NF_STAGE_PLACE 1
+#endif
 
 namespace nf {
 
@@ -141,14 +145,23 @@ __device__ __forceinline__ double strided_sum256(const double *__restrict__ p, i
     for (; i < cnt; i += 256) s += p[i];
     return s;
 }
+// Workgroup barrier.  RAW (the staged y / z pass, see stage_issue): with a copy into LDS outstanding __syncthreads() is compiled as
+// s_waitcnt vmcnt(0) lgkmcnt(0); s_barrier -- it would wait for the next tile's vector in the middle of this one.  The raw form waits for
+// the wave's own LDS traffic only; whoever reads the staged buffer waits for the copy by hand first.
+template <bool RAW> __device__ __forceinline__ void block_bar()
+{
+    if constexpr (RAW) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); }
+    else __syncthreads();
+}
 // fixed-order block sum; result valid in thread 0.  sred: >= blockDim/64 doubles of LDS.
+template <bool RAW = false>
 __device__ __forceinline__ double block_sum(double v, double *sred)
 {
     v = wave_sum(v);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    __syncthreads();
+    block_bar<RAW>();
     if (lane == 0) sred[w] = v;
-    __syncthreads();
+    block_bar<RAW>();
     double s = 0.0;
     if (threadIdx.x == 0)
         for (int i = 0; i < nw; ++i) s += sred[i];
@@ -1092,23 +1105,53 @@ struct SlabArgs {
 // offset of its line's row and reaches the cells of its segment from there -- contiguous along the line, plain loads, bit-equal values
 // XC (k_cg_xcd: the producers of x and r are other workgroups of the SAME launch on the same XCD): every load of x and r bypasses the
 // compute unit's L1 -- the overlap cell too
-enum : unsigned { SV_FUSE = 1, SV_NT = 2, SV_ZW = 4, SV_SR = 8, SV_DICT = 16, SV_ALL = 31 };   // bit order = the order of the report's "variant"
+// SV_STAGE (table-backed plain lines, full-width tiles): a block walks tiles b, b + blocks, ... and the NEXT tile's x is copied into LDS while
+// this one is scanned (stage_issue); xv comes out of that buffer, everything behind it is the unstaged pass: same values, same arithmetic
+enum : unsigned { SV_FUSE = 1, SV_NT = 2, SV_ZW = 4, SV_SR = 8, SV_DICT = 16, SV_STAGE = 32, SV_ALL = 63 };   // bit order = the order of the report's "variant"
 // The instantiations of k_schur_s: the shapes (16- and 32-cell segments for RT0-P0 only, slabs cut z lines only) and the bits that a shape admits.
 // The kernel asserts this and the host instantiates exactly the combinations for which it holds.
 constexpr bool schur_s_legal(int SEG, int DIR, bool SLAB, int NB, unsigned V)
 {
     const bool p0 = NB == 0, s8 = p0 && SEG == 8;                // RT0-P0; its 8-cell segments
-    const unsigned admits = (SLAB && p0 ? SV_FUSE : 0) | (s8 ? SV_NT : 0) | (!SLAB && p0 ? SV_ZW : 0) | (SLAB && s8 && DIR == 2 ? SV_SR : 0) | (!SLAB && (V & SV_NT) ? SV_DICT : 0);
+    const unsigned admits = (SLAB && p0 ? SV_FUSE : 0) | (s8 ? SV_NT : 0) | (!SLAB && p0 ? SV_ZW : 0) | (SLAB && s8 && DIR == 2 ? SV_SR : 0) | (!SLAB && (V & SV_NT) ? SV_DICT : 0)
+                            | (!SLAB && s8 && (V & SV_NT) && (V & SV_DICT) ? SV_STAGE : 0);
     return (SEG == 4 || SEG == 8 || (p0 && (SEG == 16 || SEG == 32))) && (DIR == 2 || (DIR == 1 && !SLAB)) && NB >= 0 && NB <= 2 && !(V & ~admits);
+}
+// The staged pass's copy of one tile of x into LDS.  The image is the tile as it lies in memory: [cell][TX] doubles, src = the first cell of the
+// tile's first column, rows sl doubles apart.  One wave-instruction writes 1 KiB lane-linear (no register destination), i.e. 1024 / (8 TX) whole
+// rows: the lane's SOURCE address picks the row and lanes whose row lies past the line are switched off.  Needs TX a power of two in 8 .. 64,
+// full-width tiles and 16-byte aligned rows (the host's s_stage).  The copy counts on vmcnt: the issuing wave waits for it by hand, and a barrier
+// separates that wait from the first read of the buffer: every wave waits ahead of its stores (schur_s_tile), the block meets at the top of
+// the next tile (k_schur_s).  The lane's row of the table of distinct lines travels the same way: the id of the next tile's line is asked for
+// next to the copy, so that the table loads of a tile do not start with a dependent round trip.
+struct StageCtx {
+    const double *buf = nullptr, *next = nullptr;                // the staged image of THIS tile; where the next tile of this block starts (null: none)
+    const int *next_id = nullptr;                                // LineDict::id of the next tile's first column
+    int id = 0;                                                  // this lane's table row in THIS tile; replaced by the next tile's on the way
+};
+template <bool NT>
+__device__ __forceinline__ void stage_issue(const double *buf, const double *src, int n, long sl, int TX)
+{
+    typedef __attribute__((address_space(1))) const void *gptr_t;
+    typedef __attribute__((address_space(3))) void *lptr_t;
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+    const int lpr = TX >> 1, rpp = 64 / lpr;                     // lanes per row (16 bytes each), rows per 1-KiB piece
+    const int rl = lane / lpr, cl = lane % lpr;
+    const char *dst = reinterpret_cast<const char *>(buf);
+    for (int p = w, np = (n + rpp - 1) / rpp; p < np; p += nw) {
+        const int r = p * rpp + rl;
+        if (r < n) __builtin_amdgcn_global_load_lds((gptr_t)(src + (long)r * sl + 2 * cl), (lptr_t)(dst + p * 1024), 16, 0, NT ? 2 : 0);   // aux 2: nt, as ldg<NT>
+    }
 }
 template <int SEG, int DIR, bool SLAB, int NB, unsigned V = 0, class Mid = NoMid, bool XC = false>
 __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G, const double *__restrict__ L, const double *__restrict__ DR,
                                                const double *__restrict__ D0, int n, long sl, long outer_stride, int nx, int TX, int NSEG,
                                                unsigned bx, unsigned by, unsigned bz, unsigned gy, int tid, bool act, double *sm,
                                                const SlabArgs &sa, const CgFuse &fz, bool fuse, bool fro, double f_alpha, double f_beta, bool acc,
-                                               long long *stamp = nullptr, Mid mid = Mid(), double *extra = nullptr, const LineDict &ld = LineDict())
+                                               long long *stamp = nullptr, Mid mid = Mid(), double *extra = nullptr, const LineDict &ld = LineDict(),
+                                               StageCtx *sg = nullptr)
 {
-    constexpr bool FUSE = V & SV_FUSE, NT = V & SV_NT, ZW = V & SV_ZW, SR = V & SV_SR, DICT = V & SV_DICT;
+    constexpr bool FUSE = V & SV_FUSE, NT = V & SV_NT, ZW = V & SV_ZW, SR = V & SV_SR, DICT = V & SV_DICT, STAGE = V & SV_STAGE;
     static_assert(SLAB || !(FUSE || SR), "fused update, single-reduction sums: slab passes (k_schur_s checks the rest: schur_s_legal)");
     const double *x = ma.x[0];                                   // no __restrict__: the fused slab pass rewrites this vector (fz.p)
     double *__restrict__ y = ma.y[0];
@@ -1185,7 +1228,8 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
     constexpr bool O32 = NB > 0 && !SLAB;
     const unsigned ob8 = (unsigned)(base * 8), sl8 = (unsigned)(sl * 8);
     unsigned tb8 = 0;                                            // DICT: byte offset of this column's row in the table
-    if (DICT) tb8 = valid ? (unsigned)ld.id[lineid] * (unsigned)ld.pitch * 8u : 0u;
+    if constexpr (STAGE) tb8 = valid ? (unsigned)sg->id * (unsigned)ld.pitch * 8u : 0u;
+    else if (DICT) tb8 = valid ? (unsigned)ld.id[lineid] * (unsigned)ld.pitch * 8u : 0u;
 #define NF_A8(c) (ob8 + (unsigned)(c) * sl8)
 #define NF_T8(c) (tb8 + (unsigned)(c) * 8u)
     double rv[(SLAB && !FUSE) ? 1 : SEG + 1], sv[FUSE ? SEG : 1];   // r of the same cells; slab fuse: x_sol of the owned cells
@@ -1197,7 +1241,8 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
         const int c = c0 + i; const bool ok = valid && c < n;
         const long a = base + (long)c * sl;
         // the overlap cell (i == SEG) is the next segment's first: keep that line for it (see k_schur_c on why this is not a ternary on i)
-        if (O32) xv[i] = ok ? ldo<NT>(x, NF_A8(c)) : 0.0;
+        if constexpr (STAGE) { const double v = sg->buf[(c < n ? c : n - 1) * TX + ixl]; xv[i] = ok ? v : 0.0; }   // staged image (rows past the line were not copied)
+        else if (O32) xv[i] = ok ? ldo<NT>(x, NF_A8(c)) : 0.0;
         else if (i < SEG || XC) xv[i] = ok ? ldg<NT>(x + a) : 0.0; else xv[i] = ok ? x[a] : 0.0;
         if (!SLAB || FUSE) rv[(SLAB && !FUSE) ? 0 : i] = (fr && ok) ? (SLAB ? fz.r[a] : (O32 ? ldo<NT>(x + roff, NF_A8(c)) : ldg<NT>(x + a + roff))) : 0.0;
         if (FUSE && i < SEG) sv[FUSE ? i : 0] = (fuse && ok) ? fz.xsol[a] : 0.0;
@@ -1279,8 +1324,17 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
     NF_STAMP(stamp, 4);
     if (act) { sA[si] = P; sB[si] = lz; }
     if (act && seg == 0) sZ0[ixl] = x_before - xL0;
-    __syncthreads();
+    if constexpr (STAGE) {
+        // 1/d is first used behind the barrier: with a copy in flight the compiler waits there for EVERYTHING outstanding, the copy included
+        // (it cannot count across the copy loop).  Ask for the table values here, where nothing else is in flight yet.
+#pragma unroll
+        for (int i = 0; i < SEG; ++i) asm volatile("" :: "v"(Rv[i]));
+        asm volatile("" :: "v"(dinv_s));
+    }
+    block_bar<STAGE>();
     NF_STAMP(stamp, 5);
+    // every thread holds its x in registers and the buffer is free: the next tile's copy flies during the rest of this tile
+    if constexpr (STAGE && NF_STAGE_PLACE == 0) { if (sg->next) { stage_issue<NT>(sg->buf, sg->next, n, sl, TX); sg->id = sg->next_id[ixl]; } }
     if (wscan) {
         // forward: incoming value of segment s = (f_{s-1} o ... o f_0)(z0); inclusive Hillis-Steele over the lanes of a column
         int W = 16; while (W < NSEG) W <<= 1;
@@ -1295,7 +1349,7 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
                 const double Ae = __shfl_up(A, 1, W), Be = __shfl_up(B, 1, W), z0 = sZ0[c];
                 if (s_ < NSEG) sB[c * NSP + s_] = s_ == 0 ? z0 : Ae * z0 + Be;
             }
-        __syncthreads();
+        block_bar<STAGE>();
     }
     if (SLAB && fuse && valid) {                                 // every read of the old p in this block is behind the barrier
 #pragma unroll
@@ -1345,8 +1399,9 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
             if (NB > 1) y2o[NB > 1 ? i : 0] = okl ? (O32 ? ldo<false>(ma.y[2], NF_A8(c0 + i)) : ma.y[2][a]) : 0.0;
         }
     }
+    if constexpr (STAGE && NF_STAGE_PLACE == 1) { if (sg->next) { stage_issue<NT>(sg->buf, sg->next, n, sl, TX); sg->id = sg->next_id[ixl]; } }   // this tile's y first in the queue
     NF_STAMP(stamp, 6);
-    __syncthreads();
+    block_bar<STAGE>();
     NF_STAMP(stamp, 7);
     if (SR && !FUSE) {                                             // r of the owned cells (for r.q): asked for behind the barrier, so that it is not alive across
 #pragma unroll                                                   // the scans (the pass sits at 128 VGPRs = four blocks of 256 threads per CU); it flies during the backward replay
@@ -1367,7 +1422,7 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
                 const double Bn = __shfl_down(B, 1, W);
                 if (s_ < NSEG) sA2[c * NSP + s_] = s_ == W - 1 ? 0.0 : Bn;
             }
-        __syncthreads();
+        block_bar<STAGE>();
         if (act) u = sA2[si];
     } else if (act) for (int s = NSEG - 1; s > seg; --s) u = sA2[s * TX + ixl] * u + sB2[s * TX + ixl];
 #pragma unroll
@@ -1391,6 +1446,16 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
                 const double v = ma.Gc[1] * x2[NB > 1 ? i : 0] * ma.iM[1] * icv[i] - (ma.eL[1] * lo + ma.eR[1] * w[i]);
                 y2o[NB > 1 ? i : 0] = y2o[NB > 1 ? i : 0] + ma.Ta * ma.Gc[1] * v; dot += in ? x2[NB > 1 ? i : 0] * y2o[NB > 1 ? i : 0] : 0.0;
             }
+        }
+        if constexpr (STAGE) {
+            // the values are formed HERE: in the z.w form nothing but the store uses them, and the compiler would sink each sum into its
+            // store's predicated region, where it waits for every older memory operation -- the previous cell's store among them
+#pragma unroll
+            for (int i = 0; i < SEG; ++i) asm volatile("" : "+v"(yo[i]));
+            asm volatile("" : "+v"(sg->id));                       // the next tile's table row too: asked for here, not behind the stores
+            // y is here, and with it everything older: this wave's part of the next tile's copy has landed.  Said by hand, because the
+            // top of the next tile relies on it and does not wait again -- the stores below drain under the next tile's table loads
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
 #pragma unroll
         for (int i = 0; i < SEG; ++i) {
@@ -1510,16 +1575,54 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
 
 // Slab variants keep r and x_sol of their cells in registers next to x, L, 1/d (loads first, see schur_s_tile): blocks of at most 512
 // threads, so that the register budget is 256 per thread (the host picks TX accordingly)
+struct StageGrid { unsigned gx = 0, gy = 0; };                  // SV_STAGE: the tile grid that a persistent launch walks (gridDim holds the block count)
 template <int SEG, int DIR, bool SLAB, int NB, unsigned V = 0>
 __global__ __launch_bounds__(SLAB ? 512 : 1024, SLAB ? (NB > 0 ? 2 : ((V & SV_FUSE) ? ((V & SV_SR) ? NF_SR_Z1_WAVES : 3) : ((V & SV_SR) ? NF_SR_Z2_WAVES : 4))) : 1) void k_schur_s(ModeArgs ma0, ModeTab mt, Geom G, const double *__restrict__ L, const double *__restrict__ DR,
                           const double *__restrict__ D0, int n, long sl, long outer_stride, int nx, int TX, int NSEG,
                           int last, double *__restrict__ partials, const CgScalars *__restrict__ cg, SlabArgs sa, CgFuse fz, CgLean lean,
-                          LineDict ld = LineDict())
+                          LineDict ld = LineDict(), StageGrid sgr = StageGrid())
 {
     static_assert(schur_s_legal(SEG, DIR, SLAB, NB, V), "not a variant of k_schur_s");
     constexpr bool FUSE = V & SV_FUSE, SR = V & SV_SR;
     extern __shared__ double sm[];
     if (cg && cg->done) return;
+    if constexpr (V & SV_STAGE) {
+        // Persistent form: gridDim.x blocks walk the gx * gy tiles, block b takes b, b + gridDim.x, ...  A tile's (bx, by) and its slot in
+        // `partials` are what the one-tile-per-block launch derives from blockIdx (the XCD-contiguous order included), so the first-stage
+        // sums land where they land there.  Every barrier between a copy's issue and the wait at the top of the next tile is the raw one.
+        const ModeArgs ma = select_mode(ma0, mt, blockIdx.z, NB + 1);
+        double *sred = sm + 4 * TX * (NSEG + 1) + TX;
+        const double *buf = sred + 32;                            // behind the summary arrays and the reduction scratch (SegPlan::lds)
+        const unsigned gx = sgr.gx, gy = sgr.gy, tiles = gx * gy;
+        const bool remap = sa.xcd && tiles % 8 == 0;
+        auto origin = [&](unsigned t, unsigned &bx, unsigned &by) {
+            const unsigned nl = remap ? (t % 8) * (tiles / 8) + t / 8 : t;
+            bx = nl % gx; by = nl / gx;
+        };
+        auto tile_x = [&](unsigned t) { unsigned bx, by; origin(t, bx, by); return ma.x[0] + ((long)by * outer_stride + (long)bx * TX); };
+        auto tile_id = [&](unsigned t) { unsigned bx, by; origin(t, bx, by); return ld.id + ((long)by * nx + (long)bx * TX); };
+        const int ixl0 = (int)threadIdx.x < TX * NSEG ? (int)threadIdx.x % TX : 0;   // schur_s_tile's ixl
+        unsigned t = blockIdx.x;
+        StageCtx sg; sg.buf = buf;
+        if (t < tiles) { stage_issue<(V & SV_NT) != 0>(buf, tile_x(t), n, sl, TX); sg.id = tile_id(t)[ixl0]; }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the first tile's copy; the later ones are waited for inside the tile before
+        asm volatile("" : "+v"(sg.id));                           // (the compiler's own wait for the table row: here, not behind a tile's stores)
+        for (; t < tiles; t += gridDim.x) {
+            unsigned bx, by; origin(t, bx, by);
+            const bool more = t + gridDim.x < tiles;
+            sg.next = more ? tile_x(t + gridDim.x) : nullptr; sg.next_id = more ? tile_id(t + gridDim.x) : nullptr;
+            // the copy of this tile has landed: every issuing wave has seen its counter drain, and here the block meets
+            block_bar<true>();
+            const double dot = schur_s_tile<SEG, DIR, SLAB, NB, V>(ma, G, L, DR, D0, n, sl, outer_stride, nx, TX, NSEG, bx, by, blockIdx.z, gy,
+                                                                    (int)threadIdx.x, true, sm, sa, fz, false, false, 0.0, 0.0, !sa.noacc,
+                                                                    nullptr, NoMid(), nullptr, ld, &sg);
+            if (last && partials) {
+                const double s = block_sum<true>(dot, sred);
+                if (threadIdx.x == 0) partials[((long)blockIdx.z * gy + by) * gx + bx] = s;
+            }
+        }
+        return;
+    }
     const ModeArgs ma = select_mode(ma0, mt, blockIdx.z, NB + 1);
     // fused CG on slabs: the endpoint pass (mode 1) is the first to read p in an iteration, so it carries the deferred
     // x_sol += alpha p, p = r + beta p (see CgFuse); every cell of the local line is owned by exactly one thread.
