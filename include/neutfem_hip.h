@@ -446,6 +446,55 @@ int nf_get_precursors(nf_handle h, int family, double *c_host);
 /* ends the transient and releases the twin and the precursors (nf_destroy does the same); NF_OK without one */
 int nf_transient_end(nf_handle h);
 
+/* ---- adjoint-weighted kinetics parameters and dynamic reactivity (no counterpart in the reference) ---------------------
+ * What a state or a transient IS in point-kinetics terms: reactivity rho (also in dollars), beta_eff with its split over the families and
+ * the generation time Lambda, as bilinear functionals weighted with the handle's adjoint flux.  Notation of the sections above: all vectors
+ * in DOF layout, every product the plain dot product of coefficient vectors (the matrices carry the mass weights);
+ *   K0 = blockdiag(S_g) - Ms, the BUILT operator of the handle (never the dt-shifted step operator),  F = chi (x) Mf,
+ *   tf(phi) = sum_g' Mf_g' phi_g',  W_p(e) the mass weight of a unit cross section,  w = the handle's adjoint flux (nf_solve_adjoint or
+ *   nf_set_phi_adj),  chi_d per group and DOF as nf_transient_begin takes it (the ng given values in every cell, or the handle's Chi per
+ *   cell when NULL),  k0 the given eigenvalue.
+ * Raw forms, all returned:
+ *   production         = w^T F phi = sum_j (sum_g chi_g w_g)_j tf_j                    (nf_sensitivity's Nrm)
+ *   delayed_production = sum_j (sum_g chi_d,g w_g)_j tf_j
+ *   removal_leakage    = sum_g w_g^T S_g phi_g
+ *   scatter            = sum_{g != g'} w_g^T Ms[g <- g'] phi_g'                         (the built blocks)
+ *   amplitude          = T = sum_g w_g^T diag(W / v_g) phi_g
+ *   c_amp[i]           = C_i = sum_j (sum_g chi_d,g w_g)_j c_i,j                        (nf_transient_kinetics only; 0 otherwise)
+ * The 1e-14 drop of chi / k at P >= 1 is ignored, as in nf_sensitivity.  Derived on the host from those, in exactly these expressions:
+ *   fw = production / k0                       rho = (production / k0 - removal_leakage + scatter) / fw
+ *   beta_eff_i[i] = beta_i delayed_production / production,  beta_eff = their sum (in the order of the families)
+ *   gen_time = Lambda = amplitude / fw         rho_dollars = rho / beta_eff (0 when beta_eff = 0)
+ * Two identities hold for ANY weight w:
+ *   1. exact perturbation: with (phi', k') the eigenpair of the built operator, rho = 1 - k0 / k';
+ *   2. discrete point kinetics: after every completed implicit-Euler step of nf_transient_step, with everything evaluated on phi^{n+1},
+ *      c^{n+1} and the handle's current cross sections, (T^{n+1} - T^n) / dt = (rho - beta_eff) fw + sum_i lambda_i C_i^{n+1}.
+ * beta_eff_i = beta_i exactly when chi_d is NULL.  A caller who wants the classical weighting solves the adjoint at the initial critical
+ * state, THEN perturbs and rebuilds: the adjoint flux is kept across nf_upload_xs / nf_build.
+ * nf_kinetics_params evaluates the forms on the handle's current flux with the kinetics data and keff given (n_families precursor
+ * families enter beta_eff_i only); nf_transient_kinetics on the running transient's own flux and precursors, with the kinetics data and
+ * the keff of nf_transient_begin, at the transient's time.  Both form y_g = S_g phi_g with the launch functions of nf_schur_apply under
+ * the handle's options, then all 5 + I sums in one streaming pass (k_kin_forms) whose block shares are added in a fixed order: the
+ * results are deterministic.  Device memory during the call: ng n_phi doubles for y, n_phi doubles for W when no transient runs (a
+ * running transient lends its copy), and 13 x 1024 doubles of block shares.  nf_set_option "kin_grid" = blocks of 256 threads of that pass
+ * (default and cap 1024; it walks larger meshes with a grid stride).
+ * Neither call changes any state: the flux, the adjoint flux, Gamma+, nf_get_J, the warm k-eff state, the history, nf_progress, the
+ * timers and the transient (time, flux, precursors, step operator, nf_info "transient_rebuilds") are untouched; nf_kinetics_params works
+ * with a transient running and leaves it alone.
+ * Errors (the text names the function): handle not built, no adjoint flux, nf_transient_kinetics without a running transient ->
+ * NF_ERR_STATE; invalid kinetics data (the rules of nf_transient_begin), keff non-finite or <= 0, res NULL -> NF_ERR_ARG; production zero
+ * or non-finite, or any non-finite form -> NF_ERR_NUMERIC (res then still holds the raw forms, the derived fields are 0); slab teams,
+ * multi-rank teams, a handle with cut-out cells (nf_set_void) and meshes of 2^32 cells or more -> NF_ERR_UNSUPPORTED, before any launch
+ * or collective.  After any error the handle stays usable. */
+typedef struct nf_pk_result {
+    double rho, rho_dollars, beta_eff, beta_eff_i[NF_PRECURSORS_MAX], gen_time, fw;
+    double production, delayed_production, removal_leakage, scatter, amplitude, c_amp[NF_PRECURSORS_MAX];
+    double keff, time;            /* k0 used; t of the transient (0 for nf_kinetics_params) */
+    int n_families, from_transient;
+} nf_pk_result;
+int nf_kinetics_params(nf_handle h, const nf_kinetics *kin, double keff, nf_pk_result *res);  /* the handle's current flux */
+int nf_transient_kinetics(nf_handle h, nf_pk_result *res);  /* the running transient's own flux, precursors, kin and k0 of begin */
+
 /* NeutFEM::SolveCoarse (src/NeutFEM.cpp:2380-2611): returns k_coarse and the prolonged flux
  * (ng*n_phi doubles, host) without touching the fine solution. */
 int nf_solve_coarse(nf_handle h, const nf_keff_opts *opts, double *k_coarse, double *phi_host);
@@ -568,7 +617,9 @@ int nf_time_device_copy(nf_handle h, size_t bytes, int reps, double *gbps);
  *   the current one is scanned.  -1 = the directions that measurably gain, where a block has at least two tiles, 0 = off,
  *   1 = wherever eligible.  Only loads move: the results are bit-identical.  nf_apply_plan reports "stage" and "blocks" per pass;
  *   "transient_rebalance" (default 1): nf_transient_step scales the iterate of every outer by the balance factor f; 0 = plain source
- *   iteration (same fixed point, a contraction of about 1 - beta per outer: for measurements).
+ *   iteration (same fixed point, a contraction of about 1 - beta per outer: for measurements);
+ *   "kin_grid" (default 1024, at most 1024): blocks of 256 threads of the k_kin_forms pass of nf_kinetics_params / nf_transient_kinetics
+ *   (larger meshes are walked with a grid stride; 1 makes the stride wrap on any mesh, for tests); "sens_grid" the same for nf_sensitivity.
  * The handles the library derives from h solve under h's options: the step operator of nf_transient_step (at every call), the fine
  * handle of nf_refine / nf_zoom_resolved (as they are when it is made) and, for the options that choose its solve, the coarse twin of SolveCoarse.
  * nf_info keys beyond the mesh sizes: "last_path" (0 host-driven outer loop, 1 diagonal device loop, 2 resident kernel, 3 one-XCD kernel),

@@ -16,7 +16,7 @@ SYMBOLS = [
     "nf_schur_apply", "nf_solve_group", "nf_build_diagonal_cache", "nf_get_diagonal_cache", "nf_solve_keff",
     "nf_upload_source", "nf_solve_subcritical", "nf_solve_modes", "nf_get_mode", "nf_block_gram", "nf_block_rotate", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_apply_plan", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_project_flux", "nf_project_power", "nf_refine", "nf_zoom_source", "nf_get_source", "nf_set_phi_adj", "nf_zoom_resolved", "nf_sensitivity", "nf_solve_gpt", "nf_get_gamma", "nf_set_gamma", "nf_gpt_source", "nf_gpt_sensitivity", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
     "nf_get_warm_state", "nf_get_history", "nf_profile_get", "nf_profile_reset", "nf_time_schur_apply", "nf_time_device_copy", "nf_progress", "nf_set_progress_callback", "nf_local_matrices",
-    "nf_transient_begin", "nf_transient_step", "nf_get_precursors", "nf_transient_end",
+    "nf_transient_begin", "nf_transient_step", "nf_get_precursors", "nf_transient_end", "nf_kinetics_params", "nf_transient_kinetics",
     "nf_set_option", "nf_mem_info", "nf_dev_alloc", "nf_dev_free", "nf_memcpy_h2d", "nf_memcpy_d2h", "nf_synchronize", "nf_stream",
 ]
 
@@ -85,6 +85,18 @@ class TransientResult(C.Structure):
     def as_dict(self): return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PkResult(C.Structure):
+    _fields_ = [("rho", C.c_double), ("rho_dollars", C.c_double), ("beta_eff", C.c_double), ("beta_eff_i", C.c_double * PRECURSORS_MAX),
+                ("gen_time", C.c_double), ("fw", C.c_double), ("production", C.c_double), ("delayed_production", C.c_double),
+                ("removal_leakage", C.c_double), ("scatter", C.c_double), ("amplitude", C.c_double), ("c_amp", C.c_double * PRECURSORS_MAX),
+                ("keff", C.c_double), ("time", C.c_double), ("n_families", C.c_int), ("from_transient", C.c_int)]
+
+    def as_dict(self):
+        d = {name: getattr(self, name) for name, _ in self._fields_}
+        d["beta_eff_i"], d["c_amp"] = list(self.beta_eff_i)[:self.n_families], list(self.c_amp)[:self.n_families]
+        return d
+
+
 _LIB = None
 
 
@@ -146,6 +158,8 @@ def load():
     L.nf_transient_step.argtypes = [vp, C.POINTER(KeffOpts), C.c_double, C.c_int, dp, C.POINTER(TransientResult)]
     L.nf_get_precursors.argtypes = [vp, C.c_int, dp]
     L.nf_transient_end.argtypes = [vp]
+    L.nf_kinetics_params.argtypes = [vp, C.POINTER(KineticsArgs), C.c_double, C.POINTER(PkResult)]
+    L.nf_transient_kinetics.argtypes = [vp, C.POINTER(PkResult)]
     L.nf_set_phi.argtypes = [vp, dp]
     L.nf_get_phi.argtypes = [vp, dp]
     L.nf_get_J.argtypes = [vp, dp]
@@ -331,9 +345,8 @@ class HipSolver:
         """mode i of the last solve_modes of that kind, (ng, n_phi) in the host DOF layout of get_phi; unit L2 norm"""
         out = np.empty(self.ng * self.n_phi); self._chk(self.L.nf_get_mode(self.h, int(i), int(adjoint), _dp(out))); return out.reshape(self.ng, self.n_phi)
 
-    def transient_begin(self, velocity, beta, lam, keff, chi_delayed=None):
-        """nf_transient_begin: a transient from the current flux and the eigenvalue keff; velocity (ng), beta / lam (one entry per
-        precursor family, at most PRECURSORS_MAX; empty = prompt neutrons only), chi_delayed (ng values, None = the handle's Chi)"""
+    def _kinetics_args(self, velocity, beta, lam, chi_delayed):
+        """(KineticsArgs, the arrays its pointers refer to -- keep them alive over the call)"""
         v = np.ascontiguousarray(velocity, dtype=np.float64).ravel(); assert v.size == self.ng
         b, l = (np.asarray(a, dtype=np.float64).ravel() for a in (beta, lam)); assert b.size == l.size
         k = KineticsArgs(); k.n_families = int(b.size)
@@ -344,7 +357,27 @@ class HipSolver:
         if cd is not None:
             assert cd.size == self.ng
             k.chi_delayed_host = _dp(cd)
+        return k, (v, cd)
+
+    def transient_begin(self, velocity, beta, lam, keff, chi_delayed=None):
+        """nf_transient_begin: a transient from the current flux and the eigenvalue keff; velocity (ng), beta / lam (one entry per
+        precursor family, at most PRECURSORS_MAX; empty = prompt neutrons only), chi_delayed (ng values, None = the handle's Chi)"""
+        k, _keep = self._kinetics_args(velocity, beta, lam, chi_delayed)
         self._chk(self.L.nf_transient_begin(self.h, C.byref(k), float(keff)))
+
+    def kinetics_params(self, velocity, beta, lam, keff, chi_delayed=None):
+        """nf_kinetics_params: reactivity, beta_eff, generation time and the raw adjoint-weighted forms of the CURRENT flux at keff (the
+        arguments of transient_begin); the nf_pk_result as a dict, beta_eff_i / c_amp as lists of one entry per family"""
+        k, _keep = self._kinetics_args(velocity, beta, lam, chi_delayed)
+        r = PkResult()
+        self._chk(self.L.nf_kinetics_params(self.h, C.byref(k), float(keff), C.byref(r)))
+        return r.as_dict()
+
+    def transient_kinetics(self):
+        """nf_transient_kinetics: the same on the running transient's own flux and precursors, with the data and keff of transient_begin"""
+        r = PkResult()
+        self._chk(self.L.nf_transient_kinetics(self.h, C.byref(r)))
+        return r.as_dict()
 
     def transient_step(self, dt, n_steps=1):
         """nf_transient_step with the tolerances / linear solver of this object: (result dict, relative power after every step)"""

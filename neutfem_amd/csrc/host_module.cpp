@@ -299,6 +299,56 @@ public:
         d["cg_total"] = r.cg_total; d["n_unconverged"] = r.n_unconverged;
         return d;
     }
+    // Adjoint-weighted kinetics parameters (extension; include/neutfem_hip.h, nf_kinetics_params / nf_transient_kinetics).
+    // kinetics_parameters evaluates the solved flux with k = last_keff_ and the fields of the host mirrors, pushed the way sensitivity_maps
+    // pushes them; get_transient_kinetics the running transient's own state with the adjoint flux of the mirror.  Both return the
+    // nf_pk_result as a dict (the arrays cut to n_families) and change neither mirror.
+    static py::dict PkDict(const nf_pk_result &r)
+    {
+        py::dict d;
+        d["rho"] = r.rho; d["rho_dollars"] = r.rho_dollars; d["beta_eff"] = r.beta_eff; d["gen_time"] = r.gen_time; d["fw"] = r.fw;
+        d["production"] = r.production; d["delayed_production"] = r.delayed_production; d["removal_leakage"] = r.removal_leakage;
+        d["scatter"] = r.scatter; d["amplitude"] = r.amplitude; d["keff"] = r.keff; d["time"] = r.time;
+        d["n_families"] = r.n_families; d["from_transient"] = r.from_transient;
+        py::list bi, ca;
+        for (int i = 0; i < r.n_families; ++i) { bi.append(r.beta_eff_i[i]); ca.append(r.c_amp[i]); }
+        d["beta_eff_i"] = bi; d["c_amp"] = ca;
+        return d;
+    }
+    py::dict KineticsParameters(arr_t velocity, arr_t beta, arr_t decay, py::object chi_delayed)
+    {
+        if (!h_) throw std::runtime_error("kinetics_parameters: call BuildMatrices() first (there is no CPU fallback)");
+        if (!has_valid_keff_ || !has_valid_adjoint_)
+            throw std::runtime_error(std::string("kinetics_parameters: call ") + (!has_valid_keff_ ? "SolveKeff()" : "SolveAdjoint()") +
+                                     " first (the parameters need a solved flux, a solved adjoint flux and k-eff)");
+        if (velocity.size() != ng_) throw std::runtime_error("kinetics_parameters: velocity needs one entry per group");
+        if (beta.size() != decay.size()) throw std::runtime_error("kinetics_parameters: beta and decay need one entry per precursor family each");
+        if (beta.size() > NF_PRECURSORS_MAX) throw std::runtime_error("kinetics_parameters: at most " + std::to_string(NF_PRECURSORS_MAX) + " precursor families");
+        nf_kinetics kin{};
+        kin.n_families = (int)beta.size();
+        for (int i = 0; i < kin.n_families; ++i) { kin.beta[i] = beta.data()[i]; kin.lambda[i] = decay.data()[i]; }
+        kin.velocity_host = velocity.data();
+        arr_t cd;
+        if (!chi_delayed.is_none()) {
+            cd = chi_delayed.cast<arr_t>();
+            if (cd.size() != ng_) throw std::runtime_error("kinetics_parameters: chi_delayed needs one entry per group");
+            kin.chi_delayed_host = cd.data();
+        }
+        chk(nf_set_phi(h_, Phi_.data())); chk(nf_set_phi_adj(h_, PhiAdj_.data()));
+        nf_pk_result r{};
+        chk(nf_kinetics_params(h_, &kin, last_keff_, &r));
+        return PkDict(r);
+    }
+    py::dict GetTransientKinetics()
+    {
+        if (!h_) throw std::runtime_error("get_transient_kinetics: call BuildMatrices() first (there is no CPU fallback)");
+        if (!has_transient_) throw std::runtime_error("get_transient_kinetics: call begin_transient() first");
+        if (!has_valid_adjoint_) throw std::runtime_error("get_transient_kinetics: call SolveAdjoint() first (the parameters are weighted with the adjoint flux)");
+        chk(nf_set_phi_adj(h_, PhiAdj_.data()));
+        nf_pk_result r{};
+        chk(nf_transient_kinetics(h_, &r));
+        return PkDict(r);
+    }
     // SolveModes (extension; include/neutfem_hip.h, nf_solve_modes): the n_modes leading lambda-modes by block power iteration with the
     // tolerances and the linear solver of this object; returns the eigenvalues, descending.  Flux, adjoint flux and GetLastKeff stay as they are
     std::vector<double> SolveModes(int n_modes, int n_guard, bool adjoint)
@@ -773,6 +823,10 @@ PYBIND11_MODULE(_neutfem_eigen, m)
         .def("step_transient", &NeutFEM::StepTransient, py::arg("dt"), py::arg("n_steps") = 1,
              "extension: n_steps implicit-Euler steps of length dt; returns P / P(0) after every step; get_flux() then holds the flux at time t")
         .def("get_precursors", &NeutFEM::GetPrecursors, py::arg("i"), "extension: precursor family i of the running transient, cell values shaped like one group of get_flux()")
+        .def("kinetics_parameters", &NeutFEM::KineticsParameters, py::arg("velocity"), py::arg("beta"), py::arg("decay"), py::arg("chi_delayed") = py::none(),
+             "extension: adjoint-weighted rho, beta_eff (and its split), generation time and the raw forms of the solved flux at GetLastKeff() as a dict (arguments of begin_transient)")
+        .def("get_transient_kinetics", &NeutFEM::GetTransientKinetics,
+             "extension: the same for the running transient's own flux and precursors, with the data and keff of begin_transient")
         .def("get_transient_info", &NeutFEM::GetTransientInfo,
              "extension: the last step_transient's nf_transient_result as a dict (time, power, production, phi_int, precursors, rebalance, step and outer counts)");
 }

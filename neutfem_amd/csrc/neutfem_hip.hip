@@ -199,6 +199,7 @@ struct nf_team {
     // the round-2 latency work: 64^3 19.1 vs 27.2 us per CG iteration, 80^3 39.1 vs 34.5, 128^3 77.7 vs 70.9, 160^3 221 vs 150
     int opt_fuse3 = 1; long fuse3_max_cells = 400000;
     int opt_sens_grid = RED_GRID;                         // blocks of the nf_sensitivity launches (grid stride beyond; option "sens_grid")
+    int opt_kin_grid = RED_GRID;                          // blocks of k_kin_forms, at most RED_GRID (grid stride beyond; option "kin_grid")
     // whole CG solve in one launch on the workgroups of one XCD (k_cg_xcd): RT0-P0 meshes between the one-workgroup resident kernel and
     // xcd_max_cells.  One XCD has an eighth of the chip's compute units and L2 (4 MiB): beyond that the launch path wins back.
     int opt_cgx = 1, opt_keffx = 1, xcd_id = 0, xcd_groups = 32, last_xcd = 0; long xcd_min_cells = 2000, xcd_max_cells = 28000, xcd_solves = 0, xcd_refused = 0;
@@ -2657,7 +2658,7 @@ static void team_copy_options(nf_team *C, const nf_team *T, bool same_mesh_kind)
     C->s_long_min = T->s_long_min; C->s_long_min_y = T->s_long_min_y; C->opt_s_seg = T->opt_s_seg; C->opt_s_tx = T->opt_s_tx;
     C->opt_wsmin = T->opt_wsmin; C->opt_c_early = T->opt_c_early; C->opt_s_stage = T->opt_s_stage; C->opt_s_stage_grid = T->opt_s_stage_grid; C->opt_x_p2 = T->opt_x_p2; C->opt_split_dot = T->opt_split_dot; C->opt_xcd = T->opt_xcd;
     C->opt_xy_overlap = T->opt_xy_overlap; C->xy_overlap_max_cells = T->xy_overlap_max_cells; C->opt_vec_reduce = T->opt_vec_reduce;
-    C->opt_pub = T->opt_pub; C->opt_sens_grid = T->opt_sens_grid; C->prof_every = T->prof_every;
+    C->opt_pub = T->opt_pub; C->opt_sens_grid = T->opt_sens_grid; C->opt_kin_grid = T->opt_kin_grid; C->prof_every = T->prof_every;
     if (dict_moved) { (void)hipSetDevice(C->device); for (auto *X : C->slabs) line_dict_drop(X); }
     else if (regime_moved) for (auto *X : C->slabs) if (!X->d_lid[0] && !X->d_lid[1] && !X->d_lid[2]) X->ld_tried = false;
 }
@@ -3799,6 +3800,27 @@ int nf_transient_end(nf_handle S)
     return NF_OK;
 }
 
+// the kinetics data of nf_transient_begin, nf_kinetics_params: one set of rules, `who` names the caller in the text
+static int kinetics_check(const nf_solver *S, const nf_kinetics *kin, double keff, const char *who)
+{
+    const int ng = S->ng, I = kin->n_families;
+    if (!(keff > 0.0) || !std::isfinite(keff)) return fail(NF_ERR_ARG, "%s: keff must be finite and > 0 (got %g)", who, keff);
+    if (I < 0 || I > NF_PRECURSORS_MAX) return fail(NF_ERR_ARG, "%s: n_families must be 0 .. %d (got %d)", who, NF_PRECURSORS_MAX, I);
+    if (!kin->velocity_host) return fail(NF_ERR_ARG, "%s: velocity_host is NULL", who);
+    for (int g = 0; g < ng; ++g) {
+        if (!(kin->velocity_host[g] > 0.0) || !std::isfinite(kin->velocity_host[g])) return fail(NF_ERR_ARG, "%s: velocity of group %d must be finite and > 0 (got %g)", who, g, kin->velocity_host[g]);
+        if (kin->chi_delayed_host && !std::isfinite(kin->chi_delayed_host[g])) return fail(NF_ERR_ARG, "%s: non-finite delayed spectrum in group %d", who, g);
+    }
+    double bsum = 0.0;
+    for (int i = 0; i < I; ++i) {
+        if (!(kin->beta[i] >= 0.0) || !std::isfinite(kin->beta[i])) return fail(NF_ERR_ARG, "%s: beta of family %d must be finite and >= 0 (got %g)", who, i, kin->beta[i]);
+        if (!(kin->lambda[i] > 0.0) || !std::isfinite(kin->lambda[i])) return fail(NF_ERR_ARG, "%s: lambda of family %d must be finite and > 0 (got %g)", who, i, kin->lambda[i]);
+        bsum += kin->beta[i];
+    }
+    if (!(bsum < 1.0)) return fail(NF_ERR_ARG, "%s: the delayed fractions sum to %g (must be < 1)", who, bsum);
+    return NF_OK;
+}
+
 int nf_transient_begin(nf_handle S, const nf_kinetics *kin, double keff)
 {
     if (!S || !kin) return fail(NF_ERR_ARG, "nf_transient_begin: bad arguments");
@@ -3807,20 +3829,7 @@ int nf_transient_begin(nf_handle S, const nf_kinetics *kin, double keff)
     if (T->nproc > 1 || !team_is_single(T)) return fail(NF_ERR_UNSUPPORTED, "nf_transient_begin works on an undivided mesh of one process (not on slab or multi-rank teams)");
     if (!S->built) return fail(NF_ERR_STATE, "nf_transient_begin: call nf_build first");
     const int ng = S->ng, I = kin->n_families;
-    if (!(keff > 0.0) || !std::isfinite(keff)) return fail(NF_ERR_ARG, "nf_transient_begin: keff must be finite and > 0 (got %g)", keff);
-    if (I < 0 || I > NF_PRECURSORS_MAX) return fail(NF_ERR_ARG, "nf_transient_begin: n_families must be 0 .. %d (got %d)", NF_PRECURSORS_MAX, I);
-    if (!kin->velocity_host) return fail(NF_ERR_ARG, "nf_transient_begin: velocity_host is NULL");
-    for (int g = 0; g < ng; ++g) {
-        if (!(kin->velocity_host[g] > 0.0) || !std::isfinite(kin->velocity_host[g])) return fail(NF_ERR_ARG, "nf_transient_begin: velocity of group %d must be finite and > 0 (got %g)", g, kin->velocity_host[g]);
-        if (kin->chi_delayed_host && !std::isfinite(kin->chi_delayed_host[g])) return fail(NF_ERR_ARG, "nf_transient_begin: non-finite delayed spectrum in group %d", g);
-    }
-    double bsum = 0.0;
-    for (int i = 0; i < I; ++i) {
-        if (!(kin->beta[i] >= 0.0) || !std::isfinite(kin->beta[i])) return fail(NF_ERR_ARG, "nf_transient_begin: beta of family %d must be finite and >= 0 (got %g)", i, kin->beta[i]);
-        if (!(kin->lambda[i] > 0.0) || !std::isfinite(kin->lambda[i])) return fail(NF_ERR_ARG, "nf_transient_begin: lambda of family %d must be finite and > 0 (got %g)", i, kin->lambda[i]);
-        bsum += kin->beta[i];
-    }
-    if (!(bsum < 1.0)) return fail(NF_ERR_ARG, "nf_transient_begin: the delayed fractions sum to %g (must be < 1)", bsum);
+    NFCHK(kinetics_check(S, kin, keff, "nf_transient_begin"));
     HIPCHK(hipSetDevice(S->device));
     transient_drop(S);
     Transient *R = new Transient();
@@ -4055,6 +4064,100 @@ int nf_get_precursors(nf_handle S, int family, double *c_host)
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipMemcpy(c_host, src, (size_t)S->nphi * sizeof(double), hipMemcpyDeviceToHost));
     return NF_OK;
+}
+
+// ---- adjoint-weighted kinetics parameters and dynamic reactivity (no counterpart in the reference) ----------------------
+// The bilinear forms of the point-kinetics balance on (w = the handle's adjoint flux, phi, c): y_g = S_g phi_g by the launch functions of
+// the plain nf_schur_apply on the BUILT operator of the handle (never the dt-shifted twin), then one k_kin_forms pass and k_finalize.
+struct KinData {                                                  // what both fronts hand to pk_body
+    int nfam; const double *beta, *lambda, *v, *chid;             // chid: ng values of the delayed spectrum, nullptr = the handle's Chi per cell
+    const double *d_c, *d_W;                                      // the precursors (nullptr: no transient, c_amp = 0) and the transient's mass weights (nullptr: built here)
+    double time; int from_transient;
+};
+static const int KIN_ROWS = 5 + NF_PRECURSORS_MAX;
+// the state both fronts need, judged before any launch
+static int pk_args(nf_handle S, nf_pk_result *res, const char *who)
+{
+    if (!S || !res) return fail(NF_ERR_ARG, "%s: bad arguments", who);
+    NFCHK(void_refuse(S, who));
+    nf_team *T = S->team;
+    if (T->nproc > 1 || !team_is_single(T)) return fail(NF_ERR_UNSUPPORTED, "%s works on an undivided mesh of one process (not on slab or multi-rank teams)", who);
+    if (S->N > 0xFFFFFFFFL) return fail(NF_ERR_UNSUPPORTED, "%s: %ld cells (meshes of 2^32 cells or more are not supported)", who, S->N);
+    if (!S->built) return fail(NF_ERR_STATE, "%s: call nf_build first", who);
+    if (!S->d_phi_adj) return fail(NF_ERR_STATE, "%s: no adjoint flux (nf_solve_adjoint or nf_set_phi_adj first)", who);
+    return NF_OK;
+}
+static int pk_body(nf_solver *S, const char *who, const double *phi, const KinData &K, double k0, nf_pk_result *res)
+{
+    nf_team *T = S->team; hipStream_t st = T->stream;
+    const int ng = S->ng, I = K.nfam; const long N = S->N, NP = S->nphi;
+    memset(res, 0, sizeof *res);
+    res->keff = k0; res->time = K.time; res->n_families = I; res->from_transient = K.from_transient;
+    HIPCHK(hipSetDevice(S->device));
+    (void)hipGetLastError();
+    DevTmp<double> y, part, W;
+    NFCHK(dalloc(&y.p, (size_t)NP * ng)); NFCHK(dalloc(&part.p, (size_t)KIN_ROWS * RED_GRID + KIN_ROWS));
+    double *sums = part.p + (size_t)KIN_ROWS * RED_GRID;
+    const double *dW = K.d_W;
+    if (!dW) {
+        NFCHK(dalloc(&W.p, (size_t)NP));
+        ChatArgs ch; ch.nloc = S->nloc;                           // C-hat_pp as nf_build forms it
+        for (int p = 0; p < S->nloc; ++p) {
+            int q = p; double c = 1.0;
+            for (int t = 0; t < S->dim; ++t) { c *= 2.0 / (2.0 * (q % S->n1) + 1.0); q /= S->n1; }
+            ch.c[p] = c;
+        }
+        hipLaunchKernelGGL(k_tr_weights, dim3(grid_for(N)), dim3(256), 0, st, W.p, S->d_hx, S->d_hy, S->d_hz, S->nx, S->ny, N, S->dim, ch);
+        dW = W.p;
+    }
+    NFCHK(line_dict_prepare(T));                                  // as nf_schur_apply
+    const bool prof = T->profile; T->profile = false;             // no event brackets: the timers stay as they are
+    int rc = NF_OK;
+    for (int g = 0; g < ng && rc == NF_OK; ++g) rc = team_schur_apply(T, g, { phi + (size_t)g * NP }, { y.p + (size_t)g * NP }, false, ApplyCg());
+    T->profile = prof;
+    if (rc != NF_OK) { (void)hipStreamSynchronize(st); return rc; }
+    TrGroups ivel, chid; memset(&ivel, 0, sizeof ivel); memset(&chid, 0, sizeof chid);
+    for (int g = 0; g < ng; ++g) { ivel.v[g] = 1.0 / K.v[g]; if (K.chid) chid.v[g] = K.chid[g]; }
+    const int grid = grid_for(NP, 256, T->opt_kin_grid), nfam = K.d_c ? I : 0, rows = 5 + nfam;   // without precursors no c_amp row is formed
+    hipLaunchKernelGGL(k_kin_forms, dim3(grid), dim3(256), 0, st, (const double *)S->d_phi_adj, phi, (const double *)y.p, (const double *)S->d_Mf,
+                       (const double *)S->d_Chi, dW, (const double *const *)S->d_Ms_tab, K.d_c, N, NP, ng, ivel, chid, K.chid ? 0 : 1, nfam,
+                       part.p, (long)RED_GRID);
+    for (int r0 = 0; r0 < rows; r0 += 4) tr_finalize(T, part.p + (size_t)r0 * RED_GRID, grid, std::min(4, rows - r0), sums + r0);   // k_finalize takes four rows
+    double h[KIN_ROWS]; memset(h, 0, sizeof h);
+    HIPCHK(hipMemcpyAsync(h, sums, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));                             // the temporaries are freed on return
+    HIPCHK(hipGetLastError());
+    res->production = h[0]; res->delayed_production = h[1]; res->removal_leakage = h[2]; res->scatter = h[3]; res->amplitude = h[4];
+    bool finite = true;
+    for (int r = 0; r < 5; ++r) finite = finite && std::isfinite(h[r]);
+    for (int i = 0; i < nfam; ++i) { res->c_amp[i] = h[5 + i]; finite = finite && std::isfinite(res->c_amp[i]); }
+    if (!finite || res->production == 0.0)
+        return fail(NF_ERR_NUMERIC, "%s: the forms are not usable: production phi+^T F phi = %g, delayed %g, removal + leakage %g, scatter %g, amplitude %g "
+                    "(orthogonal, zero or non-finite fields, or no fission)", who, h[0], h[1], h[2], h[3], h[4]);
+    res->fw = res->production / k0;
+    res->rho = (res->production / k0 - res->removal_leakage + res->scatter) / res->fw;
+    for (int i = 0; i < I; ++i) { res->beta_eff_i[i] = K.beta[i] * res->delayed_production / res->production; res->beta_eff += res->beta_eff_i[i]; }
+    res->gen_time = res->amplitude / res->fw;
+    res->rho_dollars = res->beta_eff == 0.0 ? 0.0 : res->rho / res->beta_eff;
+    return NF_OK;
+}
+
+int nf_kinetics_params(nf_handle S, const nf_kinetics *kin, double keff, nf_pk_result *res)
+{
+    NFCHK(pk_args(S, res, "nf_kinetics_params"));
+    if (!kin) return fail(NF_ERR_ARG, "nf_kinetics_params: bad arguments");
+    NFCHK(kinetics_check(S, kin, keff, "nf_kinetics_params"));
+    KinData K = { kin->n_families, kin->beta, kin->lambda, kin->velocity_host, kin->chi_delayed_host, nullptr, S->tr ? S->tr->d_W : nullptr, 0.0, 0 };
+    return pk_body(S, "nf_kinetics_params", S->d_phi, K, keff, res);
+}
+
+int nf_transient_kinetics(nf_handle S, nf_pk_result *res)
+{
+    NFCHK(pk_args(S, res, "nf_transient_kinetics"));
+    const Transient *R = S->tr;
+    if (!R) return fail(NF_ERR_STATE, "nf_transient_kinetics: call nf_transient_begin first");
+    KinData K = { R->nfam, R->beta, R->lambda, R->v.data(), R->has_chid ? R->chid.data() : nullptr, R->d_c, R->d_W, R->time, 1 };
+    return pk_body(S, "nf_transient_kinetics", R->d_phi, K, R->k0, res);
 }
 
 // ---- SolveAdjoint (src/NeutFEM.cpp:1877-2082) -----------------------------------------------------
@@ -5337,6 +5440,7 @@ int nf_set_option(nf_handle S, const char *key, long value)
     else if (!strcmp(key, "cg_fuse3_max_cells")) T->fuse3_max_cells = value;
     else if (!strcmp(key, "cg_lean_grid")) T->opt_lean_grid = (int)std::max(1L, std::min(1024L, value));
     else if (!strcmp(key, "sens_grid")) T->opt_sens_grid = (int)std::max(1L, std::min(65536L, value));
+    else if (!strcmp(key, "kin_grid")) T->opt_kin_grid = (int)std::max(1L, std::min((long)RED_GRID, value));
     else if (!strcmp(key, "transient_rebalance")) S->opt_tr_rebalance = value != 0;
     else return fail(NF_ERR_ARG, "nf_set_option: unknown key %s", key);
     // options that move a mesh into or out of the streaming kernels: look again at the next apply (a mesh whose lines do not repeat pays the

@@ -2762,6 +2762,60 @@ __global__ __launch_bounds__(256) void k_tr_precursors(const double *__restrict_
     sc = block_sum(sc, sred); sp = block_sum(sp, sred);
     if (threadIdx.x == 0) { partials[blockIdx.x] = sc; partials[stride + blockIdx.x] = sp; }
 }
+// ---- adjoint-weighted kinetics parameters, nf_kinetics_params / nf_transient_kinetics ----------------------------------
+// All bilinear forms of the point-kinetics balance in ONE streaming pass over the n DOF indices of a group: with w the adjoint flux,
+// y_g = S_g phi_g (the Schur apply of the built operator, formed before this launch), tf = sum_g Mf_g phi_g, xw = sum_g chi_g w_g and
+// xd = sum_g chi_d,g w_g (chi_d as in k_tr_chi), the rows of the partials are
+//   0 production = sum xw tf    1 delayed_production = sum xd tf    2 removal_leakage = sum_g w_g y_g
+//   3 scatter = sum_{g != g'} w_g Ms[g<-g'] phi_g' (the built blocks, Ms as k_tr_emission takes them)
+//   4 amplitude = sum W sum_g w_g phi_g / v_g (ivel.v[g] = 1 / v_g)    5 + i  c_amp[i] = sum xd c_i   (i < nfam; c may be NULL with nfam = 0)
+// Per index: w_g, phi_g, y_g, Mf_g of every group, chi_g of the cell, W, the non-empty scatter blocks and the nfam precursor vectors,
+// each read once with consecutive lanes on consecutive doubles (phi_g' of a scatter term is the load of the group loop again); xw, xd, tf
+// and the 5 + NF_PRECURSORS_MAX running sums stay in registers (the family loop is unrolled over its bound so that they do).  The cell
+// of an index is carried along the grid stride (one modulo per thread, not one per index).  One share per block and sum, k_finalize adds them.
+__global__ __launch_bounds__(256) void k_kin_forms(const double *__restrict__ w, const double *__restrict__ phi, const double *__restrict__ y,
+                                                   const double *__restrict__ Mf, const double *__restrict__ chi, const double *__restrict__ W,
+                                                   const double *const *__restrict__ Ms, const double *__restrict__ c, long N, long n, int ng,
+                                                   TrGroups ivel, TrGroups chid, int per_cell, int nfam, double *__restrict__ partials, long stride)
+{
+    __shared__ double sred[4];
+    double sp = 0.0, sd = 0.0, sl = 0.0, ss = 0.0, sa = 0.0, sc[NF_PRECURSORS_MAX];
+#pragma unroll
+    for (int i = 0; i < NF_PRECURSORS_MAX; ++i) sc[i] = 0.0;
+    const long step = gridDim.x * 256L, estep = step % N;
+    long j = blockIdx.x * 256L + threadIdx.x, e = j % N;
+    for (; j < n; j += step) {
+        double xw = 0.0, xd = 0.0, tf = 0.0, am = 0.0;
+        for (int g = 0; g < ng; ++g) {
+            const double wg = w[g * n + j], pg = phi[g * n + j], cg = chi[g * N + e];
+            xw += cg * wg; xd += (per_cell ? cg : chid.v[g]) * wg;
+            tf += Mf[g * n + j] * pg;
+            sl += wg * y[g * n + j];
+            am += ivel.v[g] * (wg * pg);
+            for (int gp = 0; gp < ng; ++gp) {
+                const double *M = Ms[g * ng + gp];
+                if (gp == g || !M) continue;
+                ss += wg * (M[j] * phi[gp * n + j]);
+            }
+        }
+        sa += W[j] * am; sp += xw * tf; sd += xd * tf;
+#pragma unroll
+        for (int i = 0; i < NF_PRECURSORS_MAX; ++i)
+            if (i < nfam) sc[i] += xd * c[i * n + j];
+        e += estep; if (e >= N) e -= N;
+    }
+    sp = block_sum(sp, sred); sd = block_sum(sd, sred); sl = block_sum(sl, sred); ss = block_sum(ss, sred); sa = block_sum(sa, sred);
+#pragma unroll
+    for (int i = 0; i < NF_PRECURSORS_MAX; ++i)
+        if (i < nfam) sc[i] = block_sum(sc[i], sred);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = sp; partials[stride + blockIdx.x] = sd; partials[2 * stride + blockIdx.x] = sl;
+        partials[3 * stride + blockIdx.x] = ss; partials[4 * stride + blockIdx.x] = sa;
+#pragma unroll
+        for (int i = 0; i < NF_PRECURSORS_MAX; ++i)
+            if (i < nfam) partials[(5 + i) * stride + blockIdx.x] = sc[i];
+    }
+}
 // phi /= norm, then ChebyshevAccel::operator() (src/solvers.cpp:720-756).  mode 0: no acceleration,
 // 1: store phi0, 2: phi1 = phi0 + a1 (phi - phi0), 3: three-term.  cur <- result.
 __global__ __launch_bounds__(256) void k_normalize_cheb(const double *__restrict__ raw, double *__restrict__ cur,
