@@ -536,7 +536,8 @@ int nf_timers(nf_handle h, char *json_buf, size_t len);
  * itself), "dict" (the pass reads its line factors from the table of distinct lines, see "line_dict") and "early" (level of early vector
  * loads of a table-backed chunked pass, option "c_early"; 0 for every other pass); y / z passes also "stage" (the staged form of
  * k_schur_s, option "s_stage"; "variant" then ends in "stage") and "blocks" (workgroups launched: the tiles of "grid", or the
- * persistent blocks of a staged pass -- "grid" stays the tile grid); at the top level "line_dict":
+ * persistent blocks of a staged pass -- "grid" stays the tile grid) and "full" (the whole-tile form of the pass, option "tile_full";
+ * never part of "variant"); at the top level "line_dict":
  * {"x", "y", "z"}, the distinct lines of the largest group per direction (0: no table in use).  Built from the predicates the launch functions
  * themselves call.  The one thing it does besides reporting: where the next apply would first build the tables of distinct lines
  * (once per build), the report builds them, since whether a direction verifies is part of the plan; otherwise it launches nothing
@@ -616,6 +617,12 @@ int nf_time_device_copy(nf_handle h, size_t bytes, int reps, double *gbps);
  *   launch of "s_stage_grid" blocks (default 0 = one per compute unit) walks the tiles, and the next tile's vector is copied into LDS while
  *   the current one is scanned.  -1 = the directions that measurably gain, where a block has at least two tiles, 0 = off,
  *   1 = wherever eligible.  Only loads move: the results are bit-identical.  nf_apply_plan reports "stage" and "blocks" per pass;
+ *   "tile_full" (default -1): whole-tile form of the staged y / z pass on k_schur_s ("stage") and of the chunked pass on its table with early
+ *   loads (family c, "dict", "early" 2).  Taken where the tile grid has no partial tile: nx a multiple of the tile width, lines of exactly
+ *   8 NSEG cells (chunked: 16 NS), one thread per (column, segment) in the block, summaries not scanned by whole wavefronts ("s_wsmin").  The
+ *   per-access predicates of the body are then true at compile time: straight-line loads and stores at 32-bit byte offsets.  Values and
+ *   arithmetic are untouched: the results are bit-identical.  -1 and 1 = wherever eligible, 0 = the predicated bodies; a refused staged
+ *   launch falls back to the predicated unstaged pass as before.  nf_apply_plan reports "full" per y / z pass;
  *   "transient_rebalance" (default 1): nf_transient_step scales the iterate of every outer by the balance factor f; 0 = plain source
  *   iteration (same fixed point, a contraction of about 1 - beta per outer: for measurements);
  *   "kin_grid" (default 1024, at most 1024): blocks of 256 threads of the k_kin_forms pass of nf_kinetics_params / nf_transient_kinetics

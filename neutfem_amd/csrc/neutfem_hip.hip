@@ -194,6 +194,7 @@ struct nf_team {
     // s_stage: -1 = the directions of S_STAGE_AUTO_DIRS where a block has a next tile to fetch, 0 = off, 1 = wherever eligible;
     // s_stage_grid: blocks of such a launch, 0 = one per compute unit
     int opt_s_stage = -1, opt_s_stage_grid = 0, ncu = 256;
+    int opt_tile_full = -1;                               // whole-tile form of the staged k_schur_s and the table-backed early-load k_schur_c (FULL): -1 auto (on where eligible), 0, 1
     size_t lds_limit = 160 * 1024;                        // dynamic LDS a block may ask for (hipDeviceAttributeMaxSharedMemoryPerBlock at team creation)
     // fused-direction CG (two launches per iteration) up to this many cells.  Measured crossover against the four-launch lean path after
     // the round-2 latency work: 64^3 19.1 vs 27.2 us per CG iteration, 80^3 39.1 vs 34.5, 128^3 77.7 vs 70.9, 160^3 221 vs 150
@@ -1457,6 +1458,22 @@ static bool s_stage(const nf_solver *S, int d, int zmode, const SegPlan &sp, uns
     if (T->opt_s_stage > 0) return true;
     return ((S_STAGE_AUTO_DIRS >> (d - 1)) & 1) && sp.grid.x * sp.grid.y >= 2 * s_stage_blocks(S, sp);
 }
+// Whole-tile form (FULL) of the staged pass and of the table-backed early-load chunked pass: the grid has no partial tile -- the tile width divides
+// nx, the line is a whole number of segments (of chunks), the block has one thread per (column, segment) and the summaries are not scanned by whole
+// wavefronts.  The bodies then drop the per-access predicates and address the vectors by 32-bit byte offsets (one group's array below 4 GiB).
+static bool s_full(const nf_solver *S, int d, const SegPlan &sp, unsigned V)
+{
+    const nf_team *T = S->team; const int n = d == 1 ? S->ny : S->nz;
+    if (T->opt_tile_full == 0 || !(V & SV_STAGE)) return false;
+    const int wsmin = T->opt_wsmin > 0 ? T->opt_wsmin : 64, nt = sp.TX * sp.NSEG;
+    const bool wscan = sp.NSEG >= wsmin && sp.NSEG <= 64 && (nt & 63) == 0;   // schur_s_tile's test
+    return S->nx % sp.TX == 0 && n == sp.SEG * sp.NSEG && (unsigned)nt == sp.block.x && !wscan && (size_t)S->N * sizeof(double) < (1ull << 32);
+}
+static bool c_full(const nf_solver *S, int d, const ChunkPlan &cp, bool dict, int early)
+{
+    const int n = d == 1 ? S->ny : S->nz;
+    return S->team->opt_tile_full != 0 && dict && early == 2 && S->nx % cp.TX == 0 && n == C_NCH * C_SEG * cp.NS && (unsigned)(cp.TX * cp.NS) == c_block(cp);
+}
 static bool s_fold(const nf_team *T, int zmode) { return zmode == 2 && T->sep_sweeps == 0 && T->opt_sepfold; }   // thick slabs: the accumulation pass forms the separator values itself
 // tiles of a (gx, gy) launch move under the XCD-contiguous order only when their count is a multiple of 8 (the kernels' own test) beyond 8 (the identity)
 static bool xcd_permutes(bool order, unsigned tiles) { return order && tiles % 8 == 0 && tiles > 8; }
@@ -1558,7 +1575,7 @@ static int line_dict_prepare(nf_team *T)
 }
 // One y / z pass, chosen: launch_s executes this, plan_s prints it, and neither derives a flag of its own.
 // V: the k_schur_s variant (SV_* of nf_kernels.h); for the chunked kernel SV_NT and SV_DICT are its template flags and SV_ZW says that it forms a dot product.
-struct SPass { int rc = NF_OK; bool chunked = false; ChunkPlan cp; SegPlan seg; unsigned V = 0; int xcd = 0, early = 0; bool fold = false, fuse = false; };
+struct SPass { int rc = NF_OK; bool chunked = false; ChunkPlan cp; SegPlan seg; unsigned V = 0; int xcd = 0, early = 0, full = 0; bool fold = false, fuse = false; };
 static std::string variant_name(unsigned V)                      // "fuse+nt+sr"; "" for the base kernel
 {
     static const char *const bit[] = { "fuse", "nt", "zw", "sr", "dict", "stage" };
@@ -1577,7 +1594,7 @@ static SPass s_pass(const nf_solver *S, int d, int zmode, bool want_dot, bool zw
     if (R.cp.ok && (!want_dot || zw_dot)) {
         const bool nt = c_nt(S), dict = c_dict(S, d, nt);
         R.chunked = true; R.V = (nt ? SV_NT : 0) | (want_dot ? SV_ZW : 0) | (dict ? SV_DICT : 0);
-        R.xcd = c_xcd(S, d, nt); R.early = c_early(S, dict);
+        R.xcd = c_xcd(S, d, nt); R.early = c_early(S, dict); R.full = c_full(S, d, R.cp, dict, R.early);
         return R;
     }
     R.seg = seg_plan(S, d, zmode);
@@ -1591,6 +1608,7 @@ static SPass s_pass(const nf_solver *S, int d, int zmode, bool want_dot, bool zw
         | (sr ? SV_SR : 0) | (s_dict(S, d, zmode, SEG) ? SV_DICT : 0);
     if (s_stage(S, d, zmode, R.seg, R.V)) R.V |= SV_STAGE;
     R.xcd = s_xcd(S, d, zmode); R.fold = s_fold(S->team, zmode);
+    R.full = s_full(S, d, R.seg, R.V);
     return R;
 }
 // zmode: 0 = plain line kernel (y lines, or z lines of an undivided mesh); 1 / 2 = slab chain passes (z lines)
@@ -1608,20 +1626,20 @@ static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const 
         const ChunkPlan &cp = ps.cp;
         const dim3 grid = c_grid(S, d, cp), block(c_block(cp));
         const DictArgs da = dict_args(S, d, g, (ps.V & SV_DICT) != 0);
-        const unsigned key = ((unsigned)ps.early * 2 + da.on) * 4 + ((ps.V & SV_NT) ? 2 : 0) + (unsigned)(d - 1);
+        const unsigned key = (((unsigned)ps.full * 3 + (unsigned)ps.early) * 2 + da.on) * 4 + ((ps.V & SV_NT) ? 2 : 0) + (unsigned)(d - 1);
         bool launched = false;                                    // false: the device refused the LDS, or the launch (LDS, block size) -> the one-chunk kernel below
-        const bool hit = with_index<3 * 2 * 2 * 2>(key, [&](auto i) {
+        const bool hit = with_index<2 * 3 * 2 * 2 * 2>(key, [&](auto i) {
             constexpr unsigned I = decltype(i)::value;
-            constexpr int DIR = 1 + (I & 1), EARLY = I / 8; constexpr bool NT = I & 2, DICT = I & 4;
-            if constexpr (!schur_c_legal(DIR, NT, DICT, EARLY)) return false;
-            else if (lds_opt_in((const void *)k_schur_c<DIR, NT, DICT, EARLY>, cp.lds)) {
-                hipLaunchKernelGGL((k_schur_c<DIR, NT, DICT, EARLY>), grid, block, cp.lds, T->stream, ma.x[0], ma.y[0], ma.Ta, da.on ? da.L : L, da.on ? da.DR : DR, D0, n, sl, ostride,
+            constexpr int DIR = 1 + (I & 1), EARLY = I / 8 % 3, FULL = I / 24; constexpr bool NT = I & 2, DICT = I & 4;
+            if constexpr (!schur_c_legal(DIR, NT, DICT, EARLY, FULL)) return false;
+            else if (lds_opt_in((const void *)k_schur_c<DIR, NT, DICT, EARLY, FULL>, cp.lds)) {
+                hipLaunchKernelGGL((k_schur_c<DIR, NT, DICT, EARLY, FULL>), grid, block, cp.lds, T->stream, ma.x[0], ma.y[0], ma.Ta, da.on ? da.L : L, da.on ? da.DR : DR, D0, n, sl, ostride,
                                    S->nx, cp.TX, cp.NS, last, partials, cg, ps.xcd, da.ld);
                 launched = hipGetLastError() == hipSuccess;
             }
             return true;
         });
-        if (!hit) return fail(NF_ERR_ARG, "k_schur_c: no instantiation for direction %d, nt %d, dict %d, early %d", d, (ps.V & SV_NT) ? 1 : 0, da.on ? 1 : 0, ps.early);
+        if (!hit) return fail(NF_ERR_ARG, "k_schur_c: no instantiation for direction %d, nt %d, dict %d, early %d, full %d", d, (ps.V & SV_NT) ? 1 : 0, da.on ? 1 : 0, ps.early, ps.full);
         if (launched) { if (nparts) *nparts = (int)(grid.x * grid.y); return NF_OK; }
         ps = pick(false);
     }
@@ -1660,31 +1678,31 @@ static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const 
     }
     // staged form: persistent blocks over the same tile grid, the staged tile behind the summaries.  A vector that is not 16-byte aligned, a
     // refused LDS opt-in or a refused launch leave the pass to the unstaged variant (as the chunked kernel steps back above)
-    if ((ps.V & SV_STAGE) && ((uintptr_t)ma.x[0] & 15)) ps.V &= ~SV_STAGE;
+    if ((ps.V & SV_STAGE) && ((uintptr_t)ma.x[0] & 15)) { ps.V &= ~SV_STAGE; ps.full = 0; }
     int lg = 0; while ((4 << lg) < ps.seg.SEG) ++lg;
     for (;;) {
         bool staged = true;
-        const unsigned key = (4 << lg) == ps.seg.SEG ? ((ps.V * 3 + (zmode != 0 ? 2u : d - 1u)) * 3 + (unsigned)S->nb) * 4 + (unsigned)lg : ~0u;   // shapes: y lines, z lines, z lines of a slab
-        const bool hit = with_index<(SV_ALL + 1) * 3 * 3 * 4>(key, [&](auto i) {
-            constexpr unsigned I = decltype(i)::value, V = I / 36;
+        const unsigned key = (4 << lg) == ps.seg.SEG ? ((((unsigned)ps.full * (SV_ALL + 1) + ps.V) * 3 + (zmode != 0 ? 2u : d - 1u)) * 3 + (unsigned)S->nb) * 4 + (unsigned)lg : ~0u;   // shapes: y lines, z lines, z lines of a slab
+        const bool hit = with_index<2 * (SV_ALL + 1) * 3 * 3 * 4>(key, [&](auto i) {
+            constexpr unsigned I = decltype(i)::value, V = I / 36 % (SV_ALL + 1); constexpr int FULL = I / (36 * (SV_ALL + 1));
             constexpr int SEG = 4 << (I & 3), NB = I / 4 % 3, DIR = I / 12 % 3 == 0 ? 1 : 2; constexpr bool SLAB = I / 12 % 3 == 2;
-            if constexpr (!schur_s_legal(SEG, DIR, SLAB, NB, V)) return false;
+            if constexpr (!schur_s_legal(SEG, DIR, SLAB, NB, V) || (FULL && !(V & SV_STAGE))) return false;
             else if constexpr ((V & SV_STAGE) != 0) {
                 const size_t lds = ps.seg.lds + s_stage_bytes(n, ps.seg.TX);
                 const StageGrid sgr{ ps.seg.grid.x, ps.seg.grid.y };
                 staged = false;
-                if (lds_opt_in((const void *)k_schur_s<SEG, DIR, SLAB, NB, V>, lds)) {
-                    hipLaunchKernelGGL((k_schur_s<SEG, DIR, SLAB, NB, V>), dim3(s_stage_blocks(S, ps.seg), 1, ps.seg.grid.z), ps.seg.block, lds, st, ma, mt, G, da.on ? da.L : L, da.on ? da.DR : DR,
+                if (lds_opt_in((const void *)k_schur_s<SEG, DIR, SLAB, NB, V, FULL>, lds)) {
+                    hipLaunchKernelGGL((k_schur_s<SEG, DIR, SLAB, NB, V, FULL>), dim3(s_stage_blocks(S, ps.seg), 1, ps.seg.grid.z), ps.seg.block, lds, st, ma, mt, G, da.on ? da.L : L, da.on ? da.DR : DR,
                                        D0, n, sl, ostride, S->nx, ps.seg.TX, ps.seg.NSEG, last, partials, cg, sa, fz, lz, da.ld, sgr);
                     staged = hipGetLastError() == hipSuccess;
                 }
             }
-            else hipLaunchKernelGGL((k_schur_s<SEG, DIR, SLAB, NB, V>), ps.seg.grid, ps.seg.block, ps.seg.lds, st, ma, mt, G, da.on ? da.L : L, da.on ? da.DR : DR, D0, n, sl, ostride, S->nx,
+            else hipLaunchKernelGGL((k_schur_s<SEG, DIR, SLAB, NB, V, FULL>), ps.seg.grid, ps.seg.block, ps.seg.lds, st, ma, mt, G, da.on ? da.L : L, da.on ? da.DR : DR, D0, n, sl, ostride, S->nx,
                                     ps.seg.TX, ps.seg.NSEG, last, partials, cg, sa, fz, lz, da.ld);
             return true;
         });
-        if (hit && (ps.V & SV_STAGE) && !staged) { ps.V &= ~SV_STAGE; continue; }   // refused: the unstaged variant
-        return hit ? NF_OK : fail(NF_ERR_ARG, "k_schur_s: no instantiation for SEG = %d (s_seg), direction %d, zmode %d, NB = %d, variant \"%s\"", ps.seg.SEG, d, zmode, S->nb, variant_name(ps.V).c_str());
+        if (hit && (ps.V & SV_STAGE) && !staged) { ps.V &= ~SV_STAGE; ps.full = 0; continue; }   // refused: the unstaged variant
+        return hit ? NF_OK : fail(NF_ERR_ARG, "k_schur_s: no instantiation for SEG = %d (s_seg), direction %d, zmode %d, NB = %d, variant \"%s\", full %d", ps.seg.SEG, d, zmode, S->nb, variant_name(ps.V).c_str(), ps.full);
     }
 }
 
@@ -2067,7 +2085,7 @@ static CgPlan cg_plan(const nf_team *T)
 // split_dot, xy_overlap); apart from building the tables of distinct lines where the next
 // apply would (line_dict_prepare) it launches nothing and writes no state.  The one thing it cannot know is a device
 // that refuses the chunked kernel's LDS at launch time (launch_s then falls back to the one-chunk kernel).
-struct PlanPass { const char *dir, *family; int mode, SEG, NCH, TX, NSEG; dim3 grid; unsigned block; bool nt, p2, zw, order; unsigned tiles; bool fold = false, dict = false; int early = 0; unsigned V = 0, blocks = 0; };
+struct PlanPass { const char *dir, *family; int mode, SEG, NCH, TX, NSEG; dim3 grid; unsigned block; bool nt, p2, zw, order; unsigned tiles; bool fold = false, dict = false; int early = 0; unsigned V = 0, blocks = 0; int full = 0; };
 static void plan_emit(std::string &js, const PlanPass &p)
 {
     char tmp[416];
@@ -2076,7 +2094,8 @@ static void plan_emit(std::string &js, const PlanPass &p)
              p.SEG, p.NCH, p.TX, p.NSEG, p.grid.x, p.grid.y, p.grid.z, p.block, p.nt ? 1 : 0, p.p2 ? 1 : 0, p.zw ? 1 : 0, p.order ? 1 : 0, xcd_permutes(p.order, p.tiles) ? 1 : 0, p.fold ? 1 : 0, p.dict ? 1 : 0, p.early);
     js += tmp;
     if (!strcmp(p.family, "s")) js += ", \"variant\": \"" + variant_name(p.V) + "\"";   // which k_schur_s
-    if (p.dir[0] != 'x') js += ", \"stage\": " + std::to_string((p.V & SV_STAGE) && !strcmp(p.family, "s") ? 1 : 0) + ", \"blocks\": " + std::to_string(p.blocks);   // launched blocks (staged: persistent)
+    if (p.dir[0] != 'x') js += ", \"stage\": " + std::to_string((p.V & SV_STAGE) && !strcmp(p.family, "s") ? 1 : 0) + ", \"blocks\": " + std::to_string(p.blocks)   // launched blocks (staged: persistent)
+                            + ", \"full\": " + std::to_string(p.full);
     js += "}";
 }
 static int plan_s(std::string &js, const nf_solver *S, int d, int zmode, bool want_dot, bool zw_dot, bool fuse, bool cg1)   // a launch_s call
@@ -2086,7 +2105,7 @@ static int plan_s(std::string &js, const nf_solver *S, int d, int zmode, bool wa
     const dim3 gr = ps.chunked ? c_grid(S, d, ps.cp) : ps.seg.grid;
     plan_emit(js, { d == 1 ? "y" : "z", ps.chunked ? "c" : "s", zmode, ps.chunked ? C_SEG : ps.seg.SEG, ps.chunked ? C_NCH : 1, ps.chunked ? ps.cp.TX : ps.seg.TX, ps.chunked ? ps.cp.NS : ps.seg.NSEG,
                     gr, ps.chunked ? c_block(ps.cp) : ps.seg.block.x, (ps.V & SV_NT) != 0, false, (ps.V & SV_ZW) != 0, ps.xcd != 0, gr.x * gr.y, ps.fold, (ps.V & SV_DICT) != 0, ps.early, ps.V,
-                    !ps.chunked && (ps.V & SV_STAGE) ? s_stage_blocks(S, ps.seg) * gr.z : gr.x * gr.y * gr.z });
+                    !ps.chunked && (ps.V & SV_STAGE) ? s_stage_blocks(S, ps.seg) * gr.z : gr.x * gr.y * gr.z, ps.full });
     return NF_OK;
 }
 int nf_apply_plan(nf_handle S, int in_cg, char *json_buf, size_t len)
@@ -2656,7 +2675,7 @@ static void team_copy_options(nf_team *C, const nf_team *T, bool same_mesh_kind)
     C->opt_line_dict = T->opt_line_dict; C->line_dict_dirs = T->line_dict_dirs; C->line_dict_fp_bits = T->line_dict_fp_bits; C->line_dict_max_bytes = T->line_dict_max_bytes;
     C->opt_nt_loads = T->opt_nt_loads; C->nt_min_cells = T->nt_min_cells; C->opt_s_long = T->opt_s_long; C->opt_s_long_dirs = T->opt_s_long_dirs;
     C->s_long_min = T->s_long_min; C->s_long_min_y = T->s_long_min_y; C->opt_s_seg = T->opt_s_seg; C->opt_s_tx = T->opt_s_tx;
-    C->opt_wsmin = T->opt_wsmin; C->opt_c_early = T->opt_c_early; C->opt_s_stage = T->opt_s_stage; C->opt_s_stage_grid = T->opt_s_stage_grid; C->opt_x_p2 = T->opt_x_p2; C->opt_split_dot = T->opt_split_dot; C->opt_xcd = T->opt_xcd;
+    C->opt_wsmin = T->opt_wsmin; C->opt_c_early = T->opt_c_early; C->opt_s_stage = T->opt_s_stage; C->opt_s_stage_grid = T->opt_s_stage_grid; C->opt_tile_full = T->opt_tile_full; C->opt_x_p2 = T->opt_x_p2; C->opt_split_dot = T->opt_split_dot; C->opt_xcd = T->opt_xcd;
     C->opt_xy_overlap = T->opt_xy_overlap; C->xy_overlap_max_cells = T->xy_overlap_max_cells; C->opt_vec_reduce = T->opt_vec_reduce;
     C->opt_pub = T->opt_pub; C->opt_sens_grid = T->opt_sens_grid; C->opt_kin_grid = T->opt_kin_grid; C->prof_every = T->prof_every;
     if (dict_moved) { (void)hipSetDevice(C->device); for (auto *X : C->slabs) line_dict_drop(X); }
@@ -5403,6 +5422,7 @@ int nf_set_option(nf_handle S, const char *key, long value)
     else if (!strcmp(key, "s_long_min")) T->s_long_min = (int)std::max(1L, std::min(1000000L, value));
     else if (!strcmp(key, "c_early")) T->opt_c_early = value < 0 ? -1 : (int)std::min(2L, value);
     else if (!strcmp(key, "s_stage")) T->opt_s_stage = value < 0 ? -1 : (value > 0 ? 1 : 0);
+    else if (!strcmp(key, "tile_full")) T->opt_tile_full = value < 0 ? -1 : (value > 0 ? 1 : 0);
     else if (!strcmp(key, "s_stage_grid")) T->opt_s_stage_grid = (int)std::max(0L, std::min(1L << 20, value));
     else if (!strcmp(key, "line_dict") || !strcmp(key, "line_dict_dirs") || !strcmp(key, "line_dict_max_bytes") || !strcmp(key, "line_dict_fp_bits")) {
         if (!strcmp(key, "line_dict")) T->opt_line_dict = value < 0 ? -1 : (value > 0 ? 1 : 0);

@@ -1107,6 +1107,10 @@ struct SlabArgs {
 // compute unit's L1 -- the overlap cell too
 // SV_STAGE (table-backed plain lines, full-width tiles): a block walks tiles b, b + blocks, ... and the NEXT tile's x is copied into LDS while
 // this one is scanned (stage_issue); xv comes out of that buffer, everything behind it is the unstaged pass: same values, same arithmetic
+// FULL (a template flag beside V, SV_STAGE only; the host's s_full): the tile grid has no partial tile -- nx a multiple of TX, n = SEG NSEG, TX NSEG
+// threads, no wavefront scan.  Every per-access predicate (act, valid, c < n) is then true at compile time except the one of the overlap cell
+// behind a line's last segment, and y is addressed like the many-array passes (ldo / sto: wave-uniform base + 32-bit byte offset).  Same values,
+// same arithmetic, same slot in `partials`
 enum : unsigned { SV_FUSE = 1, SV_NT = 2, SV_ZW = 4, SV_SR = 8, SV_DICT = 16, SV_STAGE = 32, SV_ALL = 63 };   // bit order = the order of the report's "variant"
 // The instantiations of k_schur_s: the shapes (16- and 32-cell segments for RT0-P0 only, slabs cut z lines only) and the bits that a shape admits.
 // The kernel asserts this and the host instantiates exactly the combinations for which it holds.
@@ -1129,12 +1133,15 @@ struct StageCtx {
     const int *next_id = nullptr;                                // LineDict::id of the next tile's first column
     int id = 0;                                                  // this lane's table row in THIS tile; replaced by the next tile's on the way
 };
-template <bool NT>
+// REDO (the whole-tile form, which has no register to spare): the lane's part of the source address is formed again at every call instead of
+// living across the tile loop
+template <bool NT, bool REDO = false>
 __device__ __forceinline__ void stage_issue(const double *buf, const double *src, int n, long sl, int TX)
 {
     typedef __attribute__((address_space(1))) const void *gptr_t;
     typedef __attribute__((address_space(3))) void *lptr_t;
-    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+    int lane = threadIdx.x & 63; const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+    if (REDO) asm volatile("" : "+v"(lane));
     const int lpr = TX >> 1, rpp = 64 / lpr;                     // lanes per row (16 bytes each), rows per 1-KiB piece
     const int rl = lane / lpr, cl = lane % lpr;
     const char *dst = reinterpret_cast<const char *>(buf);
@@ -1143,7 +1150,7 @@ __device__ __forceinline__ void stage_issue(const double *buf, const double *src
         if (r < n) __builtin_amdgcn_global_load_lds((gptr_t)(src + (long)r * sl + 2 * cl), (lptr_t)(dst + p * 1024), 16, 0, NT ? 2 : 0);   // aux 2: nt, as ldg<NT>
     }
 }
-template <int SEG, int DIR, bool SLAB, int NB, unsigned V = 0, class Mid = NoMid, bool XC = false>
+template <int SEG, int DIR, bool SLAB, int NB, unsigned V = 0, class Mid = NoMid, bool XC = false, bool FULL = false>
 __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G, const double *__restrict__ L, const double *__restrict__ DR,
                                                const double *__restrict__ D0, int n, long sl, long outer_stride, int nx, int TX, int NSEG,
                                                unsigned bx, unsigned by, unsigned bz, unsigned gy, int tid, bool act, double *sm,
@@ -1153,6 +1160,7 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
 {
     constexpr bool FUSE = V & SV_FUSE, NT = V & SV_NT, ZW = V & SV_ZW, SR = V & SV_SR, DICT = V & SV_DICT, STAGE = V & SV_STAGE;
     static_assert(SLAB || !(FUSE || SR), "fused update, single-reduction sums: slab passes (k_schur_s checks the rest: schur_s_legal)");
+    static_assert(!FULL || (STAGE && !SLAB && NB == 0), "whole-tile form: the staged pass");
     const double *x = ma.x[0];                                   // no __restrict__: the fused slab pass rewrites this vector (fz.p)
     double *__restrict__ y = ma.y[0];
     const int T = TX * NSEG;
@@ -1163,15 +1171,17 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
     // 59 -> 66 us).  Needs full, aligned wavefronts.
     // (one wavefront spans a column's summaries: at most 64 segments -- a wider scan would need shuffles across wavefronts; longer
     // lines keep the serial loops)
-    const bool wscan = NSEG >= (sa.wsmin > 0 ? sa.wsmin : 64) && NSEG <= 64 && (T & 63) == 0;
+    const bool wscan = !FULL && NSEG >= (sa.wsmin > 0 ? sa.wsmin : 64) && NSEG <= 64 && (T & 63) == 0;
     const int NSP = wscan ? (NSEG | 1) : NSEG;                   // odd row length: conflict-free column-major rows
     const int TP = wscan ? TX * NSP : T;
     double *sA = sm, *sB = sm + TP, *sA2 = sm + 2 * TP, *sB2 = sm + 3 * TP, *sZ0 = sm + 4 * TP;
-    act = act && tid < T;
+    // FULL (the host's s_full): every thread owns a segment of a column inside the mesh, and every cell of it lies on the line -- the predicates
+    // below are true at compile time, and what is left is the overlap cell of a line's last segment
+    act = FULL || (act && tid < T);
     const int ixl = act ? tid % TX : 0, seg = act ? tid / TX : 0;
     const int si = wscan ? ixl * NSP + seg : seg * TX + ixl;     // this thread's slot in the summary arrays
     const int ix = bx * TX + ixl;
-    const bool valid = act && ix < nx;
+    const bool valid = FULL || (act && ix < nx);
     long base = (long)by * outer_stride + ix;
     const long lineid = (long)by * nx + ix;
     const long lm = SLAB ? (long)bz * ((long)nx * gy) + lineid : 0;   // slab exchange planes: [mode][line]
@@ -1225,7 +1235,7 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
     if (SLAB && !FUSE) fuse = false;
     const bool fr = SLAB ? fuse : fro;                           // the input vector is r + beta x (wave-uniform)
     // higher-order passes of undivided meshes touch up to eleven arrays per cell: 32-bit byte offsets from the wave-uniform bases (ldo / sto)
-    constexpr bool O32 = NB > 0 && !SLAB;
+    constexpr bool O32 = (NB > 0 && !SLAB) || FULL;
     const unsigned ob8 = (unsigned)(base * 8), sl8 = (unsigned)(sl * 8);
     unsigned tb8 = 0;                                            // DICT: byte offset of this column's row in the table
     if constexpr (STAGE) tb8 = valid ? (unsigned)sg->id * (unsigned)ld.pitch * 8u : 0u;
@@ -1238,10 +1248,10 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
     double r1[NB > 0 ? SEG + 1 : 1], r2[NB > 1 ? SEG + 1 : 1], v1a[NB > 0 ? SEG + 1 : 1], v2a[NB > 1 ? SEG + 1 : 1], Dv[NB > 0 ? SEG : 1];
 #pragma unroll
     for (int i = 0; i <= SEG; ++i) {
-        const int c = c0 + i; const bool ok = valid && c < n;
+        const int c = c0 + i; const bool ok = valid && ((FULL && i < SEG) || c < n);
         const long a = base + (long)c * sl;
         // the overlap cell (i == SEG) is the next segment's first: keep that line for it (see k_schur_c on why this is not a ternary on i)
-        if constexpr (STAGE) { const double v = sg->buf[(c < n ? c : n - 1) * TX + ixl]; xv[i] = ok ? v : 0.0; }   // staged image (rows past the line were not copied)
+        if constexpr (STAGE) { const double v = sg->buf[((FULL && i < SEG) || c < n ? c : n - 1) * TX + ixl]; xv[i] = ok ? v : 0.0; }   // staged image (rows past the line were not copied)
         else if (O32) xv[i] = ok ? ldo<NT>(x, NF_A8(c)) : 0.0;
         else if (i < SEG || XC) xv[i] = ok ? ldg<NT>(x + a) : 0.0; else xv[i] = ok ? x[a] : 0.0;
         if (!SLAB || FUSE) rv[(SLAB && !FUSE) ? 0 : i] = (fr && ok) ? (SLAB ? fz.r[a] : (O32 ? ldo<NT>(x + roff, NF_A8(c)) : ldg<NT>(x + a + roff))) : 0.0;
@@ -1268,7 +1278,7 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
         }
     }
     double dinv_s = 0.0;
-    if (DICT) { if (valid && c0 < n) dinv_s = c0 == 0 ? D0[lineid] : ldo<false>(DR, NF_T8(c0 - 1)); }
+    if (DICT) { if (FULL || (valid && c0 < n)) dinv_s = c0 == 0 ? D0[lineid] : ldo<false>(DR, NF_T8(c0 - 1)); }
     else if (valid && c0 < n) dinv_s = c0 == 0 ? D0[lineid] : DR[base + (long)(c0 - 1) * sl];
     NF_STAMP(stamp, 3);
     if (mid(f_alpha, f_beta)) return 0.0;                        // e.g. the reduction that yields beta: runs with the loads above in flight
@@ -1334,7 +1344,7 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
     block_bar<STAGE>();
     NF_STAMP(stamp, 5);
     // every thread holds its x in registers and the buffer is free: the next tile's copy flies during the rest of this tile
-    if constexpr (STAGE && NF_STAGE_PLACE == 0) { if (sg->next) { stage_issue<NT>(sg->buf, sg->next, n, sl, TX); sg->id = sg->next_id[ixl]; } }
+    if constexpr (STAGE && NF_STAGE_PLACE == 0) { if (sg->next) { stage_issue<NT, FULL>(sg->buf, sg->next, n, sl, TX); sg->id = sg->next_id[ixl]; } }
     if (wscan) {
         // forward: incoming value of segment s = (f_{s-1} o ... o f_0)(z0); inclusive Hillis-Steele over the lanes of a column
         int W = 16; while (W < NSEG) W <<= 1;
@@ -1386,7 +1396,7 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
     // y is only needed by the output stage: issue its loads here so they fly during the barrier + backward scan
 #pragma unroll
     for (int i = 0; i < SEG; ++i) {
-        const int c = c0 + i; const bool ok = acc && valid && c < n && wr;
+        const int c = c0 + i; const bool ok = acc && (FULL || (valid && c < n && wr));
         yo[i] = ok ? (O32 ? ldo<NT>(y, NF_A8(c)) : ldg<NT>(y + base + (long)c * sl)) : 0.0;
         if (SLAB && NB == 0 && sa.yadd) yo[i] += ok ? sa.yadd[base + (long)c * sl] : 0.0;     // same order on every cell: (y_x + y_y) + z part
     }
@@ -1399,7 +1409,7 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
             if (NB > 1) y2o[NB > 1 ? i : 0] = okl ? (O32 ? ldo<false>(ma.y[2], NF_A8(c0 + i)) : ma.y[2][a]) : 0.0;
         }
     }
-    if constexpr (STAGE && NF_STAGE_PLACE == 1) { if (sg->next) { stage_issue<NT>(sg->buf, sg->next, n, sl, TX); sg->id = sg->next_id[ixl]; } }   // this tile's y first in the queue
+    if constexpr (STAGE && NF_STAGE_PLACE == 1) { if (sg->next) { stage_issue<NT, FULL>(sg->buf, sg->next, n, sl, TX); sg->id = sg->next_id[ixl]; } }   // this tile's y first in the queue
     NF_STAMP(stamp, 6);
     block_bar<STAGE>();
     NF_STAMP(stamp, 7);
@@ -1435,8 +1445,12 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
 #pragma unroll
         for (int i = 0; i < SEG; ++i) {
             const double lo = i == 0 ? ulo : w[i > 0 ? i - 1 : 0];
-            const bool in = valid && c0 + i < n;                 // a select, not a branch (slab chains: xv of the cell behind the chain end is the edge cell)
-            yo[i] = yo[i] + ma.Ta * (w[i] - lo); if (!ZW) dot += in ? xv[i] * yo[i] : 0.0;
+            const bool in = FULL || (valid && c0 + i < n);       // a select, not a branch (slab chains: xv of the cell behind the chain end is the edge cell)
+            yo[i] = yo[i] + ma.Ta * (w[i] - lo);
+            if constexpr (FULL && !ZW) {                         // the select below keeps product and sum apart; without it they must not fuse into an fma either
+#pragma clang fp contract(off)
+                dot += xv[i] * yo[i];
+            } else if (!ZW) dot += in ? xv[i] * yo[i] : 0.0;
             if (SR && !FUSE) { sqq += in ? yo[i] * yo[i] : 0.0; srq += in ? rq_[(SR && !FUSE) ? i : 0] * yo[i] : 0.0; }
             if (NB > 0) {
                 const double v = ma.Gc[0] * x1[i] * ma.iM[0] * icv[i] - (ma.eL[0] * lo + ma.eR[0] * w[i]);
@@ -1460,9 +1474,10 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
 #pragma unroll
         for (int i = 0; i < SEG; ++i) {
             const int c = c0 + i;
-            if (valid && c < n) {
+            if (FULL || (valid && c < n)) {
                 const long a = base + (long)c * sl;
-                if (O32) {
+                if (FULL) sto(y, NF_A8(c), yo[i]);
+                else if (O32) {
                     sto(y, NF_A8(c), yo[i]); sto(ma.y[1], NF_A8(c), y1o[i]);
                     if (NB > 1) sto(ma.y[2], NF_A8(c), y2o[NB > 1 ? i : 0]);
                 } else {
@@ -1576,13 +1591,14 @@ __device__ __forceinline__ double schur_s_tile(const ModeArgs &ma, const Geom &G
 // Slab variants keep r and x_sol of their cells in registers next to x, L, 1/d (loads first, see schur_s_tile): blocks of at most 512
 // threads, so that the register budget is 256 per thread (the host picks TX accordingly)
 struct StageGrid { unsigned gx = 0, gy = 0; };                  // SV_STAGE: the tile grid that a persistent launch walks (gridDim holds the block count)
-template <int SEG, int DIR, bool SLAB, int NB, unsigned V = 0>
+template <int SEG, int DIR, bool SLAB, int NB, unsigned V = 0, int FULL = 0>   // FULL: the staged pass on a grid of whole tiles, see schur_s_tile
 __global__ __launch_bounds__(SLAB ? 512 : 1024, SLAB ? (NB > 0 ? 2 : ((V & SV_FUSE) ? ((V & SV_SR) ? NF_SR_Z1_WAVES : 3) : ((V & SV_SR) ? NF_SR_Z2_WAVES : 4))) : 1) void k_schur_s(ModeArgs ma0, ModeTab mt, Geom G, const double *__restrict__ L, const double *__restrict__ DR,
                           const double *__restrict__ D0, int n, long sl, long outer_stride, int nx, int TX, int NSEG,
                           int last, double *__restrict__ partials, const CgScalars *__restrict__ cg, SlabArgs sa, CgFuse fz, CgLean lean,
                           LineDict ld = LineDict(), StageGrid sgr = StageGrid())
 {
     static_assert(schur_s_legal(SEG, DIR, SLAB, NB, V), "not a variant of k_schur_s");
+    static_assert(FULL == 0 || (FULL == 1 && (V & SV_STAGE)), "whole-tile form: the staged pass");
     constexpr bool FUSE = V & SV_FUSE, SR = V & SV_SR;
     extern __shared__ double sm[];
     if (cg && cg->done) return;
@@ -1613,7 +1629,7 @@ __global__ __launch_bounds__(SLAB ? 512 : 1024, SLAB ? (NB > 0 ? 2 : ((V & SV_FU
             sg.next = more ? tile_x(t + gridDim.x) : nullptr; sg.next_id = more ? tile_id(t + gridDim.x) : nullptr;
             // the copy of this tile has landed: every issuing wave has seen its counter drain, and here the block meets
             block_bar<true>();
-            const double dot = schur_s_tile<SEG, DIR, SLAB, NB, V>(ma, G, L, DR, D0, n, sl, outer_stride, nx, TX, NSEG, bx, by, blockIdx.z, gy,
+            const double dot = schur_s_tile<SEG, DIR, SLAB, NB, V, NoMid, false, FULL != 0>(ma, G, L, DR, D0, n, sl, outer_stride, nx, TX, NSEG, bx, by, blockIdx.z, gy,
                                                                     (int)threadIdx.x, true, sm, sa, fz, false, false, 0.0, 0.0, !sa.noacc,
                                                                     nullptr, NoMid(), nullptr, ld, &sg);
             if (last && partials) {
@@ -1643,8 +1659,8 @@ __global__ __launch_bounds__(SLAB ? 512 : 1024, SLAB ? (NB > 0 ? 2 : ((V & SV_FU
         const unsigned nblk = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
         if (nblk % 8 == 0) { const unsigned nl = (lin % 8) * (nblk / 8) + lin / 8; bx = nl % gridDim.x; by = nl / gridDim.x; }
     }
-    double extra[2] = { 0.0, 0.0 };
-    const double dot = schur_s_tile<SEG, DIR, SLAB, NB, V>(ma, G, L, DR, D0, n, sl, outer_stride, nx, TX, NSEG, bx, by, blockIdx.z, gridDim.y,
+    double extra[2] = { 0.0, 0.0 };                              // (the staged variants have returned above: the whole-tile body is not instantiated here)
+    const double dot = schur_s_tile<SEG, DIR, SLAB, NB, V, NoMid, false, false>(ma, G, L, DR, D0, n, sl, outer_stride, nx, TX, NSEG, bx, by, blockIdx.z, gridDim.y,
                                                             (int)threadIdx.x, true, sm, sa, fz, fuse, false, f_alpha, f_beta, !(!SLAB && NB == 0 && sa.noacc),
                                                             nullptr, NoMid(), SR ? extra : nullptr, ld);
     if (SLAB && sa.mode == 3) return;
@@ -1742,15 +1758,18 @@ __global__ __launch_bounds__(256) void k_endpoint_w(double *__restrict__ p, doub
 // loads (chunk 0 first, so that a counted wait lets its sweep start on its own data); 2: also y of chunk 1 before the barrier of chunk 1's
 // forward sweep and y of chunk 0 before the first barrier of the backward half.  Same predicates, same hints, no arithmetic moves: the bits
 // of y and of the dot product are those of EARLY = 0.  The tile, the grid and the LDS layout stay as they are.
-// The instantiations: the table next to the streaming loads only; early loads (levels 1, 2) with the table only, see EARLY
-constexpr bool schur_c_legal(int DIR, bool NT, bool DICT, int EARLY) { return (DIR == 1 || DIR == 2) && (!DICT || NT) && EARLY >= 0 && EARLY <= (DICT ? 2 : 0); }
-template <int DIR, bool NT, bool DICT = false, int EARLY = 0>
+// FULL (EARLY = 2 only; the host's c_full): the tile grid has no partial tile -- nx a multiple of TX, n = 16 NS, TX NS threads -- so every predicate
+// on a load or a store is true at compile time but the one of the overlap cell behind the line's last segment: straight-line accesses, counted
+// waits, a third fewer instructions.  Values and arithmetic are untouched.
+// The instantiations: the table next to the streaming loads only; early loads (levels 1, 2) with the table only, see EARLY; FULL with EARLY = 2 only
+constexpr bool schur_c_legal(int DIR, bool NT, bool DICT, int EARLY, int FULL = 0) { return (DIR == 1 || DIR == 2) && (!DICT || NT) && EARLY >= 0 && EARLY <= (DICT ? 2 : 0) && (FULL == 0 || (FULL == 1 && DICT && EARLY == 2)); }
+template <int DIR, bool NT, bool DICT = false, int EARLY = 0, int FULL = 0>   // FULL: a grid of whole tiles, see below
 __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ x, double *__restrict__ y, double Ta,
                                                      const double *__restrict__ L, const double *__restrict__ DR, const double *__restrict__ D0,
                                                      int n, long sl, long outer_stride, int nx, int TX, int NS, int last,
                                                      double *__restrict__ partials, const CgScalars *__restrict__ cg, int xcd, LineDict ld = LineDict())
 {
-    static_assert(schur_c_legal(DIR, NT, DICT, EARLY), "not a variant of k_schur_c");
+    static_assert(schur_c_legal(DIR, NT, DICT, EARLY, FULL), "not a variant of k_schur_c");
     extern __shared__ double sm[];
     if (cg && cg->done) return;
     constexpr int SEG = 8;
@@ -1762,10 +1781,10 @@ __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ 
         if (nblk % 8 == 0) { const unsigned nl = (lin % 8) * (nblk / 8) + lin / 8; bx = nl % gridDim.x; by = nl / gridDim.x; }
     }
     const int tid = (int)threadIdx.x;
-    const bool act = tid < T;
+    const bool act = FULL || tid < T;                            // FULL (the host's c_full): one thread per (column, segment), every cell of both chunks on the line
     const int ixl = act ? tid % TX : 0, seg = act ? tid / TX : 0, si = seg * TX + ixl;
     const int ix = (int)bx * TX + ixl;
-    const bool valid = act && ix < nx;
+    const bool valid = FULL || (act && ix < nx);
     const unsigned slb = (unsigned)(sl * 8);                     // bytes between the cells of a line
     const unsigned ob = (unsigned)(((long)by * outer_stride + ix) * 8);   // byte offset of the line's first cell
     const long lineid = (long)by * nx + ix;
@@ -1782,7 +1801,7 @@ __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ 
         const unsigned o0 = ob + (unsigned)c0 * slb;
 #pragma unroll
         for (int i = 0; i <= SEG; ++i) {                         // loads only (see schur_s_tile)
-            const bool ok = valid && c0 + i < n;
+            const bool ok = valid && ((FULL && (i < SEG || ch == 0)) || c0 + i < n);   // FULL: all but the overlap cell of the line's last segment
             const unsigned a = o0 + (unsigned)i * slb;
             // the overlap cell (i == SEG) is the next segment's first: a plain load keeps that line for it.  Two statements, not a
             // ternary on i: before the loop is unrolled a ternary is one load in each arm of a branch, which the optimiser merges
@@ -1799,13 +1818,13 @@ __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ 
             else { xv[i] = ok ? ldo<false>(x, a) : 0.0; Lv[i] = ok ? ldo<false>(L, a) : 0.0; }
         }
         double ds = 0.0;
-        if (DICT) { if (valid && c0 < n) ds = c0 == 0 ? D0[lineid] : ldo<false>(DR, tb + (unsigned)(c0 - 1) * 8u); }
+        if (DICT) { if (FULL || (valid && c0 < n)) ds = c0 == 0 ? D0[lineid] : ldo<false>(DR, tb + (unsigned)(c0 - 1) * 8u); }
         else if (valid && c0 < n) ds = c0 == 0 ? D0[lineid] : ldo<false>(DR, o0 - slb);
         if (EARLY >= 1 && ch == 0) {                             // chunk 1's x behind chunk 0's loads: same predicate, same hints, two statements
 #pragma unroll
             for (int i = 0; i <= SEG; ++i) {
                 const int c1 = CH + seg * SEG + i;
-                const bool ok = valid && c1 < n;
+                const bool ok = valid && ((FULL && i < SEG) || c1 < n);
                 const unsigned a = ob + (unsigned)c1 * slb;
                 if (i < SEG) x1[i] = ok ? ldo<NT>(x, a) : 0.0;
                 else x1[i] = ok ? ldo<false>(x, a) : 0.0;
@@ -1813,7 +1832,7 @@ __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ 
         }
         if (EARLY >= 2 && ch == 1) {                             // chunk 1's y: lands under this sweep, consumed by the backward one
 #pragma unroll
-            for (int i = 0; i < SEG; ++i) yo[i] = (valid && c0 + i < n) ? ldo<NT>(y, o0 + (unsigned)i * slb) : 0.0;
+            for (int i = 0; i < SEG; ++i) yo[i] = (FULL || (valid && c0 + i < n)) ? ldo<NT>(y, o0 + (unsigned)i * slb) : 0.0;
         }
         if (ch) __syncthreads();                                 // chunk 0's summaries and carry have been consumed
         double P = 1.0, lz = 0.0;
@@ -1842,7 +1861,7 @@ __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ 
     double ucar = 0.0;
     if (EARLY >= 2) {                                            // chunk 0's y: lands under chunk 1's backward sweep
 #pragma unroll
-        for (int i = 0; i < SEG; ++i) { const int c = seg * SEG + i; y0[i] = (valid && c < n) ? ldo<NT>(y, ob + (unsigned)c * slb) : 0.0; }
+        for (int i = 0; i < SEG; ++i) { const int c = seg * SEG + i; y0[i] = (FULL || (valid && c < n)) ? ldo<NT>(y, ob + (unsigned)c * slb) : 0.0; }
     }
 #pragma unroll
     for (int ch = 1; ch >= 0; --ch) {
@@ -1858,7 +1877,7 @@ __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ 
             Lv[SEG] = seg < NS - 1 ? pL[(seg + 1) * SEG * TX + ixl] : sL1[ixl];   // written before the barriers in between
             zin = pZ[si];
             dinv_s = 0.0;
-            if (DICT) { if (valid && c0 < n) dinv_s = c0 == 0 ? D0[lineid] : ldo<false>(DR, tb + (unsigned)(c0 - 1) * 8u); }
+            if (DICT) { if (FULL || (valid && c0 < n)) dinv_s = c0 == 0 ? D0[lineid] : ldo<false>(DR, tb + (unsigned)(c0 - 1) * 8u); }
             else if (valid && c0 < n) dinv_s = c0 == 0 ? D0[lineid] : ldo<false>(DR, o0 - slb);
         }
 #pragma unroll
@@ -1886,7 +1905,7 @@ __global__ __launch_bounds__(1024, 1) void k_schur_c(const double *__restrict__ 
         }
 #pragma unroll
         for (int i = 0; i < SEG; ++i)
-            if (valid && c0 + i < n) *reinterpret_cast<double *>(reinterpret_cast<char *>(y) + (o0 + (unsigned)i * slb)) = yo[i];
+            if (FULL || (valid && c0 + i < n)) *reinterpret_cast<double *>(reinterpret_cast<char *>(y) + (o0 + (unsigned)i * slb)) = yo[i];
     }
     if (need_dot) {
         const double s = block_sum(Ta * dot, sred);
