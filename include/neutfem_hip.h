@@ -530,7 +530,7 @@ int nf_timers(nf_handle h, char *json_buf, size_t len);
  * One entry of "passes" per direction that exists; the z direction of a slab has two (mode 1 = endpoint pass, mode 2 = accumulation
  * pass).  Per entry: "dir" (x / y / z), "mode", "family" (x = k_schur_x, s = k_schur_s, c = k_schur_c, endpoint_w = k_endpoint_w),
  * "SEG" (cells per segment), "NCH" (chunks per lane / block), "TX" (columns per block; lanes per line for x), "NSEG" (segments per
- * line; NS of the chunked kernel), "grid" [x, y, z], "block", "nt" (streaming loads), "p2" (two load phases), "zw" (the pass's share
+ * line; NS of the chunked kernel), "grid" [x, y, z], "block", "nt" (streaming loads), "zw" (the pass's share
  * of x.y in the z.w form), "xcd_order" (the XCD-contiguous tile order is requested) and "xcd_permutes" (requested, and the tile count
  * is a multiple of 8 beyond 8: tiles really move), "fold" (accumulation pass of a slab: it forms the separator values
  * itself), "dict" (the pass reads its line factors from the table of distinct lines, see "line_dict") and "early" (level of early vector
@@ -635,6 +635,8 @@ int nf_time_device_copy(nf_handle h, size_t bytes, int reps, double *gbps);
  * "transient_steps" (steps completed since nf_transient_begin; 0 without a transient), "transient_rebuilds" (builds of the step operator
  * since nf_transient_begin). */
 int nf_set_option(nf_handle h, const char *key, long value);
+/* the value a key holds now, as nf_set_option normalised it (retired keys read 0); an unknown key -> NF_ERR_ARG */
+int nf_get_option(nf_handle h, const char *key, long *value);
 
 /* raw device-memory helpers so callers without torch can drive the *_dev entry points */
 /* free / total HBM of a device (hipMemGetInfo): sizing of decompositions, leak checks */

@@ -17,7 +17,7 @@ SYMBOLS = [
     "nf_upload_source", "nf_solve_subcritical", "nf_solve_modes", "nf_get_mode", "nf_block_gram", "nf_block_rotate", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_apply_plan", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_project_flux", "nf_project_power", "nf_refine", "nf_zoom_source", "nf_get_source", "nf_set_phi_adj", "nf_zoom_resolved", "nf_sensitivity", "nf_solve_gpt", "nf_get_gamma", "nf_set_gamma", "nf_gpt_source", "nf_gpt_sensitivity", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
     "nf_get_warm_state", "nf_get_history", "nf_profile_get", "nf_profile_reset", "nf_time_schur_apply", "nf_time_device_copy", "nf_progress", "nf_set_progress_callback", "nf_local_matrices",
     "nf_transient_begin", "nf_transient_step", "nf_get_precursors", "nf_transient_end", "nf_kinetics_params", "nf_transient_kinetics",
-    "nf_set_option", "nf_mem_info", "nf_dev_alloc", "nf_dev_free", "nf_memcpy_h2d", "nf_memcpy_d2h", "nf_synchronize", "nf_stream",
+    "nf_set_option", "nf_get_option", "nf_mem_info", "nf_dev_alloc", "nf_dev_free", "nf_memcpy_h2d", "nf_memcpy_d2h", "nf_synchronize", "nf_stream",
 ]
 
 
@@ -182,6 +182,7 @@ def load():
     L.nf_set_progress_callback.argtypes = [vp, vp, vp]
     L.nf_local_matrices.argtypes = [vp, C.c_int, C.c_int, ip, dp, dp, dp, C.c_int, C.c_int, dp]
     L.nf_set_option.argtypes = [vp, C.c_char_p, C.c_long]
+    L.nf_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_long)]
     L.nf_mem_info.argtypes = [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.nf_dev_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.nf_dev_free.argtypes = [vp, vp]
@@ -637,6 +638,11 @@ class HipSolver:
         return c.value, ms.value
 
     def set_option(self, key, value): self._chk(self.L.nf_set_option(self.h, key.encode(), int(value)))
+
+    def get_option(self, key):
+        v = C.c_long(0)
+        self._chk(self.L.nf_get_option(self.h, key.encode(), C.byref(v)))
+        return v.value
 
     def profile_reset(self): self._chk(self.L.nf_profile_reset(self.h))
 

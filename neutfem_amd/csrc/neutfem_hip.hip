@@ -14,6 +14,7 @@
 #include "nf_kernels.h"
 #include "nf_assembly.h"
 #include "nf_line_groups.h"
+#include "nf_options.h"
 #include "nf_small_eig.h"
 
 #include <dlfcn.h>
@@ -46,6 +47,7 @@ static int fail(int code, const char *fmt, ...)
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(NF_ERR_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 #define NFCHK(x) do { int r_ = (x); if (r_ != NF_OK) return r_; } while (0)
 
+static_assert(NF_OPT_RED_GRID == 1024, "nf_options.h: defaults and cap of the reduction-shaped grids follow RED_GRID");
 static const int RED_GRID = 1024;          // fixed grid of the streaming/reduction kernels
 static const int MAX_LOCAL_SLABS = 16;
 
@@ -113,6 +115,7 @@ static int rccl_load()
 struct nf_solver;
 struct Transient;                                                 // the running transient of a handle (nf_transient_begin), defined with its code
 struct nf_team {
+    NfOptions opt;                       // what nf_set_option sets (nf_options.h); team_copy_options hands it to the team of a derived handle
     std::vector<nf_solver *> slabs;
     int device = 0;
     hipStream_t stream = nullptr;
@@ -120,21 +123,13 @@ struct nf_team {
     // small slabs (a rank's share at strong-scaling sizes): a pass on 2 M cells does not fill the chip, so the y pass runs BESIDE the x
     // pass on a stream of its own, into its own vector; the accumulation pass of the z lines adds the two (SlabArgs::yadd)
     hipStream_t y_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int opt_xy_overlap = 1; long xy_overlap_max_cells = 6L << 20;
     hipEvent_t ev_z1 = nullptr, ev_xchg = nullptr;
     int nproc = 1, rank = 0;
     ncclComm_t comm = nullptr;
-    // option "xchg_comm": the interface planes travel on a communicator of their own (created collectively in team_prepare), so that the
-    // first contact with RCCL on several GPUs can A/B "one communicator driven from two streams" against "one communicator per stream"
-    ncclComm_t comm_x = nullptr; int opt_xchg_comm = 0;
-    // single-reduction CG on slab teams (Cg1 in nf_kernels.h): one all-reduce per CG iteration instead of two
-    // -1 (default): slabs of at most cg1_max_cells cells on every rank (the largest slab of the TEAM decides, all-reduced in team_prepare).  With the
-    // chain-solve endpoint pass the form cost 4 us per rank and iteration at 2 M cells per slab and 40 us at 16.8 M -- more than an all-reduce -- and
-    // was limited to small slabs; with the weighted-sum endpoint pass (k_endpoint_w) it is FASTER than the two-reduction route in device time alone
-    // at every size measured (256^3 as 2 / 4 / 8 slabs: -6.5 / -7.9 / -5.5 %, 512^3 as 8: -3.2 %; profiles/r04_d_*), so the limit is out of the way.
-    int opt_cg1 = -1, last_cg_reductions = 0; long cg1_max_cells = 1L << 40, team_max_cells = 0;
+    ncclComm_t comm_x = nullptr;    // option "xchg_comm": the communicator of the interface planes (created collectively in team_prepare)
+    int last_cg_reductions = 0; long team_max_cells = 0;   // single-reduction CG on slab teams (option "cg_single_reduce"): all-reduces per iteration of the last solve, largest slab of the team
     int last_cg_form = 0;           // the CgForm the last cg_solve ran (nf_info "cg_form")
-    int opt_endpoint_w = 1, last_endpoint_w = 0;   // its endpoint pass as two weighted sums per line (k_endpoint_w) instead of a chain solve
+    int last_endpoint_w = 0;        // its endpoint pass ran as two weighted sums per line (option "endpoint_weights")
     bool rccl_reduce = false;       // scalar reductions go through ncclAllReduce (nproc > 1, or forced for testing)
     double *d_partials = nullptr; long partial_stride = 0, slab_cap = 0;
     CgScalars *d_cg = nullptr;
@@ -149,7 +144,7 @@ struct nf_team {
     // (a few KB: still latency-bound) into d_vec and the consuming kernels sum them, every block redundantly, like the lean CG of an
     // undivided mesh -- the two one-block k_finalize launches per CG iteration leave the critical path (7 -> 5 kernels per rank).
     double *d_vec = nullptr; long vec_stride = 0;          // 2 rows: all-reduced p.q partials, all-reduced |r|^2 partials (+ flag slot each)
-    int vec_cnt_pq = 0, vec_cnt_rr = 0; bool vec_ok = false; int opt_vec_reduce = 1, last_vec_reduce = 0;
+    int vec_cnt_pq = 0, vec_cnt_rr = 0; bool vec_ok = false; int last_vec_reduce = 0;
     bool dead = false;              // a collective timed out (NF_ERR_COMM): the streams may hold operations that never complete -- no further solve, no stream waits at teardown
     bool poisoned = false; int poison_rc = 0; char poison_msg[256] = { 0 };
     int xchg_in_apply = 0;          // interface exchanges issued since the current Schur apply began
@@ -167,48 +162,19 @@ struct nf_team {
     std::vector<double> hist_k, hist_dk, hist_dphi; std::vector<int> hist_cg;
     int has_valid_keff = 0; double last_keff = 1.0;
     // profiling
-    HostPub *h_pub = nullptr, *d_pub = nullptr; unsigned long long pub_seq = 0; int opt_pub = 1;   // low-latency scalar readback (k_publish)
-    bool profile = false; long prof_tick = 0; int prof_every = 8;   // event-timed launches: every prof_every-th Schur apply of a profiled solve
+    HostPub *h_pub = nullptr, *d_pub = nullptr; unsigned long long pub_seq = 0;   // low-latency scalar readback (k_publish, option "host_pub")
+    bool profile = false; long prof_tick = 0;   // event-timed launches: every prof_every-th Schur apply of a profiled solve
     std::map<std::string, ProfSlot> prof;
     struct Ev { hipEvent_t a, b; int slot; };
     std::vector<Ev> ev_pending; std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_free;
-    int cg_batch = 0;
-    // 192^3 (7.1 M cells): 229 -> 233 us per CG iteration with them, 224^3 (11.2 M): 389 -> 356, 256^3: 599 -> 550
-    int opt_nt_loads = 1; long nt_min_cells = 8000000;   // streaming (non-temporal) loads in the y / z passes of undivided meshes larger than this
-    int opt_fuse = 1, opt_xcd = -1, opt_outer_dev = 1, opt_lean = 1, opt_lean_grid = RED_GRID, opt_sepfold = 1;
-    long lean_max_cells = 4L << 20;                     // above that the redundant partial sums of 16 k x-pass blocks cost what the two tiny kernels cost
     OuterState *d_ost = nullptr; double *d_hist = nullptr; int hist_cap = 0;   // device-resident outer loop (diagonal path)
-    int opt_s_tx = 0, opt_s_seg = 0, opt_wsmin = 0;       // tuning overrides (nf_set_option)
-    int opt_x_p2 = 0;                                     // x pass inside CG: two load phases (k_schur_x P2); measured no gain, off
-    int opt_split_dot = 1;                                // big undivided RT0-P0 meshes: per-pass shares of p.q (team_schur_apply)
-    int opt_s_long_dirs = 3;                              // directions that may take the chunked kernel: bit 0 = y, bit 1 = z
-    int s_long_min_y = 255;                               // y lines longer than this take the chunked kernel (s_long_min: z lines)
-    // tables of distinct lines (LineDict in nf_kernels.h) for the streaming passes of undivided RT0-P0 meshes.  line_dict: -1 = the directions
-    // that measurably gain (LINE_DICT_AUTO_DIRS), 0 = off, 1 = every direction whose lines qualify; line_dict_dirs: bit 0 = x, 1 = y, 2 = z;
-    // line_dict_max_bytes: per group and direction (three 512 KiB tables stay below half of one XCD's 4 MiB L2; not swept -- the benchmark's
-    // tables are 12 - 110 KB); line_dict_fp_bits < 128 truncates the fingerprints so that tests can make them collide
-    int opt_line_dict = -1, line_dict_dirs = 7, line_dict_fp_bits = 128; long line_dict_max_bytes = 512L * 1024;
-    int opt_s_long = -1, s_long_min = 256;                // chunked long-line pass (k_schur_c): -1 auto (lines longer than s_long_min), 0 off, 1 always
-    int opt_c_early = -1;                                 // its table-backed form: vector loads of both chunks issued up front (k_schur_c EARLY): -1 auto (C_EARLY_AUTO), 0, 1, 2
-    // staged form of the table-backed y / z passes (k_schur_s SV_STAGE: persistent blocks, the next tile's x copied into LDS under the scans).
-    // s_stage: -1 = the directions of S_STAGE_AUTO_DIRS where a block has a next tile to fetch, 0 = off, 1 = wherever eligible;
-    // s_stage_grid: blocks of such a launch, 0 = one per compute unit
-    int opt_s_stage = -1, opt_s_stage_grid = 0, ncu = 256;
-    int opt_tile_full = -1;                               // whole-tile form of the staged k_schur_s and the table-backed early-load k_schur_c (FULL): -1 auto (on where eligible), 0, 1
+    int ncu = 256;                                        // compute units of the device (a staged launch of s_stage_grid 0 takes one block each)
     size_t lds_limit = 160 * 1024;                        // dynamic LDS a block may ask for (hipDeviceAttributeMaxSharedMemoryPerBlock at team creation)
-    // fused-direction CG (two launches per iteration) up to this many cells.  Measured crossover against the four-launch lean path after
-    // the round-2 latency work: 64^3 19.1 vs 27.2 us per CG iteration, 80^3 39.1 vs 34.5, 128^3 77.7 vs 70.9, 160^3 221 vs 150
-    int opt_fuse3 = 1; long fuse3_max_cells = 400000;
-    int opt_sens_grid = RED_GRID;                         // blocks of the nf_sensitivity launches (grid stride beyond; option "sens_grid")
-    int opt_kin_grid = RED_GRID;                          // blocks of k_kin_forms, at most RED_GRID (grid stride beyond; option "kin_grid")
-    // whole CG solve in one launch on the workgroups of one XCD (k_cg_xcd): RT0-P0 meshes between the one-workgroup resident kernel and
-    // xcd_max_cells.  One XCD has an eighth of the chip's compute units and L2 (4 MiB): beyond that the launch path wins back.
-    int opt_cgx = 1, opt_keffx = 1, xcd_id = 0, xcd_groups = 32, last_xcd = 0; long xcd_min_cells = 2000, xcd_max_cells = 28000, xcd_solves = 0, xcd_refused = 0;
+    int last_xcd = 0; long xcd_solves = 0, xcd_refused = 0;   // one-XCD CG (k_cg_xcd, option "cg_xcd"): the last solve took it; solves / refused launches so far
     XcdState *d_xcd = nullptr; double *d_xpart = nullptr;
-    int opt_resident = 1, opt_resident_lds = 1, opt_resident_serial = 1, opt_resident_two_sided = 1, last_resident_serial = 0; long resident_max_dofs = 2500, resident_serial_max_dofs = 5120;  // whole SolveKeff in one workgroup (k_resident_keff) up to this many flux DOFs per group
+    int last_resident_serial = 0;                         // whole SolveKeff in one workgroup (k_resident_keff): the last one ran its serial variant
     int *d_hist_cg = nullptr; int hist_cg_cap = 0; ResidentOut *d_rout = nullptr;
     int last_path = 0;                                    // 0 host-driven outer loop, 1 diagonal device loop, 2 resident kernel, 3 one-XCD kernel (nf_info "last_path")
-    long direct_max_dofs = 6000;                          // explicit-S branch with a dense S^-1 up to this many flux DOFs per group (the oracle's own limit: exact on both sides over the same range; 288 MB per group at 6000)
     int last_direct = 0;                                  // the last solve used: 0 CG as configured, 1 dense S^-1, 2 CG to 1e-14 standing in
     long standin_unconverged = 0;                         // group solves of the stand-in that ended above 1e-14
     // coarse twin of the team (SolveCoarse): built on the first coarse-mesh start and kept until the cross sections, the boundary
@@ -523,7 +489,7 @@ static int create_impl(int rt_order, int p_order, int ng, int nxb, const double 
         if (hipDeviceGetAttribute(&a, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && a > 0) T->ncu = a;
         (void)hipGetLastError();
     }
-    const char *cb = getenv("NEUTFEM_CG_BATCH"); T->cg_batch = cb ? atoi(cb) : 0;
+    const char *cb = getenv("NEUTFEM_CG_BATCH"); T->opt.cg_batch = cb ? atoi(cb) : 0;
     *out = S;
     int rc = NF_OK;
     // NEUTFEM_OPTS="key=value,key=value": nf_set_option on every handle at creation (A/B runs of programs that do not expose the options,
@@ -948,16 +914,16 @@ static int team_stream_wait(nf_team *T, hipStream_t st)
 // Read the CG scalars and / or nout doubles of `out` back to the host: through the mapped page when available, else D2H copy + wait.
 static bool pub_ready(nf_team *T)                                 // the mapped page exists (created on first use)
 {
-    if (T->opt_pub && !T->h_pub) {
+    if (T->opt.host_pub && !T->h_pub) {
         void *hp = nullptr;
         if (hipHostMalloc(&hp, sizeof(HostPub), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
             void *dp = nullptr;
             if (hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) { T->h_pub = (HostPub *)hp; T->d_pub = (HostPub *)dp; memset(hp, 0, sizeof(HostPub)); }
             else (void)hipHostFree(hp);
         }
-        if (!T->h_pub) { (void)hipGetLastError(); T->opt_pub = 0; }
+        if (!T->h_pub) { (void)hipGetLastError(); T->opt.host_pub = 0; }
     }
-    return T->opt_pub && T->h_pub;
+    return T->opt.host_pub && T->h_pub;
 }
 static int pub_wait(nf_team *T, unsigned long long seq, CgScalars *h_cg, double *h_out, int nout)   // a kernel of the stream publishes `seq`
 {
@@ -1077,7 +1043,7 @@ static int team_prepare(nf_team *T)
 {
     NFCHK(line_dict_prepare(T));                                 // once per build too, but on its own flag: options may drop the tables alone
     if (T->linked_ready) return NF_OK;
-    if (T->opt_xchg_comm && T->nproc > 1 && T->comm && !T->comm_x) {
+    if (T->opt.xchg_comm && T->nproc > 1 && T->comm && !T->comm_x) {
         // collective: rank 0 draws a second unique id and hands it to the others through the first communicator (an all-reduce(sum) of
         // its 128 bytes as doubles, zeros from everyone else)
         ncclUniqueId id2; memset(&id2, 0, sizeof id2);
@@ -1170,7 +1136,7 @@ static int team_prepare(nf_team *T)
     // endpoint functionals for the single-reduction CG (k_endpoint_w): the response of c_lo / c_hi to the unit vector of every plane, measured with
     // the endpoint pass itself -- nz launches per group, once per BuildMatrices
     for (auto *S : T->slabs) S->w_valid = false;
-    if (T->opt_endpoint_w && T->opt_cg1 != 0 && (T->opt_cg1 > 0 || T->team_max_cells <= T->cg1_max_cells))
+    if (T->opt.endpoint_weights && T->opt.cg_single_reduce != 0 && (T->opt.cg_single_reduce > 0 || T->team_max_cells <= T->opt.cg_single_reduce_max_cells))
         for (auto *S : T->slabs) {
             if (!(S->if_lo || S->if_hi) || S->nb != 0 || S->dim != 3 || S->nloc != 1) continue;
             const size_t NG = (size_t)S->N * S->ng; const long nxy = S->nlines[2];
@@ -1302,7 +1268,7 @@ static bool lds_opt_in(const void *fn, size_t lds)
 }
 // ---- Schur apply -----------------------------------------------------------------------------
 // The choices of the launch functions below as small predicates: the launches and nf_apply_plan (the read-only report) both call them.
-static bool nt_regime(const nf_solver *S) { return S->team->opt_nt_loads && S->N > S->team->nt_min_cells; }   // streaming loads beyond the caches (per slab on teams)
+static bool nt_regime(const nf_solver *S) { return S->team->opt.nt_loads && S->N > S->team->opt.nt_min_cells; }   // streaming loads beyond the caches (per slab on teams)
 static bool x_nt(const nf_solver *S, int NB) { return NB == 0 && S->nx % 2 == 0 && nt_regime(S); }
 // Table of distinct lines instead of the line's own factors (LineDict): where the streaming instantiation is taken and line_dict_prepare
 // found the direction's lines repeating and verified them.  x_dict / c_dict / s_dict sit next to x_nt / c_nt / s_nt in the launches.
@@ -1319,11 +1285,7 @@ static DictArgs dict_args(const nf_solver *S, int d, int g, bool on)
     A.ld.id = S->d_lid[d] + (long)g * S->nlines[d]; A.ld.pitch = S->ld_pitch[d];
     return A;
 }
-// inside CG: two load phases (schur_x_task, P2): 116 instead of 140 VGPRs at four chunks per lane, four waves per SIMD instead of
-// three -- and no faster (512^3: 1548 vs 1529 us, 256^3: 185.9 vs 186.3; profiles/r03_e_ab_cg.txt).  Kept as an option, off.
-// Instantiated next to the streaming loads only.
-static bool x_p2(const nf_solver *S, int NB, int NCH, bool fused_here, bool nt) { return nt && NB == 0 && NCH >= 2 && fused_here && S->team->opt_x_p2 == 1; }
-static bool x_xcd(const nf_solver *S, bool nt) { return nt && S->team->opt_xcd >= 0 && (S->team->opt_xcd & 4); }   // bit 1 of k_schur_x's `first`: the streaming instantiations only
+static bool x_xcd(const nf_solver *S, bool nt) { return nt && S->team->opt.xcd >= 0 && (S->team->opt.xcd & 4); }   // bit 1 of k_schur_x's `first`: the streaming instantiations only
 static bool x_fuses(const nf_solver *S) { return !(S->if_lo || S->if_hi); }                                       // slabs fuse in their endpoint pass instead
 // f(std::integral_constant<unsigned, key>()), key < N: how a launch function gets from runtime values to an instantiation.  f decodes its index,
 // returns false under `if constexpr` where the combination is not legal and launches otherwise: exactly the legal ones are instantiated.
@@ -1335,17 +1297,16 @@ template <class F, unsigned... I> static bool with_index(unsigned key, F &f, std
 }
 template <unsigned N, class F> static bool with_index(unsigned key, F &&f) { return with_index(key, f, std::make_integer_sequence<unsigned, N>()); }
 
-// The instantiations of k_schur_x<2, NCH, VEC, NB, NT, P2, DICT>: up to 32 chunks per lane (16, 32: RT0-P0 only), streaming loads for RT0-P0 lines
-// of even length, two load phases and the table next to the streaming loads only
-constexpr bool schur_x_legal(int NCH, bool VEC, int NB, bool NT, bool P2, bool DICT)
+// The instantiations of k_schur_x<2, NCH, VEC, NB, NT, DICT>: up to 32 chunks per lane (16, 32: RT0-P0 only), streaming loads for RT0-P0 lines
+// of even length, the table next to the streaming loads only
+constexpr bool schur_x_legal(int NCH, bool VEC, int NB, bool NT, bool DICT)
 {
     return NCH >= 1 && NCH <= (NB == 0 ? 32 : 8) && (NCH & (NCH - 1)) == 0 && NB >= 0 && NB <= 2
-        && (!NT || (VEC && NB == 0)) && (!P2 || (NT && NCH >= 2)) && (!DICT || (NT && NCH <= X_DICT_MAX_NCH));
+        && (!NT || (VEC && NB == 0)) && (!DICT || (NT && NCH <= X_DICT_MAX_NCH));
 }
-// the x pass: launch shape, NCH = the instantiation's chunks per lane (0: the line is refused), and what else picks the instantiation.
-// fused: a fused CG update rides in this pass.
-struct XPlan { int lpl_log2 = 0, NCH = 0; unsigned grid = 0; bool vec = false, nt = false, p2 = false, xcd = false, dict = false; };
-static XPlan x_plan(const nf_solver *S, bool fused = false)
+// the x pass: launch shape, NCH = the instantiation's chunks per lane (0: the line is refused), and what else picks the instantiation
+struct XPlan { int lpl_log2 = 0, NCH = 0; unsigned grid = 0; bool vec = false, nt = false, xcd = false, dict = false; };
+static XPlan x_plan(const nf_solver *S)
 {
     XPlan P; const int K = 2;
     const int lanes = (S->nx + K - 1) / K;
@@ -1355,12 +1316,12 @@ static XPlan x_plan(const nf_solver *S, bool fused = false)
     P.grid = (unsigned)((S->nlines[0] + 4 * LPW - 1) / (4 * LPW));
     for (int c = 1; c <= (S->nb == 0 ? 32 : 8); c *= 2) if (nch <= c) { P.NCH = c; break; }   // long lines (16, 32: RT0-P0 only): more registers per lane, lower occupancy
     P.vec = S->nx % 2 == 0; P.nt = x_nt(S, S->nb);
-    P.p2 = x_p2(S, S->nb, P.NCH, fused && x_fuses(S), P.nt); P.xcd = x_xcd(S, P.nt); P.dict = x_dict(S, S->nb, P.NCH, P.nt);
+    P.xcd = x_xcd(S, P.nt); P.dict = x_dict(S, S->nb, P.NCH, P.nt);
     return P;
 }
 static int launch_x(const nf_solver *S, int g, const ModeArgs &ma0, const Geom &G, int last, double *partials, const PassCg &P, int *nparts)
 {
-    const XPlan xp = x_plan(S, P.fuse.p != nullptr);
+    const XPlan xp = x_plan(S);
     if (!xp.NCH) return fail(NF_ERR_UNSUPPORTED, "nx = %d exceeds the x-line kernel limit (%d cells)", S->nx, S->nb == 0 ? 4096 : 1024);
     if (nparts) *nparts = (int)xp.grid * n_modes(S);
     const CgFuse fz = x_fuses(S) ? P.fuse : CgFuse{ nullptr, nullptr, nullptr };
@@ -1371,16 +1332,16 @@ static int launch_x(const nf_solver *S, int g, const ModeArgs &ma0, const Geom &
     ModeArgs ma = ma0; if (da.on) ma.Cd[0] = da.C;
     const double *L = da.on ? da.L : S->d_L[0] + g * S->N, *DR = da.on ? da.DR : S->d_DR[0] + g * S->N, *D0 = S->d_D0[0] + g * S->nlines[0];
     int lg = 0; while ((1 << lg) < xp.NCH) ++lg;
-    const unsigned key = ((((unsigned)lg * 3 + (unsigned)S->nb) * 2 + xp.vec) * 2 + xp.nt) * 4 + xp.p2 * 2 + xp.dict;
-    const bool hit = with_index<6 * 3 * 16>(key, [&](auto i) {
+    const unsigned key = ((((unsigned)lg * 3 + (unsigned)S->nb) * 2 + xp.vec) * 2 + xp.nt) * 2 + xp.dict;
+    const bool hit = with_index<6 * 3 * 8>(key, [&](auto i) {
         constexpr unsigned I = decltype(i)::value;
-        constexpr int NCH = 1 << (I / 48), NB = I / 16 % 3; constexpr bool VEC = I & 8, NT = I & 4, P2 = I & 2, DICT = I & 1;
-        if constexpr (!schur_x_legal(NCH, VEC, NB, NT, P2, DICT)) return false;
-        else hipLaunchKernelGGL((k_schur_x<2, NCH, VEC, NB, NT, P2, DICT>), gr, dim3(256), 0, S->team->stream, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], xp.lpl_log2,
+        constexpr int NCH = 1 << (I / 24), NB = I / 8 % 3; constexpr bool VEC = I & 4, NT = I & 2, DICT = I & 1;
+        if constexpr (!schur_x_legal(NCH, VEC, NB, NT, DICT)) return false;
+        else hipLaunchKernelGGL((k_schur_x<2, NCH, VEC, NB, NT, DICT>), gr, dim3(256), 0, S->team->stream, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], xp.lpl_log2,
                                 first, last, partials, P.cg, fz, P.lean, da.ld);
         return true;
     });
-    return hit ? NF_OK : fail(NF_ERR_ARG, "k_schur_x: no instantiation for NCH = %d, NB = %d, vec %d, nt %d, p2 %d, dict %d", xp.NCH, S->nb, xp.vec, xp.nt, xp.p2, xp.dict);
+    return hit ? NF_OK : fail(NF_ERR_ARG, "k_schur_x: no instantiation for NCH = %d, NB = %d, vec %d, nt %d, dict %d", xp.NCH, S->nb, xp.vec, xp.nt, xp.dict);
 }
 
 // Does direction d (1 = y, 2 = z) of this mesh take the chunked long-line kernel (k_schur_c)?  Plain lines of RT0-P0 meshes beyond
@@ -1391,16 +1352,16 @@ static ChunkPlan chunk_plan(const nf_solver *S, int d)
 {
     ChunkPlan P; const nf_team *T = S->team;
     const int n = d == 1 ? S->ny : S->nz;
-    if (S->nb != 0 || d < 1 || d >= S->dim || (d == 2 && (S->if_lo || S->if_hi)) || !((T->opt_s_long_dirs >> (d - 1)) & 1)) return P;
+    if (S->nb != 0 || d < 1 || d >= S->dim || (d == 2 && (S->if_lo || S->if_hi)) || !((T->opt.s_long_dirs >> (d - 1)) & 1)) return P;
     // y lines already from 256 cells (32 columns x 512 threads, two blocks per CU: y 128 -> 120 us inside CG at 256^3, 510 -> 502 us per
     // iteration; nothing at 192^3, a loss at 128^3); z lines from 257: the last pass would need the split dot product, which eats its
     // 6 us at 256^3 (profiles/r03_i_ab_cg_chunked_y.txt)
-    const int nmin = d == 1 ? T->s_long_min_y : T->s_long_min;
-    if (!(T->opt_s_long == 1 || (T->opt_s_long < 0 && n > nmin)) || (size_t)S->N * sizeof(double) >= (1ull << 32)) return P;
+    const int nmin = d == 1 ? T->opt.s_long_min_y : T->opt.s_long_min;
+    if (!(T->opt.s_long == 1 || (T->opt.s_long < 0 && n > nmin)) || (size_t)S->N * sizeof(double) >= (1ull << 32)) return P;
     P.NS = (n + 15) / 16;                                        // segments of 8 cells per chunk, two chunks
     // 32 columns: 512-thread blocks at 256-cell lines (two per CU: one block's load phase overlaps the other's scans) beat 64 columns
     // x 1024 threads there (y 113 vs 117 us, z 116 vs 127 at 256^3, profiles/r03_h_ab_256.txt); at 512 cells 32 columns need the full 1024
-    P.TX = T->opt_s_tx ? T->opt_s_tx : 32;
+    P.TX = T->opt.s_tx ? T->opt.s_tx : 32;
     while (P.TX > 8 && P.TX * P.NS > 1024) P.TX >>= 1;
     while (P.TX > 8 && P.TX / 2 >= S->nx) P.TX >>= 1;
     P.lds = (size_t)(3 * P.TX * P.NS + 2 * P.TX + 16 + 2 * 8 * P.NS * P.TX) * sizeof(double);
@@ -1408,7 +1369,7 @@ static ChunkPlan chunk_plan(const nf_solver *S, int d)
     // up to 256 cells per line the one-chunk kernel has 32 columns too, and the chunked one only wins through two blocks per CU
     // overlapping: that needs tiles to overlap with.  A 256 x 256 x 32 slab has 256 of them -- one per CU -- and loses (y 22.8 vs 20.8 us,
     // 8-slab loopback 983 vs 971 us per CG iteration, profiles/r03_n_thin_slab_tiles.txt); 256^3 has 2048 and wins.
-    if (P.ok && n <= 256 && T->opt_s_long < 1) {
+    if (P.ok && n <= 256 && T->opt.s_long < 1) {
         const long tiles = (long)((S->nx + P.TX - 1) / P.TX) * (d == 1 ? S->nz : S->ny);
         if (tiles < 1024) P.ok = false;
     }
@@ -1423,8 +1384,8 @@ static bool c_nt(const nf_solver *S) { return nt_regime(S); }
 static bool c_dict(const nf_solver *S, int d, bool nt) { return nt && dict_dir(S, d); }
 static const int C_EARLY_AUTO = 2;                               // what c_early = -1 resolves to
 // early vector loads of the chunked kernel (k_schur_c EARLY): the table-backed passes only, 0 for every other pass
-static int c_early(const nf_solver *S, bool dict) { const int e = S->team->opt_c_early; return dict ? (e < 0 ? C_EARLY_AUTO : e) : 0; }
-static int c_xcd(const nf_solver *S, int d, bool nt) { const nf_team *T = S->team; return T->opt_xcd >= 0 ? (T->opt_xcd >> (d - 1)) & 1 : (d == 1 && nt); }
+static int c_early(const nf_solver *S, bool dict) { const int e = S->team->opt.c_early; return dict ? (e < 0 ? C_EARLY_AUTO : e) : 0; }
+static int c_xcd(const nf_solver *S, int d, bool nt) { const nf_team *T = S->team; return T->opt.xcd >= 0 ? (T->opt.xcd >> (d - 1)) & 1 : (d == 1 && nt); }
 // one-chunk kernel (k_schur_s).  XCD-contiguous tile order: bit 0 = y passes, bit 1 = z passes; -1 (default) = the y passes of meshes in the streaming
 // regime -- the 8 x tiles of a row set then run on one XCD back to back (256^3: y 133 -> 123 us, 501 -> 493 us per CG iteration;
 // z passes lose 10 us with it; neutral to -0.5 % at 96^3 ... 192^3)
@@ -1433,7 +1394,7 @@ static int c_xcd(const nf_solver *S, int d, bool nt) { const nf_team *T = S->tea
 static int s_xcd(const nf_solver *S, int d, int zmode)
 {
     const nf_team *T = S->team;
-    return T->opt_xcd >= 0 ? (T->opt_xcd >> (d - 1)) & 1 : ((d == 1 && nt_regime(S)) || ((zmode == 1 || zmode == 2) && S->N <= (6L << 20)));
+    return T->opt.xcd >= 0 ? (T->opt.xcd >> (d - 1)) & 1 : ((d == 1 && nt_regime(S)) || ((zmode == 1 || zmode == 2) && S->N <= (6L << 20)));
 }
 // undivided meshes beyond the caches (the classic path's sizes): the variant with streaming loads (SV_NT)
 static bool s_nt(const nf_solver *S, int zmode, int SEG) { return zmode != 3 && S->nb == 0 && SEG == 8 && nt_regime(S); }   // plain lines and the z passes of a slab
@@ -1446,16 +1407,16 @@ static const int S_STAGE_AUTO_DIRS = 2;                          // bit 0 = y, b
 static size_t s_stage_bytes(int n, int TX) { const int rpp = 1024 / (8 * TX); return (size_t)((n + rpp - 1) / rpp) * 1024; }
 static unsigned s_stage_blocks(const nf_solver *S, const SegPlan &sp)
 {
-    const unsigned tiles = sp.grid.x * sp.grid.y, want = (unsigned)(S->team->opt_s_stage_grid > 0 ? S->team->opt_s_stage_grid : S->team->ncu);
+    const unsigned tiles = sp.grid.x * sp.grid.y, want = (unsigned)(S->team->opt.s_stage_grid > 0 ? S->team->opt.s_stage_grid : S->team->ncu);
     return std::min(tiles, want);
 }
 static bool s_stage(const nf_solver *S, int d, int zmode, const SegPlan &sp, unsigned V)
 {
     const nf_team *T = S->team;
-    if (zmode != 0 || T->opt_s_stage == 0 || !(V & SV_NT) || !(V & SV_DICT) || (V & ~(SV_NT | SV_DICT | SV_ZW))) return false;
+    if (zmode != 0 || T->opt.s_stage == 0 || !(V & SV_NT) || !(V & SV_DICT) || (V & ~(SV_NT | SV_DICT | SV_ZW))) return false;
     if (sp.TX < 8 || sp.TX > 64 || (sp.TX & (sp.TX - 1)) || S->nx % sp.TX != 0) return false;
     if (sp.lds + s_stage_bytes(d == 1 ? S->ny : S->nz, sp.TX) > T->lds_limit) return false;
-    if (T->opt_s_stage > 0) return true;
+    if (T->opt.s_stage > 0) return true;
     return ((S_STAGE_AUTO_DIRS >> (d - 1)) & 1) && sp.grid.x * sp.grid.y >= 2 * s_stage_blocks(S, sp);
 }
 // Whole-tile form (FULL) of the staged pass and of the table-backed early-load chunked pass: the grid has no partial tile -- the tile width divides
@@ -1464,17 +1425,17 @@ static bool s_stage(const nf_solver *S, int d, int zmode, const SegPlan &sp, uns
 static bool s_full(const nf_solver *S, int d, const SegPlan &sp, unsigned V)
 {
     const nf_team *T = S->team; const int n = d == 1 ? S->ny : S->nz;
-    if (T->opt_tile_full == 0 || !(V & SV_STAGE)) return false;
-    const int wsmin = T->opt_wsmin > 0 ? T->opt_wsmin : 64, nt = sp.TX * sp.NSEG;
+    if (T->opt.tile_full == 0 || !(V & SV_STAGE)) return false;
+    const int wsmin = T->opt.s_wsmin > 0 ? T->opt.s_wsmin : 64, nt = sp.TX * sp.NSEG;
     const bool wscan = sp.NSEG >= wsmin && sp.NSEG <= 64 && (nt & 63) == 0;   // schur_s_tile's test
     return S->nx % sp.TX == 0 && n == sp.SEG * sp.NSEG && (unsigned)nt == sp.block.x && !wscan && (size_t)S->N * sizeof(double) < (1ull << 32);
 }
 static bool c_full(const nf_solver *S, int d, const ChunkPlan &cp, bool dict, int early)
 {
     const int n = d == 1 ? S->ny : S->nz;
-    return S->team->opt_tile_full != 0 && dict && early == 2 && S->nx % cp.TX == 0 && n == C_NCH * C_SEG * cp.NS && (unsigned)(cp.TX * cp.NS) == c_block(cp);
+    return S->team->opt.tile_full != 0 && dict && early == 2 && S->nx % cp.TX == 0 && n == C_NCH * C_SEG * cp.NS && (unsigned)(cp.TX * cp.NS) == c_block(cp);
 }
-static bool s_fold(const nf_team *T, int zmode) { return zmode == 2 && T->sep_sweeps == 0 && T->opt_sepfold; }   // thick slabs: the accumulation pass forms the separator values itself
+static bool s_fold(const nf_team *T, int zmode) { return zmode == 2 && T->sep_sweeps == 0 && T->opt.sep_fold; }   // thick slabs: the accumulation pass forms the separator values itself
 // tiles of a (gx, gy) launch move under the XCD-contiguous order only when their count is a multiple of 8 (the kernels' own test) beyond 8 (the identity)
 static bool xcd_permutes(bool order, unsigned tiles) { return order && tiles % 8 == 0 && tiles > 8; }
 // 8-cell segments up to 1024 cells per line (16 / 32 cells spill to scratch: 1.4x slower even though TX drops to 8 at 1024)
@@ -1484,10 +1445,10 @@ static SegPlan seg_plan(const nf_solver *S, int d, int zmode)     // direction d
 {
     SegPlan P; const nf_team *T = S->team;
     const int n = d == 1 ? S->ny : S->nz, nouter = d == 1 ? S->nz : S->ny;
-    P.SEG = T->opt_s_seg ? T->opt_s_seg : (S->nb > 0 ? ((n <= 256 || (S->nb == 2 && n <= 512)) ? 4 : 8) : (n <= 1024 ? 8 : (n <= 2048 ? 16 : 32)));
+    P.SEG = T->opt.s_seg ? T->opt.s_seg : (S->nb > 0 ? ((n <= 256 || (S->nb == 2 && n <= 512)) ? 4 : 8) : (n <= 1024 ? 8 : (n <= 2048 ? 16 : 32)));
     P.NSEG = (n + P.SEG - 1) / P.SEG;
     if (P.NSEG > 128) { P.rc = fail(NF_ERR_UNSUPPORTED, "line length %d exceeds the segmented kernel limit", n); return P; }
-    P.TX = T->opt_s_tx ? T->opt_s_tx : 64;
+    P.TX = T->opt.s_tx ? T->opt.s_tx : 64;
     const int tmax = zmode != 0 ? 512 : 1024;                     // slab variants: 512 threads (register budget, see k_schur_s)
     while (P.TX > 8 && P.TX * P.NSEG > tmax) P.TX >>= 1;
     if (P.TX * P.NSEG > tmax) { P.rc = fail(NF_ERR_UNSUPPORTED, "line length %d needs more than %d threads per block", n, tmax); return P; }
@@ -1504,8 +1465,8 @@ static const int LINE_DICT_AUTO_DIRS = 7;
 static bool line_dict_eligible(const nf_solver *S, int d)
 {
     const nf_team *T = S->team;
-    if (T->opt_line_dict == 0 || d >= S->dim || T->slabs.size() != 1 || S->if_lo || S->if_hi || S->k != 0 || S->nb != 0 || S->nloc != 1 || !nt_regime(S)) return false;
-    const int dirs = T->line_dict_dirs & (T->opt_line_dict < 0 ? LINE_DICT_AUTO_DIRS : 7);
+    if (T->opt.line_dict == 0 || d >= S->dim || T->slabs.size() != 1 || S->if_lo || S->if_hi || S->k != 0 || S->nb != 0 || S->nloc != 1 || !nt_regime(S)) return false;
+    const int dirs = T->opt.line_dict_dirs & (T->opt.line_dict < 0 ? LINE_DICT_AUTO_DIRS : 7);
     if (!((dirs >> d) & 1)) return false;
     if (d == 0) { const int nch = x_plan(S).NCH; return x_nt(S, 0) && nch >= 1 && nch <= X_DICT_MAX_NCH; }
     if (chunk_plan(S, d).ok && c_nt(S)) return true;
@@ -1532,7 +1493,7 @@ static int line_dict_prepare(nf_team *T)
             DevTmp<LineFp> fp; NFCHK(dalloc(&fp.p, (size_t)nl * ng));
             for (int g = 0; g < ng; ++g)
                 hipLaunchKernelGGL(k_line_fp, dim3(gl), dim3(64), 0, st, d, S->nx, S->ny, S->nz, (const double *)(S->d_L[d] + g * N), (const double *)(S->d_DR[d] + g * N),
-                                   (const double *)(S->d_D0[d] + g * nl), Cd(g), nl, T->line_dict_fp_bits, fp.p + (size_t)g * nl);
+                                   (const double *)(S->d_D0[d] + g * nl), Cd(g), nl, T->opt.line_dict_fp_bits, fp.p + (size_t)g * nl);
             std::vector<nf_fp128> h((size_t)nl * ng);
             HIPCHK(hipMemcpyAsync(h.data(), fp.p, h.size() * sizeof(nf_fp128), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
@@ -1544,7 +1505,7 @@ static int line_dict_prepare(nf_team *T)
                 std::copy(idg.begin(), idg.end(), ids.begin() + (size_t)g * nl);
                 reps.insert(reps.end(), repg.begin(), repg.end());
                 off[g] = total; total += (long)rows[g] * pitch * narr;
-                fits = fits && (long)rows[g] * 4 <= nl && (long)rows[g] * pitch * narr * (long)sizeof(double) <= T->line_dict_max_bytes;
+                fits = fits && (long)rows[g] * 4 <= nl && (long)rows[g] * pitch * narr * (long)sizeof(double) <= T->opt.line_dict_max_bytes;
             }
             if (!fits) continue;
             DevTmp<int> drep, dmis; int mism = 0;
@@ -1650,7 +1611,7 @@ static int launch_s(const nf_solver *S, int d, int g, const ModeArgs &ma, const 
     SlabArgs sa; memset(&sa, 0, sizeof sa);
     sa.noacc = P.noacc ? 1 : 0; sa.yadd = P.yadd;
     sa.xcd = ps.xcd;
-    sa.wsmin = T->opt_wsmin;
+    sa.wsmin = T->opt.s_wsmin;
     const CgFuse fz = ps.fuse ? P.fuse : CgFuse{ nullptr, nullptr, nullptr };
     const CgLean lz = fz.p ? P.lean_z1 : CgLean{ nullptr, nullptr, 0, 0, 0 };
     if (ps.V & SV_SR) {
@@ -1712,7 +1673,7 @@ static dim3 endpoint_w_grid(const nf_solver *S) { return dim3((unsigned)((S->nx 
 static bool endpoint_w_taken(const nf_team *T, const nf_solver *S, bool sr, bool fuse_reads_x)
 {
     const dim3 gr = endpoint_w_grid(S);
-    return sr && S->w_valid && T->opt_endpoint_w && fuse_reads_x && (long)gr.x * gr.y <= T->slab_cap;
+    return sr && S->w_valid && T->opt.endpoint_weights && fuse_reads_x && (long)gr.x * gr.y <= T->slab_cap;
 }
 // Partition method, first half (slab teams): the endpoint pass of every slab (mode 1), the plane exchange and the separator
 // values (+ Jacobi sweeps for thin slabs).  The exchange and the separator kernels run on the comm stream; ev_xchg marks
@@ -1774,15 +1735,15 @@ static bool team_is_single(const nf_team *T) { return T->slabs.size() == 1 && !T
 static bool split_dot(const nf_team *T, bool want_dot, bool lean)
 {
     const int dim = T->slabs[0]->dim;
-    bool split = want_dot && dim >= 2 && team_is_single(T) && T->slabs[0]->nb == 0 && !lean && T->opt_split_dot;
-    if (split && T->opt_split_dot < 2) split = chunk_plan(T->slabs[0], dim - 1).ok;
+    bool split = want_dot && dim >= 2 && team_is_single(T) && T->slabs[0]->nb == 0 && !lean && T->opt.split_dot;
+    if (split && T->opt.split_dot < 2) split = chunk_plan(T->slabs[0], dim - 1).ok;
     return split;
 }
 // x || y (slab teams, RT0-P0, slabs small enough not to fill the chip)
 static bool xy_overlap(const nf_team *T, bool any_if, bool prof)
 {
-    const bool xy = T->slabs[0]->dim == 3 && any_if && T->opt_xy_overlap && T->slabs[0]->nb == 0 && T->y_stream && !prof;
-    bool xy_all = xy; if (xy) for (auto *X : T->slabs) xy_all = xy_all && X->N <= T->xy_overlap_max_cells && !chunk_plan(X, 1).ok;
+    const bool xy = T->slabs[0]->dim == 3 && any_if && T->opt.xy_overlap && T->slabs[0]->nb == 0 && T->y_stream && !prof;
+    bool xy_all = xy; if (xy) for (auto *X : T->slabs) xy_all = xy_all && X->N <= T->opt.xy_overlap_max_cells && !chunk_plan(X, 1).ok;
     return xy_all;
 }
 
@@ -1797,7 +1758,7 @@ static int team_schur_apply(nf_team *T, int g, const std::vector<const double *>
     hipEvent_t a, b, ta = nullptr, tb = nullptr;
     // event-timed: every prof_every-th apply (an event record keeps the launches around it from being dispatched back to back:
     // eight records per apply cost 36 us per CG iteration at 256^3, 6 % of the iteration they are meant to measure)
-    const bool prof = T->profile && (T->prof_tick++ % T->prof_every == 0);
+    const bool prof = T->profile && (T->prof_tick++ % T->opt.prof_every == 0);
     if (prof) prof_begin(T, 3, &ta, &tb);
     if (any_if) {                                                 // partition method step 1 + interface exchange
         if (prof) prof_begin(T, 4, &a, &b);
@@ -1965,9 +1926,9 @@ static int launch_apply3(nf_solver *S, int g, const Fuse3Plan &P, const double *
 // CgScalars hold the outcome of FIN_RHS, r = p = rhs, x = 0.  One launch; the kernel publishes the final scalars to the host itself.
 static bool xcd_eligible(const nf_team *T, const nf_solver *S, const Fuse3Plan &P)
 {
-    if (!T->opt_cgx || !P.ok || T->profile || S->d_void) return false;   // nf_set_void: the one-launch kernels keep their CG vectors to themselves and know no mask
+    if (!T->opt.cg_xcd || !P.ok || T->profile || S->d_void) return false;   // nf_set_void: the one-launch kernels keep their CG vectors to themselves and know no mask
     if (S->nb == 0 ? (S->nloc != 1 || n_modes(S) != 1) : (P.seg != 4 || n_modes(S) > 9 || S->nb > 2)) return false;   // P0 flux: one unknown per cell; bubble moments: the SEG = 4 tiles
-    if (S->nphi < T->xcd_min_cells || S->nphi > T->xcd_max_cells) return false;                                      // the window counts unknowns per group
+    if (S->nphi < T->opt.cg_xcd_min_cells || S->nphi > T->opt.cg_xcd_max_cells) return false;                                      // the window counts unknowns per group
     for (int r = 0; r < 2; ++r) if (S->dim >= r + 2 && (P.A.NSEG[r] >= 64 || P.A.TX[r] * P.A.NSEG[r] > 448)) return false;   // no wavefront scan in the packed tiles; a tile fits beside the other roles
     return S->nx <= 128;                                          // x lines: at most two chunks per lane (128 VGPRs at 1024 threads)
 }
@@ -1997,7 +1958,7 @@ static int xcd_fill(nf_solver *S, int g, const Fuse3Plan &P, XcdArgs &A, int *nc
     int nch = (lanes + (1 << lpl_log2) - 1) >> lpl_log2;
     if (nch == 1 && lpl_log2 == 5) {
         // 32 lanes, one chunk (the shorter chain) if the three roles of a workgroup still fit its wavefronts in one round
-        const int Pn = T->xcd_groups, tasks = (int)((S->nlines[0] + 1) / 2) * A.nmodes;
+        const int Pn = T->opt.cg_xcd_groups, tasks = (int)((S->nlines[0] + 1) / 2) * A.nmodes;
         int waves = (tasks + Pn - 1) / Pn;
         for (int r = 0; r < 2; ++r) if (S->dim >= r + 2) waves += (((P.A.gx[r] * P.A.gy[r] * A.nmodes + Pn - 1) / Pn) * P.A.TX[r] * P.A.NSEG[r] + 63) / 64;
         if (waves > XCD_THREADS / 64) { lpl_log2 = 4; nch = 2; }
@@ -2007,7 +1968,7 @@ static int xcd_fill(nf_solver *S, int g, const Fuse3Plan &P, XcdArgs &A, int *nc
     for (int r = 0; r < 2; ++r) { A.n[r] = P.A.n[r]; A.TX[r] = P.A.TX[r]; A.NSEG[r] = P.A.NSEG[r]; A.gx[r] = P.A.gx[r]; A.gy[r] = P.A.gy[r]; A.sl[r] = P.A.sl[r]; A.ostride[r] = P.A.ostride[r]; }
     if (S->dim < 2) { A.TX[0] = A.NSEG[0] = 1; } if (S->dim < 3) { A.TX[1] = A.NSEG[1] = 1; }
     A.pA = S->d_p; A.pB = S->d_p2; A.r = S->d_r;
-    A.part = T->d_xpart; A.st = T->d_xcd; A.xcc = T->xcd_id;
+    A.part = T->d_xpart; A.st = T->d_xcd; A.xcc = T->opt.cg_xcd_id;
     *nch_out = nch;
     return NF_OK;
 }
@@ -2034,7 +1995,7 @@ static int launch_cg_xcd(nf_solver *S, int g, const Fuse3Plan &P, double *xsol, 
     XcdArgs A; int nch = 1;
     NFCHK(xcd_fill(S, g, P, A, &nch));
     A.xsol = xsol; A.cg = T->d_cg; A.hp = T->d_pub; A.seq = seq;
-    const size_t lds = XCD_LDS; const unsigned G = 8u * (unsigned)T->xcd_groups;
+    const size_t lds = XCD_LDS; const unsigned G = 8u * (unsigned)T->opt.cg_xcd_groups;
     NFCHK(xcd_select("k_cg_xcd", S, P, nch, [&](auto t) -> int { using I = decltype(t);
         if (!lds_opt_in((const void *)k_cg_xcd<I::NCH, I::VEC, I::NB, I::SEG>, lds)) return fail(NF_ERR_HIP, "k_cg_xcd: %zu bytes of LDS refused", lds);
         hipLaunchKernelGGL((k_cg_xcd<I::NCH, I::VEC, I::NB, I::SEG>), dim3(G), dim3(XCD_THREADS), lds, st, A);
@@ -2057,22 +2018,22 @@ struct CgPlan {
 static CgPlan cg_plan(const nf_team *T)
 {
     CgPlan P; const nf_solver *S0 = T->slabs[0]; const bool single = team_is_single(T);
-    P.fused = T->opt_fuse != 0 && (single || S0->nloc == 1);
+    P.fused = T->opt.cg_fuse != 0 && (single || S0->nloc == 1);
     P.reductions = single ? 0 : 2;
     P.form = P.fused ? CG_FUSED : CG_CLASSIC;
-    if (!P.fused || !T->opt_lean) return P;
+    if (!P.fused || !T->opt.cg_lean) return P;
     if (!single) {
-        bool sr = T->opt_cg1 > 0 || (T->opt_cg1 < 0 && T->team_max_cells <= T->cg1_max_cells);
-        for (auto *S : T->slabs) sr = sr && S->dim == 3 && S->nb == 0 && (T->opt_s_seg == 0 || T->opt_s_seg == 8) && S->nz <= 1024;
-        const bool vec = T->nproc > 1 && T->slabs.size() == 1 && T->vec_ok && T->opt_vec_reduce;
+        bool sr = T->opt.cg_single_reduce > 0 || (T->opt.cg_single_reduce < 0 && T->team_max_cells <= T->opt.cg_single_reduce_max_cells);
+        for (auto *S : T->slabs) sr = sr && S->dim == 3 && S->nb == 0 && (T->opt.s_seg == 0 || T->opt.s_seg == 8) && S->nz <= 1024;
+        const bool vec = T->nproc > 1 && T->slabs.size() == 1 && T->vec_ok && T->opt.vec_reduce;
         P.form = sr ? CG_TEAM_SR : vec ? CG_TEAM_VEC : CG_TEAM_LEAN; P.reductions = sr ? 1 : 2;
         return P;
     }
-    if (T->rccl_reduce || S0->N > T->lean_max_cells) return P;
+    if (T->rccl_reduce || S0->N > T->opt.cg_lean_max_cells) return P;
     P.form = CG_LEAN;
     // every block of the next x pass sums the |r|^2 partials; fewer partials (cg_lean_grid) cost k_cg_rupdate more than they save (measured)
-    P.gru = grid_for(S0->nphi, 256, T->opt_lean_grid);
-    if (!T->opt_fuse3 || S0->N > T->fuse3_max_cells) return P;
+    P.gru = grid_for(S0->nphi, 256, T->opt.cg_lean_grid);
+    if (!T->opt.cg_fuse3 || S0->N > T->opt.cg_fuse3_max_cells) return P;
     P.f3 = fuse3_plan(S0);
     if (P.f3.ok && P.f3.nblocks > T->slab_cap) P.f3.ok = false;  // cannot decide: slab_partial_need counts a partial per block of this launch
     if (P.f3.ok) P.form = xcd_eligible(T, S0, P.f3) ? CG_XCD : CG_FUSE3;
@@ -2085,13 +2046,13 @@ static CgPlan cg_plan(const nf_team *T)
 // split_dot, xy_overlap); apart from building the tables of distinct lines where the next
 // apply would (line_dict_prepare) it launches nothing and writes no state.  The one thing it cannot know is a device
 // that refuses the chunked kernel's LDS at launch time (launch_s then falls back to the one-chunk kernel).
-struct PlanPass { const char *dir, *family; int mode, SEG, NCH, TX, NSEG; dim3 grid; unsigned block; bool nt, p2, zw, order; unsigned tiles; bool fold = false, dict = false; int early = 0; unsigned V = 0, blocks = 0; int full = 0; };
+struct PlanPass { const char *dir, *family; int mode, SEG, NCH, TX, NSEG; dim3 grid; unsigned block; bool nt, zw, order; unsigned tiles; bool fold = false, dict = false; int early = 0; unsigned V = 0, blocks = 0; int full = 0; };
 static void plan_emit(std::string &js, const PlanPass &p)
 {
     char tmp[416];
     snprintf(tmp, sizeof tmp, "%s{\"dir\": \"%s\", \"mode\": %d, \"family\": \"%s\", \"SEG\": %d, \"NCH\": %d, \"TX\": %d, \"NSEG\": %d, \"grid\": [%u, %u, %u], "
-             "\"block\": %u, \"nt\": %d, \"p2\": %d, \"zw\": %d, \"xcd_order\": %d, \"xcd_permutes\": %d, \"fold\": %d, \"dict\": %d, \"early\": %d", js.back() == '[' ? "" : ", ", p.dir, p.mode, p.family,
-             p.SEG, p.NCH, p.TX, p.NSEG, p.grid.x, p.grid.y, p.grid.z, p.block, p.nt ? 1 : 0, p.p2 ? 1 : 0, p.zw ? 1 : 0, p.order ? 1 : 0, xcd_permutes(p.order, p.tiles) ? 1 : 0, p.fold ? 1 : 0, p.dict ? 1 : 0, p.early);
+             "\"block\": %u, \"nt\": %d, \"zw\": %d, \"xcd_order\": %d, \"xcd_permutes\": %d, \"fold\": %d, \"dict\": %d, \"early\": %d", js.back() == '[' ? "" : ", ", p.dir, p.mode, p.family,
+             p.SEG, p.NCH, p.TX, p.NSEG, p.grid.x, p.grid.y, p.grid.z, p.block, p.nt ? 1 : 0, p.zw ? 1 : 0, p.order ? 1 : 0, xcd_permutes(p.order, p.tiles) ? 1 : 0, p.fold ? 1 : 0, p.dict ? 1 : 0, p.early);
     js += tmp;
     if (!strcmp(p.family, "s")) js += ", \"variant\": \"" + variant_name(p.V) + "\"";   // which k_schur_s
     if (p.dir[0] != 'x') js += ", \"stage\": " + std::to_string((p.V & SV_STAGE) && !strcmp(p.family, "s") ? 1 : 0) + ", \"blocks\": " + std::to_string(p.blocks)   // launched blocks (staged: persistent)
@@ -2104,7 +2065,7 @@ static int plan_s(std::string &js, const nf_solver *S, int d, int zmode, bool wa
     if (ps.rc != NF_OK) return ps.rc;
     const dim3 gr = ps.chunked ? c_grid(S, d, ps.cp) : ps.seg.grid;
     plan_emit(js, { d == 1 ? "y" : "z", ps.chunked ? "c" : "s", zmode, ps.chunked ? C_SEG : ps.seg.SEG, ps.chunked ? C_NCH : 1, ps.chunked ? ps.cp.TX : ps.seg.TX, ps.chunked ? ps.cp.NS : ps.seg.NSEG,
-                    gr, ps.chunked ? c_block(ps.cp) : ps.seg.block.x, (ps.V & SV_NT) != 0, false, (ps.V & SV_ZW) != 0, ps.xcd != 0, gr.x * gr.y, ps.fold, (ps.V & SV_DICT) != 0, ps.early, ps.V,
+                    gr, ps.chunked ? c_block(ps.cp) : ps.seg.block.x, (ps.V & SV_NT) != 0, (ps.V & SV_ZW) != 0, ps.xcd != 0, gr.x * gr.y, ps.fold, (ps.V & SV_DICT) != 0, ps.early, ps.V,
                     !ps.chunked && (ps.V & SV_STAGE) ? s_stage_blocks(S, ps.seg) * gr.z : gr.x * gr.y * gr.z, ps.full });
     return NF_OK;
 }
@@ -2134,12 +2095,12 @@ int nf_apply_plan(nf_handle S, int in_cg, char *json_buf, size_t len)
     for (int d = 0; d < S->dim; ++d) {
         const bool last = d == S->dim - 1, want_dot = cg && (last || split);
         if (d == 0) {
-            const XPlan xp = x_plan(S, fused);
+            const XPlan xp = x_plan(S);
             if (!xp.NCH) return fail(NF_ERR_UNSUPPORTED, "nx = %d exceeds the x-line kernel limit (%d cells)", S->nx, S->nb == 0 ? 4096 : 1024);
-            plan_emit(js, { "x", "x", 0, 0, xp.NCH, 1 << xp.lpl_log2, 0, dim3(xp.grid, (unsigned)n_modes(S)), 256u, xp.nt, xp.p2, false, xp.xcd, xp.grid, false, xp.dict });
+            plan_emit(js, { "x", "x", 0, 0, xp.NCH, 1 << xp.lpl_log2, 0, dim3(xp.grid, (unsigned)n_modes(S)), 256u, xp.nt, false, xp.xcd, xp.grid, false, xp.dict });
         } else if (d == 2 && slab) {
             // endpoint pass: inside the fused CG the update reads the vector the pass is applied to (cg_solve applies to d_p)
-            if (endpoint_w_taken(T, S, sr, fused)) { const dim3 gr = endpoint_w_grid(S); plan_emit(js, { "z", "endpoint_w", 1, 0, 0, 64, 0, gr, 256u, false, false, false, false, gr.x * gr.y }); }
+            if (endpoint_w_taken(T, S, sr, fused)) { const dim3 gr = endpoint_w_grid(S); plan_emit(js, { "z", "endpoint_w", 1, 0, 0, 64, 0, gr, 256u, false, false, false, gr.x * gr.y }); }
             else NFCHK(plan_s(js, S, 2, 1, false, false, fused, sr));
             NFCHK(plan_s(js, S, 2, 2, want_dot, split, fused, sr));
         } else if (d == 1 && xy_all) NFCHK(plan_s(js, S, 1, 0, false, split, fused, sr));
@@ -2190,7 +2151,7 @@ static int cg_step_fuse3(CgRun &R, int index)
     double *A = S0->d_p, *B = S0->d_p2;
     double *pin = (index == 0 || (index & 1)) ? A : B, *pout = pin == A ? B : A;
     hipEvent_t ta = nullptr, tb = nullptr;
-    const bool prof = T->profile && (T->prof_tick++ % T->prof_every == 0);
+    const bool prof = T->profile && (T->prof_tick++ % T->opt.prof_every == 0);
     if (prof) prof_begin(T, 3, &ta, &tb);
     const int rc = launch_apply3(S0, R.g, R.P.f3, pin, pout, R.x[0], cg_apply_args(R, index).lean);
     if (prof) (void)hipEventRecord(tb, T->stream);
@@ -2320,7 +2281,7 @@ static int cg_solve(nf_team *T, int g, const std::vector<const double *> &rhs, c
         // barrier timed out in the middle of the solve (a participant stalled for longer than the bound: another process on the GPU, a
         // debugger): x, r and p are half-way, but the right-hand side is intact (the kernels have all left by now: the flag that ended
         // one ended the others).  Either way this solve starts again on the launch path, and so do the following ones of this solver
-        T->opt_cgx = 0; ++T->xcd_refused; R.form = CG_FUSE3;
+        T->opt.cg_xcd = 0; ++T->xcd_refused; R.form = CG_FUSE3;
         if (sc.err == 4) { HIPCHK(hipStreamSynchronize(T->stream)); init(); }
         NFCHK(team_finalize(T, FIN_RHS, R.gcnt, 1, T->d_out, tol, maxit));
         memset(&sc, 0, sizeof sc);
@@ -2330,7 +2291,7 @@ static int cg_solve(nf_team *T, int g, const std::vector<const double *> &rhs, c
     int launched = 0, rc = NF_OK;
     // first batch: what the previous solve of this group needed, plus two (an iteration launched past convergence costs five
     // early-exit kernels, ~10 us; a second host check costs a D2H copy and a stream drain, ~50 us)
-    int batch = T->cg_batch > 0 ? T->cg_batch : (T->last_its[g] > 0 ? T->last_its[g] + 2 : 1), grow = 2;
+    int batch = T->opt.cg_batch > 0 ? T->opt.cg_batch : (T->last_its[g] > 0 ? T->last_its[g] + 2 : 1), grow = 2;
     while (launched < maxit && rc == NF_OK) {
         const int nb = std::min(batch, maxit - launched);
         for (int it = 0; it < nb && rc == NF_OK; ++it) rc = cg_step(R, launched + it, T->cg_iter_total++);
@@ -2340,7 +2301,7 @@ static int cg_solve(nf_team *T, int g, const std::vector<const double *> &rhs, c
         if (rc != NF_OK || sc.done) break;
         // after the first (predicted) batch grow geometrically: an iteration launched past convergence is five early-exit
         // kernels (~10 us), a host check is a D2H copy + stream drain (~50 us)
-        batch = T->cg_batch > 0 ? T->cg_batch : (launched < 8 ? 1 : grow);
+        batch = T->opt.cg_batch > 0 ? T->opt.cg_batch : (launched < 8 ? 1 : grow);
         if (launched >= 8) grow = std::min(64, 2 * grow);
     }
     NFCHK(rc);
@@ -2657,30 +2618,15 @@ static void dense_solve(nf_team *T, int g, const double *rhs, double *sol)
 // twin has the caller's orders and runs its passes at the caller's scale (the step operator of a transient, nf_refine's fine handle), so
 // it also gets what the launch plans of an apply and the scalar readback (pub_ready) read.  The coarse twin of SolveCoarse is RT0-P0 on a
 // mesh many times smaller: pass tuning meant for the caller's mesh stays off it.
-static void team_copy_options(nf_team *C, const nf_team *T, bool same_mesh_kind)
+// what a changed option invalidates on the slabs of a team (NF_FX_DICT / NF_FX_REGIME of nf_options.h; DICT covers REGIME)
+static int team_apply_table_effects(nf_team *T, unsigned fx)
 {
-    C->opt_cg1 = T->opt_cg1; C->cg1_max_cells = T->cg1_max_cells; C->opt_endpoint_w = T->opt_endpoint_w; C->opt_fuse = T->opt_fuse; C->opt_lean = T->opt_lean;
-    C->opt_sepfold = T->opt_sepfold; C->opt_lean_grid = T->opt_lean_grid; C->lean_max_cells = T->lean_max_cells;
-    C->opt_fuse3 = T->opt_fuse3; C->fuse3_max_cells = T->fuse3_max_cells; C->opt_cgx = T->opt_cgx; C->opt_keffx = T->opt_keffx;
-    C->xcd_min_cells = T->xcd_min_cells; C->xcd_max_cells = T->xcd_max_cells; C->xcd_id = T->xcd_id; C->xcd_groups = T->xcd_groups;
-    C->opt_resident = T->opt_resident; C->opt_resident_lds = T->opt_resident_lds; C->opt_resident_serial = T->opt_resident_serial;
-    C->opt_resident_two_sided = T->opt_resident_two_sided; C->resident_max_dofs = T->resident_max_dofs; C->resident_serial_max_dofs = T->resident_serial_max_dofs;
-    C->cg_batch = T->cg_batch; C->opt_outer_dev = T->opt_outer_dev; C->direct_max_dofs = T->direct_max_dofs;
-    if (!same_mesh_kind) return;
-    // the tables of distinct lines are built under these: a cached twin whose values change drops its tables (as nf_set_option does)
-    const bool dict_moved = C->opt_line_dict != T->opt_line_dict || C->line_dict_dirs != T->line_dict_dirs || C->line_dict_fp_bits != T->line_dict_fp_bits ||
-                            C->line_dict_max_bytes != T->line_dict_max_bytes;
-    const bool regime_moved = C->opt_nt_loads != T->opt_nt_loads || C->nt_min_cells != T->nt_min_cells || C->opt_s_long != T->opt_s_long || C->opt_s_long_dirs != T->opt_s_long_dirs ||
-                              C->s_long_min != T->s_long_min || C->s_long_min_y != T->s_long_min_y || C->opt_s_seg != T->opt_s_seg || C->opt_s_tx != T->opt_s_tx;
-    C->opt_line_dict = T->opt_line_dict; C->line_dict_dirs = T->line_dict_dirs; C->line_dict_fp_bits = T->line_dict_fp_bits; C->line_dict_max_bytes = T->line_dict_max_bytes;
-    C->opt_nt_loads = T->opt_nt_loads; C->nt_min_cells = T->nt_min_cells; C->opt_s_long = T->opt_s_long; C->opt_s_long_dirs = T->opt_s_long_dirs;
-    C->s_long_min = T->s_long_min; C->s_long_min_y = T->s_long_min_y; C->opt_s_seg = T->opt_s_seg; C->opt_s_tx = T->opt_s_tx;
-    C->opt_wsmin = T->opt_wsmin; C->opt_c_early = T->opt_c_early; C->opt_s_stage = T->opt_s_stage; C->opt_s_stage_grid = T->opt_s_stage_grid; C->opt_tile_full = T->opt_tile_full; C->opt_x_p2 = T->opt_x_p2; C->opt_split_dot = T->opt_split_dot; C->opt_xcd = T->opt_xcd;
-    C->opt_xy_overlap = T->opt_xy_overlap; C->xy_overlap_max_cells = T->xy_overlap_max_cells; C->opt_vec_reduce = T->opt_vec_reduce;
-    C->opt_pub = T->opt_pub; C->opt_sens_grid = T->opt_sens_grid; C->opt_kin_grid = T->opt_kin_grid; C->prof_every = T->prof_every;
-    if (dict_moved) { (void)hipSetDevice(C->device); for (auto *X : C->slabs) line_dict_drop(X); }
-    else if (regime_moved) for (auto *X : C->slabs) if (!X->d_lid[0] && !X->d_lid[1] && !X->d_lid[2]) X->ld_tried = false;
+    if (fx & NF_FX_DICT) { HIPCHK(hipSetDevice(T->device)); for (auto *X : T->slabs) line_dict_drop(X); }
+    else if (fx & NF_FX_REGIME) for (auto *X : T->slabs) if (!X->d_lid[0] && !X->d_lid[1] && !X->d_lid[2]) X->ld_tried = false;
+    return NF_OK;
 }
+// a cached twin whose values change drops its tables or looks again, as nf_set_option has it
+static void team_copy_options(nf_team *C, const nf_team *T, bool same_mesh_kind) { (void)team_apply_table_effects(C, nf_options_copy(C->opt, T->opt, same_mesh_kind)); }
 
 // ---- SolveCoarse (src/NeutFEM.cpp:2380-2611) ---------------------------------------------------
 static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff, int *n_outer);
@@ -3159,7 +3105,7 @@ static bool resident_plan(const nf_solver *S, ResidentArgs *A)
 // does the line-per-lane variant of the resident kernel take this mesh?  (the same arithmetic as the plan inside solve_keff_resident)
 static bool resident_serial_fits(const nf_team *T, const nf_solver *S)
 {
-    if (!T->opt_resident_serial || !T->opt_resident_lds) return false;
+    if (!T->opt.resident_serial || !T->opt.resident_lds) return false;
     const long cap = (long)T->lds_limit / 8 - 32;
     const long Np = (long)(S->nx | 1) * S->ny * S->nz;
     long lines = 0; for (int d = 0; d < S->dim; ++d) lines += (S->nlines[d] + 1) & ~1L;
@@ -3203,14 +3149,14 @@ static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, 
     // factors and first pivots); r, x_sol and the C diagonal follow as far as there is room
     const long cap = (long)T->lds_limit / 8 - 32;
     bool serial = false;
-    if (S->nb == 0 && T->opt_resident_serial && T->opt_resident_lds && S->nphi <= T->resident_serial_max_dofs) {
+    if (S->nb == 0 && T->opt.resident_serial && T->opt.resident_lds && S->nphi <= T->opt.resident_serial_max_dofs) {
         const long Np = (long)(S->nx | 1) * S->ny * S->nz;     // rows padded to an odd length (bank-conflict-free x lines)
         const int pitch = Np <= 1536 ? 1536 : 2560;              // multiples of 512 (cells per thread) and of 64 (ds_read2st64)
         long need = 64 + 16 + (1 + 3L * S->dim) * pitch;
         int slot = 0;
         for (int d = 0; d < S->dim; ++d) {
             const int nd = d == 0 ? S->nx : d == 1 ? S->ny : S->nz;
-            A.tw[d] = (nd >= 4 && T->opt_resident_two_sided) ? 1 : 0;   // two lanes per line, meeting in the middle
+            A.tw[d] = (nd >= 4 && T->opt.resident_two_sided) ? 1 : 0;   // two lanes per line, meeting in the middle
             need += 3 * ((S->nlines[d] + 1) & ~1L); A.slot0[d] = slot; slot += (int)((S->nlines[d] * (A.tw[d] ? 2 : 1) + 63) / 64) * 64;
         }
         for (int d = S->dim; d < 4; ++d) A.slot0[d] = slot;
@@ -3224,7 +3170,7 @@ static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, 
         }
     }
     // RT_k-P_m with bubble moments: the same idea, DOF = moment * PC + padded cell, one contribution vector per direction
-    if (S->nb > 0 && T->opt_resident_serial && T->opt_resident_lds && S->nphi <= T->resident_serial_max_dofs) {
+    if (S->nb > 0 && T->opt.resident_serial && T->opt.resident_lds && S->nphi <= T->opt.resident_serial_max_dofs) {
         const long Np = (long)(S->nx | 1) * S->ny * S->nz;
         const long PC = (Np + 63) & ~63L, NPp = PC * S->nloc;
         const int nm = n_modes(S);
@@ -3232,7 +3178,7 @@ static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, 
         int slot = 0;
         for (int d = 0; d < S->dim; ++d) {
             const int nd = d == 0 ? S->nx : d == 1 ? S->ny : S->nz;
-            A.tw[d] = (nd >= 4 && T->opt_resident_two_sided) ? 1 : 0;
+            A.tw[d] = (nd >= 4 && T->opt.resident_two_sided) ? 1 : 0;
             need += 3 * ((S->nlines[d] + 1) & ~1L); A.slot0[d] = slot; slot += (int)((S->nlines[d] * nm * (A.tw[d] ? 2 : 1) + 63) / 64) * 64;
         }
         for (int d = S->dim; d < 4; ++d) A.slot0[d] = slot;
@@ -3258,7 +3204,7 @@ static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, 
     if (!serial && !planned) return fail(NF_ERR_STATE, "resident solve: mesh not eligible");
     if (!serial) {
     long used = 5 * B + 64 + 16;
-    if (T->opt_resident_lds) {
+    if (T->opt.resident_lds) {
         const long NP2 = (S->nphi + 1) & ~1L, N2 = (S->N + 1) & ~1L;
         const int bits[11] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10 };
         for (int b : bits) {
@@ -3325,7 +3271,7 @@ static int solve_keff_xcd(nf_team *T, const nf_keff_opts *o, const Fuse3Plan &P,
     if (T->hist_cg_cap < o->max_outer * ng) { NFCHK(dalloc(&T->d_hist_cg, (size_t)o->max_outer * ng)); T->hist_cg_cap = o->max_outer * ng; }
     if (!T->d_rout) NFCHK(dalloc(&T->d_rout, 1));
     O.hist = T->d_hist; O.hist_cg = T->d_hist_cg; O.out = T->d_rout;
-    const size_t lds = XCD_LDS; const unsigned G = 8u * (unsigned)T->xcd_groups;
+    const size_t lds = XCD_LDS; const unsigned G = 8u * (unsigned)T->opt.cg_xcd_groups;
     NFCHK(xcd_select("k_keff_xcd", S, P, nch, [&](auto t) -> int { using I = decltype(t);
         if (!lds_opt_in((const void *)k_keff_xcd<I::NCH, I::VEC, I::NB, I::SEG>, lds)) return NF_RESIDENT_UNAVAILABLE;
         hipLaunchKernelGGL((k_keff_xcd<I::NCH, I::VEC, I::NB, I::SEG>), dim3(G), dim3(XCD_THREADS), lds, st, A, O);
@@ -3335,8 +3281,8 @@ static int solve_keff_xcd(nf_team *T, const nf_keff_opts *o, const Fuse3Plan &P,
     ResidentOut ro;
     HIPCHK(hipMemcpyAsync(&ro, T->d_rout, sizeof ro, hipMemcpyDeviceToHost, st));
     HIPCHK(stream_wait(st));
-    if (ro.status == 3) { T->opt_keffx = 0; T->opt_cgx = 0; ++T->xcd_refused; return NF_RESIDENT_UNAVAILABLE; }
-    if (ro.status == 4) { T->opt_keffx = 0; T->opt_cgx = 0; return fail(NF_ERR_HIP, "XCD-local SolveKeff (k_keff_xcd): a grid barrier timed out in outer iteration %d (a participant was lost); the path is now off for this solver", ro.n_outer); }
+    if (ro.status == 3) { T->opt.keff_xcd = 0; T->opt.cg_xcd = 0; ++T->xcd_refused; return NF_RESIDENT_UNAVAILABLE; }
+    if (ro.status == 4) { T->opt.keff_xcd = 0; T->opt.cg_xcd = 0; return fail(NF_ERR_HIP, "XCD-local SolveKeff (k_keff_xcd): a grid barrier timed out in outer iteration %d (a participant was lost); the path is now off for this solver", ro.n_outer); }
     const int n = ro.n_outer;
     T->hist_k.resize(n); T->hist_dk.resize(n); T->hist_dphi.resize(n); T->hist_cg.resize((size_t)n * ng);
     if (n > 0) {
@@ -3365,7 +3311,7 @@ static InnerPlan inner_plan(const nf_team *T, const nf_keff_opts *o)
     long Ntot = 0; for (auto *S : T->slabs) Ntot += S->nphi;
     InnerPlan p;
     p.direct = !o->solver_type_pushed || o->solver_type <= 2 || (single && Ntot < 200);
-    p.dense = p.direct && single && !T->rccl_reduce && Ntot <= T->direct_max_dofs && !T->slabs[0]->d_void;   // nf_set_void: the dense S^-1 is formed without the mask; CG to 1e-14 stands in
+    p.dense = p.direct && single && !T->rccl_reduce && Ntot <= T->opt.direct_max_dofs && !T->slabs[0]->d_void;   // nf_set_void: the dense S^-1 is formed without the mask; CG to 1e-14 stands in
     p.cg_tol = p.direct ? 1e-14 : o->tol_flux;                    // SetTolerance forwards tol_flux (:334)
     p.cg_max = p.direct ? (int)std::min<long>(20 * Ntot + 50, 200000L) : o->max_inner;   // CG ends in <= n steps in exact arithmetic
     return p;
@@ -3404,7 +3350,7 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
     T->hist_k.clear(); T->hist_dk.clear(); T->hist_dphi.clear(); T->hist_cg.clear();
     T->last_outer = 0; T->last_cg_total = 0;
     T->profile = o->profile != 0;
-    if (use_diag && single && !use_cmfd && !T->rccl_reduce && T->opt_outer_dev && o->max_outer > 0) {
+    if (use_diag && single && !use_cmfd && !T->rccl_reduce && T->opt.outer_dev && o->max_outer > 0) {
         NFCHK(solve_keff_diag_device(T, o, keff, ca, cbv, sigma, &keff));
         HIPCHK(hipStreamSynchronize(T->stream));
         T->profile = false; T->last_path = 1;
@@ -3417,8 +3363,8 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
     T->last_path = 0;
     {
         ResidentArgs probe;
-        if (single && !use_diag && !use_cmfd && !direct && !T->rccl_reduce && T->opt_resident && o->max_outer > 0 && !S0->d_void &&   // nf_set_void: the resident kernel knows no mask
-            ((S0->nphi <= T->resident_max_dofs && resident_plan(S0, &probe)) || (S0->nphi <= T->resident_serial_max_dofs && resident_serial_fits(T, S0)))) {
+        if (single && !use_diag && !use_cmfd && !direct && !T->rccl_reduce && T->opt.resident && o->max_outer > 0 && !S0->d_void &&   // nf_set_void: the resident kernel knows no mask
+            ((S0->nphi <= T->opt.resident_max_dofs && resident_plan(S0, &probe)) || (S0->nphi <= T->opt.resident_serial_max_dofs && resident_serial_fits(T, S0)))) {
             const bool prof_req = T->profile;
             T->last_path = 2; T->profile = false;
             const int rr = solve_keff_resident(T, o, keff, ca, cbv, sigma, cg_tol, cg_max, &keff);
@@ -3436,7 +3382,7 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
     // mid-size meshes (2 k - 28 k unknowns per group, every order): the whole power iteration in one launch on one XCD (k_keff_xcd),
     // where the group solves would take the one-XCD form of CG
     const CgPlan cp = cg_plan(T);
-    if (!use_diag && !use_cmfd && !direct && o->max_outer > 0 && T->opt_keffx && cp.form == CG_XCD) {
+    if (!use_diag && !use_cmfd && !direct && o->max_outer > 0 && T->opt.keff_xcd && cp.form == CG_XCD) {
         T->last_path = 3;
         const int rx = solve_keff_xcd(T, o, cp.f3, keff, ca, cbv, sigma, cg_tol, cg_max, &keff);
         if (rx != NF_RESIDENT_UNAVAILABLE) {
@@ -4051,7 +3997,7 @@ int nf_transient_step(nf_handle S, const nf_keff_opts *o, double dt, int n_steps
         }
         // nf_info on the handle reports the step's solves; a one-XCD start the device refused switches the path off for the handle as well
         T->xcd_solves += TT->xcd_solves - xcd0; T->xcd_refused += TT->xcd_refused - refused0;
-        if (TT->xcd_refused != refused0) { T->opt_cgx = TT->opt_cgx; T->opt_keffx = TT->opt_keffx; }
+        if (TT->xcd_refused != refused0) { T->opt.cg_xcd = TT->opt.cg_xcd; T->opt.keff_xcd = TT->opt.keff_xcd; }
         if (!ip.dense && r.n_outer > 0) { T->last_cg_form = TT->last_cg_form; T->last_cg_reductions = TT->last_cg_reductions; T->last_xcd = TT->last_xcd; }
         HIPCHK(hipStreamSynchronize(st));
         HIPCHK(hipGetLastError());
@@ -4137,7 +4083,7 @@ static int pk_body(nf_solver *S, const char *who, const double *phi, const KinDa
     if (rc != NF_OK) { (void)hipStreamSynchronize(st); return rc; }
     TrGroups ivel, chid; memset(&ivel, 0, sizeof ivel); memset(&chid, 0, sizeof chid);
     for (int g = 0; g < ng; ++g) { ivel.v[g] = 1.0 / K.v[g]; if (K.chid) chid.v[g] = K.chid[g]; }
-    const int grid = grid_for(NP, 256, T->opt_kin_grid), nfam = K.d_c ? I : 0, rows = 5 + nfam;   // without precursors no c_amp row is formed
+    const int grid = grid_for(NP, 256, T->opt.kin_grid), nfam = K.d_c ? I : 0, rows = 5 + nfam;   // without precursors no c_amp row is formed
     hipLaunchKernelGGL(k_kin_forms, dim3(grid), dim3(256), 0, st, (const double *)S->d_phi_adj, phi, (const double *)y.p, (const double *)S->d_Mf,
                        (const double *)S->d_Chi, dW, (const double *const *)S->d_Ms_tab, K.d_c, N, NP, ng, ivel, chid, K.chid ? 0 : 1, nfam,
                        part.p, (long)RED_GRID);
@@ -4633,7 +4579,7 @@ static void launch_sens_current_d(const nf_solver *S, int grid, hipStream_t st, 
     else if (S->k == 1) hipLaunchKernelGGL((k_sens_current<DIM, 1>), dim3(grid), dim3(256), 0, st, G, O, j, ja, D, sc, S->N, dD);
     else hipLaunchKernelGGL((k_sens_current<DIM, 2>), dim3(grid), dim3(256), 0, st, G, O, j, ja, D, sc, S->N, dD);
 }
-static int gpt_grid(const nf_solver *S, long n) { return grid_for(n, 256, S->team->opt_sens_grid); }
+static int gpt_grid(const nf_solver *S, long n) { return grid_for(n, 256, S->team->opt.sens_grid); }
 // The bilinear forms of DESIGN.md 14 on (phi, adj) with the three device scalars (Nrm, c, -c / k) of one of two scalar kernels:
 // gpt = false: k_sens_norm + k_sens_scalars (c = -k^2 / Nrm; Nrm zero or non-finite is an error) -- nf_sensitivity, launch for launch what
 // it always issued; gpt = true: k_fission + k_gpt_defl_dot + k_gpt_scalars (Nrm = <adj, F phi> as measured, c = -1) -- nf_gpt_sensitivity.
@@ -4643,7 +4589,7 @@ static int sens_body(nf_solver *S, const double *adj, bool gpt, const char *who,
 {
     hipStream_t st = S->team->stream;
     const long N = S->N;
-    const int ng = S->ng, grid = grid_for(N, 256, S->team->opt_sens_grid);
+    const int ng = S->ng, grid = grid_for(N, 256, S->team->opt.sens_grid);
     const int gx = gpt_grid(S, S->nphi), npart = gpt ? std::max(2 * gx * ng, grid) : grid;
     DevTmp<double> part; NFCHK(dalloc(&part.p, (size_t)npart + 3));    // the blocks' shares of Nrm, then Nrm, c, -c / k
     double *sc = part.p + npart;
@@ -5005,7 +4951,7 @@ static int gpt_response(nf_solver *S, GptWork &W, double *sc, double *sums)
 }
 static int gpt_work(nf_solver *S, GptWork &W)
 {
-    W.stride = (long)S->team->opt_sens_grid * S->ng;
+    W.stride = (long)S->team->opt.sens_grid * S->ng;
     return dalloc(&W.part.p, (size_t)2 * W.stride);
 }
 // the checks every GPT entry shares, before any launch
@@ -5269,10 +5215,10 @@ int nf_time_schur_apply(nf_handle S, int g, int reps, double *avg_ms)
         xs.push_back(X->d_p); ys.push_back(X->d_q);
     }
     NFCHK(team_schur_apply(T, g, xs, ys, false, ApplyCg()));   // warm-up
-    T->profile = true; const int every = T->prof_every; T->prof_every = 1;
+    T->profile = true; const int every = T->opt.prof_every; T->opt.prof_every = 1;
     for (int i = 0; i < std::min(reps, 8); ++i) NFCHK(team_schur_apply(T, g, xs, ys, false, ApplyCg()));
     HIPCHK(hipStreamSynchronize(T->stream));
-    prof_collect(T); T->profile = false; T->prof_every = every;
+    prof_collect(T); T->profile = false; T->opt.prof_every = every;
     hipEvent_t a, b; HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
     HIPCHK(hipEventRecord(a, T->stream));
     for (int i = 0; i < reps; ++i) NFCHK(team_schur_apply(T, g, xs, ys, false, ApplyCg()));
@@ -5394,79 +5340,18 @@ int nf_set_option(nf_handle S, const char *key, long value)
 {
     if (!S || !key) return fail(NF_ERR_ARG, "nf_set_option: bad arguments");
     nf_team *T = S->team;
-    // tuning overrides of the y/z line kernel: 0 = automatic; the partial-sum buffer is sized for >= 8 columns per block
-    // (slab_partial_need) and the kernel is instantiated for these segment lengths only
-    if (!strcmp(key, "s_tx")) {
-        if (value != 0 && value != 8 && value != 16 && value != 32 && value != 64) return fail(NF_ERR_ARG, "nf_set_option: s_tx must be 0 (auto), 8, 16, 32 or 64");
-        T->opt_s_tx = (int)value;
-        if (T->nproc > 1) T->linked_ready = false;               // the partial counts agreed for the vector reduce depend on the tile shape: agree again
-    } else if (!strcmp(key, "s_seg")) {
-        if (value != 0 && value != 4 && value != 8 && value != 16 && value != 32) return fail(NF_ERR_ARG, "nf_set_option: s_seg must be 0 (auto), 4, 8, 16 or 32");
-        T->opt_s_seg = (int)value;
-        if (T->nproc > 1) T->linked_ready = false;
-    }
-    else if (!strcmp(key, "s_pair")) { /* retired: the two-columns-per-thread variant lost to occupancy */ }
-    else if (!strcmp(key, "s_wsmin")) T->opt_wsmin = (int)std::max(0L, std::min(100000L, value));
-    else if (!strcmp(key, "vec_reduce")) T->opt_vec_reduce = value != 0;
-    else if (!strcmp(key, "cg_single_reduce")) { T->opt_cg1 = value < 0 ? -1 : (value != 0); T->linked_ready = false; }
-    else if (!strcmp(key, "cg_single_reduce_max_cells")) { T->cg1_max_cells = std::max(0L, value); T->linked_ready = false; }
-    else if (!strcmp(key, "endpoint_weights")) { T->opt_endpoint_w = value != 0; T->linked_ready = false; }
-    else if (!strcmp(key, "xchg_comm")) { T->opt_xchg_comm = value != 0; if (T->nproc > 1) T->linked_ready = false; }
-    else if (!strcmp(key, "xy_overlap")) T->opt_xy_overlap = value != 0;
-    else if (!strcmp(key, "xy_overlap_max_cells")) T->xy_overlap_max_cells = std::max(0L, value);
-    else if (!strcmp(key, "split_dot")) T->opt_split_dot = (int)std::max(0L, std::min(2L, value));   // 0 never, 1 where a chunked pass runs, 2 always (big undivided RT0-P0 meshes)
-    else if (!strcmp(key, "x_two_phase")) T->opt_x_p2 = value < 0 ? -1 : (value > 0 ? 1 : 0);
-    else if (!strcmp(key, "s_long")) T->opt_s_long = value < 0 ? -1 : (value > 0 ? 1 : 0);
-    else if (!strcmp(key, "s_long_dirs")) T->opt_s_long_dirs = (int)(value & 3);
-    else if (!strcmp(key, "s_long_min_y")) T->s_long_min_y = (int)std::max(1L, std::min(1000000L, value));
-    else if (!strcmp(key, "s_long_min")) T->s_long_min = (int)std::max(1L, std::min(1000000L, value));
-    else if (!strcmp(key, "c_early")) T->opt_c_early = value < 0 ? -1 : (int)std::min(2L, value);
-    else if (!strcmp(key, "s_stage")) T->opt_s_stage = value < 0 ? -1 : (value > 0 ? 1 : 0);
-    else if (!strcmp(key, "tile_full")) T->opt_tile_full = value < 0 ? -1 : (value > 0 ? 1 : 0);
-    else if (!strcmp(key, "s_stage_grid")) T->opt_s_stage_grid = (int)std::max(0L, std::min(1L << 20, value));
-    else if (!strcmp(key, "line_dict") || !strcmp(key, "line_dict_dirs") || !strcmp(key, "line_dict_max_bytes") || !strcmp(key, "line_dict_fp_bits")) {
-        if (!strcmp(key, "line_dict")) T->opt_line_dict = value < 0 ? -1 : (value > 0 ? 1 : 0);
-        else if (!strcmp(key, "line_dict_dirs")) T->line_dict_dirs = (int)(value & 7);
-        else if (!strcmp(key, "line_dict_max_bytes")) T->line_dict_max_bytes = std::max(0L, std::min(1L << 30, value));   // 32-bit byte offsets inside the kernels
-        else T->line_dict_fp_bits = (int)std::max(0L, std::min(128L, value));
-        HIPCHK(hipSetDevice(T->device));
-        for (auto *X : T->slabs) line_dict_drop(X);
-    }
-    else if (!strcmp(key, "cg_batch")) T->cg_batch = (int)value;
-    else if (!strcmp(key, "cg_fuse")) T->opt_fuse = value != 0;
-    else if (!strcmp(key, "xcd")) T->opt_xcd = value < 0 ? -1 : (int)(value & 7);
-    else if (!strcmp(key, "host_pub")) T->opt_pub = value != 0;
-    else if (!strcmp(key, "prof_every")) { if (value < 1) return fail(NF_ERR_ARG, "prof_every must be >= 1"); T->prof_every = (int)value; }
-    else if (!strcmp(key, "nt_loads")) T->opt_nt_loads = value != 0;
-    else if (!strcmp(key, "nt_min_cells")) T->nt_min_cells = value;
-    else if (!strcmp(key, "outer_dev")) T->opt_outer_dev = value != 0;
-    else if (!strcmp(key, "cg_lean")) T->opt_lean = value != 0;
-    else if (!strcmp(key, "sep_fold")) T->opt_sepfold = value != 0;
-    else if (!strcmp(key, "cg_lean_max_cells")) T->lean_max_cells = value;
-    else if (!strcmp(key, "resident")) T->opt_resident = value != 0;
-    else if (!strcmp(key, "resident_lds")) T->opt_resident_lds = value != 0;
-    else if (!strcmp(key, "resident_serial")) T->opt_resident_serial = value != 0;
-    else if (!strcmp(key, "resident_two_sided")) T->opt_resident_two_sided = value != 0;
-    else if (!strcmp(key, "resident_max_dofs")) { T->resident_max_dofs = value; T->resident_serial_max_dofs = std::min<long>(value, 5120); }   // one knob caps both variants
-    else if (!strcmp(key, "resident_serial_max_dofs")) T->resident_serial_max_dofs = value;
-    else if (!strcmp(key, "direct_max_dofs")) T->direct_max_dofs = std::max(0L, std::min(8192L, value));
-    else if (!strcmp(key, "cg_fuse3")) T->opt_fuse3 = value != 0;
-    else if (!strcmp(key, "cg_xcd")) T->opt_cgx = value != 0;
-    else if (!strcmp(key, "keff_xcd")) T->opt_keffx = value != 0;
-    else if (!strcmp(key, "cg_xcd_min_cells")) T->xcd_min_cells = value;
-    else if (!strcmp(key, "cg_xcd_max_cells")) T->xcd_max_cells = value;
-    else if (!strcmp(key, "cg_xcd_id")) T->xcd_id = (int)(value & 15);   // 8..15: no such XCD -- nobody registers, the solve falls back (tests)
-    else if (!strcmp(key, "cg_xcd_groups")) T->xcd_groups = (int)std::max<long>(1, std::min<long>(value, 64));
-    else if (!strcmp(key, "cg_fuse3_max_cells")) T->fuse3_max_cells = value;
-    else if (!strcmp(key, "cg_lean_grid")) T->opt_lean_grid = (int)std::max(1L, std::min(1024L, value));
-    else if (!strcmp(key, "sens_grid")) T->opt_sens_grid = (int)std::max(1L, std::min(65536L, value));
-    else if (!strcmp(key, "kin_grid")) T->opt_kin_grid = (int)std::max(1L, std::min((long)RED_GRID, value));
-    else if (!strcmp(key, "transient_rebalance")) S->opt_tr_rebalance = value != 0;
-    else return fail(NF_ERR_ARG, "nf_set_option: unknown key %s", key);
-    // options that move a mesh into or out of the streaming kernels: look again at the next apply (a mesh whose lines do not repeat pays the
-    // fingerprints and the host sort once per build, not once per option)
-    if (!strcmp(key, "nt_loads") || !strcmp(key, "nt_min_cells") || !strncmp(key, "s_long", 6) || !strcmp(key, "s_seg") || !strcmp(key, "s_tx"))
-        for (auto *X : T->slabs) if (!X->d_lid[0] && !X->d_lid[1] && !X->d_lid[2]) X->ld_tried = false;
+    const bool own = !strcmp(key, "transient_rebalance");          // the one option kept per handle: the table normalises it
+    NfOptions mine; unsigned fx = 0; std::string err;
+    if (!nf_options_set(own ? mine : T->opt, key, value, &fx, &err)) return fail(NF_ERR_ARG, "%s", err.c_str());
+    if (own) S->opt_tr_rebalance = (int)mine.transient_rebalance;
+    if ((fx & NF_FX_RELINK) || ((fx & NF_FX_RELINK_MULTI) && T->nproc > 1)) T->linked_ready = false;
+    return team_apply_table_effects(T, fx);
+}
+int nf_get_option(nf_handle S, const char *key, long *value)
+{
+    if (!S || !key || !value) return fail(NF_ERR_ARG, "nf_get_option: bad arguments");
+    if (!nf_options_get(S->team->opt, key, value)) return fail(NF_ERR_ARG, "nf_get_option: unknown key %s", key);
+    if (!strcmp(key, "transient_rebalance")) *value = S->opt_tr_rebalance;
     return NF_OK;
 }
 

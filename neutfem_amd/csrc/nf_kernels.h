@@ -846,12 +846,9 @@ __global__ void k_line_gather(int d, int nx, int ny, int nz, const double *__res
 // DPPS: cross-lane traffic of the scans through data-parallel primitives (VALU) instead of ds_bpermute (LDS crossbar).  That halves
 // the latency of a lone wave-task (resident kernel: 14.2 k -> 10.9 k cycles per x pass) but costs VALU issue slots: with many waves
 // per SIMD the crossbar version is faster (fused-direction launch at 128^3: 76.8 vs 82.9 us per CG iteration on the same box).
-// P2 (long lines inside CG, NCH >= 4): two load phases instead of one -- p, r, x_sol first (the deferred CG update consumes r and
-// x_sol at once), then L, 1/d and the C diagonal.  Everything in flight at once costs 140 VGPRs at four chunks per lane (three waves
-// per SIMD); in two phases the peak is the sweep's own working set.
 // DICT (streaming instantiations of RT0-P0 meshes whose lines repeat, see LineDict): L, DR and ma.Cd[0] point at the table of distinct lines
 // and the line's row replaces its own cells -- plain loads (the table is meant to stay in L2), same shapes, bit-equal values.
-template <int K, int NCH, bool VEC, int NB, class Mid = NoMid, bool DPPS = false, bool NT = false, bool P2 = false, bool DICT = false>
+template <int K, int NCH, bool VEC, int NB, class Mid = NoMid, bool DPPS = false, bool NT = false, bool DICT = false>
 __device__ __forceinline__ double schur_x_task(const ModeArgs &ma, const Geom &G, const double *__restrict__ L, const double *__restrict__ DR,
                                                const double *__restrict__ D0, int nx, int ny, long nlines, int lpl_log2, int first,
                                                long task, int lane, bool active, bool fuse, double f_alpha, double f_beta, const CgFuse &fz, Mid mid = Mid(),
@@ -876,17 +873,13 @@ __device__ __forceinline__ double schur_x_task(const ModeArgs &ma, const Geom &G
     for (int ch = 0; ch < NCH; ++ch) {
         const int c0 = (ch * LPL + li) * K;
         const bool ok = lv && c0 < nx, ok2 = lv && c0 + 1 < nx;
-        if (!P2) {
-            ld2<NTC>(L, cbase + c0, ok, VEC, Ls[ch][0], Ls[ch][1], ok2);
-            ld2<NTC>(DR, cbase + c0, ok, VEC, Rs[ch][0], Rs[ch][1], ok2);
-        }
+        ld2<NTC>(L, cbase + c0, ok, VEC, Ls[ch][0], Ls[ch][1], ok2);
+        ld2<NTC>(DR, cbase + c0, ok, VEC, Rs[ch][0], Rs[ch][1], ok2);
 #pragma unroll
         for (int q = 0; q <= NB; ++q) {
             ld2<NT>(ma.x[q], base + c0, ok, VEC, xm[q][ch][0], xm[q][ch][1], ok2);
-            if (!P2) {
-                if (DICT && first) ld2<false>(ma.Cd[q], cbase + c0, ok, VEC, yo[q][ch][0], yo[q][ch][1], ok2);
-                else ld2<NT>(first ? ma.Cd[q] : ma.y[q], base + c0, ok, VEC, yo[q][ch][0], yo[q][ch][1], ok2);
-            }
+            if (DICT && first) ld2<false>(ma.Cd[q], cbase + c0, ok, VEC, yo[q][ch][0], yo[q][ch][1], ok2);
+            else ld2<NT>(first ? ma.Cd[q] : ma.y[q], base + c0, ok, VEC, yo[q][ch][0], yo[q][ch][1], ok2);
             if (fuse) {                                          // ma.x[q] points into p: the same offset addresses r and x_sol
                 const long mo = (ma.x[q] - fz.p) + base + c0;
                 ld2<NT>(fz.r, mo, ok, VEC, rq[q][ch][0], rq[q][ch][1], ok2);
@@ -928,20 +921,6 @@ __device__ __forceinline__ double schur_x_task(const ModeArgs &ma, const Geom &G
                 for (int l = 0; l < NB; ++l) { const double gx = ma.Gc[l] * xm[l + 1][ch][j]; pl += ma.eL[l] * gx; pr += ma.eR[l] * gx; }
             }
             xL[ch][j] = xm[0][ch][j] + pl; xR[ch][j] = xm[0][ch][j] - pr;
-        }
-    }
-    if (P2) {
-#pragma unroll
-        for (int ch = 0; ch < NCH; ++ch) {                       // second load phase: what the sweeps and the output need
-            const int c0 = (ch * LPL + li) * K;
-            const bool ok = lv && c0 < nx, ok2 = lv && c0 + 1 < nx;
-            ld2<NTC>(L, cbase + c0, ok, VEC, Ls[ch][0], Ls[ch][1], ok2);
-            ld2<NTC>(DR, cbase + c0, ok, VEC, Rs[ch][0], Rs[ch][1], ok2);
-#pragma unroll
-            for (int q = 0; q <= NB; ++q) {
-                if (DICT && first) ld2<false>(ma.Cd[q], cbase + c0, ok, VEC, yo[q][ch][0], yo[q][ch][1], ok2);
-                else ld2<NT>(first ? ma.Cd[q] : ma.y[q], base + c0, ok, VEC, yo[q][ch][0], yo[q][ch][1], ok2);
-            }
         }
     }
     const double d0 = lv ? D0[line] : 0.0;
@@ -1026,7 +1005,7 @@ __device__ __forceinline__ double schur_x_task(const ModeArgs &ma, const Geom &G
     return dot;
 }
 
-template <int K, int NCH, bool VEC, int NB, bool NT = false, bool P2 = false, bool DICT = false>
+template <int K, int NCH, bool VEC, int NB, bool NT = false, bool DICT = false>
 __global__ __launch_bounds__(256) void k_schur_x(ModeArgs ma0, ModeTab mt, Geom G, const double *__restrict__ L, const double *__restrict__ DR,
                                                  const double *__restrict__ D0, int nx, int ny, long nlines, int lpl_log2,
                                                  int first, int last, double *__restrict__ partials,
@@ -1049,8 +1028,8 @@ __global__ __launch_bounds__(256) void k_schur_x(ModeArgs ma0, ModeTab mt, Geom 
     // bit 1 of `first`: XCD-contiguous block order (consecutive workgroups go round-robin to the 8 XCDs; each then walks one eighth of the lines)
     unsigned bx = blockIdx.x;
     if ((first & 2) && gridDim.x % 8 == 0) bx = (blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8;
-    const double dot = schur_x_task<K, NCH, VEC, NB, decltype(mid), false, NT, P2, DICT>(ma, G, L, DR, D0, nx, ny, nlines, lpl_log2, first & 1, (long)bx * 4 + (threadIdx.x >> 6),
-                                                                               threadIdx.x & 63, true, fuse, alpha0, beta0, fz, mid, ld);
+    const double dot = schur_x_task<K, NCH, VEC, NB, decltype(mid), false, NT, DICT>(ma, G, L, DR, D0, nx, ny, nlines, lpl_log2, first & 1, (long)bx * 4 + (threadIdx.x >> 6),
+                                                                           threadIdx.x & 63, true, fuse, alpha0, beta0, fz, mid, ld);
     if (stopped) return;                                         // decided inside, the same in every block: nothing to reduce
     if (last && partials) {
         const double s = block_sum(dot, sred);
