@@ -3026,6 +3026,14 @@ int nf_timers(nf_handle S, char *buf, size_t len)
     return NF_OK;
 }
 
+// The scatter blocks k_group_rhs / k_diag_group read for group g: Ms[g <- g'], or Ms[g' <- g] when transposed (adjoint); nullptr beyond ng.
+static ScatterArgs scatter_args(const nf_solver *S, int g, bool transposed)
+{
+    ScatterArgs sa; sa.ng = S->ng;
+    for (int gp = 0; gp < 64; ++gp) sa.M[gp] = gp < S->ng ? S->d_Ms[transposed ? gp * S->ng + g : g * S->ng + gp] : nullptr;
+    return sa;
+}
+
 // ---- diagonal path, outer loop on the device (undivided mesh, no CMFD) --------------------------------------------
 static int solve_keff_diag_device(nf_team *T, const nf_keff_opts *o, double keff0, const double *ca, const double *cbv, double sigma,
                                   double *keff_out)
@@ -3045,15 +3053,13 @@ static int solve_keff_diag_device(nf_team *T, const nf_keff_opts *o, double keff
     const int gN = grid_for(NP);
     const long stride = T->partial_stride;
     hipLaunchKernelGGL(k_fission, dim3(gN), dim3(256), 0, st, S->d_Mf, S->d_phi, ng, NP, S->d_tf, T->d_partials, (const double *)nullptr, 0L);
-    ScatterArgs sa; sa.ng = ng;
     OuterState hs = h;
     int queued = 0;
     while (queued < o->max_outer) {
         const int nb = std::min(queued == 0 ? 8 : 32, o->max_outer - queued);
         for (int b = 0; b < nb; ++b) {
             for (int g = 0; g < ng; ++g) {
-                for (int gp = 0; gp < 64; ++gp) sa.M[gp] = gp < ng ? S->d_Ms[g * ng + gp] : nullptr;
-                hipLaunchKernelGGL(k_diag_group, dim3(gN), dim3(256), 0, st, sa, g, S->d_Chi + g * N, S->d_tf, S->d_raw, S->d_phi, S->d_Sinv + g * N,
+                hipLaunchKernelGGL(k_diag_group, dim3(gN), dim3(256), 0, st, scatter_args(S, g, false), g, S->d_Chi + g * N, S->d_tf, S->d_raw, S->d_phi, S->d_Sinv + g * N,
                                    S->d_Mf + (size_t)g * NP, S->d_raw + (size_t)g * NP, NP, T->d_ost, T->d_partials, stride);
             }
             hipLaunchKernelGGL(k_outer_logic, dim3(1), dim3(256), 0, st, T->d_partials, gN, gN, stride, T->d_ost, hk, hdk, hdp);
@@ -3317,31 +3323,114 @@ static InnerPlan inner_plan(const nf_team *T, const nf_keff_opts *o)
     return p;
 }
 
+// What the host-driven drivers do before their first sweep: team_prepare, the diagonal S^-1 where the driver allows it (flag dropped for
+// order > 0, :1640-1644; whole team, slabs exchange one edge plane per group), `between` (SolveKeff: CMFD and the coarse start), then the
+// group solver of inner_plan, last_direct, and the dense S^-1 where inner_plan picks it.  DIAG_LEAN (SolveModes) is DIAG_OK without the
+// dense S^-1 the diagonal path never reads; SolveKeff and SolveSubcritical have always formed it.
+enum DiagUse { DIAG_NEVER, DIAG_OK, DIAG_LEAN };
+struct Inner { InnerPlan ip; int use_diag; };
+template <class Between>
+static int inner_begin(nf_team *T, const nf_keff_opts *o, DiagUse diag, Inner *in, Between between)
+{
+    nf_solver *S0 = T->slabs[0];
+    NFCHK(team_prepare(T));
+    in->use_diag = (diag != DIAG_NEVER && o->use_diagonal_solver && S0->k == 0 && S0->m == 0) ? 1 : 0;
+    if (in->use_diag) NFCHK(nf_build_diagonal_cache(S0));
+    NFCHK(between());
+    in->ip = inner_plan(T, o);
+    T->last_direct = in->ip.dense ? 1 : in->ip.direct ? 2 : 0;
+    if (in->ip.dense && !(diag == DIAG_LEAN && in->use_diag)) NFCHK(dense_prepare(T));
+    return NF_OK;
+}
+static int inner_begin(nf_team *T, const nf_keff_opts *o, DiagUse diag, Inner *in) { return inner_begin(T, o, diag, in, [] { return NF_OK; }); }
+
+// ---- the group sweep (src/NeutFEM.cpp:1716-1726) -------------------------------------------------------------------
+// One Gauss-Seidel sweep over the energy groups of a team, the one rule every host-driven driver shares: for group g the right-hand side
+// fscale * emis_g * tf + scatter_g (+ q_g), the groups this sweep has already solved read from `phi_new`, the others from `phi_old`
+// (k_group_rhs: gp < g new, gp > g old -- a descending sweep therefore passes the one array as both), then the group solver: the diagonal
+// S^-1 fused into k_group_rhs, the dense S^-1, or CG.  GroupSweep states what the drivers differ in; a driver fills it once per solve
+// (sweep_for, then its own fields) and changes per sweep only what its iteration changes (fscale, a column's arrays).
+struct SweepSlab {
+    const double *emis = nullptr;                         // emission coefficient, group g at + g * N: d_Chi, d_NSF (adjoint)
+    const double *phi_new = nullptr, *phi_old = nullptr;  // all groups
+    double *sol = nullptr;                                // the solution, group g at + g * nphi
+    const double *q = nullptr;                            // external source, group g at + g * nphi; nullptr: k_group_rhs<false>
+};
+struct GroupSweep {
+    bool transposed = false, descending = false;
+    double fscale = 1.0;                                  // 1/k, or the fission scale of a fixed-source solve
+    bool ride_start = true;                               // CG: x = 0, r = p = rhs and the |rhs|^2 partials ride in k_group_rhs (cg_solve(..., inited))
+    bool skip_poisoned = false;                           // SolveKeff: a poisoned rank launches nothing of its own but stays in cg_solve's collectives
+    nf_team *count_team = nullptr;                        // whose standin_unconverged counts a stand-in solve that ended above 1e-14; nullptr: not counted
+    std::vector<SweepSlab> slab;
+    std::vector<int> grid;                                // grid_for(nphi) per slab
+    std::vector<const double *> rhs; std::vector<double *> sol;   // cg_solve's per-slab operands of the current group
+};
+static GroupSweep sweep_for(nf_team *T)
+{
+    const size_t ns = T->slabs.size();
+    GroupSweep w; w.count_team = T;
+    w.slab.resize(ns); w.grid.resize(ns); w.rhs.resize(ns); w.sol.resize(ns);
+    for (size_t i = 0; i < ns; ++i) w.grid[i] = grid_for(T->slabs[i]->nphi);
+    return w;
+}
+// formed(g): after the right-hand side of group g is in d_rhs, before its solve.  solved(g, its): after the solve.
+static void sweep_no_hook(int) { }
+template <class Formed, class Solved>
+static int group_sweep(nf_team *T, const InnerPlan &ip, int use_diag, GroupSweep &w, Formed formed, Solved solved)
+{
+    const int ns = (int)T->slabs.size(), ng = T->slabs[0]->ng;
+    const bool cgi = w.ride_start && !use_diag && !ip.dense;
+    const auto rhs_kernel = !w.slab[0].q ? k_group_rhs<false> : k_group_rhs<true>;
+    for (int s = 0; s < ng; ++s) {
+        const int g = w.descending ? ng - 1 - s : s;
+        for (int i = 0; i < ns; ++i) {
+            nf_solver *S = T->slabs[i]; const SweepSlab &b = w.slab[i]; const long N = S->N, NP = S->nphi;
+            double *sol = b.sol + g * NP;
+            w.rhs[i] = S->d_rhs; w.sol[i] = sol;
+            if (w.skip_poisoned && T->poisoned) continue;
+            hipLaunchKernelGGL(rhs_kernel, dim3(w.grid[i]), dim3(256), 0, T->stream, scatter_args(S, g, w.transposed), g,
+                               b.emis + g * N, (const double *)S->d_tf, w.fscale, b.phi_new, b.phi_old,
+                               use_diag ? S->d_Sinv + g * N : (const double *)nullptr, use_diag ? sol : S->d_rhs, NP, N,
+                               cgi ? sol : (double *)nullptr, cgi ? S->d_r : (double *)nullptr, cgi ? S->d_p : (double *)nullptr,
+                               cgi ? T->d_partials + i * T->slab_cap : (double *)nullptr, b.q ? b.q + g * NP : (const double *)nullptr);
+        }
+        formed(g);
+        int its = 0; double res = 0.0;
+        if (use_diag) { }
+        else if (ip.dense) { dense_solve(T, g, w.rhs[0], w.sol[0]); its = 1; }          // last_iterations_ = 1 (src/solvers.cpp:447)
+        else {
+            NFCHK(cg_solve(T, g, w.rhs, w.sol, ip.cg_tol, ip.cg_max, &its, w.count_team ? &res : nullptr, cgi));
+            if (w.count_team && ip.direct && !(res <= 1e-14)) ++w.count_team->standin_unconverged;
+        }
+        solved(g, its);
+    }
+    return NF_OK;
+}
+
 static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, int *n_outer)
 {
     const int ns = (int)T->slabs.size();
     nf_solver *S0 = T->slabs[0];
     const int ng = S0->ng;
     const bool single = team_is_single(T);
-    NFCHK(team_prepare(T));
-    int use_diag = (o->use_diagonal_solver && S0->k == 0 && S0->m == 0) ? 1 : 0;   // flag dropped for order > 0 (:1640-1644)
-    if (use_diag) NFCHK(nf_build_diagonal_cache(S0));         // whole team; slabs exchange one edge plane per group
     const bool use_cmfd = o->use_cmfd != 0;
-    if (use_cmfd) NFCHK(cmfd_initialize_team(T));                 // :1655-1658
-    double keff = T->has_valid_keff ? T->last_keff : 1.0;        // :1662
-    T->coarse_outer = 0;
-    if (o->use_coarse_init && o->n_coarse_factors > 0) {          // :1665-1670
-        bool done = false; double kc = 1.0;
-        std::vector<double *> dsts; for (auto *S : T->slabs) dsts.push_back(S->d_phi);
-        NFCHK(coarse_init(T, o, &kc, dsts, &done));
-        keff = done ? kc : 1.0;
-    }
-    const InnerPlan ip = inner_plan(T, o);
-    const bool direct = ip.direct, dense = ip.dense;
-    const double cg_tol = ip.cg_tol;
-    const int cg_max = ip.cg_max;
-    T->last_direct = dense ? 1 : direct ? 2 : 0;
-    if (dense) NFCHK(dense_prepare(T));
+    double keff = 1.0;
+    auto cmfd_and_coarse_start = [&]() -> int {
+        if (use_cmfd) NFCHK(cmfd_initialize_team(T));             // :1655-1658
+        keff = T->has_valid_keff ? T->last_keff : 1.0;            // :1662
+        T->coarse_outer = 0;
+        if (o->use_coarse_init && o->n_coarse_factors > 0) {      // :1665-1670
+            bool done = false; double kc = 1.0;
+            std::vector<double *> dsts; for (auto *S : T->slabs) dsts.push_back(S->d_phi);
+            NFCHK(coarse_init(T, o, &kc, dsts, &done));
+            keff = done ? kc : 1.0;
+        }
+        return NF_OK;
+    };
+    Inner in;
+    NFCHK(inner_begin(T, o, DIAG_OK, &in, cmfd_and_coarse_start));
+    const InnerPlan &ip = in.ip; const int use_diag = in.use_diag;
     // ChebyshevAccel(15, 0.98), src/solvers.cpp:664-700
     const int nmax = CHEB_NMAX; const double sigma = CHEB_SIGMA;
     double ca[16], cbv[16];
@@ -3363,11 +3452,11 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
     T->last_path = 0;
     {
         ResidentArgs probe;
-        if (single && !use_diag && !use_cmfd && !direct && !T->rccl_reduce && T->opt.resident && o->max_outer > 0 && !S0->d_void &&   // nf_set_void: the resident kernel knows no mask
+        if (single && !use_diag && !use_cmfd && !ip.direct && !T->rccl_reduce && T->opt.resident && o->max_outer > 0 && !S0->d_void &&   // nf_set_void: the resident kernel knows no mask
             ((S0->nphi <= T->opt.resident_max_dofs && resident_plan(S0, &probe)) || (S0->nphi <= T->opt.resident_serial_max_dofs && resident_serial_fits(T, S0)))) {
             const bool prof_req = T->profile;
             T->last_path = 2; T->profile = false;
-            const int rr = solve_keff_resident(T, o, keff, ca, cbv, sigma, cg_tol, cg_max, &keff);
+            const int rr = solve_keff_resident(T, o, keff, ca, cbv, sigma, ip.cg_tol, ip.cg_max, &keff);
             if (rr != NF_RESIDENT_UNAVAILABLE) {
                 NFCHK(rr);
                 S0->raw_valid = T->last_outer > 0; S0->raw_is_diag = false; S0->jz_valid = false;
@@ -3382,9 +3471,9 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
     // mid-size meshes (2 k - 28 k unknowns per group, every order): the whole power iteration in one launch on one XCD (k_keff_xcd),
     // where the group solves would take the one-XCD form of CG
     const CgPlan cp = cg_plan(T);
-    if (!use_diag && !use_cmfd && !direct && o->max_outer > 0 && T->opt.keff_xcd && cp.form == CG_XCD) {
+    if (!use_diag && !use_cmfd && !ip.direct && o->max_outer > 0 && T->opt.keff_xcd && cp.form == CG_XCD) {
         T->last_path = 3;
-        const int rx = solve_keff_xcd(T, o, cp.f3, keff, ca, cbv, sigma, cg_tol, cg_max, &keff);
+        const int rx = solve_keff_xcd(T, o, cp.f3, keff, ca, cbv, sigma, ip.cg_tol, ip.cg_max, &keff);
         if (rx != NF_RESIDENT_UNAVAILABLE) {
             NFCHK(rx);
             S0->raw_valid = T->last_outer > 0; S0->raw_is_diag = false; S0->jz_valid = false;
@@ -3395,11 +3484,12 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
         }
         T->last_path = 0;
     }
-    ScatterArgs sa; sa.ng = ng;
     double hout[5] = { 0, 0, 0, 0, 0 };
     std::vector<int> gN(ns), gT(ns);
-    std::vector<const double *> rhs(ns); std::vector<double *> sol(ns);
     for (int i = 0; i < ns; ++i) { gN[i] = grid_for(T->slabs[i]->nphi); gT[i] = grid_for(T->slabs[i]->nphi * ng); }
+    GroupSweep sw = sweep_for(T);
+    sw.skip_poisoned = true;
+    for (int i = 0; i < ns; ++i) { nf_solver *S = T->slabs[i]; sw.slab[i].emis = S->d_Chi; sw.slab[i].phi_new = S->d_raw; sw.slab[i].phi_old = S->d_phi; sw.slab[i].sol = S->d_raw; }
     const bool multi = T->nproc > 1;
     // multi-rank teams: a rank-local failure between two collectives of the outer iteration poisons the rank instead of ending its part
     // of the schedule (team_poison); every rank then leaves at the same point -- the first reduction of the next CG solve, or the
@@ -3414,28 +3504,8 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
             hipLaunchKernelGGL(k_fission, dim3(gN[i]), dim3(256), 0, T->stream, S->d_Mf, S->d_phi, ng, S->nphi, S->d_tf, T->d_partials + i * T->slab_cap, (const double *)nullptr, 0L);
         }
         NF_OUTER_CHK(team_finalize(T, FIN_SUM, gN, 1, T->d_out, 0.0, 0));
-        for (int g = 0; g < ng; ++g) {
-            for (int i = 0; i < ns && !T->poisoned; ++i) {
-                nf_solver *S = T->slabs[i]; const long N = S->N, NP = S->nphi;
-                for (int gp = 0; gp < 64; ++gp) sa.M[gp] = gp < ng ? S->d_Ms[g * ng + gp] : nullptr;
-                double *dst = use_diag ? S->d_raw + g * NP : S->d_rhs;
-                // CG path: the start of the solve (x = 0, r = p = rhs, |rhs|^2 partials) rides in the same launch (cg_solve(..., inited))
-                const bool cgi = !use_diag && !dense;
-                hipLaunchKernelGGL(k_group_rhs<false>, dim3(gN[i]), dim3(256), 0, T->stream, sa, g, S->d_Chi + g * N, S->d_tf, 1.0 / keff, S->d_raw, S->d_phi,
-                                   use_diag ? S->d_Sinv + g * N : (const double *)nullptr, dst, NP, N,
-                                   cgi ? S->d_raw + g * NP : (double *)nullptr, cgi ? S->d_r : (double *)nullptr, cgi ? S->d_p : (double *)nullptr,
-                                   cgi ? T->d_partials + i * T->slab_cap : (double *)nullptr);
-                rhs[i] = S->d_rhs; sol[i] = S->d_raw + g * NP;
-            }
-            int its = 0; double res = 0.0;
-            if (use_diag) { }
-            else if (dense) { dense_solve(T, g, rhs[0], sol[0]); its = 1; }          // last_iterations_ = 1 (src/solvers.cpp:447)
-            else {
-                NFCHK(cg_solve(T, g, rhs, sol, cg_tol, cg_max, &its, &res, true));
-                if (direct && !(res <= 1e-14)) ++T->standin_unconverged;
-            }
-            T->hist_cg.push_back(its); T->last_cg_total += its;
-        }
+        sw.fscale = 1.0 / keff;
+        NFCHK(group_sweep(T, ip, use_diag, sw, sweep_no_hook, [&](int, int its) { T->hist_cg.push_back(its); T->last_cg_total += its; }));
         if (use_cmfd && it >= 2 && !T->poisoned) { if (single) NFCHK(cmfd_step(S0, keff, use_diag)); else NFCHK(cmfd_step_team(T, keff, use_diag)); }   // :1750-1761
         if (multi && T->rank == T->inject_rank && T->inject_where == 'e' && it == T->inject_outer)
             NF_OUTER_CHK(fail(NF_ERR_HIP, "injected failure on rank %d at the end of outer iteration %d (NEUTFEM_INJECT_FAIL)", T->rank, it));
@@ -3553,43 +3623,34 @@ int nf_upload_source(nf_handle S, const double *src)
     return NF_OK;
 }
 
+// The sweep of the fixed-source drivers: raw from raw / phi with the external source d_qsrc.  transposed: the scatter blocks Ms[g' <- g] in
+// place of Ms[g <- g'] (adjoint zoom), the sweep stays in forward order as nf_solve_adjoint has it.
+static GroupSweep source_sweep(nf_team *T, bool transposed)
+{
+    GroupSweep sw = sweep_for(T);
+    sw.transposed = transposed;
+    for (size_t i = 0; i < T->slabs.size(); ++i) {
+        nf_solver *S = T->slabs[i];
+        sw.slab[i].emis = S->d_Chi; sw.slab[i].phi_new = S->d_raw; sw.slab[i].phi_old = S->d_phi; sw.slab[i].sol = S->d_raw; sw.slab[i].q = S->d_qsrc;
+    }
+    return sw;
+}
+
 // One outer of the fixed-source iteration on every slab of the team: tf from the previous outer's flux, Gauss-Seidel group sweep with the
 // group solver of `ip` (or the diagonal S^-1), then one streaming pass (k_subcrit_reduce) for Phi, P, the norms and the copy raw -> phi;
-// hout = { Phi, P, ||phi||^2, ||dphi||^2 }.  fscale scales the fission term (0: off, 1: on, no eigenvalue).  transposed: the scatter
-// blocks Ms[g' <- g] in place of Ms[g <- g'] (adjoint zoom), the sweep stays in forward order as nf_solve_adjoint has it.
-static int source_outer(nf_team *T, const InnerPlan &ip, int use_diag, double fscale, bool transposed, int *cg_total, double *hout)
+// hout = { Phi, P, ||phi||^2, ||dphi||^2 }.  fscale scales the fission term (0: off, 1: on, no eigenvalue).  sw: source_sweep of the team.
+static int source_outer(nf_team *T, const InnerPlan &ip, int use_diag, GroupSweep &sw, double fscale, int *cg_total, double *hout)
 {
     const int ns = (int)T->slabs.size();
     const int ng = T->slabs[0]->ng;
-    ScatterArgs sa; sa.ng = ng;
-    std::vector<int> gN(ns), gT(ns);
-    std::vector<const double *> rhs(ns); std::vector<double *> sol(ns);
-    for (int i = 0; i < ns; ++i) { gN[i] = grid_for(T->slabs[i]->nphi); gT[i] = grid_for(T->slabs[i]->nphi * ng); }
+    std::vector<int> gT(ns);
+    for (int i = 0; i < ns; ++i) gT[i] = grid_for(T->slabs[i]->nphi * ng);
     for (int i = 0; i < ns; ++i) {                                // tf = sum_g Mf_g phi_g of the previous outer (finite, also when scaled by 0)
         nf_solver *S = T->slabs[i];
-        hipLaunchKernelGGL(k_fission, dim3(gN[i]), dim3(256), 0, T->stream, S->d_Mf, S->d_phi, ng, S->nphi, S->d_tf, T->d_partials + i * T->slab_cap, (const double *)nullptr, 0L);
+        hipLaunchKernelGGL(k_fission, dim3(sw.grid[i]), dim3(256), 0, T->stream, S->d_Mf, S->d_phi, ng, S->nphi, S->d_tf, T->d_partials + i * T->slab_cap, (const double *)nullptr, 0L);
     }
-    for (int g = 0; g < ng; ++g) {
-        for (int i = 0; i < ns; ++i) {
-            nf_solver *S = T->slabs[i]; const long N = S->N, NP = S->nphi;
-            for (int gp = 0; gp < 64; ++gp) sa.M[gp] = gp < ng ? S->d_Ms[transposed ? gp * ng + g : g * ng + gp] : nullptr;
-            double *dst = use_diag ? S->d_raw + g * NP : S->d_rhs;
-            const bool cgi = !use_diag && !ip.dense;              // CG start rides in the same launch (cg_solve(..., inited))
-            hipLaunchKernelGGL(k_group_rhs<true>, dim3(gN[i]), dim3(256), 0, T->stream, sa, g, S->d_Chi + g * N, S->d_tf, fscale, S->d_raw, S->d_phi,
-                               use_diag ? S->d_Sinv + g * N : (const double *)nullptr, dst, NP, N,
-                               cgi ? S->d_raw + g * NP : (double *)nullptr, cgi ? S->d_r : (double *)nullptr, cgi ? S->d_p : (double *)nullptr,
-                               cgi ? T->d_partials + i * T->slab_cap : (double *)nullptr, (const double *)(S->d_qsrc + g * NP));
-            rhs[i] = S->d_rhs; sol[i] = S->d_raw + g * NP;
-        }
-        int its = 0; double cres = 0.0;
-        if (use_diag) { }
-        else if (ip.dense) { dense_solve(T, g, rhs[0], sol[0]); its = 1; }
-        else {
-            NFCHK(cg_solve(T, g, rhs, sol, ip.cg_tol, ip.cg_max, &its, &cres, true));
-            if (ip.direct && !(cres <= 1e-14)) ++T->standin_unconverged;
-        }
-        *cg_total += its;
-    }
+    sw.fscale = fscale;
+    NFCHK(group_sweep(T, ip, use_diag, sw, sweep_no_hook, [&](int, int its) { *cg_total += its; }));
     for (int i = 0; i < ns; ++i) {
         nf_solver *S = T->slabs[i];
         hipLaunchKernelGGL(k_subcrit_reduce, dim3(gT[i]), dim3(256), 0, T->stream, S->d_Mf, (const double *)S->d_raw, S->d_phi, S->d_hx, S->d_hy, S->d_hz,
@@ -3602,15 +3663,15 @@ static int source_outer(nf_team *T, const InnerPlan &ip, int use_diag, double fs
 // The fixed-source iteration with the fission term off, from phi = 0 (so the result does not depend on the flux the handles held before):
 // per group S_g phi_g = q_g + scatter_g(phi) with q = d_qsrc.  Stops when |Phi_n - Phi_{n-1}| / Phi_n < tol_keff and
 // ||phi_n - phi_{n-1}|| / ||phi_n|| < tol_flux (*conv = true) or after max_outer outers.  Shared by nf_solve_subcritical (its phase 0)
-// and nf_zoom_resolved (the whole solve; transposed = adjoint).  *n outers are added to *outers and published through nf_progress.
-static int nofission_phase(nf_team *T, const nf_keff_opts *o, const InnerPlan &ip, int use_diag, bool transposed, const char *who,
+// and nf_zoom_resolved (the whole solve; adjoint: a transposed source_sweep).  *n outers are added to *outers and published through nf_progress.
+static int nofission_phase(nf_team *T, const nf_keff_opts *o, const InnerPlan &ip, int use_diag, GroupSweep &sw, const char *who,
                            double *phi_int, double *production, int *n, int *cg_total, bool *conv, long *outers)
 {
     for (auto *S : T->slabs) HIPCHK(hipMemsetAsync(S->d_phi, 0, (size_t)S->nphi * S->ng * sizeof(double), T->stream));
     double q_old = 0.0, hout[4] = { 0, 0, 0, 0 };
     *conv = false; *n = 0;
     for (int it = 0; it < o->max_outer; ++it) {
-        NFCHK(source_outer(T, ip, use_diag, 0.0, transposed, cg_total, hout));
+        NFCHK(source_outer(T, ip, use_diag, sw, 0.0, cg_total, hout));
         const double Phi = hout[0], P = hout[1], nsq = hout[2], dsq = hout[3];
         const double dq = Phi - q_old, dphi = std::sqrt(dsq / nsq);
         const double rel = dq == 0.0 ? 0.0 : std::fabs(dq) / std::fabs(Phi);
@@ -3642,12 +3703,10 @@ static int solve_subcritical_impl(nf_team *T, const nf_keff_opts *o, nf_subcrit_
         src_total += S->src_total; src_any |= S->src_any;
     }
     if (!src_any) return fail(NF_ERR_ARG, "nf_solve_subcritical: the external source is zero on every cell");
-    NFCHK(team_prepare(T));
-    const int use_diag = (o->use_diagonal_solver && S0->k == 0 && S0->m == 0) ? 1 : 0;
-    if (use_diag) NFCHK(nf_build_diagonal_cache(S0));
-    const InnerPlan ip = inner_plan(T, o);
-    T->last_direct = ip.dense ? 1 : ip.direct ? 2 : 0;
-    if (ip.dense) NFCHK(dense_prepare(T));
+    Inner in;
+    NFCHK(inner_begin(T, o, DIAG_OK, &in));
+    const InnerPlan &ip = in.ip; const int use_diag = in.use_diag;
+    GroupSweep sw = source_sweep(T, false);
     T->last_path = 0; T->profile = false;
     std::vector<int> gT(ns);
     for (int i = 0; i < ns; ++i) gT[i] = grid_for(T->slabs[i]->nphi * ng);
@@ -3656,13 +3715,13 @@ static int solve_subcritical_impl(nf_team *T, const nf_keff_opts *o, nf_subcrit_
     double hout[4] = { 0, 0, 0, 0 };
     long outers = 0;
     bool conv[2] = { false, false };
-    int rc = nofission_phase(T, o, ip, use_diag, false, "nf_solve_subcritical", &r.phi_int, &r.production, &r.n_outer_nofission, &r.cg_total, &conv[0], &outers);
+    int rc = nofission_phase(T, o, ip, use_diag, sw, "nf_solve_subcritical", &r.phi_int, &r.production, &r.n_outer_nofission, &r.cg_total, &conv[0], &outers);
     r.phi_int_nofission = r.phi_int;
     if (rc == NF_OK) {
         double q_old = r.production, dq_old = 0.0;                // P of phi0 and its change at the previous outer
         int streak = 0, n = 0;
         for (int it = 0; it < o->max_outer; ++it) {
-            if ((rc = source_outer(T, ip, use_diag, 1.0, false, &r.cg_total, hout)) != NF_OK) break;
+            if ((rc = source_outer(T, ip, use_diag, sw, 1.0, &r.cg_total, hout)) != NF_OK) break;
             const double Phi = hout[0], P = hout[1], nsq = hout[2], dsq = hout[3];
             const double dq = P - q_old, dphi = std::sqrt(dsq / nsq);
             const double rel = dq == 0.0 ? 0.0 : std::fabs(dq) / std::fabs(P);
@@ -3893,29 +3952,19 @@ static int transient_iterate(nf_solver *S, nf_solver *F, const nf_keff_opts *o, 
     hipLaunchKernelGGL(k_tr_source, dim3(gP), dim3(256), 0, st, (const double *)R->d_phi, (const double *)R->d_c, (const double *)R->d_W,
                        (const double *)S->d_Chi, R->d_q, N, NP, ng, ivdt, tr_chid(R), R->has_chid ? 0 : 1, fam, part + TR_ROW_Q * RED_GRID);
     tr_finalize(TT, part + TR_ROW_Q * RED_GRID, gP, 1, sums + TR_Q);
-    ScatterArgs sa; sa.ng = ng;
     const double inv_k = 1.0 / R->k0;
+    // the sweep runs on the twin (emission chi~, source q of this step) and counts its stand-in solves on the caller's team
+    GroupSweep sw = sweep_for(TT);
+    sw.fscale = inv_k; sw.count_team = S->team;
+    sw.slab[0].emis = F->d_Chi; sw.slab[0].phi_new = F->d_raw; sw.slab[0].phi_old = F->d_phi; sw.slab[0].sol = F->d_raw; sw.slab[0].q = R->d_q;
     double P_old = R->production;
     int n = 0;
     *conv = false;
     for (int it = 0; it < o->max_outer; ++it) {
         hipLaunchKernelGGL(k_fission, dim3(gP), dim3(256), 0, st, F->d_Mf, F->d_phi, ng, NP, F->d_tf, TT->d_partials, (const double *)nullptr, 0L);
-        for (int g = 0; g < ng; ++g) {
-            for (int gp = 0; gp < 64; ++gp) sa.M[gp] = gp < ng ? F->d_Ms[g * ng + gp] : nullptr;
-            const bool cgi = !ip.dense;                           // CG start rides in the same launch (cg_solve(..., inited))
-            hipLaunchKernelGGL(k_group_rhs<true>, dim3(gP), dim3(256), 0, st, sa, g, F->d_Chi + g * N, F->d_tf, inv_k, F->d_raw, F->d_phi,
-                               (const double *)nullptr, F->d_rhs, NP, N,
-                               cgi ? F->d_raw + g * NP : (double *)nullptr, cgi ? F->d_r : (double *)nullptr, cgi ? F->d_p : (double *)nullptr,
-                               cgi ? TT->d_partials : (double *)nullptr, (const double *)(R->d_q + g * NP));
-            hipLaunchKernelGGL(k_tr_rhs_sum, dim3(gC), dim3(256), 0, st, (const double *)F->d_rhs, N, part + TR_ROW_U * RED_GRID, g == 0 ? 1 : 0);
-            int its = 0; double cres = 0.0;
-            if (ip.dense) { dense_solve(TT, g, F->d_rhs, F->d_raw + g * NP); its = 1; }
-            else {
-                NFCHK(cg_solve(TT, g, { F->d_rhs }, { F->d_raw + g * NP }, ip.cg_tol, ip.cg_max, &its, &cres, true));
-                if (ip.direct && !(cres <= 1e-14)) ++S->team->standin_unconverged;
-            }
-            r->cg_total += its;
-        }
+        NFCHK(group_sweep(TT, ip, 0, sw,
+                          [&](int g) { hipLaunchKernelGGL(k_tr_rhs_sum, dim3(gC), dim3(256), 0, st, (const double *)F->d_rhs, N, part + TR_ROW_U * RED_GRID, g == 0 ? 1 : 0); },
+                          [&](int, int its) { r->cg_total += its; }));
         tr_finalize(TT, part + TR_ROW_U * RED_GRID, gC, 1, sums + TR_U);
         hipLaunchKernelGGL(k_tr_emission, dim3(gC), dim3(256), 0, st, F->d_Mf, (const double *)F->d_raw, (const double *)F->d_Chi,
                            (const double *const *)F->d_Ms_tab, inv_k, N, NP, ng, part + TR_ROW_E * RED_GRID);
@@ -3968,10 +4017,10 @@ int nf_transient_step(nf_handle S, const nf_keff_opts *o, double dt, int n_steps
         nf_solver *F = R->twin; nf_team *TT = F->team; hipStream_t st = TT->stream;
         team_copy_options(TT, T, true);                           // the twin is kept across steps: an option set since the last one holds for this one
         const long xcd0 = TT->xcd_solves, refused0 = TT->xcd_refused;
-        NFCHK(team_prepare(TT));
-        const InnerPlan ip = inner_plan(TT, o);
-        T->last_direct = ip.dense ? 1 : ip.direct ? 2 : 0;
-        if (ip.dense) NFCHK(dense_prepare(TT));
+        Inner in;
+        NFCHK(inner_begin(TT, o, DIAG_NEVER, &in));
+        const InnerPlan &ip = in.ip;
+        T->last_direct = TT->last_direct;
         TT->last_path = 0; TT->profile = false;
         TrFamilies fam; memset(&fam, 0, sizeof fam); fam.n = R->nfam;   // c_i <- (c_i + dt beta_i tf / k0) / (1 + lambda_i dt)
         for (int i = 0; i < R->nfam; ++i) { fam.a[i] = 1.0 / (1.0 + R->lambda[i] * dt); fam.b[i] = dt * R->beta[i] / (R->k0 * (1.0 + R->lambda[i] * dt)); }
@@ -4136,7 +4185,9 @@ int nf_solve_adjoint(nf_handle S, const nf_keff_opts *o, int normalize_to_direct
     nf_team *T = S->team;
     for (auto *X : T->slabs) if (!X->built) return fail(NF_ERR_STATE, "nf_solve_adjoint: call nf_build first");
     HIPCHK(hipSetDevice(T->device));
-    NFCHK(team_prepare(T));
+    Inner in;
+    NFCHK(inner_begin(T, o, DIAG_NEVER, &in));                    // S is symmetric: the same group solver, the same S^-1
+    const InnerPlan &ip = in.ip;
     const int ns = (int)T->slabs.size();
     nf_solver *S0 = T->slabs[0];
     const int ng = S0->ng;
@@ -4154,7 +4205,6 @@ int nf_solve_adjoint(nf_handle S, const nf_keff_opts *o, int normalize_to_direct
     }
     std::vector<DevTmp<double>> nsft(ns);
     std::vector<int> gN(ns), gT(ns);
-    std::vector<const double *> rhs(ns); std::vector<double *> sol(ns);
     for (int i = 0; i < ns; ++i) {
         nf_solver *X = T->slabs[i];
         const long NT = X->nphi * ng;
@@ -4164,19 +4214,17 @@ int nf_solve_adjoint(nf_handle S, const nf_keff_opts *o, int normalize_to_direct
         NFCHK(dalloc(&nsft[i].p, (size_t)X->N));
         hipLaunchKernelGGL(k_sum_groups, dim3(grid_for(X->N)), dim3(256), 0, st, X->d_NSF, nsft[i].p, X->N, ng);    // :1898-1905
     }
-    const InnerPlan ip = inner_plan(T, o);                       // S is symmetric: the same group solver, the same S^-1
-    const bool dense = ip.dense;
-    const double cg_tol = ip.cg_tol;
-    const int cg_max = ip.cg_max;
-    T->last_direct = dense ? 1 : ip.direct ? 2 : 0;
-    if (dense) NFCHK(dense_prepare(T));
     const int nmax = CHEB_NMAX; const double sigma = CHEB_SIGMA;
     double ca[16], cbv[16];
     cheb_tables(ca, cbv);
     int cheb_it = 0;
     T->hist_k.clear(); T->hist_dk.clear(); T->hist_dphi.clear(); T->hist_cg.clear();
     T->last_outer = 0; T->last_cg_total = 0;
-    ScatterArgs sa; sa.ng = ng;
+    // forward-ordered sweep on the transposed blocks (:1944-1950), emission nu Sigma_f; the reference starts this CG plainly and counts no
+    // stand-in solve here: both kept as they are
+    GroupSweep sw = sweep_for(T);
+    sw.transposed = true; sw.ride_start = false; sw.count_team = nullptr;
+    for (int i = 0; i < ns; ++i) { nf_solver *X = T->slabs[i]; sw.slab[i].emis = X->d_NSF; sw.slab[i].phi_new = X->d_raw; sw.slab[i].phi_old = X->d_phi_adj; sw.slab[i].sol = X->d_raw; }
     double hout[4];
     int rc = NF_OK;
     // sum_e nsf_tot[e] * (M_chi v)[e, dof 0] over the team, result in `out` (:1912-1936)
@@ -4190,20 +4238,8 @@ int nf_solve_adjoint(nf_handle S, const nf_keff_opts *o, int normalize_to_direct
     };
     for (int it = 0; it < o->max_outer && rc == NF_OK; ++it) {
         if ((rc = chi_product(false, T->d_out)) != NF_OK) break;
-        for (int g = 0; g < ng && rc == NF_OK; ++g) {
-            for (int i = 0; i < ns; ++i) {
-                nf_solver *X = T->slabs[i];
-                for (int gp = 0; gp < 64; ++gp) sa.M[gp] = gp < ng ? X->d_Ms[gp * ng + g] : nullptr;       // transposed blocks (:1944-1950)
-                hipLaunchKernelGGL(k_group_rhs<false>, dim3(gN[i]), dim3(256), 0, st, sa, g, X->d_NSF + g * X->N, X->d_tf, 1.0 / keff, X->d_raw, X->d_phi_adj,
-                                   (const double *)nullptr, X->d_rhs, X->nphi, X->N);
-                rhs[i] = X->d_rhs; sol[i] = X->d_raw + g * X->nphi;
-            }
-            int its = 0;
-            if (dense) { dense_solve(T, g, rhs[0], sol[0]); its = 1; }
-            else rc = cg_solve(T, g, rhs, sol, cg_tol, cg_max, &its, nullptr);
-            T->hist_cg.push_back(its); T->last_cg_total += its;
-        }
-        if (rc != NF_OK) break;
+        sw.fscale = 1.0 / keff;
+        if ((rc = group_sweep(T, ip, 0, sw, sweep_no_hook, [&](int, int its) { T->hist_cg.push_back(its); T->last_cg_total += its; })) != NF_OK) break;
         // NB: chi_product(true) overwrites d_tf with M_chi raw; the next outer recomputes it from phi_adj first
         if ((rc = chi_product(true, T->d_out + 1)) != NF_OK) break;
         for (int i = 0; i < ns; ++i) {
@@ -4514,16 +4550,15 @@ static int zoom_solve(nf_handle C, nf_handle F, const nf_keff_opts *o, int adjoi
 {
     NFCHK(nf_zoom_source(C, F, adjoint, keff));
     nf_team *T = F->team;
-    NFCHK(team_prepare(T));
-    const InnerPlan ip = inner_plan(T, o);
-    T->last_direct = ip.dense ? 1 : ip.direct ? 2 : 0;
-    if (ip.dense) NFCHK(dense_prepare(T));
+    Inner in;
+    NFCHK(inner_begin(T, o, DIAG_NEVER, &in));
+    GroupSweep sw = source_sweep(T, adjoint != 0);
     T->last_path = 0; T->profile = false;
     nf_zoom_result r; memset(&r, 0, sizeof r);
     r.source = F->src_total; r.n_cells = F->N;
     bool conv = false; long outers = 0;
     __atomic_store_n(&T->outers_done, 0L, __ATOMIC_RELEASE);
-    NFCHK(nofission_phase(T, o, ip, 0, adjoint != 0, "nf_zoom_resolved", &r.phi_int, &r.production, &r.n_outer, &r.cg_total, &conv, &outers));
+    NFCHK(nofission_phase(T, o, in.ip, 0, sw, "nf_zoom_resolved", &r.phi_int, &r.production, &r.n_outer, &r.cg_total, &conv, &outers));
     HIPCHK(hipStreamSynchronize(T->stream));
     HIPCHK(hipGetLastError());
     F->raw_valid = true; F->raw_is_diag = false; F->jz_valid = false;
@@ -4756,12 +4791,9 @@ static int solve_modes_impl(nf_solver *S, const nf_keff_opts *o, int m, int b, i
     nf_team *T = S->team;
     const int ng = S->ng; const long N = S->N, NP = S->nphi, NT = NP * ng;
     hipStream_t st = T->stream;
-    NFCHK(team_prepare(T));
-    const int use_diag = (o->use_diagonal_solver && S->k == 0 && S->m == 0) ? 1 : 0;
-    if (use_diag) NFCHK(nf_build_diagonal_cache(S));
-    const InnerPlan ip = inner_plan(T, o);
-    T->last_direct = ip.dense ? 1 : ip.direct ? 2 : 0;
-    if (!use_diag && ip.dense) NFCHK(dense_prepare(T));
+    Inner in;
+    NFCHK(inner_begin(T, o, DIAG_LEAN, &in));
+    const InnerPlan &ip = in.ip; const int use_diag = in.use_diag;
     T->profile = false;
     DevTmp<double> Qb, Zb;
     NFCHK(dalloc(&Qb.p, (size_t)b * NT)); NFCHK(dalloc(&Zb.p, (size_t)b * NT));
@@ -4772,31 +4804,17 @@ static int solve_modes_impl(nf_solver *S, const nf_keff_opts *o, int m, int b, i
     const int gN = grid_for(NP);
     nf_modes_result r; memset(&r, 0, sizeof r);
     r.n_modes = m; r.n_block = b;
-    ScatterArgs sa; sa.ng = ng;
     // z_j = A q_j for the first nc columns: fission source of q_j, then the group sweep (direct: ascending; adjoint: descending on the
-    // transposed blocks); with downscatter only every scatter term reads a group of z_j the sweep has already solved
+    // transposed blocks), in place in z_j; with downscatter only every scatter term reads a group of z_j the sweep has already solved
+    GroupSweep sw = sweep_for(T);
+    sw.transposed = sw.descending = adjoint != 0;
+    sw.slab[0].emis = emi;
     auto apply = [&](int nc) -> int {
         for (int j = 0; j < nc; ++j) {
             const double *q = Q + (size_t)j * NT; double *z = Z + (size_t)j * NT;
             hipLaunchKernelGGL(k_fission, dim3(gN), dim3(256), 0, st, fis, q, ng, NP, S->d_tf, T->d_partials, (const double *)nullptr, 0L);
-            for (int s = 0; s < ng; ++s) {
-                const int g = adjoint ? ng - 1 - s : s;
-                for (int gp = 0; gp < 64; ++gp) sa.M[gp] = gp < ng ? S->d_Ms[adjoint ? gp * ng + g : g * ng + gp] : nullptr;
-                double *sol = z + (size_t)g * NP, *dst = use_diag ? sol : S->d_rhs;
-                const bool cgi = !use_diag && !ip.dense;
-                hipLaunchKernelGGL(k_group_rhs<false>, dim3(gN), dim3(256), 0, st, sa, g, emi + g * N, S->d_tf, 1.0, (const double *)z, (const double *)z,
-                                   use_diag ? S->d_Sinv + g * N : (const double *)nullptr, dst, NP, N,
-                                   cgi ? sol : (double *)nullptr, cgi ? S->d_r : (double *)nullptr, cgi ? S->d_p : (double *)nullptr,
-                                   cgi ? T->d_partials : (double *)nullptr);
-                int its = 0; double cres = 0.0;
-                if (use_diag) { }
-                else if (ip.dense) { dense_solve(T, g, S->d_rhs, sol); its = 1; }
-                else {
-                    NFCHK(cg_solve(T, g, { (const double *)S->d_rhs }, { sol }, ip.cg_tol, ip.cg_max, &its, &cres, true));
-                    if (ip.direct && !(cres <= 1e-14)) ++T->standin_unconverged;
-                }
-                r.cg_total += its;
-            }
+            sw.slab[0].phi_new = sw.slab[0].phi_old = z; sw.slab[0].sol = z;
+            NFCHK(group_sweep(T, ip, use_diag, sw, sweep_no_hook, [&](int, int its) { r.cg_total += its; }));
         }
         return NF_OK;
     };
@@ -5008,10 +5026,9 @@ static int solve_gpt_impl(nf_solver *S, const nf_keff_opts *o, double keff, nf_g
     nf_team *T = S->team;
     const int ng = S->ng; const long N = S->N, NP = S->nphi, NT = NP * ng;
     hipStream_t st = T->stream;
-    NFCHK(team_prepare(T));
-    const InnerPlan ip = inner_plan(T, o);
-    T->last_direct = ip.dense ? 1 : ip.direct ? 2 : 0;
-    if (ip.dense) NFCHK(dense_prepare(T));
+    Inner in;
+    NFCHK(inner_begin(T, o, DIAG_NEVER, &in));
+    const InnerPlan &ip = in.ip;
     T->profile = false;
     GptWork W; NFCHK(gpt_work(S, W));
     double *sc = S->d_gpt_sc;
@@ -5040,32 +5057,18 @@ static int solve_gpt_impl(nf_solver *S, const nf_keff_opts *o, double keff, nf_g
     double *G = S->d_gamma;
     HIPCHK(hipMemsetAsync(G, 0, (size_t)NT * sizeof(double), st));
     HIPCHK(hipMemsetAsync(old.p, 0, (size_t)NT * sizeof(double), st));
-    ScatterArgs sa; sa.ng = ng;
-    const double inv_k = 1.0 / keff;
+    // the sweep runs from the last group to the first on the transposed scatter blocks, in place: in the descending sweep the groups above g
+    // are the new ones, k_group_rhs reads both from the one array
+    GroupSweep sw = sweep_for(T);
+    sw.transposed = sw.descending = true; sw.fscale = 1.0 / keff;
+    sw.slab[0].emis = S->d_NSF; sw.slab[0].phi_new = sw.slab[0].phi_old = G; sw.slab[0].sol = G; sw.slab[0].q = src.p;
     double dprev = 0.0, h[3];
     bool conv = false;
     for (int it = 0; it < o->max_outer; ++it) {
         // the adjoint fission term of the previous iterate, then the group sweep from the last group to the first on the transposed
         // scatter blocks, in place: with downscatter only every scatter term reads a group this sweep has already solved
         hipLaunchKernelGGL(k_fission, dim3(gN), dim3(256), 0, st, S->d_Mchi, (const double *)G, ng, NP, S->d_tf, T->d_partials, (const double *)nullptr, 0L);
-        for (int s = 0; s < ng; ++s) {
-            const int g = ng - 1 - s;
-            for (int gp = 0; gp < 64; ++gp) sa.M[gp] = gp < ng ? S->d_Ms[gp * ng + g] : nullptr;
-            // in the descending sweep the groups above g are the new ones: k_group_rhs reads both from the one array
-            double *sol = G + (size_t)g * NP;
-            const bool cgi = !ip.dense;
-            hipLaunchKernelGGL(k_group_rhs<true>, dim3(gN), dim3(256), 0, st, sa, g, S->d_NSF + g * N, S->d_tf, inv_k, (const double *)G, (const double *)G,
-                               (const double *)nullptr, S->d_rhs, NP, N,
-                               cgi ? sol : (double *)nullptr, cgi ? S->d_r : (double *)nullptr, cgi ? S->d_p : (double *)nullptr,
-                               cgi ? T->d_partials : (double *)nullptr, (const double *)(src.p + (size_t)g * NP));
-            int its = 0; double cres = 0.0;
-            if (ip.dense) { dense_solve(T, g, S->d_rhs, sol); its = 1; }
-            else {
-                NFCHK(cg_solve(T, g, { (const double *)S->d_rhs }, { sol }, ip.cg_tol, ip.cg_max, &its, &cres, true));
-                if (ip.direct && !(cres <= 1e-14)) ++T->standin_unconverged;
-            }
-            r.cg_total += its;
-        }
+        NFCHK(group_sweep(T, ip, 0, sw, sweep_no_hook, [&](int, int its) { r.cg_total += its; }));
         // deflation: Gamma -= (<Gamma, F phi> / <phi+, F phi>) phi+, beta formed on the device; norms and old <- Gamma in the same sweep
         hipLaunchKernelGGL(k_gpt_defl_dot, dim3(gx, ng), dim3(256), 0, st, (const double *)G, (const double *)S->d_Chi, (const double *)tfphi.p, N, NP, W.part.p, W.stride);
         hipLaunchKernelGGL(k_block_finalize, dim3(1), dim3(256), 0, st, (const double *)W.part.p, W.stride, gx * ng, sc + GPT_NUM);

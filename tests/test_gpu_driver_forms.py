@@ -1,9 +1,9 @@
 """Every solve driver on every form of the CG iteration, against the driver's exact twin.
 
 SolveKeff is checked on every form (tests/test_gpu_paths.py, test_gpu_variants.py, test_gpu_cg_forms.py).  The other drivers enter the same
-cg_solve with their own right-hand-side launch and their own vectors: solve_subcritical and transient_step with the CG start riding in
-k_group_rhs, the transient on a twin handle; solve_modes into a column of its block, the adjoint modes on transposed blocks;
-zoom_resolved on the fine handle nf_refine makes; solve_adjoint with a plain start.  CASES is one explicit table of (driver, mesh, route,
+cg_solve through the one group_sweep, each with its own settings and its own vectors: solve_subcritical and transient_step
+with the CG start riding in k_group_rhs, the transient on a twin handle; solve_modes into a column of its block, the adjoint modes on
+transposed blocks; zoom_resolved on the fine handle nf_refine makes; solve_adjoint with a plain start.  CASES is one explicit table of (driver, mesh, route,
 expected form).  Every entry asserts the form before the call (apply_plan(True)["form"]; the transient: on the caller's handle, whose
 options its step operator takes; the zoom: on the returned fine handle, which takes the coarse handle's), the form, the one-XCD counters
 and last_direct after it (nf_info), and the numbers against the twin at the bar the driver's own test file applies at the same tolerances:
