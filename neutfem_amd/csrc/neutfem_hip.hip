@@ -2567,14 +2567,15 @@ int nf_get_J(nf_handle S, double *J_host)
     return NF_OK;
 }
 
-// ChebyshevAccel(15, 0.98) coefficient tables a_n, b_n (src/solvers.cpp:664-700), shared by the direct and adjoint iterations
-static const int CHEB_NMAX = 15;
-static const double CHEB_SIGMA = 0.98;
-static void cheb_tables(double *ca, double *cbv)
+// phi = Chebyshev(raw / norm) on one slab with the step of cheb_next (nf_outer.h): p0 / p1 on first use, the launch, the swap after a
+// three-term step.  Shared by the host-driven direct and adjoint iterations; each keeps its own handling of the code returned.
+static int normalize_cheb(nf_solver *S, hipStream_t st, double *cur, double norm, bool do_norm, const ChebStep &cs)
 {
-    const double sigma = CHEB_SIGMA, Gm = std::acosh(2. / sigma - 1.);
-    ca[0] = cbv[0] = 0.; ca[1] = 2. / (2. - sigma); cbv[1] = 0.;
-    for (int i = 2; i < CHEB_NMAX; ++i) { ca[i] = std::cosh((i - 1) * Gm) / std::cosh(i * Gm); cbv[i] = std::cosh((i - 2) * Gm) / std::cosh(i * Gm); }
+    const long NT = S->nphi * S->ng;
+    if (cs.mode && !S->d_p0) { NFCHK(dalloc(&S->d_p0, (size_t)NT)); NFCHK(dalloc(&S->d_p1, (size_t)NT)); }
+    hipLaunchKernelGGL(k_normalize_cheb, dim3(grid_for(NT)), dim3(256), 0, st, S->d_raw, cur, S->d_p0, S->d_p1, NT, norm, do_norm ? 1 : 0, cs.mode, cs.a, cs.b);
+    if (cs.mode == 3) std::swap(S->d_p0, S->d_p1);
+    return NF_OK;
 }
 
 // ---- explicit-S branch (src/solvers.cpp:114-124, 259-509) ----------------------------------------
@@ -3034,21 +3035,48 @@ static ScatterArgs scatter_args(const nf_solver *S, int g, bool transposed)
     return sa;
 }
 
+// ---- the history of a solve whose outer loop ran on the device ----------------------------------------------------
+// d_hist: three rows (k, dk, dphi) of max_outer entries (+ 8 for NF_STAMPS); with CG counts (cg: the one-launch solves) d_hist_cg and d_rout
+static int hist_reserve(nf_team *T, int max_outer, bool cg)
+{
+    const int ng = T->slabs[0]->ng;
+    if (T->hist_cap < max_outer) { NFCHK(dalloc(&T->d_hist, (size_t)3 * max_outer + 8)); T->hist_cap = max_outer; }
+    if (cg && T->hist_cg_cap < max_outer * ng) { NFCHK(dalloc(&T->d_hist_cg, (size_t)max_outer * ng)); T->hist_cg_cap = max_outer * ng; }
+    if (cg && !T->d_rout) NFCHK(dalloc(&T->d_rout, 1));
+    return NF_OK;
+}
+// n outers of it into hist_k / dk / dphi / cg (`row`: the row length the kernels wrote d_hist with), last_its, last_outer, last_cg_total;
+// status 2 of the device loop is the divergence the host-driven loop reports
+static int hist_fetch(nf_team *T, int n, size_t row, bool cg, long cg_total, int status)
+{
+    const int ng = T->slabs[0]->ng;
+    T->hist_k.resize(n); T->hist_dk.resize(n); T->hist_dphi.resize(n); T->hist_cg.assign((size_t)n * ng, 0);
+    if (n > 0) {
+        HIPCHK(hipMemcpy(T->hist_k.data(), T->d_hist, n * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(T->hist_dk.data(), T->d_hist + row, n * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(T->hist_dphi.data(), T->d_hist + 2 * row, n * sizeof(double), hipMemcpyDeviceToHost));
+        if (cg) {
+            HIPCHK(hipMemcpy(T->hist_cg.data(), T->d_hist_cg, (size_t)n * ng * sizeof(int), hipMemcpyDeviceToHost));
+            for (int g = 0; g < ng; ++g) T->last_its[g] = T->hist_cg[(size_t)(n - 1) * ng + g];
+        }
+    }
+    T->last_outer = n; T->last_cg_total = cg_total;
+    if (status == 2) return fail(NF_ERR_NUMERIC, "power iteration diverged (outer %d: k=%g dphi=%g)", n - 1, n > 0 ? T->hist_k[n - 1] : 0.0, n > 0 ? T->hist_dphi[n - 1] : 0.0);
+    return NF_OK;
+}
+
 // ---- diagonal path, outer loop on the device (undivided mesh, no CMFD) --------------------------------------------
-static int solve_keff_diag_device(nf_team *T, const nf_keff_opts *o, double keff0, const double *ca, const double *cbv, double sigma,
-                                  double *keff_out)
+static int solve_keff_diag_device(nf_team *T, const nf_keff_opts *o, double keff0, const ChebTable &cheb, double *keff_out)
 {
     nf_solver *S = T->slabs[0];
     const int ng = S->ng; const long N = S->N, NP = S->nphi, NT = NP * ng;
     hipStream_t st = T->stream;
     if (!S->d_p0) { NFCHK(dalloc(&S->d_p0, (size_t)NT)); NFCHK(dalloc(&S->d_p1, (size_t)NT)); }
     if (!T->d_ost) NFCHK(dalloc(&T->d_ost, 1));
-    if (T->hist_cap < o->max_outer) { NFCHK(dalloc(&T->d_hist, (size_t)3 * o->max_outer + 8)); T->hist_cap = o->max_outer; }
-    double *hk = T->d_hist, *hdk = hk + T->hist_cap, *hdp = hdk + T->hist_cap;
+    NFCHK(hist_reserve(T, o->max_outer, false));
+    double *hk = T->d_hist, *hdk = hk + T->hist_cap, *hdp = hdk + T->hist_cap;   // the row length here is hist_cap
     OuterState h; memset(&h, 0, sizeof h);
-    h.keff = keff0; h.tol_keff = o->tol_keff; h.tol_flux = o->tol_flux; h.max_outer = o->max_outer;
-    h.ca1 = ca[1];
-    for (int i = 2; i < 15; ++i) { h.a3[i] = (4. / sigma) * ca[i]; h.cb[i] = cbv[i]; }
+    h.keff = keff0; h.tol_keff = o->tol_keff; h.tol_flux = o->tol_flux; h.max_outer = o->max_outer; h.cheb = cheb;
     HIPCHK(hipMemcpyAsync(T->d_ost, &h, sizeof h, hipMemcpyHostToDevice, st));
     const int gN = grid_for(NP);
     const long stride = T->partial_stride;
@@ -3071,15 +3099,7 @@ static int solve_keff_diag_device(nf_team *T, const nf_keff_opts *o, double keff
         if (hs.done || hs.done_next) break;
     }
     HIPCHK(hipGetLastError());
-    const int n = hs.it;
-    T->hist_k.resize(n); T->hist_dk.resize(n); T->hist_dphi.resize(n); T->hist_cg.assign((size_t)n * ng, 0);
-    if (n > 0) {
-        HIPCHK(hipMemcpy(T->hist_k.data(), hk, n * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(T->hist_dk.data(), hdk, n * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(T->hist_dphi.data(), hdp, n * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    T->last_outer = n; T->last_cg_total = 0;
-    if (hs.done == 2) return fail(NF_ERR_NUMERIC, "power iteration diverged (outer %d: k=%g dphi=%g)", n - 1, T->hist_k[n - 1], T->hist_dphi[n - 1]);
+    NFCHK(hist_fetch(T, hs.it, (size_t)T->hist_cap, false, 0, hs.done));
     *keff_out = hs.keff;
     return NF_OK;
 }
@@ -3120,8 +3140,7 @@ static bool resident_serial_fits(const nf_team *T, const nf_solver *S)
     return NPp <= 5120 && n_modes(S) <= 9 && S->nloc <= 27 && 64 + 16 + 176 + (1 + S->dim) * NPp + 2L * S->dim * PC + 3 * lines <= cap;
 }
 static const int NF_RESIDENT_UNAVAILABLE = 1;                     // positive: not an error code of the C ABI
-static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, const double *ca, const double *cbv, double sigma,
-                               double cg_tol, int cg_max, double *keff_out)
+static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, const ChebTable &cheb, double cg_tol, int cg_max, double *keff_out)
 {
     nf_solver *S = T->slabs[0];
     const int ng = S->ng; hipStream_t st = T->stream;
@@ -3137,14 +3156,11 @@ static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, 
     A.Mf = S->d_Mf; A.Chi = S->d_Chi; A.Ms = S->d_Ms_tab;
     A.phi = S->d_phi; A.raw = S->d_raw; A.p0 = S->d_p0; A.p1 = S->d_p1; A.tf = S->d_tf; A.r = S->d_r; A.p = S->d_p; A.q = S->d_q;
     A.keff0 = keff0; A.tol_keff = o->tol_keff; A.tol_flux = o->tol_flux; A.cg_tol = cg_tol; A.cg_max = cg_max; A.max_outer = o->max_outer;
-    A.ca1 = ca[1];
-    for (int i = 2; i < 15; ++i) { A.a3[i] = (4. / sigma) * ca[i]; A.cb[i] = cbv[i]; }
-    if (T->hist_cap < o->max_outer) { NFCHK(dalloc(&T->d_hist, (size_t)3 * o->max_outer + 8)); T->hist_cap = o->max_outer; }
+    A.cheb = cheb;
+    NFCHK(hist_reserve(T, o->max_outer, true));
 #ifdef NF_STAMPS
     (void)hipMemsetAsync(T->d_hist + 3 * (size_t)o->max_outer, 0, 8 * sizeof(double), st);
 #endif
-    if (T->hist_cg_cap < o->max_outer * ng) { NFCHK(dalloc(&T->d_hist_cg, (size_t)o->max_outer * ng)); T->hist_cg_cap = o->max_outer * ng; }
-    if (!T->d_rout) NFCHK(dalloc(&T->d_rout, 1));
     A.hist = T->d_hist; A.hist_cg = T->d_hist_cg; A.out = T->d_rout;
     // the kernel indexes its history with max_outer as the row length
     const int B = 512;
@@ -3233,17 +3249,7 @@ static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, 
     ResidentOut ro;
     HIPCHK(hipMemcpyAsync(&ro, T->d_rout, sizeof ro, hipMemcpyDeviceToHost, st));
     HIPCHK(stream_wait(st));
-    const int n = ro.n_outer;
-    T->hist_k.resize(n); T->hist_dk.resize(n); T->hist_dphi.resize(n); T->hist_cg.resize((size_t)n * ng);
-    if (n > 0) {
-        HIPCHK(hipMemcpy(T->hist_k.data(), T->d_hist, n * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(T->hist_dk.data(), T->d_hist + o->max_outer, n * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(T->hist_dphi.data(), T->d_hist + 2 * (size_t)o->max_outer, n * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(T->hist_cg.data(), T->d_hist_cg, (size_t)n * ng * sizeof(int), hipMemcpyDeviceToHost));
-        for (int g = 0; g < ng; ++g) T->last_its[g] = T->hist_cg[(size_t)(n - 1) * ng + g];
-    }
-    T->last_outer = n; T->last_cg_total = ro.cg_total;
-    if (ro.status == 2) return fail(NF_ERR_NUMERIC, "power iteration diverged (outer %d: k=%g dphi=%g)", n - 1, T->hist_k[n - 1], T->hist_dphi[n - 1]);
+    NFCHK(hist_fetch(T, ro.n_outer, (size_t)o->max_outer, true, ro.cg_total, ro.status));
 #ifdef NF_STAMPS
     { long long acc[5]; (void)hipMemcpy(acc, T->d_hist + 3 * (size_t)o->max_outer, sizeof acc, hipMemcpyDeviceToHost);
       if (acc[4] > 0) fprintf(stderr, "[resident stamps] %lld CG iterations: x pass %.0f, y/z passes %.0f, p.q reduction %.0f, r update + |r|^2 reduction %.0f cycles per iteration\n",
@@ -3255,8 +3261,8 @@ static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, 
 
 // ---- whole SolveKeff on one XCD (k_keff_xcd): the meshes of k_cg_xcd, iterative full-Schur path ------------------------
 // returns NF_RESIDENT_UNAVAILABLE when the workgroups did not assemble (nothing has been touched: the host-driven path takes over)
-static int solve_keff_xcd(nf_team *T, const nf_keff_opts *o, const Fuse3Plan &P, double keff0, const double *ca, const double *cbv, double sigma,
-                          double cg_tol, int cg_max, double *keff_out)
+static int solve_keff_xcd(nf_team *T, const nf_keff_opts *o, const Fuse3Plan &P, double keff0, const ChebTable &cheb, double cg_tol, int cg_max,
+                          double *keff_out)
 {
     nf_solver *S = T->slabs[0];
     const int ng = S->ng; hipStream_t st = T->stream;
@@ -3271,11 +3277,8 @@ static int solve_keff_xcd(nf_team *T, const nf_keff_opts *o, const Fuse3Plan &P,
     O.phi = S->d_phi; O.raw = S->d_raw; O.p0 = S->d_p0; O.p1 = S->d_p1; O.tf = S->d_tf;
     for (int d = 0; d < 3; ++d) O.nl[d] = S->nlines[d < S->dim ? d : 0];
     O.keff0 = keff0; O.tol_keff = o->tol_keff; O.tol_flux = o->tol_flux; O.cg_tol = cg_tol; O.cg_max = cg_max; O.max_outer = o->max_outer;
-    O.ca1 = ca[1];
-    for (int i = 2; i < 15; ++i) { O.a3[i] = (4. / sigma) * ca[i]; O.cb[i] = cbv[i]; }
-    if (T->hist_cap < o->max_outer) { NFCHK(dalloc(&T->d_hist, (size_t)3 * o->max_outer + 8)); T->hist_cap = o->max_outer; }
-    if (T->hist_cg_cap < o->max_outer * ng) { NFCHK(dalloc(&T->d_hist_cg, (size_t)o->max_outer * ng)); T->hist_cg_cap = o->max_outer * ng; }
-    if (!T->d_rout) NFCHK(dalloc(&T->d_rout, 1));
+    O.cheb = cheb;
+    NFCHK(hist_reserve(T, o->max_outer, true));
     O.hist = T->d_hist; O.hist_cg = T->d_hist_cg; O.out = T->d_rout;
     const size_t lds = XCD_LDS; const unsigned G = 8u * (unsigned)T->opt.cg_xcd_groups;
     NFCHK(xcd_select("k_keff_xcd", S, P, nch, [&](auto t) -> int { using I = decltype(t);
@@ -3289,17 +3292,8 @@ static int solve_keff_xcd(nf_team *T, const nf_keff_opts *o, const Fuse3Plan &P,
     HIPCHK(stream_wait(st));
     if (ro.status == 3) { T->opt.keff_xcd = 0; T->opt.cg_xcd = 0; ++T->xcd_refused; return NF_RESIDENT_UNAVAILABLE; }
     if (ro.status == 4) { T->opt.keff_xcd = 0; T->opt.cg_xcd = 0; return fail(NF_ERR_HIP, "XCD-local SolveKeff (k_keff_xcd): a grid barrier timed out in outer iteration %d (a participant was lost); the path is now off for this solver", ro.n_outer); }
-    const int n = ro.n_outer;
-    T->hist_k.resize(n); T->hist_dk.resize(n); T->hist_dphi.resize(n); T->hist_cg.resize((size_t)n * ng);
-    if (n > 0) {
-        HIPCHK(hipMemcpy(T->hist_k.data(), T->d_hist, n * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(T->hist_dk.data(), T->d_hist + o->max_outer, n * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(T->hist_dphi.data(), T->d_hist + 2 * (size_t)o->max_outer, n * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(T->hist_cg.data(), T->d_hist_cg, (size_t)n * ng * sizeof(int), hipMemcpyDeviceToHost));
-        for (int g = 0; g < ng; ++g) T->last_its[g] = T->hist_cg[(size_t)(n - 1) * ng + g];
-    }
-    T->last_outer = n; T->last_cg_total = ro.cg_total; T->xcd_solves += (long)n * ng; T->last_xcd = 1;
-    if (ro.status == 2) return fail(NF_ERR_NUMERIC, "power iteration diverged (outer %d: k=%g dphi=%g)", n - 1, n > 0 ? T->hist_k[n - 1] : 0.0, n > 0 ? T->hist_dphi[n - 1] : 0.0);
+    T->xcd_solves += (long)ro.n_outer * ng; T->last_xcd = 1;
+    NFCHK(hist_fetch(T, ro.n_outer, (size_t)o->max_outer, true, ro.cg_total, ro.status));
     *keff_out = ro.keff;
     return NF_OK;
 }
@@ -3431,23 +3425,25 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
     Inner in;
     NFCHK(inner_begin(T, o, DIAG_OK, &in, cmfd_and_coarse_start));
     const InnerPlan &ip = in.ip; const int use_diag = in.use_diag;
-    // ChebyshevAccel(15, 0.98), src/solvers.cpp:664-700
-    const int nmax = CHEB_NMAX; const double sigma = CHEB_SIGMA;
-    double ca[16], cbv[16];
-    cheb_tables(ca, cbv);
+    const ChebTable cheb = cheb_table();                          // ChebyshevAccel(15, 0.98), src/solvers.cpp:664-700
     int cheb_it = 0;
     T->hist_k.clear(); T->hist_dk.clear(); T->hist_dphi.clear(); T->hist_cg.clear();
     T->last_outer = 0; T->last_cg_total = 0;
     T->profile = o->profile != 0;
-    if (use_diag && single && !use_cmfd && !T->rccl_reduce && T->opt.outer_dev && o->max_outer > 0) {
-        NFCHK(solve_keff_diag_device(T, o, keff, ca, cbv, sigma, &keff));
-        HIPCHK(hipStreamSynchronize(T->stream));
-        T->profile = false; T->last_path = 1;
-        S0->raw_valid = T->last_outer > 0; S0->raw_is_diag = true;
+    // every exit of a finished solve (:1808-1809).  jz_valid is read by nf_get_J on slabs with an interface only, which the exits of the
+    // undivided paths never see (team_is_single): clearing it there too changes nothing
+    auto finish = [&](bool is_diag) {
+        for (auto *S : T->slabs) { S->raw_valid = T->last_outer > 0; S->raw_is_diag = is_diag; S->jz_valid = false; }
         T->has_valid_keff = 1; T->last_keff = keff;
         if (keff_out) *keff_out = keff;
         if (n_outer) *n_outer = T->last_outer;
         return NF_OK;
+    };
+    if (use_diag && single && !use_cmfd && !T->rccl_reduce && T->opt.outer_dev && o->max_outer > 0) {
+        NFCHK(solve_keff_diag_device(T, o, keff, cheb, &keff));
+        HIPCHK(hipStreamSynchronize(T->stream));
+        T->profile = false; T->last_path = 1;
+        return finish(true);
     }
     T->last_path = 0;
     {
@@ -3456,15 +3452,8 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
             ((S0->nphi <= T->opt.resident_max_dofs && resident_plan(S0, &probe)) || (S0->nphi <= T->opt.resident_serial_max_dofs && resident_serial_fits(T, S0)))) {
             const bool prof_req = T->profile;
             T->last_path = 2; T->profile = false;
-            const int rr = solve_keff_resident(T, o, keff, ca, cbv, sigma, ip.cg_tol, ip.cg_max, &keff);
-            if (rr != NF_RESIDENT_UNAVAILABLE) {
-                NFCHK(rr);
-                S0->raw_valid = T->last_outer > 0; S0->raw_is_diag = false; S0->jz_valid = false;
-                T->has_valid_keff = 1; T->last_keff = keff;
-                if (keff_out) *keff_out = keff;
-                if (n_outer) *n_outer = T->last_outer;
-                return NF_OK;
-            }
+            const int rr = solve_keff_resident(T, o, keff, cheb, ip.cg_tol, ip.cg_max, &keff);
+            if (rr != NF_RESIDENT_UNAVAILABLE) { NFCHK(rr); return finish(false); }
             T->last_path = 0; T->profile = prof_req;              // the device refused the LDS the resident kernel plans with: host-driven path
         }
     }
@@ -3473,15 +3462,8 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
     const CgPlan cp = cg_plan(T);
     if (!use_diag && !use_cmfd && !ip.direct && o->max_outer > 0 && T->opt.keff_xcd && cp.form == CG_XCD) {
         T->last_path = 3;
-        const int rx = solve_keff_xcd(T, o, cp.f3, keff, ca, cbv, sigma, ip.cg_tol, ip.cg_max, &keff);
-        if (rx != NF_RESIDENT_UNAVAILABLE) {
-            NFCHK(rx);
-            S0->raw_valid = T->last_outer > 0; S0->raw_is_diag = false; S0->jz_valid = false;
-            T->has_valid_keff = 1; T->last_keff = keff;
-            if (keff_out) *keff_out = keff;
-            if (n_outer) *n_outer = T->last_outer;
-            return NF_OK;
-        }
+        const int rx = solve_keff_xcd(T, o, cp.f3, keff, cheb, ip.cg_tol, ip.cg_max, &keff);
+        if (rx != NF_RESIDENT_UNAVAILABLE) { NFCHK(rx); return finish(false); }
         T->last_path = 0;
     }
     double hout[5] = { 0, 0, 0, 0, 0 };
@@ -3520,35 +3502,18 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
             if (T->poisoned) return team_poison_result(T);
             return fail(NF_ERR_REMOTE, "another rank of the team reported an error during outer iteration %d; every rank stopped there", it);
         }
-        const double prod_old = hout[0], prod_new = hout[1], nsq = hout[2], dsq = hout[3];
-        const double keff_new = keff * (prod_new / prod_old);
-        const double dk = std::fabs(keff_new - keff);
-        if (it >= 1) keff = keff_new;                             // :1774
-        const double dphi = std::sqrt(dsq / nsq), norm = std::sqrt(nsq);
-        if (!std::isfinite(keff_new) || !std::isfinite(dphi))
-            return fail(NF_ERR_NUMERIC, "power iteration diverged (outer %d: k=%g dphi=%g)", it, keff_new, dphi);
+        const OuterStep os = outer_step(keff, it, hout[0], hout[1], hout[2], hout[3]);
+        keff = os.keff;
+        if (!os.finite) return fail(NF_ERR_NUMERIC, "power iteration diverged (outer %d: k=%g dphi=%g)", it, os.keff_new, os.dphi);
         // normalise + Chebyshev (:1780-1788, src/solvers.cpp:720-756)
-        int mode = 0; double a = 0.0, b = 0.0;
-        if (it >= 2 && !use_cmfd) {                               // :1786-1788
-            if (cheb_it == nmax) cheb_it = 0;
-            if (cheb_it == 0) { mode = 1; }
-            else if (cheb_it == 1) { mode = 2; a = ca[1]; }
-            else { mode = 3; a = (4. / sigma) * ca[cheb_it]; b = cbv[cheb_it]; }
-        }
-        for (int i = 0; i < ns; ++i) {
-            nf_solver *S = T->slabs[i]; const long NT = S->nphi * ng;
-            if (mode && !S->d_p0) { NF_OUTER_CHK(dalloc(&S->d_p0, (size_t)NT)); if (!T->poisoned) NF_OUTER_CHK(dalloc(&S->d_p1, (size_t)NT)); }
-            if (T->poisoned) break;
-            hipLaunchKernelGGL(k_normalize_cheb, dim3(gT[i]), dim3(256), 0, T->stream, S->d_raw, S->d_phi, S->d_p0, S->d_p1, NT, norm,
-                               norm > 1e-14 ? 1 : 0, mode, a, b);
-            if (mode == 3) std::swap(S->d_p0, S->d_p1);
-        }
-        if (it >= 2 && !use_cmfd) ++cheb_it;
-        T->hist_k.push_back(keff); T->hist_dk.push_back(dk); T->hist_dphi.push_back(dphi);
+        const ChebStep cs = cheb_next(cheb_it, cheb, it >= 2 && !use_cmfd);       // :1786-1788
+        for (int i = 0; i < ns && !T->poisoned; ++i)              // a failed allocation poisons a rank of a team
+            NF_OUTER_CHK(normalize_cheb(T->slabs[i], T->stream, T->slabs[i]->d_phi, os.norm, os.do_norm, cs));
+        T->hist_k.push_back(keff); T->hist_dk.push_back(os.dk); T->hist_dphi.push_back(os.dphi);
         T->last_outer = it + 1;
         __atomic_store_n(&T->outers_done, (long)(it + 1), __ATOMIC_RELEASE);
-        if (T->progress_fn) T->progress_fn(T->progress_user, it, keff, dk, dphi);
-        if (dk < o->tol_keff && dphi < o->tol_flux && !T->poisoned) break;        // :1799-1802 (a poisoned rank stays in the schedule until the flag has gone round)
+        if (T->progress_fn) T->progress_fn(T->progress_user, it, keff, os.dk, os.dphi);
+        if (outer_converged(os.dk, os.dphi, o->tol_keff, o->tol_flux) && !T->poisoned) break;   // :1799-1802 (a poisoned rank stays in the schedule until the flag has gone round)
     }
 #undef NF_OUTER_CHK
     if (T->poisoned) {                                            // poisoned in the last outer the loop ran: one more reduction takes the flag to everybody
@@ -3560,11 +3525,7 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
     HIPCHK(hipGetLastError());
     if (T->profile) prof_collect(T);
     T->profile = false;
-    for (auto *S : T->slabs) { S->raw_valid = T->last_outer > 0; S->raw_is_diag = use_diag != 0; S->jz_valid = false; }
-    T->has_valid_keff = 1; T->last_keff = keff;                   // :1808-1809
-    if (keff_out) *keff_out = keff;
-    if (n_outer) *n_outer = T->last_outer;
-    return NF_OK;
+    return finish(use_diag != 0);
 }
 
 int nf_solve_keff(nf_handle S, const nf_keff_opts *o, double *keff, int *n_outer)
@@ -4214,9 +4175,7 @@ int nf_solve_adjoint(nf_handle S, const nf_keff_opts *o, int normalize_to_direct
         NFCHK(dalloc(&nsft[i].p, (size_t)X->N));
         hipLaunchKernelGGL(k_sum_groups, dim3(grid_for(X->N)), dim3(256), 0, st, X->d_NSF, nsft[i].p, X->N, ng);    // :1898-1905
     }
-    const int nmax = CHEB_NMAX; const double sigma = CHEB_SIGMA;
-    double ca[16], cbv[16];
-    cheb_tables(ca, cbv);
+    const ChebTable cheb = cheb_table();
     int cheb_it = 0;
     T->hist_k.clear(); T->hist_dk.clear(); T->hist_dphi.clear(); T->hist_cg.clear();
     T->last_outer = 0; T->last_cg_total = 0;
@@ -4253,6 +4212,7 @@ int nf_solve_adjoint(nf_handle S, const nf_keff_opts *o, int normalize_to_direct
         }
         hout[0] = h5[0]; hout[1] = h5[1];
         const double prod_old = hout[0], prod_new = hout[1], nsq = h5[3], dsq = h5[4];
+        // not outer_step: the reference's adjoint guards the quotient (|prod_old| > 1e-14, from outer 1), takes sqrt(dsq) / sqrt(nsq), and freezes k
         double keff_new = keff, dk;
         if (!use_direct_keff || !T->has_valid_keff) {                          // :1966-1975
             if (std::fabs(prod_old) > 1e-14 && it > 0) keff_new = keff * (prod_new / prod_old);
@@ -4260,18 +4220,8 @@ int nf_solve_adjoint(nf_handle S, const nf_keff_opts *o, int normalize_to_direct
         } else dk = 0.0;
         const double dphi = std::sqrt(dsq) / std::sqrt(nsq), norm = std::sqrt(nsq);
         if (!std::isfinite(keff) || !std::isfinite(dphi)) { rc = fail(NF_ERR_NUMERIC, "adjoint iteration diverged (outer %d: k=%g dphi=%g)", it, keff, dphi); break; }
-        int mode = 0; double a = 0.0, b = 0.0;
-        if (!use_direct_keff && it >= 5) {                                     // :1990-1992
-            if (cheb_it == nmax) cheb_it = 0;
-            if (cheb_it == 0) mode = 1; else if (cheb_it == 1) { mode = 2; a = ca[1]; } else { mode = 3; a = (4. / sigma) * ca[cheb_it]; b = cbv[cheb_it]; }
-            ++cheb_it;
-        }
-        for (int i = 0; i < ns && rc == NF_OK; ++i) {
-            nf_solver *X = T->slabs[i]; const long NT = X->nphi * ng;
-            if (mode && !X->d_p0) { if ((rc = dalloc(&X->d_p0, (size_t)NT)) != NF_OK || (rc = dalloc(&X->d_p1, (size_t)NT)) != NF_OK) break; }
-            hipLaunchKernelGGL(k_normalize_cheb, dim3(gT[i]), dim3(256), 0, st, X->d_raw, X->d_phi_adj, X->d_p0, X->d_p1, NT, norm, norm > 1e-14 ? 1 : 0, mode, a, b);
-            if (mode == 3) std::swap(X->d_p0, X->d_p1);
-        }
+        const ChebStep cs = cheb_next(cheb_it, cheb, !use_direct_keff && it >= 5);   // :1990-1992
+        for (int i = 0; i < ns && rc == NF_OK; ++i) rc = normalize_cheb(T->slabs[i], st, T->slabs[i]->d_phi_adj, norm, norm > 1e-14, cs);
         if (rc != NF_OK) break;
         T->hist_k.push_back(keff); T->hist_dk.push_back(dk); T->hist_dphi.push_back(dphi);
         T->last_outer = it + 1;

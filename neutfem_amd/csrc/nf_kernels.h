@@ -13,6 +13,7 @@
 //     scalars of CG (alpha, beta, stop test) never leave the device inside a solve.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "nf_outer.h"
 
 // in-kernel cycle stamps: diagnostic builds only (-DNF_STAMPS, scratch library; never in the shipped one)
 #ifdef NF_STAMPS
@@ -2331,7 +2332,7 @@ struct XcdOuter {
     double *phi, *raw, *p0, *p1, *tf;
     long nl[3];
     double keff0, tol_keff, tol_flux, cg_tol; int cg_max, max_outer;
-    double ca1, a3[16], cb[16];
+    ChebTable cheb;
     double *hist; int *hist_cg; ResidentOut *out;                // status 3: the workgroups did not assemble (nothing touched), 4: a barrier timed out
 };
 template <int NCH, bool VEC, int NB = 0, int SEG = 8>
@@ -2396,36 +2397,18 @@ __global__ __launch_bounds__(XCD_THREADS) void k_keff_xcd(XcdArgs A, XcdOuter O)
         double v3[3] = { 0.0, 0.0, 0.0 };
         for (long i = g0; i < NT; i += gs) { const double v = __builtin_nontemporal_load(O.raw + i), d = v - __builtin_nontemporal_load(O.phi + i); v3[0] += O.Mf[i] * v; v3[1] += v * v; v3[2] += d * d; }
         if (!xcd_total<3>(v3, A.part, A.st, C, sred, &s_i[3])) { status = 4; break; }
-        const double prod_new = v3[0], nsq = v3[1], dsq = v3[2];
-        const double keff_new = keff * (prod_new / prod_old);
-        const double dk = fabs(keff_new - keff);
-        if (it >= 1) keff = keff_new;                               // :1774
-        const double dphi = sqrt(dsq / nsq), norm = sqrt(nsq);
-        if (tid == 0 && C.widx == 0) { O.hist[it] = keff; O.hist[O.max_outer + it] = dk; O.hist[2 * O.max_outer + it] = dphi; }
+        const OuterStep os = outer_step(keff, it, prod_old, v3[0], v3[1], v3[2]);
+        keff = os.keff;
+        if (tid == 0 && C.widx == 0) { O.hist[it] = keff; O.hist[O.max_outer + it] = os.dk; O.hist[2 * O.max_outer + it] = os.dphi; }
         n_outer = it + 1;
-        if (!isfinite(keff_new) || !isfinite(dphi)) { status = 2; break; }
+        if (!os.finite) { status = 2; break; }
         status = 0;
         // normalise + Chebyshev (:1780-1788, src/solvers.cpp:720-756)
-        int mode = 0; double ca = 0.0, cb = 0.0;
-        if (it >= 2) {
-            if (cheb_it == 15) cheb_it = 0;
-            if (cheb_it == 0) mode = 1;
-            else if (cheb_it == 1) { mode = 2; ca = O.ca1; }
-            else { mode = 3; ca = O.a3[cheb_it]; cb = O.cb[cheb_it]; }
-            ++cheb_it;
-        }
-        const bool do_norm = norm > 1e-14;
-        for (long i = g0; i < NT; i += gs) {
-            double v = __builtin_nontemporal_load(O.raw + i);
-            if (do_norm) v /= norm;
-            if (mode == 1) pa[i] = v;
-            else if (mode == 2) { const double a = pa[i]; v = a + ca * (v - a); pb[i] = v; }
-            else if (mode == 3) { const double a = pa[i], b = pb[i]; v = b + ca * (v - b) + cb * (b - a); pa[i] = v; }
-            O.phi[i] = v;
-        }
-        if (mode == 3) { double *t = pa; pa = pb; pb = t; }
+        const ChebStep cs = cheb_next(cheb_it, O.cheb, it >= 2);
+        for (long i = g0; i < NT; i += gs) O.phi[i] = cheb_update(__builtin_nontemporal_load(O.raw + i), os.do_norm, os.norm, cs, pa, pb, i);
+        if (cs.mode == 3) { double *t = pa; pa = pb; pb = t; }
         if (!xcd_barrier(A.st, (unsigned)C.P * ++C.nbar, &s_i[3])) { status = 4; break; }   // the new phi before the next fission source
-        if (dk < O.tol_keff && dphi < O.tol_flux) break;            // :1799-1802
+        if (outer_converged(os.dk, os.dphi, O.tol_keff, O.tol_flux)) break;   // :1799-1802
     }
     if (tid == 0 && C.widx == 0) { O.out->keff = keff; O.out->n_outer = n_outer; O.out->status = status; O.out->cg_total = cg_total; }
 }
@@ -2814,24 +2797,14 @@ __global__ __launch_bounds__(256) void k_kin_forms(const double *__restrict__ w,
             if (i < nfam) partials[(5 + i) * stride + blockIdx.x] = sc[i];
     }
 }
-// phi /= norm, then ChebyshevAccel::operator() (src/solvers.cpp:720-756).  mode 0: no acceleration,
-// 1: store phi0, 2: phi1 = phi0 + a1 (phi - phi0), 3: three-term.  cur <- result.
+// phi /= norm, then ChebyshevAccel::operator() (src/solvers.cpp:720-756) with the step of cheb_next.  cur <- result; after mode 3 the
+// caller swaps p0 / p1.
 __global__ __launch_bounds__(256) void k_normalize_cheb(const double *__restrict__ raw, double *__restrict__ cur,
                                                         double *__restrict__ p0, double *__restrict__ p1, long ntot,
                                                         double norm, int do_norm, int mode, double ca, double cb)
 {
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < ntot; i += gridDim.x * 256L) {
-        double v = raw[i];
-        if (do_norm) v /= norm;
-        if (mode == 1) p0[i] = v;
-        else if (mode == 2) { const double a = p0[i]; v = a + ca * (v - a); p1[i] = v; }
-        else if (mode == 3) {
-            const double a = p0[i], b = p1[i];
-            v = b + ca * (v - b) + cb * (b - a);
-            p0[i] = v;                       // caller swaps p0/p1: p0 <- old p1, p1 <- new
-        }
-        cur[i] = v;
-    }
+    const ChebStep cs = { mode, ca, cb };
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < ntot; i += gridDim.x * 256L) cur[i] = cheb_update(raw[i], do_norm, norm, cs, p0, p1, i);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2843,7 +2816,7 @@ __global__ __launch_bounds__(256) void k_normalize_cheb(const double *__restrict
 struct OuterState {
     double keff, norm, a, b;
     double tol_keff, tol_flux;
-    double ca1, a3[16], cb[16];     // Chebyshev coefficients: a_1, (4/sigma) a_n and b_n for n >= 2 (host-computed, same bits)
+    ChebTable cheb;
     int mode, do_norm, it, cheb_it, swap, swap_next, max_outer;
     int done;                       // 0 running, 1 finished (converged or max_outer), 2 diverged
     int done_next;                  // the current outer is the last one: its normalise kernel still runs (:1780-1802)
@@ -2892,31 +2865,19 @@ __global__ __launch_bounds__(256) void k_outer_logic(const double *__restrict__ 
         tot[q] = block_sum(s, sred);
     }
     if (threadIdx.x != 0) return;
-    const double prod_old = tot[0], prod_new = tot[1], nsq = tot[2], dsq = tot[3];
     const int it = st->it;
-    double keff = st->keff;
-    const double keff_new = keff * (prod_new / prod_old);
-    const double dk = fabs(keff_new - keff);
-    if (it >= 1) keff = keff_new;                               // :1774
-    const double dphi = sqrt(dsq / nsq), norm = sqrt(nsq);
-    st->keff = keff;
-    hist_k[it] = keff; hist_dk[it] = dk; hist_dphi[it] = dphi;
-    if (!isfinite(keff_new) || !isfinite(dphi)) { st->it = it + 1; st->done = 2; return; }
-    int mode = 0; double a = 0.0, b = 0.0;
+    const OuterStep os = outer_step(st->keff, it, tot[0], tot[1], tot[2], tot[3]);
+    st->keff = os.keff;
+    hist_k[it] = os.keff; hist_dk[it] = os.dk; hist_dphi[it] = os.dphi;
+    if (!os.finite) { st->it = it + 1; st->done = 2; return; }
     int cheb_it = st->cheb_it;
-    if (it >= 2) {                                              // src/solvers.cpp:720-756
-        if (cheb_it == 15) cheb_it = 0;
-        if (cheb_it == 0) mode = 1;
-        else if (cheb_it == 1) { mode = 2; a = st->ca1; }
-        else { mode = 3; a = st->a3[cheb_it]; b = st->cb[cheb_it]; }
-        ++cheb_it;
-    }
+    const ChebStep cs = cheb_next(cheb_it, st->cheb, it >= 2);  // src/solvers.cpp:720-756
     st->cheb_it = cheb_it;
     st->swap = st->swap_next;                                   // orientation of (p0, p1) for this outer's normalise kernel
-    st->swap_next = st->swap ^ (mode == 3 ? 1 : 0);
-    st->mode = mode; st->a = a; st->b = b; st->norm = norm; st->do_norm = norm > 1e-14 ? 1 : 0;
+    st->swap_next = st->swap ^ (cs.mode == 3 ? 1 : 0);
+    st->mode = cs.mode; st->a = cs.a; st->b = cs.b; st->norm = os.norm; st->do_norm = os.do_norm ? 1 : 0;
     st->it = it + 1;
-    if ((dk < st->tol_keff && dphi < st->tol_flux) || it + 1 >= st->max_outer) st->done_next = 1;   // :1799-1802
+    if (outer_converged(os.dk, os.dphi, st->tol_keff, st->tol_flux) || it + 1 >= st->max_outer) st->done_next = 1;   // :1799-1802
 }
 // phi_g = Chebyshev(raw_g / norm) for every group of a cell, and the next outer's total_fiss + prod_old partials (:1700-1707)
 __global__ __launch_bounds__(256) void k_normalize_fission(const double *__restrict__ raw, double *__restrict__ cur,
@@ -2927,19 +2888,16 @@ __global__ __launch_bounds__(256) void k_normalize_fission(const double *__restr
 {
     __shared__ double sred[4];
     if (st->done) return;
-    const double norm = st->norm, ca = st->a, cb = st->b;
-    const int do_norm = st->do_norm, mode = st->mode;
+    const double norm = st->norm;
+    const int do_norm = st->do_norm;
+    const ChebStep cs = { st->mode, st->a, st->b };
     double *pa = st->swap ? p1 : p0, *pb = st->swap ? p0 : p1;
     double s = 0.0;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) {
         double t = 0.0;
         for (int g = 0; g < ng; ++g) {
             const long j = g * n + i;
-            double v = raw[j];
-            if (do_norm) v /= norm;
-            if (mode == 1) pa[j] = v;
-            else if (mode == 2) { const double a = pa[j]; v = a + ca * (v - a); pb[j] = v; }
-            else if (mode == 3) { const double a = pa[j], b = pb[j]; v = b + ca * (v - b) + cb * (b - a); pa[j] = v; }
+            const double v = cheb_update(raw[j], do_norm, norm, cs, pa, pb, j);
             cur[j] = v;
             t += Mf[j] * v;
         }
@@ -2966,7 +2924,7 @@ struct ResidentArgs {
     int lpl_log2, ntask_x;
     int n[2], TX[2], NSEG[2], gx[2], gy[2]; long sl[2], ostride[2];
     double keff0, tol_keff, tol_flux, cg_tol; int cg_max, max_outer;
-    double ca1, a3[16], cb[16];
+    ChebTable cheb;
     double *hist; int *hist_cg; ResidentOut *out;
     // LDS residency (host plan, greedy by priority): bit 0 p, 1 q, 2 r, 3 x_sol, 4+2d L[d], 5+2d DR[d], 10 C diagonal.  One CU
     // moves ~10 B/cycle to and from L2 but 128 B/cycle to and from LDS, and a barrier no longer waits for global store acks.
@@ -3702,34 +3660,17 @@ __global__ __launch_bounds__(512) void k_resident_keff(ResidentArgs A)
         double sp = 0.0, sn = 0.0, sd = 0.0;
         for (long i = tid; i < NT; i += nt) { const double v = A.raw[i], d = v - A.phi[i]; sp += A.Mf[i] * v; sn += v * v; sd += d * d; }
         const double prod_new = block_total(sp, sred), nsq = block_total(sn, sred), dsq = block_total(sd, sred);
-        const double keff_new = keff * (prod_new / prod_old);
-        const double dk = fabs(keff_new - keff);
-        if (it >= 1) keff = keff_new;                               // :1774
-        const double dphi = sqrt(dsq / nsq), norm = sqrt(nsq);
-        if (tid == 0) { A.hist[it] = keff; A.hist[A.max_outer + it] = dk; A.hist[2 * A.max_outer + it] = dphi; }
+        const OuterStep os = outer_step(keff, it, prod_old, prod_new, nsq, dsq);
+        keff = os.keff;
+        if (tid == 0) { A.hist[it] = keff; A.hist[A.max_outer + it] = os.dk; A.hist[2 * A.max_outer + it] = os.dphi; }
         n_outer = it + 1;
-        if (!isfinite(keff_new) || !isfinite(dphi)) { status = 2; break; }
+        if (!os.finite) { status = 2; break; }
         // normalise + Chebyshev (:1780-1788, src/solvers.cpp:720-756)
-        int mode = 0; double ca = 0.0, cb = 0.0;
-        if (it >= 2) {
-            if (cheb_it == 15) cheb_it = 0;
-            if (cheb_it == 0) mode = 1;
-            else if (cheb_it == 1) { mode = 2; ca = A.ca1; }
-            else { mode = 3; ca = A.a3[cheb_it]; cb = A.cb[cheb_it]; }
-            ++cheb_it;
-        }
-        const bool do_norm = norm > 1e-14;
-        for (long i = tid; i < NT; i += nt) {
-            double v = A.raw[i];
-            if (do_norm) v /= norm;
-            if (mode == 1) pa[i] = v;
-            else if (mode == 2) { const double a = pa[i]; v = a + ca * (v - a); pb[i] = v; }
-            else if (mode == 3) { const double a = pa[i], b = pb[i]; v = b + ca * (v - b) + cb * (b - a); pa[i] = v; }
-            A.phi[i] = v;
-        }
-        if (mode == 3) { double *t = pa; pa = pb; pb = t; }
+        const ChebStep cs = cheb_next(cheb_it, A.cheb, it >= 2);
+        for (long i = tid; i < NT; i += nt) A.phi[i] = cheb_update(A.raw[i], os.do_norm, os.norm, cs, pa, pb, i);
+        if (cs.mode == 3) { double *t = pa; pa = pb; pb = t; }
         __syncthreads();
-        if (dk < A.tol_keff && dphi < A.tol_flux) break;            // :1799-1802
+        if (outer_converged(os.dk, os.dphi, A.tol_keff, A.tol_flux)) break;   // :1799-1802
     }
     if (tid == 0) { A.out->keff = keff; A.out->n_outer = n_outer; A.out->status = status; A.out->cg_total = cg_total; }
 }
