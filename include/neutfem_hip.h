@@ -522,10 +522,11 @@ int nf_profile_reset(nf_handle h);
 /* the same counters, with the iteration counts of the last solve, as one JSON object */
 int nf_timers(nf_handle h, char *json_buf, size_t len);
 /* Read-only report of the launch plan: what the next Schur apply on this handle's mesh (or slab) would launch, as one JSON object
- * {"in_cg", "form", "slab", "fused", "lean", "single_reduce", "split_dot", "xy_overlap", "passes": [...]}.  in_cg = 0: a plain nf_schur_apply /
+ * {"in_cg", "form", "xsol_batch", "slab", "fused", "lean", "single_reduce", "split_dot", "xy_overlap", "passes": [...]}.  in_cg = 0: a plain nf_schur_apply /
  * nf_team_schur_apply; in_cg = 1: the apply inside an iteration of the launch-path CG.  "form": the form of the CG iteration the next
  * CG solve is planned to run (xcd, fuse3, lean, fused, classic, team_lean, team_vec, team_sr; "" for in_cg = 0), from the one function
- * the solve itself asks; "fused", "lean" and "single_reduce" follow from it.  The forms xcd and fuse3 launch no Schur pass of their own:
+ * the solve itself asks; "fused", "lean" and "single_reduce" follow from it.  "xsol_batch": the M that solve is planned to run with
+ * (option "xsol_batch"; 1 for in_cg = 0 and wherever the batched update does not apply).  The forms xcd and fuse3 launch no Schur pass of their own:
  * for them the passes are those of the launch path (lean) the solve falls back to.
  * One entry of "passes" per direction that exists; the z direction of a slab has two (mode 1 = endpoint pass, mode 2 = accumulation
  * pass).  Per entry: "dir" (x / y / z), "mode", "family" (x = k_schur_x, s = k_schur_s, c = k_schur_c, endpoint_w = k_endpoint_w),
@@ -623,6 +624,12 @@ int nf_time_device_copy(nf_handle h, size_t bytes, int reps, double *gbps);
  *   per-access predicates of the body are then true at compile time: straight-line loads and stores at 32-bit byte offsets.  Values and
  *   arithmetic are untouched: the results are bit-identical.  -1 and 1 = wherever eligible, 0 = the predicated bodies; a refused staged
  *   launch falls back to the predicated unstaged pass as before.  nf_apply_plan reports "full" per y / z pass;
+ *   "xsol_batch" (default -1): the fused form on an undivided RT0-P0 mesh (x lines of at most 1024 cells) updates x_sol in every M-th x pass
+ *   only: each new direction goes into the next slot of a ring of M buffers (M - 1 extra vectors of n_phi doubles per handle, allocated at
+ *   the first such solve, shared by all groups, dropped when the option is set; a refused allocation leaves the handle at M = 1), every M-th
+ *   pass applies the M deferred updates oldest first and the end of the solve applies what is pending.  Same fma chain per cell: the
+ *   results are bit-identical.  1 (or 0) = every pass, 2 .. 8 = that M wherever eligible, -1 = 4 beyond "cg_lean_max_cells" cells, else 1
+ *   (DESIGN.md 6f).  Other forms, slab teams and higher orders keep M = 1.  nf_apply_plan reports the M as "xsol_batch";
  *   "transient_rebalance" (default 1): nf_transient_step scales the iterate of every outer by the balance factor f; 0 = plain source
  *   iteration (same fixed point, a contraction of about 1 - beta per outer: for measurements);
  *   "kin_grid" (default 1024, at most 1024): blocks of 256 threads of the k_kin_forms pass of nf_kinetics_params / nf_transient_kinetics

@@ -16,6 +16,7 @@
 #include "nf_line_groups.h"
 #include "nf_options.h"
 #include "nf_small_eig.h"
+#include "nf_xsol_ring.h"
 
 #include <dlfcn.h>
 #include <unistd.h>
@@ -133,6 +134,7 @@ struct nf_team {
     bool rccl_reduce = false;       // scalar reductions go through ncclAllReduce (nproc > 1, or forced for testing)
     double *d_partials = nullptr; long partial_stride = 0, slab_cap = 0;
     CgScalars *d_cg = nullptr;
+    double *d_ah = nullptr;                   // alpha history of the scalar-backed CG forms (cg_logic): 8 doubles
     double *d_out = nullptr;        // 4 doubles read by the host each outer
     double *d_red = nullptr;        // 8 doubles: process-local sums awaiting the all-reduce, each followed by this rank's error flag
     // A rank that fails locally inside a solve must not leave the others waiting in the next collective:
@@ -229,6 +231,9 @@ struct nf_solver {
     double *d_phi = nullptr, *d_raw = nullptr;          // current iterate / raw group solutions, ng*N
     double *d_p0 = nullptr, *d_p1 = nullptr;            // Chebyshev history
     double *d_tf = nullptr, *d_rhs = nullptr, *d_r = nullptr, *d_p = nullptr, *d_q = nullptr;
+    // batched x_sol update of the fused CG (CgFuse, nf_xsol_ring.h): slots 1 .. ring_m-1 of the ring of directions (slot 0 is d_p), nphi doubles each,
+    // shared by all groups; ring_refused: the device had no room for them, this handle stays with one buffer
+    double *d_ring = nullptr; int ring_m = 0; bool ring_refused = false;
     double *d_p2 = nullptr, *d_qy = nullptr, *d_qz = nullptr;   // fused-direction CG (k_apply3): second buffer of the p pair, y / z outputs
     bool raw_valid = false, raw_is_diag = false;
     double *d_qsrc = nullptr;                           // external source as a load vector, ng * nphi (nf_upload_source, k_source_q)
@@ -388,6 +393,7 @@ static int team_alloc(nf_team *T)
     T->slab_cap = cap; T->partial_stride = cap * (long)T->slabs.size();
     NFCHK(dalloc(&T->d_partials, (size_t)T->partial_stride * 4));
     if (!T->d_cg) NFCHK(dalloc(&T->d_cg, 1));
+    if (!T->d_ah) { NFCHK(dalloc(&T->d_ah, 8)); HIPCHK(hipMemset(T->d_ah, 0, 8 * sizeof(double))); }
     if (!T->d_out) NFCHK(dalloc(&T->d_out, 8));
     if (!T->d_red) NFCHK(dalloc(&T->d_red, 8));
     if (!T->d_errsrc) { NFCHK(dalloc(&T->d_errsrc, 1)); HIPCHK(hipMemset(T->d_errsrc, 0, sizeof(double))); }
@@ -422,7 +428,7 @@ static void team_free(nf_team *T)
     if (T->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(T->comm);
     if (T->d_xcd) (void)hipFree(T->d_xcd);
     dfree(T->d_xpart);
-    dfree(T->d_partials); dfree(T->d_cg); dfree(T->d_out); dfree(T->d_red); dfree(T->d_errsrc); dfree(T->d_vec); dfree(T->d_ost); dfree(T->d_hist); dfree(T->d_hist_cg); dfree(T->d_rout);
+    dfree(T->d_partials); dfree(T->d_cg); dfree(T->d_ah); dfree(T->d_out); dfree(T->d_red); dfree(T->d_errsrc); dfree(T->d_vec); dfree(T->d_ost); dfree(T->d_hist); dfree(T->d_hist_cg); dfree(T->d_rout);
     if (T->h_pub) (void)hipHostFree(T->h_pub);
     if (T->comm_stream) { (void)hipStreamSynchronize(T->comm_stream); (void)hipStreamDestroy(T->comm_stream); }
     if (T->y_stream) { (void)hipStreamSynchronize(T->y_stream); (void)hipStreamDestroy(T->y_stream); }
@@ -578,7 +584,7 @@ int nf_destroy(nf_handle S)
     dfree(S->d_Wlo); dfree(S->d_Whi);
     dfree(S->d_Jz); dfree(S->d_Jzb); dfree(S->d_ctlo); dfree(S->d_cthi); dfree(S->d_elo); dfree(S->d_ehi); dfree(S->d_relo); dfree(S->d_rehi);
     dfree(S->d_phi); dfree(S->d_raw); dfree(S->d_p0); dfree(S->d_p1);
-    dfree(S->d_tf); dfree(S->d_rhs); dfree(S->d_r); dfree(S->d_p); dfree(S->d_q); dfree(S->d_p2); dfree(S->d_qy); dfree(S->d_qz);
+    dfree(S->d_tf); dfree(S->d_rhs); dfree(S->d_r); dfree(S->d_p); dfree(S->d_q); dfree(S->d_p2); dfree(S->d_qy); dfree(S->d_qz); dfree(S->d_ring);
     dfree(S->d_qsrc); dfree(S->d_modes[0]); dfree(S->d_modes[1]);
     dfree(S->d_gamma); dfree(S->d_gpt_w); dfree(S->d_gpt_sc);
     if (T) {
@@ -1025,14 +1031,23 @@ struct ApplyCg {                                        // per apply: cg_solve -
     CgLean lean = {};                                   // lean CG, undivided mesh: the x pass consumes the |r|^2 partials
     CgLean lean_z1 = {};                                // lean CG, slab teams: the endpoint pass of the z lines consumes the all-reduced |r|^2
     Cg1 cg1 = {};                                       // slab teams, single-reduction CG: the z passes take their SR instantiations
+    // batched x_sol update (undivided RT0-P0 mesh, CgPlan::xsol_batch > 1): the x pass's CgFuse with the ring slots of this iteration and which
+    // k_schur_x<..., XB> takes it; pnew = the slot the x pass writes, which the y / z passes read
+    bool ring = false; CgFuse ringfz = {}; int xb = XB_NOW; const double *pnew = nullptr;
 };
 struct PassCg {                                         // per launch: team_schur_apply / team_endpoint_phase -> launch_x / launch_s
     const CgScalars *cg = nullptr; CgFuse fuse = {}; CgLean lean = {}, lean_z1 = {}; Cg1 cg1 = {};   // of the apply, for this slab
     bool zw_dot = false;                                // the y / z passes emit T_a sum z_f w_f as their share of x.y (team_schur_apply, split)
     hipStream_t stream = nullptr;                       // another stream than the team's (x || y on small slabs)
     bool noacc = false; const double *yadd = nullptr;   // SlabArgs::noacc / yadd
+    int xb = XB_NOW;                                    // the x pass's template argument XB (ApplyCg::xb)
 };
-static PassCg pass_cg(const ApplyCg &A, const nf_solver *S, int i) { return { A.cg, A.fused ? CgFuse{ S->d_p, S->d_r, (*A.xsol)[i] } : CgFuse{}, A.lean, A.lean_z1, A.cg1 }; }   // slab i
+static PassCg pass_cg(const ApplyCg &A, const nf_solver *S, int i)   // slab i
+{
+    PassCg P = { A.cg, A.fused ? CgFuse{ S->d_p, S->d_r, (*A.xsol)[i] } : CgFuse{}, A.lean, A.lean_z1, A.cg1 };
+    if (A.ring) { P.fuse = A.ringfz; P.xb = A.xb; }
+    return P;
+}
 // launch shape of the one-chunk line kernel (k_schur_s); rc != NF_OK: the line length is refused
 struct SegPlan { int rc = NF_OK, SEG = 0, NSEG = 0, TX = 0, nparts = 0; dim3 grid, block; size_t lds = 0; };
 static SegPlan seg_plan(const nf_solver *S, int d, int zmode);
@@ -1168,13 +1183,13 @@ static int team_finalize(nf_team *T, int op, const std::vector<int> &counts, int
 {
     PartSegs ps = segs_for(T, counts);
     if (!T->rccl_reduce) {
-        hipLaunchKernelGGL(k_finalize, dim3(1), dim3(256), 0, T->stream, op, T->d_partials, ps, T->partial_stride, nq, T->d_cg, out, tol, maxit, 0, T->d_red, (const double *)nullptr);
+        hipLaunchKernelGGL(k_finalize, dim3(1), dim3(256), 0, T->stream, op, T->d_partials, ps, T->partial_stride, nq, T->d_cg, out, tol, maxit, 0, T->d_red, (const double *)nullptr, T->d_ah);
     } else {
         // the sums of this rank followed by its error flag: one all-reduce of nq + 1 doubles (CgScalars::err)
         hipLaunchKernelGGL(k_finalize, dim3(1), dim3(256), 0, T->stream, op, T->d_partials, ps, T->partial_stride, nq, T->d_cg, out, tol, maxit, 1, T->d_red, (const double *)T->d_errsrc);
         TRACE_COMM("rank %d allreduce finalize op=%d count=%d poisoned=%d", T->rank, op, nq + 1, (int)T->poisoned);
         NCCLCHK(g_rccl.AllReduce(T->d_red, T->d_red, (size_t)nq + 1, NCCL_DOUBLE, NCCL_SUM, T->comm, T->stream));
-        hipLaunchKernelGGL(k_cg_logic, dim3(1), dim3(1), 0, T->stream, op, T->d_red, nq, T->d_cg, out, tol, maxit, want_flag ? 2 : 1);
+        hipLaunchKernelGGL(k_cg_logic, dim3(1), dim3(1), 0, T->stream, op, T->d_red, nq, T->d_cg, out, tol, maxit, want_flag ? 2 : 1, T->d_ah);
     }
     return NF_OK;
 }
@@ -1299,10 +1314,12 @@ template <unsigned N, class F> static bool with_index(unsigned key, F &&f) { ret
 
 // The instantiations of k_schur_x<2, NCH, VEC, NB, NT, DICT>: up to 32 chunks per lane (16, 32: RT0-P0 only), streaming loads for RT0-P0 lines
 // of even length, the table next to the streaming loads only
-constexpr bool schur_x_legal(int NCH, bool VEC, int NB, bool NT, bool DICT)
+static const int X_BATCH_MAX_NCH = 8;                            // the batched x_sol update (XB_SKIP, XB_APPLY): x lines of up to 1024 cells
+constexpr bool schur_x_legal(int NCH, bool VEC, int NB, bool NT, bool DICT, int XB = XB_NOW)
 {
     return NCH >= 1 && NCH <= (NB == 0 ? 32 : 8) && (NCH & (NCH - 1)) == 0 && NB >= 0 && NB <= 2
-        && (!NT || (VEC && NB == 0)) && (!DICT || (NT && NCH <= X_DICT_MAX_NCH));
+        && (!NT || (VEC && NB == 0)) && (!DICT || (NT && NCH <= X_DICT_MAX_NCH))
+        && XB >= XB_NOW && XB <= XB_APPLY && (XB == XB_NOW || (NB == 0 && NCH <= X_BATCH_MAX_NCH));
 }
 // the x pass: launch shape, NCH = the instantiation's chunks per lane (0: the line is refused), and what else picks the instantiation
 struct XPlan { int lpl_log2 = 0, NCH = 0; unsigned grid = 0; bool vec = false, nt = false, xcd = false, dict = false; };
@@ -1332,16 +1349,16 @@ static int launch_x(const nf_solver *S, int g, const ModeArgs &ma0, const Geom &
     ModeArgs ma = ma0; if (da.on) ma.Cd[0] = da.C;
     const double *L = da.on ? da.L : S->d_L[0] + g * S->N, *DR = da.on ? da.DR : S->d_DR[0] + g * S->N, *D0 = S->d_D0[0] + g * S->nlines[0];
     int lg = 0; while ((1 << lg) < xp.NCH) ++lg;
-    const unsigned key = ((((unsigned)lg * 3 + (unsigned)S->nb) * 2 + xp.vec) * 2 + xp.nt) * 2 + xp.dict;
-    const bool hit = with_index<6 * 3 * 8>(key, [&](auto i) {
+    const unsigned key = (((((unsigned)P.xb * 6 + (unsigned)lg) * 3 + (unsigned)S->nb) * 2 + xp.vec) * 2 + xp.nt) * 2 + xp.dict;
+    const bool hit = with_index<3 * 6 * 3 * 8>(key, [&](auto i) {
         constexpr unsigned I = decltype(i)::value;
-        constexpr int NCH = 1 << (I / 24), NB = I / 8 % 3; constexpr bool VEC = I & 4, NT = I & 2, DICT = I & 1;
-        if constexpr (!schur_x_legal(NCH, VEC, NB, NT, DICT)) return false;
-        else hipLaunchKernelGGL((k_schur_x<2, NCH, VEC, NB, NT, DICT>), gr, dim3(256), 0, S->team->stream, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], xp.lpl_log2,
+        constexpr int XB = I / 144, NCH = 1 << (I / 24 % 6), NB = I / 8 % 3; constexpr bool VEC = I & 4, NT = I & 2, DICT = I & 1;
+        if constexpr (!schur_x_legal(NCH, VEC, NB, NT, DICT, XB)) return false;
+        else hipLaunchKernelGGL((k_schur_x<2, NCH, VEC, NB, NT, DICT, XB>), gr, dim3(256), 0, S->team->stream, ma, mt, G, L, DR, D0, S->nx, S->ny, S->nlines[0], xp.lpl_log2,
                                 first, last, partials, P.cg, fz, P.lean, da.ld);
         return true;
     });
-    return hit ? NF_OK : fail(NF_ERR_ARG, "k_schur_x: no instantiation for NCH = %d, NB = %d, vec %d, nt %d, dict %d", xp.NCH, S->nb, xp.vec, xp.nt, xp.dict);
+    return hit ? NF_OK : fail(NF_ERR_ARG, "k_schur_x: no instantiation for NCH = %d, NB = %d, vec %d, nt %d, dict %d, xb %d", xp.NCH, S->nb, xp.vec, xp.nt, xp.dict, P.xb);
 }
 
 // Does direction d (1 = y, 2 = z) of this mesh take the chunked long-line kernel (k_schur_c)?  Plain lines of RT0-P0 meshes beyond
@@ -1788,7 +1805,8 @@ static int team_schur_apply(nf_team *T, int g, const std::vector<const double *>
             if (xy_all && !S->d_qy) NFCHK(dalloc(&S->d_qy, S->nphi));
             {
                 double *part = (want_dot && (last || split)) ? T->d_partials + i * T->slab_cap + totals[i] : nullptr;
-                const ModeArgs ma = mode_args(S, g, d, 0, xs[i], ys[i]);     // mode 0; the kernels derive the others (ModeTab)
+                const double *xin = d > 0 && A.pnew ? A.pnew : xs[i];       // batched x_sol update: the x pass left the new direction in another slot
+                const ModeArgs ma = mode_args(S, g, d, 0, xin, ys[i]);      // mode 0; the kernels derive the others (ModeTab)
                 int np = 0;
                 PassCg P = pass_cg(A, S, i); P.zw_dot = split;
                 if (d == 0) NFCHK(launch_x(S, g, ma, G, last || split, part, P, &np));
@@ -1797,7 +1815,7 @@ static int team_schur_apply(nf_team *T, int g, const std::vector<const double *>
                     NFCHK(launch_s(S, 2, g, ma, G, last, part, P, &np, 2));
                 } else if (d == 1 && xy_all) {
                     P.stream = T->y_stream; P.noacc = true;
-                    NFCHK(launch_s(S, 1, g, mode_args(S, g, 1, 0, xs[i], S->d_qy), G, 0, nullptr, P, &np, 0));
+                    NFCHK(launch_s(S, 1, g, mode_args(S, g, 1, 0, xin, S->d_qy), G, 0, nullptr, P, &np, 0));
                 } else NFCHK(launch_s(S, d, g, ma, G, last || split, part, P, &np, 0));
                 if (part) totals[i] += np;
             }
@@ -2014,8 +2032,24 @@ struct CgPlan {
     CgForm form = CG_CLASSIC; Fuse3Plan f3; int gru = 0;         // f3: xcd, fuse3; gru: those and lean (blocks of k_cg_rupdate / k_cg_rupdate3)
     bool fused = false; int reductions = 0;                      // ApplyCg::fused (every form but classic); cross-rank reductions per iteration (nf_info "cg_reductions")
     bool lean() const { return form == CG_XCD || form == CG_FUSE3 || form == CG_LEAN; }   // ApplyCg::lean is set
+    int xsol_batch = 1;                                          // fused: x_sol is updated in every M-th x pass (nf_xsol_ring.h); 1 = in every pass
 };
+// What xsol_batch = -1 resolves to beyond cg_lean_max_cells.
+static const int XSOL_BATCH_AUTO = 4;
+static CgPlan cg_plan_form(const nf_team *T);
 static CgPlan cg_plan(const nf_team *T)
+{
+    CgPlan P = cg_plan_form(T); const nf_solver *S0 = T->slabs[0];
+    // the ring of directions: the fused form (scalars behind k_finalize: its alpha history) on an undivided RT0-P0 mesh whose x pass has the
+    // instantiations; a handle whose ring the device refused stays with one buffer
+    if (P.form != CG_FUSED || !team_is_single(T) || !x_fuses(S0) || S0->nb != 0 || S0->ring_refused) return P;
+    const int nch = x_plan(S0).NCH;
+    if (nch < 1 || nch > X_BATCH_MAX_NCH) return P;
+    const long o = T->opt.xsol_batch;
+    P.xsol_batch = o < 0 ? (S0->N > T->opt.cg_lean_max_cells ? XSOL_BATCH_AUTO : 1) : (int)std::min<long>(std::max<long>(o, 1), NF_XSOL_RING_MAX);
+    return P;
+}
+static CgPlan cg_plan_form(const nf_team *T)
 {
     CgPlan P; const nf_solver *S0 = T->slabs[0]; const bool single = team_is_single(T);
     P.fused = T->opt.cg_fuse != 0 && (single || S0->nloc == 1);
@@ -2088,9 +2122,9 @@ int nf_apply_plan(nf_handle S, int in_cg, char *json_buf, size_t len)
     const bool split = split_dot(T, cg, lean);
     bool any_if = false; for (auto *X : T->slabs) any_if |= X->if_lo || X->if_hi;
     const bool xy_all = xy_overlap(T, any_if, false);
-    char tmp[288];
-    snprintf(tmp, sizeof tmp, "{\"in_cg\": %d, \"form\": \"%s\", \"slab\": %d, \"fused\": %d, \"lean\": %d, \"single_reduce\": %d, \"split_dot\": %d, \"xy_overlap\": %d, \"passes\": [",
-             cg ? 1 : 0, cg ? CG_FORM_NAME[cp.form] : "", slab ? 1 : 0, fused ? 1 : 0, lean ? 1 : 0, sr ? 1 : 0, split ? 1 : 0, xy_all ? 1 : 0);
+    char tmp[320];
+    snprintf(tmp, sizeof tmp, "{\"in_cg\": %d, \"form\": \"%s\", \"xsol_batch\": %d, \"slab\": %d, \"fused\": %d, \"lean\": %d, \"single_reduce\": %d, \"split_dot\": %d, \"xy_overlap\": %d, \"passes\": [",
+             cg ? 1 : 0, cg ? CG_FORM_NAME[cp.form] : "", cg ? cp.xsol_batch : 1, slab ? 1 : 0, fused ? 1 : 0, lean ? 1 : 0, sr ? 1 : 0, split ? 1 : 0, xy_all ? 1 : 0);
     std::string js = tmp;
     for (int d = 0; d < S->dim; ++d) {
         const bool last = d == S->dim - 1, want_dot = cg && (last || split);
@@ -2126,6 +2160,8 @@ struct CgRun {
     std::vector<const double *> ps; std::vector<double *> qs;     // p and q = S p, per slab
     std::vector<int> gcnt, acnt, cnt3;                             // per slab: blocks of the vector kernels, p.q partials of the apply, |r|^2 partials of k_endpoint_w
     bool any_if = false;                                           // some local slab has an interface
+    int M = 1;                                                     // the plan's xsol_batch, or 1 where the ring could not be allocated
+    double *slot(int s) const { nf_solver *S = T->slabs[0]; return s == 0 ? S->d_p : S->d_ring + (size_t)(s - 1) * S->nphi; }   // of the ring of directions
     double *row1() const { return T->d_partials + T->partial_stride; }
     double *vec_rr() const { return T->d_vec + T->vec_stride; }
     // a failed call inside the iteration: NF_OK if the rank is poisoned and carries on with the schedule, the code if it must leave at once
@@ -2141,6 +2177,16 @@ static ApplyCg cg_apply_args(const CgRun &R, int index)
     if (R.form == CG_TEAM_SR) A.cg1 = Cg1{ T->d_red, T->d_cg, index };
     if (R.form == CG_TEAM_VEC) A.lean_z1 = CgLean{ T->d_cg, R.vec_rr(), T->vec_cnt_rr, index & 1, first, T->vec_cnt_rr };
     if (R.form == CG_TEAM_LEAN) A.lean_z1 = CgLean{ T->d_cg, T->d_red + 2, -1, index & 1, first };
+    if (R.M > 1) {                                                // the slots of iteration `index` (nf_xsol_ring.h)
+        const int rd = nf_ring_read(index, R.M), wr = nf_ring_write(index, R.M);
+        const NfRingBatch B = nf_ring_apply(index, R.M);
+        A.ring = true; A.xb = index == 0 ? XB_NOW : B.n ? XB_APPLY : XB_SKIP; A.pnew = R.slot(wr);
+        A.ringfz = CgFuse{ R.slot(rd), T->slabs[0]->d_r, R.x[0], wr == rd ? nullptr : R.slot(wr) };
+        if (B.n) {                                                // all but the last, which is the direction the pass reads
+            A.ringfz.nold = B.n - 1; A.ringfz.a0 = B.u[0].alpha; A.ringfz.ah = T->d_ah;
+            for (int i = 0; i + 1 < B.n; ++i) A.ringfz.old[i] = R.slot(B.u[i].slot);
+        }
+    }
     return A;
 }
 // fuse3: two launches.  p lives in a pair of buffers: iteration 0 reads A = d_p as k_cg_init left it; iteration i >= 1 reads the p of
@@ -2168,7 +2214,11 @@ static int cg_step_apply(CgRun &R, int index, long global_it)
     int ra = NF_OK;
     if (T->nproc > 1 && T->rank == T->inject_rank && global_it == T->inject_iter)
         { ra = fail(NF_ERR_HIP, "injected failure on rank %d at CG iteration %ld (NEUTFEM_INJECT_FAIL)", T->rank, global_it); TRACE_COMM("rank %d INJECT at %ld", T->rank, global_it); }
-    else if (!T->poisoned) ra = team_schur_apply(T, R.g, R.ps, R.qs, true, cg_apply_args(R, index), &R.acnt, &R.cnt3);
+    else if (!T->poisoned) {
+        const ApplyCg A = cg_apply_args(R, index);
+        if (A.ring) R.ps[0] = A.ringfz.p;                         // the x pass reads the direction of the iteration before from its slot
+        ra = team_schur_apply(T, R.g, R.ps, R.qs, true, A, &R.acnt, &R.cnt3);
+    }
     NFCHK(R.chk(ra));
     if (T->poisoned && R.any_if) {
         // the interface exchanges this apply still owes its neighbours: one per apply + one per separator sweep (team_endpoint_phase)
@@ -2271,6 +2321,14 @@ static int cg_solve(nf_team *T, int g, const std::vector<const double *> &rhs, c
         if (S0->dim >= 2 && !S0->d_qy) NFCHK(dalloc(&S0->d_qy, S0->nphi));
         if (S0->dim == 3 && !S0->d_qz) NFCHK(dalloc(&S0->d_qz, S0->nphi));
     }
+    if (P.xsol_batch > 1) {                                       // M - 1 more direction buffers; a refusal is not an error: this handle carries on with one
+        if (S0->ring_m != P.xsol_batch) {
+            dfree(S0->d_ring); S0->ring_m = 0;
+            if (hipMalloc((void **)&S0->d_ring, (size_t)(P.xsol_batch - 1) * S0->nphi * sizeof(double)) == hipSuccess) S0->ring_m = P.xsol_batch;
+            else { (void)hipGetLastError(); S0->d_ring = nullptr; S0->ring_refused = true; }
+        }
+        if (S0->ring_m == P.xsol_batch) R.M = P.xsol_batch;
+    }
     if (R.form == CG_XCD && !pub_ready(T)) R.form = CG_FUSE3;    // the kernel hands the final scalars to the host itself: no mapped page, no one-XCD solve
     if (R.form == CG_XCD) {                                       // the whole solve in one launch on one XCD (k_cg_xcd)
         const unsigned long long seq = ++T->pub_seq;
@@ -2311,11 +2369,17 @@ static int cg_solve(nf_team *T, int g, const std::vector<const double *> &rhs, c
         HIPCHK(hipMemcpyAsync(&sc, T->d_cg, sizeof sc, hipMemcpyDeviceToHost, T->stream));
         HIPCHK(hipStreamSynchronize(T->stream));
     }
-    if (P.fused)
+    if (P.fused && R.M > 1) {                                     // what the x passes of this solve left in the ring, from the final scalars
+        const NfRingBatch B = nf_ring_pending(sc.its, sc.pend, R.M);
+        FlushRing fr; memset(&fr, 0, sizeof fr); fr.n = B.n; fr.ah = T->d_ah;
+        for (int j = 0; j < B.n; ++j) { fr.alpha[j] = B.u[j].alpha; fr.p[j] = R.slot(B.u[j].slot); }
+        if (B.n > 0) hipLaunchKernelGGL(k_cg_flush, dim3(R.gcnt[0]), dim3(256), 0, T->stream, x[0], (const double *)nullptr, S0->nphi, T->d_cg, fr);
+    } else if (P.fused)
         for (int i = 0; i < ns; ++i) {
             const double *plast = T->slabs[i]->d_p;
             if (R.form == CG_FUSE3 && sc.its >= 2 && ((sc.its - 1) & 1)) plast = T->slabs[i]->d_p2;   // the direction of the last iteration (see cg_step_fuse3)
-            hipLaunchKernelGGL(k_cg_flush, dim3(R.gcnt[i]), dim3(256), 0, T->stream, x[i], plast, T->slabs[i]->nphi, T->d_cg);
+            FlushRing fr; memset(&fr, 0, sizeof fr); fr.n = -1;
+            hipLaunchKernelGGL(k_cg_flush, dim3(R.gcnt[i]), dim3(256), 0, T->stream, x[i], plast, T->slabs[i]->nphi, T->d_cg, fr);
         }
     HIPCHK(hipGetLastError());
     if (T->profile) prof_collect(T);
@@ -5298,6 +5362,7 @@ int nf_set_option(nf_handle S, const char *key, long value)
     if (!nf_options_set(own ? mine : T->opt, key, value, &fx, &err)) return fail(NF_ERR_ARG, "%s", err.c_str());
     if (own) S->opt_tr_rebalance = (int)mine.transient_rebalance;
     if ((fx & NF_FX_RELINK) || ((fx & NF_FX_RELINK_MULTI) && T->nproc > 1)) T->linked_ready = false;
+    if (!strcmp(key, "xsol_batch")) { HIPCHK(hipSetDevice(T->device)); for (auto *X : T->slabs) { dfree(X->d_ring); X->ring_m = 0; X->ring_refused = false; } }   // sized under it
     return team_apply_table_effects(T, fx);
 }
 int nf_get_option(nf_handle S, const char *key, long *value)

@@ -195,7 +195,10 @@ __device__ __forceinline__ int reduce_err(double total, double flag)       // er
 {
     return flag != 0.0 ? 2 : ((total - total) != 0.0 ? 1 : 0);            // x - x is 0 for every finite x, NaN for inf / NaN
 }
-__device__ __forceinline__ void cg_logic(int op, const double *tot, int nq, CgScalars *cg, double *out, double tol, int maxit, double flag = 0.0)
+// ah (scalar-backed forms, may be null): the alpha history -- alpha of iteration j at ah[j % 8], for the x passes and the flush that apply several
+// deferred x_sol updates at once (CgFuse::nold, nf_xsol_ring.h).  Eight doubles of their own, not part of CgScalars: the scalars travel whole
+// to the host and through the one-XCD kernels.
+__device__ __forceinline__ void cg_logic(int op, const double *tot, int nq, CgScalars *cg, double *out, double tol, int maxit, double flag = 0.0, double *ah = nullptr)
 {
     if (op == FIN_RHS) { cg->err = 0; }
     if (op != FIN_SUM) { const int e = reduce_err(tot[0], flag); if (e) { cg->err = e; cg->done = 1; if (op == FIN_RHS) { cg->rr = tot[0]; cg->its = 0; cg->pend = 0; } return; } }
@@ -211,7 +214,7 @@ __device__ __forceinline__ void cg_logic(int op, const double *tot, int nq, CgSc
         cg->pAp = tot[0];
         cg->pend = 0;                          // the x pass of this iteration has applied the deferred update
         if (fabs(tot[0]) < 1e-30) cg->done = 1;
-        else cg->alpha = cg->rr / tot[0];
+        else { cg->alpha = cg->rr / tot[0]; if (ah) ah[cg->its & 7] = cg->alpha; }
     } else if (op == FIN_RR) {                 // src/solvers.cpp:613-631
         cg->rr_new = tot[0];
         cg->its += 1;
@@ -230,7 +233,8 @@ __device__ __forceinline__ void cg_logic(int op, const double *tot, int nq, CgSc
 // reduce_only = 1: write the process-local sums to red[] (an all-reduce over ranks follows, then k_cg_logic)
 __global__ __launch_bounds__(256) void k_finalize(int op, const double *__restrict__ partials, PartSegs segs, long stride,
                                                   int nq, CgScalars *__restrict__ cg, double *__restrict__ out,
-                                                  double tol, int maxit, int reduce_only, double *__restrict__ red, const double *__restrict__ errsrc = nullptr)
+                                                  double tol, int maxit, int reduce_only, double *__restrict__ red, const double *__restrict__ errsrc = nullptr,
+                                                  double *__restrict__ ah = nullptr)
 {
     __shared__ double sred[4];
     if ((op == FIN_PAP || op == FIN_RR) && !reduce_only) { if (cg->done) return; }
@@ -247,15 +251,15 @@ __global__ __launch_bounds__(256) void k_finalize(int op, const double *__restri
     if (threadIdx.x != 0) return;
     // reduce_only: the sums go into an all-reduce over ranks, followed by this rank's error flag (errsrc, raised by the host)
     if (reduce_only) { for (int q = 0; q < nq; ++q) red[q] = tot[q]; if (errsrc) red[nq] = *errsrc; return; }
-    cg_logic(op, tot, nq, cg, out, tol, maxit);
+    cg_logic(op, tot, nq, cg, out, tol, maxit, 0.0, ah);
 }
 __global__ void k_cg_logic(int op, const double *__restrict__ red, int nq, CgScalars *__restrict__ cg, double *__restrict__ out,
-                           double tol, int maxit, int with_flag)
+                           double tol, int maxit, int with_flag, double *__restrict__ ah = nullptr)
 {
     if (op == FIN_PAP || op == FIN_RR) { if (cg->done) return; }
     double tot[4] = { 0, 0, 0, 0 };
     for (int q = 0; q < nq; ++q) tot[q] = red[q];
-    cg_logic(op, tot, nq, cg, out, tol, maxit, with_flag ? red[nq] : 0.0);   // red[nq]: the all-reduced error flags of the ranks
+    cg_logic(op, tot, nq, cg, out, tol, maxit, with_flag ? red[nq] : 0.0, ah);   // red[nq]: the all-reduced error flags of the ranks
     if (with_flag == 2) out[nq] = red[nq];                       // FIN_SUM of the outer iteration: the host reads the flags next to the sums
 }
 
@@ -768,7 +772,13 @@ __device__ __forceinline__ void sto(double *p, unsigned byte_off, double v) { *r
 // and z passes of one apply side by side, so the y / z blocks must still find the old p while the x blocks write the new
 // one: they read p and r and form r + beta p themselves (mode "read-only fuse"), and the x blocks write into the other
 // buffer of a pair.  Every site evaluates fma(beta, p, r) / fma(alpha, p, x_sol): same bits everywhere.
-struct CgFuse { double *p; const double *r; double *xsol; double *pout; };
+// Batched x_sol update (k_schur_x<..., XB>, RT0-P0; the slots and alpha entries come from nf_xsol_ring.h): x_sol is never read back by the
+// iteration, so with a ring of M direction buffers (p = the slot read, pout = the slot written) the x pass leaves it alone in M-1 of M
+// iterations (XB_SKIP: neither loaded nor stored) and every M-th pass (XB_APPLY) catches up: x_sol = fma(alpha_j, p_j, x_sol) for the
+// nold = M-1 older directions old[0] .. old[nold-1], oldest first, with alpha_j = ah[(a0 + j) & 7] (cg_logic's alpha history: launches are queued ahead
+// of the scalars), then today's fma(alpha, p, x_sol) with the direction the pass reads anyway.  The same chain per cell: the same bits.
+enum { XB_NOW = 0, XB_SKIP = 1, XB_APPLY = 2 };
+struct CgFuse { double *p; const double *r; double *xsol; double *pout; int nold; int a0; const double *ah; const double *old[7]; };
 
 // Tables of distinct lines.  A core built from a few assembly types and axial zones on a uniform mesh has only a handful of DIFFERENT lines per
 // direction (IAEA-3D at 256^3: 12 / 12 / 3 of 65 536), and lines with equal stored factors need those factors once: the streaming passes then
@@ -849,7 +859,7 @@ __global__ void k_line_gather(int d, int nx, int ny, int nz, const double *__res
 // per SIMD the crossbar version is faster (fused-direction launch at 128^3: 76.8 vs 82.9 us per CG iteration on the same box).
 // DICT (streaming instantiations of RT0-P0 meshes whose lines repeat, see LineDict): L, DR and ma.Cd[0] point at the table of distinct lines
 // and the line's row replaces its own cells -- plain loads (the table is meant to stay in L2), same shapes, bit-equal values.
-template <int K, int NCH, bool VEC, int NB, class Mid = NoMid, bool DPPS = false, bool NT = false, bool DICT = false>
+template <int K, int NCH, bool VEC, int NB, class Mid = NoMid, bool DPPS = false, bool NT = false, bool DICT = false, int XB = XB_NOW>
 __device__ __forceinline__ double schur_x_task(const ModeArgs &ma, const Geom &G, const double *__restrict__ L, const double *__restrict__ DR,
                                                const double *__restrict__ D0, int nx, int ny, long nlines, int lpl_log2, int first,
                                                long task, int lane, bool active, bool fuse, double f_alpha, double f_beta, const CgFuse &fz, Mid mid = Mid(),
@@ -857,6 +867,7 @@ __device__ __forceinline__ double schur_x_task(const ModeArgs &ma, const Geom &G
 {
     static_assert(K == 2, "two cells per lane and chunk");
     static_assert(!DICT || (NB == 0 && NT), "line tables: next to the streaming RT0-P0 instantiations only");
+    static_assert(XB == XB_NOW || NB == 0, "batched x_sol update: RT0-P0 only");
     const int LPL = 1 << lpl_log2, LPW = 64 >> lpl_log2;
     const int li = lane & (LPL - 1), sub = lane >> lpl_log2;
     const long line = task * LPW + sub;
@@ -884,12 +895,17 @@ __device__ __forceinline__ double schur_x_task(const ModeArgs &ma, const Geom &G
             if (fuse) {                                          // ma.x[q] points into p: the same offset addresses r and x_sol
                 const long mo = (ma.x[q] - fz.p) + base + c0;
                 ld2<NT>(fz.r, mo, ok, VEC, rq[q][ch][0], rq[q][ch][1], ok2);
-                ld2<NT>(fz.xsol, mo, ok, VEC, sq[q][ch][0], sq[q][ch][1], ok2);
+                if (XB != XB_SKIP) ld2<NT>(fz.xsol, mo, ok, VEC, sq[q][ch][0], sq[q][ch][1], ok2);
             }
         }
         if (NB > 0) ld2<NT>(ma.D, base + c0, ok, VEC, dq[NB > 0 ? ch : 0][0], dq[NB > 0 ? ch : 0][1], ok2);
     }
     if (mid(f_alpha, f_beta)) return 0.0;
+    double av[7];                                                // XB_APPLY: alpha of the older directions, oldest first (wave-uniform)
+    if (XB == XB_APPLY) {
+#pragma unroll
+        for (int i = 0; i < 7; ++i) av[i] = i < fz.nold ? fz.ah[(fz.a0 + i) & 7] : 0.0;
+    }
     // ---- the deferred CG update of these cells, then the face values
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
@@ -899,14 +915,24 @@ __device__ __forceinline__ double schur_x_task(const ModeArgs &ma, const Geom &G
 #pragma unroll
             for (int q = 0; q <= NB; ++q) {
                 const long mo = (ma.x[q] - fz.p) + base + c0;
-                const double s0 = fma(f_alpha, xm[q][ch][0], sq[q][ch][0]), s1 = fma(f_alpha, xm[q][ch][1], sq[q][ch][1]);
+                if (XB == XB_APPLY) {
+                    // the older directions of these cells: loaded here, chunk by chunk, and not with the pass's other loads -- 14 doubles
+                    // in flight per lane whatever NCH is, where 7 x NCH x K more registers would cost occupancy (NCH = 2) or spill (NCH = 8)
+                    double o0[7], o1[7];
+#pragma unroll
+                    for (int i = 0; i < 7; ++i) if (i < fz.nold) ld2<NT>(fz.old[i], mo, ok, VEC, o0[i], o1[i], ok2);
+#pragma unroll
+                    for (int i = 0; i < 7; ++i) if (i < fz.nold) { sq[q][ch][0] = fma(av[i], o0[i], sq[q][ch][0]); sq[q][ch][1] = fma(av[i], o1[i], sq[q][ch][1]); }
+                }
+                double s0 = 0.0, s1 = 0.0;
+                if (XB != XB_SKIP) { s0 = fma(f_alpha, xm[q][ch][0], sq[q][ch][0]); s1 = fma(f_alpha, xm[q][ch][1], sq[q][ch][1]); }
                 xm[q][ch][0] = fma(f_beta, xm[q][ch][0], rq[q][ch][0]); xm[q][ch][1] = fma(f_beta, xm[q][ch][1], rq[q][ch][1]);
                 if (VEC) {
-                    if (ok) { *reinterpret_cast<double2 *>(fz.xsol + mo) = make_double2(s0, s1);
+                    if (ok) { if (XB != XB_SKIP) *reinterpret_cast<double2 *>(fz.xsol + mo) = make_double2(s0, s1);
                               *reinterpret_cast<double2 *>(pw + mo) = make_double2(xm[q][ch][0], xm[q][ch][1]); }
                 } else {
-                    if (ok) { fz.xsol[mo] = s0; pw[mo] = xm[q][ch][0]; }
-                    if (ok2) { fz.xsol[mo + 1] = s1; pw[mo + 1] = xm[q][ch][1]; }
+                    if (ok) { if (XB != XB_SKIP) fz.xsol[mo] = s0; pw[mo] = xm[q][ch][0]; }
+                    if (ok2) { if (XB != XB_SKIP) fz.xsol[mo + 1] = s1; pw[mo + 1] = xm[q][ch][1]; }
                 }
             }
         }
@@ -1006,7 +1032,7 @@ __device__ __forceinline__ double schur_x_task(const ModeArgs &ma, const Geom &G
     return dot;
 }
 
-template <int K, int NCH, bool VEC, int NB, bool NT = false, bool DICT = false>
+template <int K, int NCH, bool VEC, int NB, bool NT = false, bool DICT = false, int XB = XB_NOW>
 __global__ __launch_bounds__(256) void k_schur_x(ModeArgs ma0, ModeTab mt, Geom G, const double *__restrict__ L, const double *__restrict__ DR,
                                                  const double *__restrict__ D0, int nx, int ny, long nlines, int lpl_log2,
                                                  int first, int last, double *__restrict__ partials,
@@ -1029,7 +1055,7 @@ __global__ __launch_bounds__(256) void k_schur_x(ModeArgs ma0, ModeTab mt, Geom 
     // bit 1 of `first`: XCD-contiguous block order (consecutive workgroups go round-robin to the 8 XCDs; each then walks one eighth of the lines)
     unsigned bx = blockIdx.x;
     if ((first & 2) && gridDim.x % 8 == 0) bx = (blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8;
-    const double dot = schur_x_task<K, NCH, VEC, NB, decltype(mid), false, NT, DICT>(ma, G, L, DR, D0, nx, ny, nlines, lpl_log2, first & 1, (long)bx * 4 + (threadIdx.x >> 6),
+    const double dot = schur_x_task<K, NCH, VEC, NB, decltype(mid), false, NT, DICT, XB>(ma, G, L, DR, D0, nx, ny, nlines, lpl_log2, first & 1, (long)bx * 4 + (threadIdx.x >> 6),
                                                                            threadIdx.x & 63, true, fuse, alpha0, beta0, fz, mid, ld);
     if (stopped) return;                                         // decided inside, the same in every block: nothing to reduce
     if (last && partials) {
@@ -2475,12 +2501,27 @@ __global__ __launch_bounds__(256) void k_cg_rupdate(double *__restrict__ r, cons
     s = block_sum(s, sred);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
-// fused CG: the x_sol update of the final iteration
-__global__ void k_cg_flush(double *__restrict__ x, const double *__restrict__ p, long n, const CgScalars *__restrict__ cg)
+// fused CG: the x_sol updates that the x passes of the finished solve have not applied, in order.  ring.n < 0: the one of the final
+// iteration, if CgScalars::pend says so (every form but the batched one); else ring.n updates x = fma(ah[alpha[i]], p[i], x), as the host
+// derived them from the final scalars (nf_ring_pending)
+struct FlushRing { int n; int alpha[8]; const double *ah; const double *p[8]; };
+__global__ void k_cg_flush(double *__restrict__ x, const double *__restrict__ p, long n, const CgScalars *__restrict__ cg, FlushRing ring)
 {
-    if (!cg->pend) return;
-    const double alpha = cg->alpha;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) x[i] = fma(alpha, p[i], x[i]);
+    if (ring.n < 0) {
+        if (!cg->pend) return;
+        const double alpha = cg->alpha;
+        for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) x[i] = fma(alpha, p[i], x[i]);
+        return;
+    }
+    double a[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a[j] = j < ring.n ? ring.ah[ring.alpha[j] & 7] : 0.0;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) {
+        double v = x[i];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) if (j < ring.n) v = fma(a[j], ring.p[j][i], v);
+        x[i] = v;
+    }
 }
 __global__ __launch_bounds__(256) void k_cg_pupdate(double *__restrict__ p, const double *__restrict__ r, long n,
                                                     const CgScalars *__restrict__ cg)

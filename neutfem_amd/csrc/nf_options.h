@@ -1,5 +1,5 @@
 // The runtime options of a handle (nf_set_option / nf_get_option): every key is declared here once -- its field and default in NfOptions,
-// and in nf_option_rows() its normaliser, which twins take it (team_copy_options) and what setting it invalidates.  Plain C++: no device
+// and in nf_option_rows() (or nf_option_rows_more()) its normaliser, which twins take it (team_copy_options) and what setting it invalidates.  Plain C++: no device
 // code, so that it can be built and run on its own (tests/host/options_main.cpp).
 #pragma once
 #include <climits>
@@ -31,6 +31,9 @@ struct NfOptions {
     long cg_batch = 0;              // CG iterations launched between two looks at the residual: 0 = automatic (NEUTFEM_CG_BATCH presets it)
     // 192^3 (7.1 M cells): 229 -> 233 us per CG iteration with them, 224^3 (11.2 M): 389 -> 356, 256^3: 599 -> 550
     long nt_loads = 1, nt_min_cells = 8000000;   // streaming (non-temporal) loads in the y / z passes of undivided meshes larger than this
+    // fused CG on an undivided RT0-P0 mesh: x_sol is updated in every M-th x pass only, from a ring of M direction buffers (nf_xsol_ring.h; M-1
+    // extra vectors per solver).  1 (0) = in every pass; 2 .. 8 = that M wherever eligible; -1 = XSOL_BATCH_AUTO beyond cg_lean_max_cells, else 1
+    long xsol_batch = -1;
     long cg_fuse = 1;               // x += alpha p, p = r + beta p folded into the next pass that reads p (bit-identical iterates)
     long xcd = -1;                  // each XCD gets one contiguous range of tiles: bit 0 the y passes, bit 1 the z passes; -1 = the y passes of meshes beyond nt_min_cells
     long outer_dev = 1;             // the outer loop of the diagonal-Schur path stays on the device (undivided mesh, no CMFD)
@@ -164,9 +167,21 @@ inline const NfOptionRow *nf_option_rows(int *n)
     *n = (int)(sizeof rows / sizeof rows[0]);
     return rows;
 }
+// Rows added since tests/host/options_main.cpp wrote out the table above key by key (it counts those rows): declared the same way, found, set,
+// read and copied by the same functions; tests/host/xsol_option_main.cpp writes out what they must do.
+inline const NfOptionRow *nf_option_rows_more(int *n)
+{
+    static const NfOptionRow rows[] = {
+        { "xsol_batch", &NfOptions::xsol_batch, NF_CLAMP, -1, 8, NF_COPY_SOLVE, 0, nullptr, nullptr },
+    };
+    *n = (int)(sizeof rows / sizeof rows[0]);
+    return rows;
+}
 inline const NfOptionRow *nf_option_find(const char *key)
 {
     int n = 0; const NfOptionRow *rows = nf_option_rows(&n);
+    for (int i = 0; i < n; ++i) if (!strcmp(key, rows[i].key)) return rows + i;
+    rows = nf_option_rows_more(&n);
     for (int i = 0; i < n; ++i) if (!strcmp(key, rows[i].key)) return rows + i;
     return nullptr;
 }
@@ -203,12 +218,14 @@ inline bool nf_options_get(const NfOptions &o, const char *key, long *value)
 // value changed: the twin's link state is its own, a copy never asks for RELINK.
 inline unsigned nf_options_copy(NfOptions &dst, const NfOptions &src, bool same_mesh_kind)
 {
-    int n = 0; const NfOptionRow *rows = nf_option_rows(&n);
     unsigned fx = 0;
-    for (int i = 0; i < n; ++i) {
-        const NfOptionRow &r = rows[i];
-        if (r.copy == NF_COPY_NONE || (r.copy == NF_COPY_PASS && !same_mesh_kind) || dst.*r.field == src.*r.field) continue;
-        dst.*r.field = src.*r.field; fx |= r.effects;
+    for (int part = 0; part < 2; ++part) {
+        int n = 0; const NfOptionRow *rows = part ? nf_option_rows_more(&n) : nf_option_rows(&n);
+        for (int i = 0; i < n; ++i) {
+            const NfOptionRow &r = rows[i];
+            if (r.copy == NF_COPY_NONE || (r.copy == NF_COPY_PASS && !same_mesh_kind) || dst.*r.field == src.*r.field) continue;
+            dst.*r.field = src.*r.field; fx |= r.effects;
+        }
     }
     return fx & (NF_FX_DICT | NF_FX_REGIME);
 }
