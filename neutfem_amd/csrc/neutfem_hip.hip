@@ -15,6 +15,7 @@
 #include "nf_assembly.h"
 #include "nf_line_groups.h"
 #include "nf_options.h"
+#include "nf_resident_lanes.h"
 #include "nf_small_eig.h"
 #include "nf_xsol_ring.h"
 
@@ -3192,16 +3193,17 @@ static bool resident_plan(const nf_solver *S, ResidentArgs *A)
     A->lpl_log2 = lpl_log2; A->ntask_x = (int)((S->nlines[0] + LPW - 1) / LPW);
     return true;
 }
-// does the line-per-lane variant of the resident kernel take this mesh?  (the same arithmetic as the plan inside solve_keff_resident)
-static bool resident_serial_fits(const nf_team *T, const nf_solver *S)
+// the plan of the line-per-lane variants for this mesh (nf_resident_lanes.h), and whether one of them takes it
+static long resident_lds_cap(const nf_team *T) { return (long)T->lds_limit / 8 - 32; }
+static LanePlan resident_lane_plan(const nf_team *T, const nf_solver *S)
 {
-    if (!T->opt.resident_serial || !T->opt.resident_lds) return false;
-    const long cap = (long)T->lds_limit / 8 - 32;
-    const long Np = (long)(S->nx | 1) * S->ny * S->nz;
-    long lines = 0; for (int d = 0; d < S->dim; ++d) lines += (S->nlines[d] + 1) & ~1L;
-    if (S->nb == 0) { const long pitch = Np <= 1536 ? 1536 : 2560; return Np <= pitch && 64 + 16 + (1 + 3L * S->dim) * pitch + 3 * lines <= cap; }
-    const long PC = (Np + 63) & ~63L, NPp = PC * S->nloc;
-    return NPp <= 5120 && n_modes(S) <= 9 && S->nloc <= 27 && 64 + 16 + 176 + (1 + S->dim) * NPp + 2L * S->dim * PC + 3 * lines <= cap;
+    return lane_plan(S->dim, S->nx, S->ny, S->nz, S->nlines, S->nb, S->nloc, n_modes(S), T->opt.resident_two_sided != 0, resident_lds_cap(T));
+}
+static bool resident_serial_fits(const nf_team *T, const nf_solver *S, LanePlan *plan = nullptr)
+{
+    const LanePlan lp = resident_lane_plan(T, S);
+    if (plan) *plan = lp;
+    return T->opt.resident_serial && T->opt.resident_lds && lp.fits;
 }
 static const int NF_RESIDENT_UNAVAILABLE = 1;                     // positive: not an error code of the C ABI
 static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, const ChebTable &cheb, double cg_tol, int cg_max, double *keff_out)
@@ -3210,7 +3212,9 @@ static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, 
     const int ng = S->ng; hipStream_t st = T->stream;
     ResidentArgs A; memset(&A, 0, sizeof A);
     const bool planned = resident_plan(S, &A);
-    if (!planned && !resident_serial_fits(T, S)) return fail(NF_ERR_STATE, "resident solve: mesh not eligible");
+    LanePlan lp;
+    const bool lanes_fit = resident_serial_fits(T, S, &lp);
+    if (!planned && !lanes_fit) return fail(NF_ERR_STATE, "resident solve: mesh not eligible");
     A.G = make_geom(S); A.ng = ng; A.dim = S->dim; A.nmodes = n_modes(S); A.N = S->N; A.nphi = S->nphi;
     for (int d = 0; d < 3; ++d) {
         const int dd = d < S->dim ? d : 0;
@@ -3231,47 +3235,23 @@ static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, 
     // LDS plan: 160 KiB per workgroup; behind the scratch of the direction passes the CG vectors and this group's factors, in
     // priority order, as far as they fit (ResidentArgs::lds_mask)
     A.Cd0 = S->d_Cd; A.lds_mask = 0;
-    // RT0-P0: the line-per-lane variant when everything its sweeps touch fits in LDS (p, the contribution of every direction, the
-    // factors and first pivots); r, x_sol and the C diagonal follow as far as there is room
-    const long cap = (long)T->lds_limit / 8 - 32;
-    bool serial = false;
-    if (S->nb == 0 && T->opt.resident_serial && T->opt.resident_lds && S->nphi <= T->opt.resident_serial_max_dofs) {
-        const long Np = (long)(S->nx | 1) * S->ny * S->nz;     // rows padded to an odd length (bank-conflict-free x lines)
-        const int pitch = Np <= 1536 ? 1536 : 2560;              // multiples of 512 (cells per thread) and of 64 (ds_read2st64)
-        long need = 64 + 16 + (1 + 3L * S->dim) * pitch;
-        int slot = 0;
-        for (int d = 0; d < S->dim; ++d) {
-            const int nd = d == 0 ? S->nx : d == 1 ? S->ny : S->nz;
-            A.tw[d] = (nd >= 4 && T->opt.resident_two_sided) ? 1 : 0;   // two lanes per line, meeting in the middle
-            need += 3 * ((S->nlines[d] + 1) & ~1L); A.slot0[d] = slot; slot += (int)((S->nlines[d] * (A.tw[d] ? 2 : 1) + 63) / 64) * 64;
-        }
-        for (int d = S->dim; d < 4; ++d) A.slot0[d] = slot;
-        if (Np <= pitch && need <= cap) {
-            serial = true;
-            const size_t lds = (size_t)need * sizeof(double);
+    // the line-per-lane variants, when everything their sweeps touch fits in LDS (p, the contribution of every direction, the factors and
+    // the per-line values): RT0-P0 at a compile-time block pitch; RT_k-P_m with bubble moments, DOF = moment * PC + padded cell
+    const long cap = resident_lds_cap(T);
+    const bool serial = S->nphi <= T->opt.resident_serial_max_dofs && lanes_fit;
+    if (serial) {
+        for (int d = 0; d < 3; ++d) A.tw[d] = lp.tw[d];
+        for (int d = 0; d < 4; ++d) A.slot0[d] = lp.slot0[d];
+        const size_t lds = (size_t)lp.need * sizeof(double);
+        if (S->nb == 0) {
 #define NF_RES_SERIAL(P) do { if (!lds_opt_in((const void *)k_resident_keff<false, 0, P>, lds)) return NF_RESIDENT_UNAVAILABLE; \
             hipLaunchKernelGGL((k_resident_keff<false, 0, P>), dim3(1), dim3(B), lds, st, A); } while (0)
-            if (pitch == 1536) NF_RES_SERIAL(1536); else NF_RES_SERIAL(2560);
+            if (lp.pitch == 1536) NF_RES_SERIAL(1536); else NF_RES_SERIAL(2560);
 #undef NF_RES_SERIAL
-        }
-    }
-    // RT_k-P_m with bubble moments: the same idea, DOF = moment * PC + padded cell, one contribution vector per direction
-    if (S->nb > 0 && T->opt.resident_serial && T->opt.resident_lds && S->nphi <= T->opt.resident_serial_max_dofs) {
-        const long Np = (long)(S->nx | 1) * S->ny * S->nz;
-        const long PC = (Np + 63) & ~63L, NPp = PC * S->nloc;
-        const int nm = n_modes(S);
-        long need = 64 + 16 + 176 + (1 + S->dim) * NPp + 2L * S->dim * PC;
-        int slot = 0;
-        for (int d = 0; d < S->dim; ++d) {
-            const int nd = d == 0 ? S->nx : d == 1 ? S->ny : S->nz;
-            A.tw[d] = (nd >= 4 && T->opt.resident_two_sided) ? 1 : 0;
-            need += 3 * ((S->nlines[d] + 1) & ~1L); A.slot0[d] = slot; slot += (int)((S->nlines[d] * nm * (A.tw[d] ? 2 : 1) + 63) / 64) * 64;
-        }
-        for (int d = S->dim; d < 4; ++d) A.slot0[d] = slot;
-        if (NPp <= 5120 && nm <= 9 && S->nloc <= 27 && need <= cap) {
-            serial = true;
-            A.PC = (int)PC;
+        } else {
+            A.PC = (int)lp.PC;
             memset(A.mom, 0, sizeof A.mom); memset(A.diagc, 0, sizeof A.diagc);
+            const int nm = n_modes(S);
             const ModeArgs c = mode_args(S, 0, 0, 0, S->d_p, S->d_q);
             for (int d = 0; d < S->dim; ++d)
                 for (int m = 0; m < nm; ++m) {
@@ -3279,7 +3259,6 @@ static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, 
                     for (int i = 0; i <= S->nb; ++i) A.mom[d][m][i] = moment_index(S, d, m, i, &Ta);
                     for (int l = 0; l < S->nb; ++l) A.diagc[A.mom[d][m][l + 1]][d] = Ta * c.Gc[l] * c.Gc[l] * c.iM[l];
                 }
-            const size_t lds = (size_t)need * sizeof(double);
 #define NF_RES_HI(NBV) do { if (!lds_opt_in((const void *)k_resident_keff<false, NBV, -1>, lds)) return NF_RESIDENT_UNAVAILABLE; \
             hipLaunchKernelGGL((k_resident_keff<false, NBV, -1>), dim3(1), dim3(B), lds, st, A); } while (0)
             if (S->nb == 1) NF_RES_HI(1); else NF_RES_HI(2);
