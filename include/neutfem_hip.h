@@ -153,6 +153,29 @@ typedef struct nf_keff_opts {
  * current flux (nf_set_phi/nf_get_phi) and has_valid_keff_/last_keff_direct_. */
 int nf_solve_keff(nf_handle h, const nf_keff_opts *opts, double *keff, int *n_outer);
 
+/* No reference counterpart: nf_solve_keff on n independent handles in one call.  Equivalent to nf_solve_keff(h[i], &opts[n_opts == 1 ? 0 : i],
+ * &keff[i], &n_outer[i]) for i = 0 .. n-1 in that order: flux, raw group fluxes, history, warm state, nf_progress and nf_info "last_path" /
+ * "last_resident_serial" / "last_outer" / "last_cg_total" of every handle are afterwards bit for bit what those calls leave.  status[i] is
+ * the code of handle i, the return value the first one that is not NF_OK; keff, n_outer, status and res may each be NULL.
+ * Batched route -- one launch with one workgroup per handle: every handle undivided, built, without a mask (nf_set_void), of the same
+ * orders, groups, dimension and nx, ny, nz (cell sizes and cross sections are free), with the same values of the options the one-workgroup
+ * solve plans with, and every (handle, opts) pair one that nf_solve_keff alone would run in one workgroup (nf_info "last_path" 2) without
+ * use_coarse_init.  The handles' streams are waited for, the launch goes to the stream of h[0].  Anything else that nf_solve_keff
+ * would still solve takes the sequential route: nf_solve_keff per handle, in order.  res says which route ran.
+ * Refused before any launch, status untouched: n < 1, h or opts NULL, a NULL handle, the same handle twice (two workgroups would write the
+ * same vectors), n_opts neither 1 nor n, handles on different devices -> NF_ERR_ARG; a slab (nf_create_slab, linked) or a handle with a
+ * communicator (nf_comm_init) -> NF_ERR_UNSUPPORTED (the batch must not reorder collectives); a handle that is not built -> NF_ERR_STATE.
+ * nf_info(h[0], "batch_launches") counts the batched launches that went to the stream of that handle, "batch_capacity" is the number of
+ * workgroups its argument array holds (it grows, never shrinks, and goes with the handle); nf_info(h, "compute_units") is the number
+ * of compute units of the handle's device (hipDeviceAttributeMultiprocessorCount): up to that many workgroups run side by side. */
+typedef struct nf_batch_result {
+    int n_batched, n_sequential;    /* handles solved by the one launch / by nf_solve_keff one after another */
+    int n_launches;                 /* 1 on the batched route, 0 on the sequential one */
+    int variant;                    /* the kernel instantiation of the batch: 1 / 2 RT0-P0 line per lane at pitch 1536 / 2560, 3 / 4 RT1-P1 / RT2-P2
+                                     * line per lane, 5 + 2 nb + (nx even) the scan variants (nb bubble moments); 0 sequential */
+} nf_batch_result;
+int nf_solve_keff_batch(nf_handle *h, int n, const nf_keff_opts *opts, int n_opts, double *keff, int *n_outer, int *status, nf_batch_result *res);
+
 /* External source SRC_data_ (include/NeutFEM.hpp:365-388, get_SRC() at src/wrapper.cpp:829; SolveSubcritical reads it,
  * src/wrapper.cpp:699-715) -> device, host layout [g*N + e] like the cross sections; on a slab, the slab's own cells (as nf_upload_xs).
  * SRC is piecewise constant per cell: it loads DOF 0 only, q_g[e, 0] = Q_g(e) |e|.  Needs no nf_build and survives one; a new upload

@@ -13,7 +13,7 @@ from . import lib_path
 SYMBOLS = [
     "nf_last_error", "nf_device_count", "nf_create", "nf_destroy", "nf_create_slab", "nf_link_slabs", "nf_comm_unique_id",
     "nf_comm_init", "nf_comm_info", "nf_comm_selftest", "nf_team_schur_apply", "nf_info", "nf_set_bc", "nf_set_void", "nf_get_void", "nf_upload_xs", "nf_build",
-    "nf_schur_apply", "nf_solve_group", "nf_build_diagonal_cache", "nf_get_diagonal_cache", "nf_solve_keff",
+    "nf_schur_apply", "nf_solve_group", "nf_build_diagonal_cache", "nf_get_diagonal_cache", "nf_solve_keff", "nf_solve_keff_batch",
     "nf_upload_source", "nf_solve_subcritical", "nf_solve_modes", "nf_get_mode", "nf_block_gram", "nf_block_rotate", "nf_solve_coarse", "nf_coarsen", "nf_prolong", "nf_timers", "nf_apply_plan", "nf_initialize_cmfd", "nf_set_cmfd_relaxation", "nf_get_cmfd_coefficients", "nf_solve_adjoint", "nf_get_phi_adj", "nf_project_flux", "nf_project_power", "nf_refine", "nf_zoom_source", "nf_get_source", "nf_set_phi_adj", "nf_zoom_resolved", "nf_sensitivity", "nf_solve_gpt", "nf_get_gamma", "nf_set_gamma", "nf_gpt_source", "nf_gpt_sensitivity", "nf_set_phi", "nf_get_phi", "nf_get_J", "nf_reset_flux", "nf_set_warm_state",
     "nf_get_warm_state", "nf_get_history", "nf_profile_get", "nf_profile_reset", "nf_time_schur_apply", "nf_time_device_copy", "nf_progress", "nf_set_progress_callback", "nf_local_matrices",
     "nf_transient_begin", "nf_transient_step", "nf_get_precursors", "nf_transient_end", "nf_kinetics_params", "nf_transient_kinetics",
@@ -26,6 +26,12 @@ class KeffOpts(C.Structure):
                 ("use_coarse_init", C.c_int), ("coarse_factors", C.c_int * 3), ("n_coarse_factors", C.c_int),
                 ("use_diagonal_solver", C.c_int), ("solver_type", C.c_int), ("solver_type_pushed", C.c_int),
                 ("profile", C.c_int), ("use_cmfd", C.c_int)]
+
+
+class BatchResult(C.Structure):
+    _fields_ = [("n_batched", C.c_int), ("n_sequential", C.c_int), ("n_launches", C.c_int), ("variant", C.c_int)]
+
+    def as_dict(self): return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class SubcritResult(C.Structure):
@@ -132,6 +138,7 @@ def load():
     L.nf_build_diagonal_cache.argtypes = [vp]
     L.nf_get_diagonal_cache.argtypes = [vp, C.c_int, dp]
     L.nf_solve_keff.argtypes = [vp, C.POINTER(KeffOpts), dp, ip]
+    L.nf_solve_keff_batch.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(KeffOpts), C.c_int, dp, ip, ip, C.POINTER(BatchResult)]
     L.nf_upload_source.argtypes = [vp, dp]
     L.nf_solve_subcritical.argtypes = [vp, C.POINTER(KeffOpts), C.POINTER(SubcritResult)]
     L.nf_solve_modes.argtypes = [vp, C.POINTER(KeffOpts), C.c_int, C.c_int, C.c_int, C.POINTER(ModesResult)]
@@ -667,6 +674,24 @@ class HipSolver:
 
     def time_device_copy(self, nbytes, reps=20):
         v = C.c_double(); self._chk(self.L.nf_time_device_copy(self.h, int(nbytes), reps, C.byref(v))); return v.value
+
+
+def solve_keff_batch(solvers, use_coarse=False, factors=(), use_diag=False, use_cmfd=False):
+    """nf_solve_keff_batch over HipSolver objects: what solve_keff() on each of them, in order, leaves on it and returns, small meshes of
+    one shape in ONE launch (one workgroup each).  Every solver's own set_tol / set_linear_solver goes into its own option set (n_opts = n).
+    Returns (k, n_outer, status) as arrays and the nf_batch_result as a dict; status[i] is the code of solver i (0 = solved).
+    RuntimeError when the call as a whole is refused (nothing was launched, no solver touched)"""
+    solvers = list(solvers); n = len(solvers)
+    L = load()
+    hs = (C.c_void_p * max(n, 1))(*[s.h for s in solvers])
+    os_ = (KeffOpts * max(n, 1))(*[s.opts(use_coarse, factors, use_diag, False, use_cmfd) for s in solvers])
+    untouched = -(2 ** 31)
+    k, no, st = np.zeros(n), np.zeros(n, dtype=np.int32), np.full(n, untouched, dtype=np.int32)
+    res = BatchResult()
+    rc = L.nf_solve_keff_batch(hs, n, os_, n, _dp(k), no.ctypes.data_as(C.POINTER(C.c_int)), st.ctypes.data_as(C.POINTER(C.c_int)), C.byref(res))
+    if rc != 0 and (n == 0 or np.all(st == untouched)):
+        raise RuntimeError(f"neutfem_hip error {rc}: {L.nf_last_error().decode()}")
+    return k, no, st, res.as_dict()
 
 
 def mem_info(device=0):

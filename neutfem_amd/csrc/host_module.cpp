@@ -172,9 +172,11 @@ public:
                   << std::setprecision(2) << dk << "  dphi = " << dphi << std::defaultfloat << std::endl;
         me->printed_upto_ = it + 5;
     }
-    double SolveKeff(bool use_coarse_init, const std::vector<int> &coarse_factors, bool use_diagonal_solver, bool use_cmfd)
+    // SolveKeff in two halves around the solve itself, which SolveKeffBatch (below the class) shares: the banner, the host mirror and the warm
+    // state pushed to the handle, this object's options; then the flux pulled back, the closing lines, last_keff_
+    nf_keff_opts keff_prepare(bool use_coarse_init, const std::vector<int> &coarse_factors, bool use_diagonal_solver, bool use_cmfd, const char *who)
     {
-        need_built("SolveKeff");
+        need_built(who);
         Log(VerbosityLevel::NORMAL, "\n=== CALCUL DE K-EFFECTIF (DIRECT) ===");
         if (use_diagonal_solver && !(rt_ == 0 && p_ == 0)) { Log(VerbosityLevel::NORMAL, "  Note: Solveur diagonal non disponible (ordre > 0)"); use_diagonal_solver = false; }
         if (use_diagonal_solver) Log(VerbosityLevel::NORMAL, "  Mode: Solveur diagonal RT0-P0 (faible RAM)");
@@ -184,14 +186,11 @@ public:
         nf_keff_opts o = make_opts(use_coarse_init, coarse_factors, use_diagonal_solver);
         o.use_cmfd = use_cmfd ? 1 : 0;
         chk(nf_set_cmfd_relaxation(h_, cmfd_omega_));
-        double k = 1.0; int nout = 0;
-        // the reference prints its progress line every 5th outer DURING the solve (src/NeutFEM.cpp:1791-1796): the host-driven loop calls back after
-        // every outer; the in-kernel paths (milliseconds) have no host in between, their lines follow from the recorded history
         printed_upto_ = 0;
-        chk(nf_set_progress_callback(h_, verb_ >= VerbosityLevel::NORMAL ? &NeutFEM::progress_line : nullptr, this));
-        const int rc_solve = nf_solve_keff(h_, &o, &k, &nout);
-        (void)nf_set_progress_callback(h_, nullptr, nullptr);
-        chk(rc_solve);
+        return o;
+    }
+    double keff_accept(double k, int nout)
+    {
         chk(nf_get_phi(h_, Phi_.data()));
         if (verb_ >= VerbosityLevel::NORMAL) {
             std::vector<double> hk(nout), hdk(nout), hdp(nout);
@@ -205,6 +204,20 @@ public:
         has_valid_keff_ = true; last_keff_ = k;
         return k;
     }
+    double SolveKeff(bool use_coarse_init, const std::vector<int> &coarse_factors, bool use_diagonal_solver, bool use_cmfd)
+    {
+        nf_keff_opts o = keff_prepare(use_coarse_init, coarse_factors, use_diagonal_solver, use_cmfd, "SolveKeff");
+        double k = 1.0; int nout = 0;
+        // the reference prints its progress line every 5th outer DURING the solve (src/NeutFEM.cpp:1791-1796): the host-driven loop calls back after
+        // every outer; the in-kernel paths (milliseconds) have no host in between, their lines follow from the recorded history
+        chk(nf_set_progress_callback(h_, verb_ >= VerbosityLevel::NORMAL ? &NeutFEM::progress_line : nullptr, this));
+        const int rc_solve = nf_solve_keff(h_, &o, &k, &nout);
+        (void)nf_set_progress_callback(h_, nullptr, nullptr);
+        chk(rc_solve);
+        return keff_accept(k, nout);
+    }
+    nf_handle handle() const { return h_; }
+    void progress_on(bool on) { (void)nf_set_progress_callback(h_, on && verb_ >= VerbosityLevel::NORMAL ? &NeutFEM::progress_line : nullptr, on ? this : nullptr); }
     // SolveSubcritical (include/NeutFEM.hpp:275-279, src/wrapper.cpp:699-715; declared, never defined there): fixed-source solve with the
     // source of get_SRC(), uploaded on every call (a source set after BuildMatrices counts); returns M = flux with / without fission
     double SolveSubcritical()
@@ -718,11 +731,49 @@ private:
     nf_transient_result transient_{}; bool has_transient_ = false;   // the last step_transient (get_transient_info)
 };
 
+// SolveKeffBatch (extension; include/neutfem_hip.h, nf_solve_keff_batch): SolveKeff() on every object of the list, each with
+// its own tolerances and linear solver; small meshes of one shape run in one launch, one workgroup each.  Every object is left as its
+// own SolveKeff() leaves it (get_flux(), GetLastKeff()).  An object whose solve failed raises after the others have been accepted.
+static nf_batch_result g_last_batch{}; static bool g_has_batch = false;
+static std::vector<double> SolveKeffBatch(const std::vector<NeutFEM *> &solvers, bool use_coarse_init, const std::vector<int> &coarse_factors,
+                                          bool use_diagonal_solver, bool use_cmfd)
+{
+    const int n = (int)solvers.size();
+    if (n < 1) throw std::invalid_argument("SolveKeffBatch: an empty list");
+    for (NeutFEM *s : solvers) if (!s) throw std::invalid_argument("SolveKeffBatch: None in the list");
+    for (int i = 0; i < n; ++i) for (int j = 0; j < i; ++j) if (solvers[i] == solvers[j]) throw std::invalid_argument("SolveKeffBatch: the same object twice");
+    std::vector<nf_keff_opts> o; std::vector<nf_handle> h;
+    for (NeutFEM *s : solvers) { o.push_back(s->keff_prepare(use_coarse_init, coarse_factors, use_diagonal_solver, use_cmfd, "SolveKeffBatch")); h.push_back(s->handle()); }
+    std::vector<double> k(n, 1.0); std::vector<int> nout(n, 0), st(n, NF_OK);
+    nf_batch_result r{};
+    for (NeutFEM *s : solvers) s->progress_on(true);
+    const int rc = nf_solve_keff_batch(h.data(), n, o.data(), n, k.data(), nout.data(), st.data(), &r);
+    for (NeutFEM *s : solvers) s->progress_on(false);
+    const std::string err = rc != NF_OK ? std::string("neutfem_amd: ") + nf_last_error() : std::string();   // before any further call of the C ABI
+    bool any = false; for (int i = 0; i < n; ++i) any |= st[i] != NF_OK;
+    if (rc != NF_OK && !any) throw std::runtime_error(err);       // refused as a whole: nothing ran
+    g_last_batch = r; g_has_batch = true;
+    for (int i = 0; i < n; ++i) if (st[i] == NF_OK) k[i] = solvers[i]->keff_accept(k[i], nout[i]);
+    if (rc != NF_OK) throw std::runtime_error(err);
+    return k;
+}
+static py::dict GetBatchInfo()
+{
+    if (!g_has_batch) throw std::runtime_error("get_batch_info: call SolveKeffBatch() first");
+    py::dict d;
+    d["n_batched"] = g_last_batch.n_batched; d["n_sequential"] = g_last_batch.n_sequential; d["n_launches"] = g_last_batch.n_launches; d["variant"] = g_last_batch.variant;
+    return d;
+}
+
 PYBIND11_MODULE(_neutfem_eigen, m)
 {
     m.doc() = "neutfem_amd: MI355X-native drop-in for jujuC31/NeutFEM's neutfem._neutfem_eigen (src/wrapper.cpp)";
     m.attr("__backend__") = "hip-gfx950";
     m.def("device_count", &nf_device_count, "number of visible HIP devices");
+    m.def("SolveKeffBatch", &SolveKeffBatch, py::arg("solvers"), py::arg("use_coarse_init") = false, py::arg("coarse_factors") = std::vector<int>{},
+          py::arg("use_diagonal_solver") = false, py::arg("use_cmfd") = false,
+          "extension: SolveKeff() on every NeutFEM object of the list, small meshes of one shape in one launch; returns the list of k");
+    m.def("get_batch_info", &GetBatchInfo, "extension: the last SolveKeffBatch's nf_batch_result as a dict (n_batched, n_sequential, n_launches, variant)");
 
     py::enum_<VerbosityLevel>(m, "VerbosityLevel")
         .value("SILENT", VerbosityLevel::SILENT).value("NORMAL", VerbosityLevel::NORMAL)

@@ -177,6 +177,7 @@ struct nf_team {
     XcdState *d_xcd = nullptr; double *d_xpart = nullptr;
     int last_resident_serial = 0;                         // whole SolveKeff in one workgroup (k_resident_keff): the last one ran its serial variant
     int *d_hist_cg = nullptr; int hist_cg_cap = 0; ResidentOut *d_rout = nullptr;
+    ResidentArgs *d_batch_args = nullptr; int batch_cap = 0; long batch_launches = 0;   // nf_solve_keff_batch with this team's handle first: one struct per workgroup (grow-only), launches so far
     int last_path = 0;                                    // 0 host-driven outer loop, 1 diagonal device loop, 2 resident kernel, 3 one-XCD kernel (nf_info "last_path")
     int last_direct = 0;                                  // the last solve used: 0 CG as configured, 1 dense S^-1, 2 CG to 1e-14 standing in
     long standin_unconverged = 0;                         // group solves of the stand-in that ended above 1e-14
@@ -429,7 +430,7 @@ static void team_free(nf_team *T)
     if (T->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(T->comm);
     if (T->d_xcd) (void)hipFree(T->d_xcd);
     dfree(T->d_xpart);
-    dfree(T->d_partials); dfree(T->d_cg); dfree(T->d_ah); dfree(T->d_out); dfree(T->d_red); dfree(T->d_errsrc); dfree(T->d_vec); dfree(T->d_ost); dfree(T->d_hist); dfree(T->d_hist_cg); dfree(T->d_rout);
+    dfree(T->d_partials); dfree(T->d_cg); dfree(T->d_ah); dfree(T->d_out); dfree(T->d_red); dfree(T->d_errsrc); dfree(T->d_vec); dfree(T->d_ost); dfree(T->d_hist); dfree(T->d_hist_cg); dfree(T->d_rout); dfree(T->d_batch_args);
     if (T->h_pub) (void)hipHostFree(T->h_pub);
     if (T->comm_stream) { (void)hipStreamSynchronize(T->comm_stream); (void)hipStreamDestroy(T->comm_stream); }
     if (T->y_stream) { (void)hipStreamSynchronize(T->y_stream); (void)hipStreamDestroy(T->y_stream); }
@@ -713,7 +714,7 @@ long nf_info(nf_handle S, const char *key)
     K("dim", S->dim); K("nx", S->nx); K("ny", S->ny); K("nz", S->nz); K("ne", S->N); K("ng", S->ng);
     K("n_phi", S->nphi); K("n_J", S->nJ); K("n_loc", S->nloc); K("rt_order", S->k); K("p_order", S->m); K("last_outer", T->last_outer);
     K("last_cg_total", T->last_cg_total); K("coarse_outer", T->coarse_outer); K("device", S->device);
-    K("last_path", T->last_path); K("last_resident_serial", T->last_resident_serial); K("last_direct", T->last_direct); K("direct_standin_unconverged", T->standin_unconverged); K("n_local_slabs", T->slabs.size()); K("n_ranks", T->nproc); K("rank", T->rank); K("vec_reduce", T->last_vec_reduce); K("cg_reductions", T->last_cg_reductions); K("cg_form", T->last_cg_form); K("endpoint_weights", T->last_endpoint_w); K("xchg_comm", T->comm_x ? 1 : 0); K("last_xcd", T->last_xcd); K("xcd_solves", T->xcd_solves); K("xcd_refused", T->xcd_refused);
+    K("last_path", T->last_path); K("last_resident_serial", T->last_resident_serial); K("batch_launches", T->batch_launches); K("batch_capacity", T->batch_cap); K("compute_units", T->ncu); K("last_direct", T->last_direct); K("direct_standin_unconverged", T->standin_unconverged); K("n_local_slabs", T->slabs.size()); K("n_ranks", T->nproc); K("rank", T->rank); K("vec_reduce", T->last_vec_reduce); K("cg_reductions", T->last_cg_reductions); K("cg_form", T->last_cg_form); K("endpoint_weights", T->last_endpoint_w); K("xchg_comm", T->comm_x ? 1 : 0); K("last_xcd", T->last_xcd); K("xcd_solves", T->xcd_solves); K("xcd_refused", T->xcd_refused);
     K("void_cells", S->void_cells);
     K("line_dict_rejected", S->ld_rejected); K("line_dict_bytes", S->ld_bytes);
     K("transient_steps", transient_steps(S)); K("transient_rebuilds", S->tr_rebuilds);
@@ -3206,15 +3207,85 @@ static bool resident_serial_fits(const nf_team *T, const nf_solver *S, LanePlan 
     return T->opt.resident_serial && T->opt.resident_lds && lp.fits;
 }
 static const int NF_RESIDENT_UNAVAILABLE = 1;                     // positive: not an error code of the C ABI
-static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, const ChebTable &cheb, double cg_tol, int cg_max, double *keff_out)
+// The instantiation a mesh takes (nf_batch_result::variant), its two entries -- one mesh per launch, one mesh per workgroup -- and the dynamic LDS
+struct ResidentKernels { void (*one)(ResidentArgs); void (*batch)(ResidentArgsConst *, int); };
+static ResidentKernels resident_kernels(int variant)
 {
-    nf_solver *S = T->slabs[0];
-    const int ng = S->ng; hipStream_t st = T->stream;
-    ResidentArgs A; memset(&A, 0, sizeof A);
+#define NF_RES_K(...) ResidentKernels{ k_resident_keff<__VA_ARGS__>, k_resident_keff_batch<__VA_ARGS__> }
+    switch (variant) {
+    case 1: return NF_RES_K(false, 0, 1536);
+    case 2: return NF_RES_K(false, 0, 2560);
+    case 3: return NF_RES_K(false, 1, -1);
+    case 4: return NF_RES_K(false, 2, -1);
+    case 5: return NF_RES_K(false, 0);
+    case 6: return NF_RES_K(true, 0);
+    case 7: return NF_RES_K(false, 1);
+    case 8: return NF_RES_K(true, 1);
+    case 9: return NF_RES_K(false, 2);
+    case 10: return NF_RES_K(true, 2);
+    default: return ResidentKernels{ nullptr, nullptr };              // 0: no plan (resident_choose refused the mesh)
+    }
+#undef NF_RES_K
+}
+static const int NF_RESIDENT_BLOCK = 512;
+// What depends on the mesh and the options alone: the plan fields of A, the instantiation and its LDS.  Changes nothing; false: not eligible.
+struct ResidentLaunch { ResidentArgs A; int variant = 0; size_t lds = 0; bool serial = false; };
+static bool resident_choose(const nf_team *T, ResidentLaunch *R)
+{
+    const nf_solver *S = T->slabs[0];
+    ResidentArgs &A = R->A; memset(&A, 0, sizeof A);
     const bool planned = resident_plan(S, &A);
     LanePlan lp;
     const bool lanes_fit = resident_serial_fits(T, S, &lp);
-    if (!planned && !lanes_fit) return fail(NF_ERR_STATE, "resident solve: mesh not eligible");
+    if (!planned && !lanes_fit) return false;
+    // LDS plan: 160 KiB per workgroup; behind the scratch of the direction passes the CG vectors and this group's factors, in
+    // priority order, as far as they fit (ResidentArgs::lds_mask)
+    A.lds_mask = 0;
+    // the line-per-lane variants, when everything their sweeps touch fits in LDS (p, the contribution of every direction, the factors and
+    // the per-line values): RT0-P0 at a compile-time block pitch; RT_k-P_m with bubble moments, DOF = moment * PC + padded cell
+    const long cap = resident_lds_cap(T);
+    R->serial = S->nphi <= T->opt.resident_serial_max_dofs && lanes_fit;
+    if (R->serial) {
+        for (int d = 0; d < 3; ++d) A.tw[d] = lp.tw[d];
+        for (int d = 0; d < 4; ++d) A.slot0[d] = lp.slot0[d];
+        R->lds = (size_t)lp.need * sizeof(double);
+        if (S->nb == 0) R->variant = lp.pitch == 1536 ? 1 : 2;
+        else {
+            R->variant = S->nb == 1 ? 3 : 4;
+            A.PC = (int)lp.PC;
+            const int nm = n_modes(S);
+            const ModeArgs c = mode_args(S, 0, 0, 0, S->d_p, S->d_q);
+            for (int d = 0; d < S->dim; ++d)
+                for (int m = 0; m < nm; ++m) {
+                    double Ta = 1.0;
+                    for (int i = 0; i <= S->nb; ++i) A.mom[d][m][i] = moment_index(S, d, m, i, &Ta);
+                    for (int l = 0; l < S->nb; ++l) A.diagc[A.mom[d][m][l + 1]][d] = Ta * c.Gc[l] * c.Gc[l] * c.iM[l];
+                }
+        }
+        return true;
+    }
+    if (!planned) return false;
+    long used = 5 * NF_RESIDENT_BLOCK + 64 + 16;
+    if (T->opt.resident_lds) {
+        const long NP2 = (S->nphi + 1) & ~1L, N2 = (S->N + 1) & ~1L;
+        const int bits[11] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10 };
+        for (int b : bits) {
+            if ((b == 6 || b == 7) && S->dim < 2) continue;
+            if ((b == 8 || b == 9) && S->dim < 3) continue;
+            const long need = (b <= 3 || b == 10) ? NP2 : N2;
+            if (used + need <= cap) { used += need; A.lds_mask |= 1 << b; }
+        }
+    }
+    R->lds = (size_t)used * sizeof(double);
+    R->variant = 5 + 2 * S->nb + (S->nx % 2 == 0 ? 1 : 0);
+    return true;
+}
+// fill: on top of a plan (resident_choose) everything else k_resident_keff reads for this solve, the history buffers included.  Launches nothing.
+static int resident_fill(nf_team *T, const nf_keff_opts *o, double keff0, const ChebTable &cheb, double cg_tol, int cg_max, ResidentLaunch *R)
+{
+    nf_solver *S = T->slabs[0];
+    const int ng = S->ng;
+    ResidentArgs &A = R->A;
     A.G = make_geom(S); A.ng = ng; A.dim = S->dim; A.nmodes = n_modes(S); A.N = S->N; A.nphi = S->nphi;
     for (int d = 0; d < 3; ++d) {
         const int dd = d < S->dim ? d : 0;
@@ -3227,68 +3298,15 @@ static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, 
     A.cheb = cheb;
     NFCHK(hist_reserve(T, o->max_outer, true));
 #ifdef NF_STAMPS
-    (void)hipMemsetAsync(T->d_hist + 3 * (size_t)o->max_outer, 0, 8 * sizeof(double), st);
+    (void)hipMemsetAsync(T->d_hist + 3 * (size_t)o->max_outer, 0, 8 * sizeof(double), T->stream);
 #endif
-    A.hist = T->d_hist; A.hist_cg = T->d_hist_cg; A.out = T->d_rout;
-    // the kernel indexes its history with max_outer as the row length
-    const int B = 512;
-    // LDS plan: 160 KiB per workgroup; behind the scratch of the direction passes the CG vectors and this group's factors, in
-    // priority order, as far as they fit (ResidentArgs::lds_mask)
-    A.Cd0 = S->d_Cd; A.lds_mask = 0;
-    // the line-per-lane variants, when everything their sweeps touch fits in LDS (p, the contribution of every direction, the factors and
-    // the per-line values): RT0-P0 at a compile-time block pitch; RT_k-P_m with bubble moments, DOF = moment * PC + padded cell
-    const long cap = resident_lds_cap(T);
-    const bool serial = S->nphi <= T->opt.resident_serial_max_dofs && lanes_fit;
-    if (serial) {
-        for (int d = 0; d < 3; ++d) A.tw[d] = lp.tw[d];
-        for (int d = 0; d < 4; ++d) A.slot0[d] = lp.slot0[d];
-        const size_t lds = (size_t)lp.need * sizeof(double);
-        if (S->nb == 0) {
-#define NF_RES_SERIAL(P) do { if (!lds_opt_in((const void *)k_resident_keff<false, 0, P>, lds)) return NF_RESIDENT_UNAVAILABLE; \
-            hipLaunchKernelGGL((k_resident_keff<false, 0, P>), dim3(1), dim3(B), lds, st, A); } while (0)
-            if (lp.pitch == 1536) NF_RES_SERIAL(1536); else NF_RES_SERIAL(2560);
-#undef NF_RES_SERIAL
-        } else {
-            A.PC = (int)lp.PC;
-            memset(A.mom, 0, sizeof A.mom); memset(A.diagc, 0, sizeof A.diagc);
-            const int nm = n_modes(S);
-            const ModeArgs c = mode_args(S, 0, 0, 0, S->d_p, S->d_q);
-            for (int d = 0; d < S->dim; ++d)
-                for (int m = 0; m < nm; ++m) {
-                    double Ta = 1.0;
-                    for (int i = 0; i <= S->nb; ++i) A.mom[d][m][i] = moment_index(S, d, m, i, &Ta);
-                    for (int l = 0; l < S->nb; ++l) A.diagc[A.mom[d][m][l + 1]][d] = Ta * c.Gc[l] * c.Gc[l] * c.iM[l];
-                }
-#define NF_RES_HI(NBV) do { if (!lds_opt_in((const void *)k_resident_keff<false, NBV, -1>, lds)) return NF_RESIDENT_UNAVAILABLE; \
-            hipLaunchKernelGGL((k_resident_keff<false, NBV, -1>), dim3(1), dim3(B), lds, st, A); } while (0)
-            if (S->nb == 1) NF_RES_HI(1); else NF_RES_HI(2);
-#undef NF_RES_HI
-        }
-    }
-    T->last_resident_serial = serial ? 1 : 0;
-    if (!serial && !planned) return fail(NF_ERR_STATE, "resident solve: mesh not eligible");
-    if (!serial) {
-    long used = 5 * B + 64 + 16;
-    if (T->opt.resident_lds) {
-        const long NP2 = (S->nphi + 1) & ~1L, N2 = (S->N + 1) & ~1L;
-        const int bits[11] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10 };
-        for (int b : bits) {
-            if ((b == 6 || b == 7) && S->dim < 2) continue;
-            if ((b == 8 || b == 9) && S->dim < 3) continue;
-            const long need = (b <= 3 || b == 10) ? NP2 : N2;
-            if (used + need <= cap) { used += need; A.lds_mask |= 1 << b; }
-        }
-    }
-    const size_t lds = (size_t)used * sizeof(double);
-#define NF_RES(VECV, NBV) do { if (!lds_opt_in((const void *)k_resident_keff<VECV, NBV>, lds)) return NF_RESIDENT_UNAVAILABLE; \
-        hipLaunchKernelGGL((k_resident_keff<VECV, NBV>), dim3(1), dim3(B), lds, st, A); } while (0)
-    const bool vec = S->nx % 2 == 0;
-    if (S->nb == 0) { if (vec) NF_RES(true, 0); else NF_RES(false, 0); }
-    else if (S->nb == 1) { if (vec) NF_RES(true, 1); else NF_RES(false, 1); }
-    else { if (vec) NF_RES(true, 2); else NF_RES(false, 2); }
-#undef NF_RES
-    }
-    HIPCHK(hipGetLastError());
+    A.hist = T->d_hist; A.hist_cg = T->d_hist_cg; A.out = T->d_rout;   // the kernel indexes its history with max_outer as the row length
+    A.Cd0 = S->d_Cd;
+    return NF_OK;
+}
+// fetch: what the kernel left for this team -- ResidentOut and the history -- once its launch is queued on `st` (or has finished)
+static int resident_fetch(nf_team *T, const nf_keff_opts *o, hipStream_t st, double *keff_out)
+{
     ResidentOut ro;
     HIPCHK(hipMemcpyAsync(&ro, T->d_rout, sizeof ro, hipMemcpyDeviceToHost, st));
     HIPCHK(stream_wait(st));
@@ -3300,6 +3318,19 @@ static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, 
 #endif
     *keff_out = ro.keff;
     return NF_OK;
+}
+static int solve_keff_resident(nf_team *T, const nf_keff_opts *o, double keff0, const ChebTable &cheb, double cg_tol, int cg_max, double *keff_out)
+{
+    ResidentLaunch R;
+    if (!resident_choose(T, &R)) return fail(NF_ERR_STATE, "resident solve: mesh not eligible");
+    NFCHK(resident_fill(T, o, keff0, cheb, cg_tol, cg_max, &R));
+    const ResidentKernels K = resident_kernels(R.variant);
+    if (!K.one) return fail(NF_ERR_STATE, "resident solve: no kernel for this plan");
+    if (!lds_opt_in((const void *)K.one, R.lds)) { if (!R.serial) T->last_resident_serial = 0; return NF_RESIDENT_UNAVAILABLE; }
+    hipLaunchKernelGGL(K.one, dim3(1), dim3(NF_RESIDENT_BLOCK), R.lds, T->stream, R.A);
+    T->last_resident_serial = R.serial ? 1 : 0;
+    HIPCHK(hipGetLastError());
+    return resident_fetch(T, o, T->stream, keff_out);
 }
 
 // ---- whole SolveKeff on one XCD (k_keff_xcd): the meshes of k_cg_xcd, iterative full-Schur path ------------------------
@@ -3365,13 +3396,14 @@ static InnerPlan inner_plan(const nf_team *T, const nf_keff_opts *o)
 // group solver of inner_plan, last_direct, and the dense S^-1 where inner_plan picks it.  DIAG_LEAN (SolveModes) is DIAG_OK without the
 // dense S^-1 the diagonal path never reads; SolveKeff and SolveSubcritical have always formed it.
 enum DiagUse { DIAG_NEVER, DIAG_OK, DIAG_LEAN };
+static bool diag_wanted(const nf_solver *S0, const nf_keff_opts *o) { return o->use_diagonal_solver && S0->k == 0 && S0->m == 0; }   // :1640-1644
 struct Inner { InnerPlan ip; int use_diag; };
 template <class Between>
 static int inner_begin(nf_team *T, const nf_keff_opts *o, DiagUse diag, Inner *in, Between between)
 {
     nf_solver *S0 = T->slabs[0];
     NFCHK(team_prepare(T));
-    in->use_diag = (diag != DIAG_NEVER && o->use_diagonal_solver && S0->k == 0 && S0->m == 0) ? 1 : 0;
+    in->use_diag = (diag != DIAG_NEVER && diag_wanted(S0, o)) ? 1 : 0;
     if (in->use_diag) NFCHK(nf_build_diagonal_cache(S0));
     NFCHK(between());
     in->ip = inner_plan(T, o);
@@ -3445,16 +3477,23 @@ static int group_sweep(nf_team *T, const InnerPlan &ip, int use_diag, GroupSweep
     return NF_OK;
 }
 
-static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, int *n_outer)
+// Whether SolveKeff of this team with these options runs in one workgroup (k_resident_keff); nf_solve_keff_batch asks the same question
+// before it touches anything.  Reads the team, the options and the group solver they pick, changes nothing.
+static bool keff_takes_resident(const nf_team *T, const nf_keff_opts *o, const InnerPlan &ip, int use_diag)
 {
-    const int ns = (int)T->slabs.size();
-    nf_solver *S0 = T->slabs[0];
-    const int ng = S0->ng;
-    const bool single = team_is_single(T);
-    const bool use_cmfd = o->use_cmfd != 0;
+    const nf_solver *S0 = T->slabs[0];
+    ResidentArgs probe;
+    return team_is_single(T) && !use_diag && !o->use_cmfd && !ip.direct && !T->rccl_reduce && T->opt.resident && o->max_outer > 0 && !S0->d_void &&   // nf_set_void: the resident kernel knows no mask
+           ((S0->nphi <= T->opt.resident_max_dofs && resident_plan(S0, &probe)) || (S0->nphi <= T->opt.resident_serial_max_dofs && resident_serial_fits(T, S0)));
+}
+// What SolveKeff does before its first outer: inner_begin with CMFD and the coarse start in between, the start value of k, the reset of
+// the history.  And every exit of a finished solve (:1808-1809).  jz_valid is read by nf_get_J on slabs with an interface only, which the
+// exits of the undivided paths never see (team_is_single): clearing it there too changes nothing
+static int keff_begin(nf_team *T, const nf_keff_opts *o, Inner *in, double *keff0)
+{
     double keff = 1.0;
     auto cmfd_and_coarse_start = [&]() -> int {
-        if (use_cmfd) NFCHK(cmfd_initialize_team(T));             // :1655-1658
+        if (o->use_cmfd) NFCHK(cmfd_initialize_team(T));          // :1655-1658
         keff = T->has_valid_keff ? T->last_keff : 1.0;            // :1662
         T->coarse_outer = 0;
         if (o->use_coarse_init && o->n_coarse_factors > 0) {      // :1665-1670
@@ -3465,23 +3504,36 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
         }
         return NF_OK;
     };
-    Inner in;
-    NFCHK(inner_begin(T, o, DIAG_OK, &in, cmfd_and_coarse_start));
-    const InnerPlan &ip = in.ip; const int use_diag = in.use_diag;
-    const ChebTable cheb = cheb_table();                          // ChebyshevAccel(15, 0.98), src/solvers.cpp:664-700
-    int cheb_it = 0;
+    NFCHK(inner_begin(T, o, DIAG_OK, in, cmfd_and_coarse_start));
     T->hist_k.clear(); T->hist_dk.clear(); T->hist_dphi.clear(); T->hist_cg.clear();
     T->last_outer = 0; T->last_cg_total = 0;
     T->profile = o->profile != 0;
-    // every exit of a finished solve (:1808-1809).  jz_valid is read by nf_get_J on slabs with an interface only, which the exits of the
-    // undivided paths never see (team_is_single): clearing it there too changes nothing
-    auto finish = [&](bool is_diag) {
-        for (auto *S : T->slabs) { S->raw_valid = T->last_outer > 0; S->raw_is_diag = is_diag; S->jz_valid = false; }
-        T->has_valid_keff = 1; T->last_keff = keff;
-        if (keff_out) *keff_out = keff;
-        if (n_outer) *n_outer = T->last_outer;
-        return NF_OK;
-    };
+    *keff0 = keff;
+    return NF_OK;
+}
+static int keff_finish(nf_team *T, double keff, bool is_diag, double *keff_out, int *n_outer)
+{
+    for (auto *S : T->slabs) { S->raw_valid = T->last_outer > 0; S->raw_is_diag = is_diag; S->jz_valid = false; }
+    T->has_valid_keff = 1; T->last_keff = keff;
+    if (keff_out) *keff_out = keff;
+    if (n_outer) *n_outer = T->last_outer;
+    return NF_OK;
+}
+
+static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, int *n_outer)
+{
+    const int ns = (int)T->slabs.size();
+    nf_solver *S0 = T->slabs[0];
+    const int ng = S0->ng;
+    const bool single = team_is_single(T);
+    const bool use_cmfd = o->use_cmfd != 0;
+    double keff = 1.0;
+    Inner in;
+    NFCHK(keff_begin(T, o, &in, &keff));
+    const InnerPlan &ip = in.ip; const int use_diag = in.use_diag;
+    const ChebTable cheb = cheb_table();                          // ChebyshevAccel(15, 0.98), src/solvers.cpp:664-700
+    int cheb_it = 0;
+    auto finish = [&](bool is_diag) { return keff_finish(T, keff, is_diag, keff_out, n_outer); };
     if (use_diag && single && !use_cmfd && !T->rccl_reduce && T->opt.outer_dev && o->max_outer > 0) {
         NFCHK(solve_keff_diag_device(T, o, keff, cheb, &keff));
         HIPCHK(hipStreamSynchronize(T->stream));
@@ -3489,16 +3541,12 @@ static int solve_keff_impl(nf_team *T, const nf_keff_opts *o, double *keff_out, 
         return finish(true);
     }
     T->last_path = 0;
-    {
-        ResidentArgs probe;
-        if (single && !use_diag && !use_cmfd && !ip.direct && !T->rccl_reduce && T->opt.resident && o->max_outer > 0 && !S0->d_void &&   // nf_set_void: the resident kernel knows no mask
-            ((S0->nphi <= T->opt.resident_max_dofs && resident_plan(S0, &probe)) || (S0->nphi <= T->opt.resident_serial_max_dofs && resident_serial_fits(T, S0)))) {
-            const bool prof_req = T->profile;
-            T->last_path = 2; T->profile = false;
-            const int rr = solve_keff_resident(T, o, keff, cheb, ip.cg_tol, ip.cg_max, &keff);
-            if (rr != NF_RESIDENT_UNAVAILABLE) { NFCHK(rr); return finish(false); }
-            T->last_path = 0; T->profile = prof_req;              // the device refused the LDS the resident kernel plans with: host-driven path
-        }
+    if (keff_takes_resident(T, o, ip, use_diag)) {
+        const bool prof_req = T->profile;
+        T->last_path = 2; T->profile = false;
+        const int rr = solve_keff_resident(T, o, keff, cheb, ip.cg_tol, ip.cg_max, &keff);
+        if (rr != NF_RESIDENT_UNAVAILABLE) { NFCHK(rr); return finish(false); }
+        T->last_path = 0; T->profile = prof_req;                  // the device refused the LDS the resident kernel plans with: host-driven path
     }
     // mid-size meshes (2 k - 28 k unknowns per group, every order): the whole power iteration in one launch on one XCD (k_keff_xcd),
     // where the group solves would take the one-XCD form of CG
@@ -3580,6 +3628,103 @@ int nf_solve_keff(nf_handle S, const nf_keff_opts *o, double *keff, int *n_outer
     HIPCHK(hipSetDevice(S->device));
     __atomic_store_n(&S->team->outers_done, 0L, __ATOMIC_RELEASE);
     return solve_keff_impl(S->team, o, keff, n_outer);
+}
+
+// ---- nf_solve_keff_batch: n independent small meshes, one workgroup each, in one launch (k_resident_keff_batch) ----------
+// Batched route or not: decided from the handles, the options and the plans alone, before anything is touched.  On the batched route every
+// handle runs keff_begin, resident_fill, resident_fetch and keff_finish -- the functions solve_keff_impl runs around its own launch -- so that
+// what a handle holds afterwards is what nf_solve_keff leaves; the one thing the handles share is the launch.
+int nf_solve_keff_batch(nf_handle *h, int n, const nf_keff_opts *opts, int n_opts, double *keff, int *n_outer, int *status, nf_batch_result *res)
+{
+    if (!h || !opts || n < 1 || (n_opts != 1 && n_opts != n)) return fail(NF_ERR_ARG, "nf_solve_keff_batch: n >= 1 handles and 1 or n option sets");
+    for (int i = 0; i < n; ++i) {
+        if (!h[i]) return fail(NF_ERR_ARG, "nf_solve_keff_batch: handle %d is NULL", i);
+        if (h[i]->device != h[0]->device) return fail(NF_ERR_ARG, "nf_solve_keff_batch: handle %d is on device %d, handle 0 on device %d", i, h[i]->device, h[0]->device);
+    }
+    { std::vector<nf_solver *> sorted(h, h + n); std::sort(sorted.begin(), sorted.end());
+      if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(NF_ERR_ARG, "nf_solve_keff_batch: the same handle twice (two workgroups would write the same vectors)"); }
+    for (int i = 0; i < n; ++i) {
+        const nf_team *T = h[i]->team;
+        if (T->dead) return fail(NF_ERR_COMM, "nf_solve_keff_batch: the team of handle %d lost a collective (NF_ERR_COMM) and is unusable", i);
+        if (!team_is_single(T)) return fail(NF_ERR_UNSUPPORTED, "nf_solve_keff_batch: handle %d is a slab (nf_create_slab / nf_link_slabs); a batch takes undivided meshes only", i);
+        if (T->nproc > 1 || T->comm || T->rccl_reduce) return fail(NF_ERR_UNSUPPORTED, "nf_solve_keff_batch: handle %d has a communicator (nf_comm_init); a batch must not reorder collectives", i);
+        if (!h[i]->built) return fail(NF_ERR_STATE, "nf_solve_keff_batch: handle %d: call nf_build first", i);
+    }
+    auto opt_of = [&](int i) { return &opts[n_opts == 1 ? 0 : i]; };
+    if (res) { res->n_batched = res->n_sequential = res->n_launches = res->variant = 0; }
+    HIPCHK(hipSetDevice(h[0]->device));
+    nf_team *T0 = h[0]->team;
+    // ---- the route
+    std::vector<ResidentLaunch> R(n);
+    bool batched = true;
+    for (int i = 0; i < n && batched; ++i) {
+        const nf_solver *S = h[i], *S0 = h[0]; const nf_team *T = S->team; const nf_keff_opts *o = opt_of(i);
+        const NfOptions &a = T->opt, &b = T0->opt;
+        batched = S->k == S0->k && S->m == S0->m && S->ng == S0->ng && S->dim == S0->dim && S->nx == S0->nx && S->ny == S0->ny && S->nz == S0->nz &&
+                  a.resident_serial == b.resident_serial && a.resident_lds == b.resident_lds && a.resident_two_sided == b.resident_two_sided &&
+                  a.resident_serial_max_dofs == b.resident_serial_max_dofs && a.resident_max_dofs == b.resident_max_dofs && T->lds_limit == T0->lds_limit &&
+                  !o->use_coarse_init && keff_takes_resident(T, o, inner_plan(T, o), diag_wanted(S, o) ? 1 : 0) && resident_choose(T, &R[i]) &&
+                  R[i].variant == R[0].variant && R[i].lds == R[0].lds;
+    }
+    const ResidentKernels K = resident_kernels(batched ? R[0].variant : 0);
+    if (batched && (!K.batch || !lds_opt_in((const void *)K.batch, R[0].lds))) batched = false;   // the device refuses the LDS the plan asks for: nothing touched yet
+    int first = NF_OK;
+    if (!batched) {
+        for (int i = 0; i < n; ++i) {
+            double k = 0.0; int no = 0;
+            const int rc = nf_solve_keff(h[i], opt_of(i), &k, &no);
+            if (keff) keff[i] = k;
+            if (n_outer) n_outer[i] = no;
+            if (status) status[i] = rc;
+            if (first == NF_OK) first = rc;
+        }
+        if (res) res->n_sequential = n;
+        return first;
+    }
+    // ---- per handle: the preamble of SolveKeff and the arguments of its workgroup
+    std::vector<ResidentArgs> args; args.reserve(n);
+    std::vector<int> live, st(n, NF_OK);
+    const ChebTable cheb = cheb_table();
+    for (int i = 0; i < n; ++i) {
+        nf_team *T = h[i]->team; const nf_keff_opts *o = opt_of(i);
+        __atomic_store_n(&T->outers_done, 0L, __ATOMIC_RELEASE);
+        Inner in; double k0 = 1.0;
+        st[i] = keff_begin(T, o, &in, &k0);
+        if (st[i] == NF_OK) { T->last_path = 2; T->profile = false; st[i] = resident_fill(T, o, k0, cheb, in.ip.cg_tol, in.ip.cg_max, &R[i]); }
+        if (st[i] == NF_OK) { live.push_back(i); args.push_back(R[i].A); }
+    }
+    // ---- one launch: the structs into the grow-only array of the first team, every handle's stream drained, one workgroup per handle
+    const int nl = (int)live.size();
+    int launch_rc = NF_OK;
+    auto launch = [&]() -> int {
+        if (nl == 0) return NF_OK;
+        if (T0->batch_cap < nl) { T0->batch_cap = 0; NFCHK(dalloc(&T0->d_batch_args, (size_t)nl)); T0->batch_cap = nl; }
+        HIPCHK(hipMemcpyAsync(T0->d_batch_args, args.data(), (size_t)nl * sizeof(ResidentArgs), hipMemcpyHostToDevice, T0->stream));
+        for (int i : live) if (h[i]->team != T0) HIPCHK(stream_wait(h[i]->team->stream));
+        hipLaunchKernelGGL(K.batch, dim3(nl), dim3(NF_RESIDENT_BLOCK), R[0].lds, T0->stream, (ResidentArgsConst *)T0->d_batch_args, nl);
+        HIPCHK(hipGetLastError());
+        ++T0->batch_launches;
+        HIPCHK(stream_wait(T0->stream));
+        return NF_OK;
+    };
+    launch_rc = launch();
+    // ---- per handle: what solve_keff_resident does after its launch, and the exit of a finished solve
+    for (int i = 0; i < n; ++i) {
+        nf_team *T = h[i]->team;
+        double k = 0.0; int no = 0;
+        if (st[i] == NF_OK && launch_rc != NF_OK) st[i] = launch_rc;
+        if (st[i] == NF_OK) {
+            T->last_resident_serial = R[i].serial ? 1 : 0;
+            st[i] = resident_fetch(T, opt_of(i), T->stream, &k);
+            if (st[i] == NF_OK) st[i] = keff_finish(T, k, false, &k, &no);
+        }
+        if (keff) keff[i] = k;
+        if (n_outer) n_outer[i] = no;
+        if (status) status[i] = st[i];
+        if (first == NF_OK) first = st[i];
+    }
+    if (res) { res->n_batched = nl; res->n_launches = nl > 0 && launch_rc == NF_OK ? 1 : 0; res->variant = R[0].variant; }
+    return first;
 }
 
 int nf_set_progress_callback(nf_handle S, nf_progress_fn fn, void *user)

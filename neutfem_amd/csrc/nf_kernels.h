@@ -3221,8 +3221,10 @@ __device__ __forceinline__ double resident_s_pass(const ResidentArgs &A, int r, 
     }
     return dot;
 }
-template <bool VEC, int NB, int PITCH = 0>                        // PITCH > 0: the line-per-lane variant (RT0-P0, everything in LDS)
-__global__ __launch_bounds__(512) void k_resident_keff(ResidentArgs A)
+// The solve of one workgroup; no blockIdx / gridDim below, nothing shared with another workgroup.  Two entries call it: k_resident_keff
+// (one mesh, the struct a kernel argument) and k_resident_keff_batch (one mesh per workgroup, the structs in a device array).
+template <bool VEC, int NB, int PITCH>                            // PITCH > 0: the line-per-lane variant (RT0-P0, everything in LDS)
+__device__ __forceinline__ void resident_keff_body(const ResidentArgs &A)
 {
     constexpr bool SERIAL = PITCH > 0;                             // RT0-P0 line-per-lane variant
     constexpr bool SERH = PITCH < 0;                               // line-per-lane variant with bubble moments
@@ -3234,6 +3236,11 @@ __global__ __launch_bounds__(512) void k_resident_keff(ResidentArgs A)
     double *sred = sm + scr + 64;
     const int tid = threadIdx.x, nt = blockDim.x, wave = tid >> 6, nw = nt >> 6;
     const int ng = A.ng; const long N = A.N, NP = A.nphi, NT = NP * ng;
+    // the lane plan's per-direction values by name (Tri, below): read here once, so that no chain d == 0 ? A.v[0] : ... is left that the
+    // optimiser could turn into a choice between addresses inside A -- with those the struct is no longer taken apart and goes to scratch whole
+    const Tri<int> aS0 = { A.slot0[0], A.slot0[1], A.slot0[2] }, aTw = { A.tw[0], A.tw[1], A.tw[2] }, aNl = { (int)A.nlines[0], (int)A.nlines[1], (int)A.nlines[2] };
+    const Tri<double> aTa = { A.ma[0].Ta, A.ma[1].Ta, A.ma[2].Ta };
+    const int aSlots = A.slot0[3];
     SlabArgs sa0; sa0.if_lo = sa0.if_hi = sa0.mode = sa0.xcd = sa0.wsmin = sa0.fold = sa0.noacc = 0; sa0.yadd = nullptr; sa0.alo = sa0.ahi = sa0.ulo = sa0.uhi = sa0.rlo = sa0.rhi = sa0.sinv_lo = sa0.sinv_hi = nullptr; sa0.clo = sa0.chi = sa0.jz = sa0.jzb = nullptr; sa0.nfa = 1; sa0.ni = 0;
     // vectors and factors that fit are kept in LDS behind the scratch area (ResidentArgs::lds_mask); the rest stays in global memory
     double *lds = sm + scr + 64 + 16;
@@ -3381,11 +3388,11 @@ __global__ __launch_bounds__(512) void k_resident_keff(ResidentArgs A)
                 struct LaneLine { bool ok, tw, top; int cnt, sl, o1, o2; double d0, dm, Ta; const lds_f64 *x, *L; lds_f64 *y; HiConst c; };
                 auto lane_line = [&](int sl_) -> LaneLine {
                     LaneLine o; o.ok = false; o.tw = o.top = false; o.cnt = o.sl = o.o1 = o.o2 = 0; o.d0 = o.dm = o.Ta = 0.0; o.x = o.L = hp; o.y = hc[0]; o.c = hcst;
-                    if (sl_ >= A.slot0[3]) return o;
-                    const int d = sl_ >= A.slot0[2] ? 2 : sl_ >= A.slot0[1] ? 1 : 0;
-                    const int nl = d == 0 ? (int)A.nlines[0] : d == 1 ? (int)A.nlines[1] : (int)A.nlines[2];
-                    const int twd = d == 0 ? A.tw[0] : d == 1 ? A.tw[1] : A.tw[2];
-                    const int rem = sl_ - (d == 0 ? A.slot0[0] : d == 1 ? A.slot0[1] : A.slot0[2]);
+                    if (sl_ >= aSlots) return o;
+                    const int d = sl_ >= aS0.c ? 2 : sl_ >= aS0.b ? 1 : 0;
+                    const int nl = aNl[d];
+                    const int twd = aTw[d];
+                    const int rem = sl_ - (aS0[d]);
                     const int lane_l = twd ? rem >> 1 : rem;
                     const int mode = lane_l / nl, l = lane_l - mode * nl;
                     if (mode >= nm) return o;
@@ -3414,7 +3421,7 @@ __global__ __launch_bounds__(512) void k_resident_keff(ResidentArgs A)
                         for (int sl_ = tid;;) {                  // one call site: slot tid from the registers, any further slot decoded on the way
                             if (o.ok) serial_line_hi<NB>(o.x, o.o1, o.o2, o.L, hPC, o.y, o.d0, o.dm, o.Ta, o.c, o.cnt, o.sl, o.tw, o.top);
                             sl_ += nt;
-                            if (sl_ >= A.slot0[3]) break;
+                            if (sl_ >= aSlots) break;
                             o = lane_line(sl_);
                         }
                     }
@@ -3485,10 +3492,10 @@ __global__ __launch_bounds__(512) void k_resident_keff(ResidentArgs A)
                 const int nx = A.G.nx, ny = A.G.ny;
                 // two-sided directions: the odd lane of every pair rewrites the upper half of its line with the mirrored factors
                 __syncthreads();
-                for (int sl_ = tid; sl_ < A.slot0[3]; sl_ += nt) {
-                    const int d = sl_ >= A.slot0[2] ? 2 : sl_ >= A.slot0[1] ? 1 : 0;
-                    const int rem = sl_ - (d == 0 ? A.slot0[0] : d == 1 ? A.slot0[1] : A.slot0[2]);
-                    const int twd = d == 0 ? A.tw[0] : d == 1 ? A.tw[1] : A.tw[2], nl = d == 0 ? (int)A.nlines[0] : d == 1 ? (int)A.nlines[1] : (int)A.nlines[2];
+                for (int sl_ = tid; sl_ < aSlots; sl_ += nt) {
+                    const int d = sl_ >= aS0.c ? 2 : sl_ >= aS0.b ? 1 : 0;
+                    const int rem = sl_ - (aS0[d]);
+                    const int twd = aTw[d], nl = aNl[d];
                     const int l = rem >> 1;
                     if (twd && (rem & 1) && l < nl) {
                         const int base = d == 0 ? l * nxp : d == 1 ? (l / nx) * nxp * ny + l % nx : (l / nx) * nxp + l % nx;
@@ -3525,10 +3532,10 @@ __global__ __launch_bounds__(512) void k_resident_keff(ResidentArgs A)
                 struct LaneLine { bool ok, tw, top; int cnt, base, sl; double d0, dm, Ta; lds_f64 *blk; };
                 auto lane_line = [&](int sl_) -> LaneLine {
                     LaneLine o; o.ok = false; o.tw = o.top = false; o.cnt = o.base = o.sl = 0; o.d0 = o.dm = o.Ta = 0.0; o.blk = lb[0];
-                    if (sl_ >= A.slot0[3]) return o;
-                    const int d = sl_ >= A.slot0[2] ? 2 : sl_ >= A.slot0[1] ? 1 : 0;
-                    const int rem = sl_ - (d == 0 ? A.slot0[0] : d == 1 ? A.slot0[1] : A.slot0[2]);
-                    const int twd = d == 0 ? A.tw[0] : d == 1 ? A.tw[1] : A.tw[2], nl = d == 0 ? (int)A.nlines[0] : d == 1 ? (int)A.nlines[1] : (int)A.nlines[2];
+                    if (sl_ >= aSlots) return o;
+                    const int d = sl_ >= aS0.c ? 2 : sl_ >= aS0.b ? 1 : 0;
+                    const int rem = sl_ - (aS0[d]);
+                    const int twd = aTw[d], nl = aNl[d];
                     const int l = twd ? rem >> 1 : rem;
                     if (l >= nl) return o;
                     o.ok = true; o.tw = twd != 0; o.top = !twd || !(rem & 1);
@@ -3536,7 +3543,7 @@ __global__ __launch_bounds__(512) void k_resident_keff(ResidentArgs A)
                     const int sl0 = d == 0 ? 1 : d == 1 ? nxp : nxp * ny, n = d == 0 ? nx : d == 1 ? ny : A.G.nz;
                     o.cnt = !twd ? n : o.top ? n / 2 : n - n / 2;
                     o.base = o.top ? base0 : base0 + (n - 1) * sl0; o.sl = o.top ? sl0 : -sl0;
-                    o.Ta = d == 0 ? A.ma[0].Ta : d == 1 ? A.ma[1].Ta : A.ma[2].Ta;
+                    o.Ta = aTa[d];
                     o.blk = d == 0 ? lb[0] : d == 1 ? lb[1] : lb[2];
                     o.d0 = o.top ? (d == 0 ? lD[0] : d == 1 ? lD[1] : lD[2])[l] : (d == 0 ? lDr[0] : d == 1 ? lDr[1] : lDr[2])[l];
                     o.dm = twd ? (d == 0 ? lDm[0] : d == 1 ? lDm[1] : lDm[2])[l] : 0.0;
@@ -3553,7 +3560,7 @@ __global__ __launch_bounds__(512) void k_resident_keff(ResidentArgs A)
                         for (int sl_ = tid;;) {                  // one call site: slot tid from the registers, any further slot decoded on the way
                             if (o.ok) serial_line_rt0<PITCH>(lp, o.blk, o.d0, o.dm, o.Ta, o.cnt, o.base, o.sl, o.tw, o.top);
                             sl_ += nt;
-                            if (sl_ >= A.slot0[3]) break;
+                            if (sl_ >= aSlots) break;
                             o = lane_line(sl_);
                         }
                     }
@@ -3714,6 +3721,22 @@ __global__ __launch_bounds__(512) void k_resident_keff(ResidentArgs A)
         if (outer_converged(os.dk, os.dphi, A.tol_keff, A.tol_flux)) break;   // :1799-1802
     }
     if (tid == 0) { A.out->keff = keff; A.out->n_outer = n_outer; A.out->status = status; A.out->cg_total = cg_total; }
+}
+template <bool VEC, int NB, int PITCH = 0>
+__global__ __launch_bounds__(512) void k_resident_keff(ResidentArgs A) { resident_keff_body<VEC, NB, PITCH>(A); }
+// N independent meshes in one launch, workgroup b solves args[b] (nf_solve_keff_batch).  No workgroup waits for another,
+// so a grid larger than the chip simply runs in turns.  args[b] has to behave like the kernel argument of the entry above: a uniform
+// address, scalar loads where a member is used, known not to change under the body's barriers and stores, never copied to registers or
+// scratch, and the pointers in it known to be global ones (SGPR base + lane offset, not a 64-bit flat address per lane).  A by-value
+// kernel argument is all that because it lies in the constant address space; so the array is declared there.  (Reading a plain global
+// pointer through a constant-address-space cast gives the scalar loads but leaves the pointers flat: +16 VGPRs and spills at RT1 / RT2.)
+typedef __attribute__((address_space(4))) const ResidentArgs ResidentArgsConst;
+template <bool VEC, int NB, int PITCH = 0>
+__global__ __launch_bounds__(512) void k_resident_keff_batch(ResidentArgsConst *args, int n)
+{
+    const int b = blockIdx.x;
+    if (b >= n) return;
+    resident_keff_body<VEC, NB, PITCH>(*(const ResidentArgs *)(args + b));
 }
 
 // ---------------------------------------------------------------------------------------------
