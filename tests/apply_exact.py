@@ -19,7 +19,9 @@ entries: with IAEA-3D's filler material (D = 1e-3, Sigma_R = 1e15) max |y| is 1e
 anything.
 
 Also here: f6_block_inputs (block-structured inputs with that filler), exact_cg2 (two CG steps on the exact apply), and ExactTwin, the
-same yardstick for the higher orders: the scipy twin's operator with exact local tables, applied by iterative refinement."""
+same yardstick for the higher orders: the scipy twin's operator with exact local tables, applied by iterative refinement.  exact_cg2_op
+runs the two CG steps on any such operator, ExactTwin.outer one outer iteration of SolveKeff for any order, and ORDER_CASES with
+order_ref_cg / order_ref_outer are the cases and shared references of tests/test_gpu_orders_exact.py."""
 import numpy as np
 
 LD = np.longdouble
@@ -131,46 +133,54 @@ def normwise(y, y_ref):
     return float(np.abs(np.asarray(y) - y_ref).max() / np.abs(y_ref).max())
 
 
-def exact_cg2(inp, g, b):
-    """two CG steps from x = 0 (src/solvers.cpp:577-636 with tol = 0, maxit = 2) in extended precision with the exact apply:
+def exact_cg2_op(apply, b):
+    """two CG steps from x = 0 (src/solvers.cpp:577-636 with tol = 0, maxit = 2) in extended precision on any operator apply(x) -> (y, s):
     x2 = c b - a0 a1 S b, c = a0 + a1 (1 + b0).  Returns (x2, scale) with scale_i = |c| |b_i| + a0 a1 s_i(b)"""
-    op = ExactApply(inp, g)
     b = np.asarray(b).astype(LD).ravel()
-    Sb, sb = op.apply(b)
+    Sb, sb = apply(b)
     rr0 = (b * b).sum()
     a0 = rr0 / (b * Sb).sum()
     r1 = b - a0 * Sb
     rr1 = (r1 * r1).sum()
     b0 = rr1 / rr0
     p1 = r1 + b0 * b
-    q1, _ = op.apply(p1)
+    q1, _ = apply(p1)
     a1 = rr1 / (p1 * q1).sum()
     c = a0 + a1 * (LD(1) + b0)
     return a0 * b + a1 * p1, np.abs(c) * np.abs(b) + a0 * a1 * sb
 
 
+def exact_cg2(inp, g, b):
+    """exact_cg2_op on the closed-form RT0-P0 apply of group g"""
+    return exact_cg2_op(ExactApply(inp, g).apply, b)
+
+
 def f6_block_inputs(shape, block, seed=11, ng=2):
     """block_inputs of tests/test_gpu_line_dict.py at the benchmark's contrast: piecewise-constant cross-sections on blocks of `block`
     cells, widths exactly 1.25, a palette of four materials of which the last is IAEA-3D's filler (D = 1e-3, Sigma_R = 1e15, no fission,
-    no scattering) -- drawn with p = (0.25, 0.25, 0.17, 0.33); the removal cross-section of the other three lies in 0.01 ... 0.13."""
-    nx, ny, nz = shape
+    no scattering) -- drawn with p = (0.25, 0.25, 0.17, 0.33); the removal cross-section of the other three lies in 0.01 ... 0.13.
+    shape = (nx, ny, nz) with block = (bx, by, bz), or the 2D form (nx, ny) with (bx, by): arrays (ng, ny, nx), z_breaks = [0.0], attributes
+    1 ... 4 -- the same palette and the same draw."""
+    dims = tuple(shape)[::-1]                                     # (nz, ny, nx), or (ny, nx) of a 2D mesh
     rng = np.random.default_rng(seed)
     npal = 4
     pal = dict(D=rng.uniform(0.3, 1.8, (ng, npal)), SigR=rng.uniform(0.01, 0.13, (ng, npal)), NSF=rng.uniform(0.0, 0.3, (ng, npal)),
                S=rng.uniform(0.005, 0.05, npal))
     pal["D"][:, 3] = F6_D; pal["SigR"][:, 3] = F6_SIGR; pal["NSF"][:, 3] = 0.0; pal["S"][3] = 0.0
-    nb = [-(-n // b) for n, b in zip((nz, ny, nx), block[::-1])]
+    nb = [-(-n // b) for n, b in zip(dims, block[::-1])]
     mat = rng.choice(npal, size=nb, p=(0.25, 0.25, 0.17, 0.33))
     for ax, b in enumerate(block[::-1]):
         mat = np.repeat(mat, b, axis=ax)
-    mat = mat[:nz, :ny, :nx]
+    mat = mat[tuple(slice(0, n) for n in dims)]
     D, SigR, NSF = (np.stack([pal[k][g][mat] for g in range(ng)]) for k in ("D", "SigR", "NSF"))
     Chi = np.zeros((ng,) + mat.shape); Chi[0] = 0.8; Chi[1:2] = 0.2; Chi[:, mat == 3] = 0.0
     SigS = np.zeros((ng, ng) + mat.shape)
     if ng > 1: SigS[1, 0] = pal["S"][mat]
     brk = lambda n: 1.25 * np.arange(n + 1)
-    return dict(x_breaks=brk(nx), y_breaks=brk(ny), z_breaks=brk(nz), D=D, SigR=SigR, NSF=NSF, Chi=Chi, SigS=SigS, bc_attr=np.arange(1, 7),
-                bc_type=np.zeros(6, int), coarse_factors=np.array([1, 1, 1]), kref=1.0, ng=ng)
+    nattr = 2 * len(dims)
+    return dict(x_breaks=brk(dims[-1]), y_breaks=brk(dims[-2]), z_breaks=brk(dims[0]) if len(dims) == 3 else np.array([0.0]), D=D, SigR=SigR,
+                NSF=NSF, Chi=Chi, SigS=SigS, bc_attr=np.arange(1, nattr + 1), bc_type=np.zeros(nattr, int), coarse_factors=np.array([1, 1, 1]),
+                kref=1.0, ng=ng)
 
 
 def f6_mask(inp, g=0):
@@ -286,3 +296,127 @@ class ExactTwin:
         y = cx + self._mv(br, bc, bv, u, r.nPhi)
         s = np.abs(cx) + self._mv(br, bc, np.abs(bv), np.abs(u), r.nPhi)
         return y, s, float(np.abs(du).max() / np.abs(u).max())
+
+    def operator(self, g, dus):
+        """group g as apply(x) -> (y, s) for exact_cg2_op; the last relative correction of every apply is appended to dus"""
+        def apply(x):
+            y, s, du = self.apply(g, x)
+            dus.append(du)
+            return y, s
+        return apply
+
+    def outer(self, phi0=None):
+        """One outer iteration of SolveKeff from the start flux (phi0 (ng, nPhi); None: 1 in every DOF; k = 1) with two CG steps per group, in extended precision:
+        the right-hand sides as oracle/ref_scipy.py solve_keff states them -- tf = sum_g Mf_g phi_g, rhs = chi_g tf / k with chi / k below
+        1e-14 set to 0 when a cell has more than one flux DOF, plus the Ms blocks in Gauss-Seidel order -- formed from this twin's own
+        diagonals, never rounded to double.  Returns dict(b, y, s: per group; du: every apply's last relative correction)"""
+        r = self.r
+        ng, nloc = r.ng, r.nloc
+        per_dof = lambda a: np.repeat(np.asarray(a).astype(LD), nloc)
+        vol = np.einsum("k,j,i->kji", *(np.asarray(h).astype(LD) for h in (r.hz, r.hy, r.hx))).ravel()
+        w = vol if r.m == 0 else self.cd                               # the mass diagonal without its cross-section (RefScipy.build)
+        phi = [np.ones(r.nPhi, dtype=LD) if phi0 is None else np.asarray(phi0[g]).astype(LD).ravel() for g in range(ng)]
+        tf = sum(per_dof(r.NSF[g]) * w * phi[g] for g in range(ng))
+        k = LD(1)
+        out = dict(b=[], y=[], s=[], du=[])
+        for g in range(ng):
+            chi = per_dof(r.Chi[g]) / k
+            if nloc > 1:
+                chi = np.where(np.abs(chi) < 1e-14, LD(0), chi)
+            rhs = chi * tf
+            for gp in range(ng):
+                ms = per_dof(r.SigS[g, gp]) * w
+                if gp != g and np.any(np.abs(ms) > 1e-14):
+                    rhs = rhs + ms * phi[gp]
+            x2, sc = exact_cg2_op(self.operator(g, out["du"]), rhs)
+            phi[g] = x2
+            out["b"].append(rhs); out["y"].append(x2); out["s"].append(sc)
+        return out
+
+
+def outer_rho(phi, ref):
+    """SolveKeff returns the normalised iterate: one scalar is fitted on group 0 (phi_0 . y_0 / y_0 . y_0, in extended precision) and
+    every group is then judged per component with it.  ref: y and s per group (ExactTwin.outer)"""
+    ng = len(ref["y"])
+    phi = np.asarray(phi).reshape(ng, -1).astype(LD)
+    c = (phi[0] * ref["y"][0]).sum() / (ref["y"][0] * ref["y"][0]).sum()
+    return [rho(phi[g] / c, ref["y"][g], ref["s"][g]) for g in range(ng)]
+
+
+# ---- the orders with bubble moments at the benchmark's contrast: cases and references of tests/test_gpu_orders_exact.py ---------------
+# name: (RT order, P order, shape, block).  a ... f cover NB = 1 and 2, 2D and 3D, P = RT and P < RT, even and odd nx; g is the even-nx RT2
+# case (the scan variants' VEC follows nx parity); h has y and z lines shorter than 4 cells (one-sided lanes beside the two-sided x
+# lanes); i is RT2-P0.  The flux carries NB = min(RT, P) bubble moments: the P0 cases e and i run the RT0-P0 instantiations on the line
+# factors of their order.  All fit a line-per-lane variant (tests/test_apply_exact.py asks lane_plan).
+ORDER_CASES = {
+    "a": (1, 1, (20, 18), (4, 3)), "b": (2, 2, (21, 20), (3, 4)), "c": (1, 1, (8, 6, 5), (4, 3, 5)), "d": (2, 2, (5, 5, 4), (2, 3, 2)),
+    "e": (1, 0, (20, 18), (4, 3)), "f": (2, 1, (8, 6, 5), (4, 3, 5)),
+    "g": (2, 2, (4, 5, 5), (2, 3, 2)), "h": (1, 1, (9, 3, 2), (3, 1, 1)), "i": (2, 0, (8, 6, 5), (4, 3, 5)),
+}
+ORDER_BAR = 4                                                     # GPU rho <= 4 x the double oracle's own rho on the same case, group and quantity
+
+
+_order_cache = {}
+
+
+def order_case(name):
+    """inputs, the built oracle factory's arguments and the exact twin of a case of ORDER_CASES, computed once"""
+    if name not in _order_cache:
+        from subcrit_exact import ref_from_inputs
+        rt, p, shape, block = ORDER_CASES[name]
+        inp = f6_block_inputs(shape, block)
+        ex = ExactTwin(ref_from_inputs(inp, rt, p))
+        _order_cache[name] = dict(name=name, rt=rt, p=p, shape=shape, inp=inp, ex=ex, nloc=ex.r.nloc, filler=np.repeat(f6_mask(inp), ex.r.nloc))
+    return _order_cache[name]
+
+
+def order_ref_cg(name):
+    """per group: b = |input vector| off the filler and 0 on it (the mask is per cell, a cell has nloc flux DOFs), the exact two CG steps
+    on the twin, their scale, the double oracle's own two steps and their rho.  Computed once, read-only"""
+    c = order_case(name)
+    if "cg" not in c:
+        from helpers import make_oracle
+        o = make_oracle(c["inp"], c["rt"], c["p"]); o.set_tol(1e-5, 0.0, 0.0, 200, 2)
+        out = dict(inp=c["inp"], groups=tuple(range(int(c["inp"]["ng"]))), x={}, y={}, s={}, rho_o={}, its_o={}, du=[])
+        for g in out["groups"]:
+            b = np.abs(np.asarray(input_vector(o.n_phi, g))) * ~c["filler"]
+            b.setflags(write=False)
+            x2, sc = exact_cg2_op(c["ex"].operator(g, out["du"]), b)
+            xo, _, its = o.solve_group(g, b, with_J=False)
+            out["x"][g], out["y"][g], out["s"][g], out["rho_o"][g], out["its_o"][g] = b, x2, sc, rho(xo, x2, sc), its
+        c["cg"] = out
+    return c["cg"]
+
+
+def order_start_flux(name, start):
+    """the start flux of the one-outer runs, (ng, nPhi) in the host DOF layout or None.  "flat": SolveKeff's own, 1 in every DOF -- then the
+    right-hand sides are equal in moments of equal mass, and an apply that confuses two such moments shows in the second CG step only,
+    which enters x2 through the one scalar a1.  "rough": uniform in 0.5 ... 1.5 per DOF, so that the first apply of every group sees a vector
+    without that symmetry"""
+    if start == "flat":
+        return None
+    assert start == "rough", start
+    r = order_case(name)["ex"].r
+    phi0 = np.random.default_rng(7).uniform(0.5, 1.5, (r.ng, r.nPhi))
+    phi0.setflags(write=False)
+    return phi0
+
+
+def order_ref_outer(name, start="flat"):
+    """ExactTwin.outer of the case from order_start_flux with the double oracle's own one-outer SolveKeff from the same start judged by it
+    under the same scalar fit"""
+    c = order_case(name)
+    key = "outer " + start
+    if key not in c:
+        from helpers import make_oracle
+        phi0 = order_start_flux(name, start)
+        out = c["ex"].outer(phi0)
+        o = make_oracle(c["inp"], c["rt"], c["p"]); o.set_tol(0.0, 0.0, 0.0, 1, 2)
+        if phi0 is not None:
+            o.phi_dofs()[...] = phi0
+        o.SolveKeff()
+        h = o.history()
+        out["n_outer_o"], out["cg_o"] = int(h["n_outer"]), np.asarray(h["cg"]).copy()
+        out["rho_o"] = outer_rho(o.phi_dofs(), out)
+        c[key] = out
+    return c[key]

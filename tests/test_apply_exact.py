@@ -13,7 +13,8 @@ import functools
 import numpy as np
 import pytest
 
-from apply_exact import EPS, LD, ExactApply, ExactTwin, exact_cg2, f6_block_inputs, f6_mask, gauss_legendre_ld, input_vector, normwise, rho
+from apply_exact import (EPS, LD, ORDER_CASES, ExactApply, ExactTwin, exact_cg2, exact_cg2_op, f6_block_inputs, f6_mask, gauss_legendre_ld, input_vector,
+                         normwise, order_case, order_ref_cg, order_ref_outer, order_start_flux, rho)
 from helpers import load_inputs, make_oracle, synthetic_inputs
 
 BAR = 64 * EPS
@@ -124,19 +125,25 @@ def test_metric_sees_what_the_normwise_bar_cannot(name):
 
 
 def test_f6_block_inputs_are_what_they_say():
-    for shape, block in F6_SHAPES.values():
+    for shape, block in list(F6_SHAPES.values()) + [((20, 18), (4, 3)), ((21, 20), (3, 4))]:
         inp = f6_block_inputs(shape, block)
         f6 = f6_mask(inp).reshape(shape[::-1])
         assert 0.2 < f6.mean() < 0.4, f6.mean()
         assert np.array_equal(f6, f6_mask(inp, 1).reshape(f6.shape))
         for k in ("x_breaks", "y_breaks", "z_breaks"):
             assert np.array_equal(np.diff(inp[k]), np.full(len(inp[k]) - 1, 1.25))
+        if len(shape) == 2:                                        # the 2D form: (ng, ny, nx), no z breaks, the four attributes of a 2D mesh
+            assert inp["D"].shape == (2,) + shape[::-1] and inp["SigS"].shape == (2, 2) + shape[::-1] and np.array_equal(inp["z_breaks"], [0.0])
+            assert list(inp["bc_attr"]) == [1, 2, 3, 4] and not inp["bc_type"].any() and len(inp["x_breaks"]) == shape[0] + 1 and len(inp["y_breaks"]) == shape[1] + 1
+            shape, block = shape + (1,), block + (1,)
+        else:
+            assert list(inp["bc_attr"]) == [1, 2, 3, 4, 5, 6] and not inp["bc_type"].any()
         assert (inp["D"][:, f6] == 1e-3).all() and (inp["SigR"][:, f6] == 1e15).all()
         assert not inp["NSF"][:, f6].any() and not inp["Chi"][:, f6].any() and not inp["SigS"][:, :, f6].any()
         assert (inp["SigR"][:, ~f6] >= 0.01).all() and (inp["SigR"][:, ~f6] <= 0.13).all()
         # piecewise constant on the blocks
         bx, by, bz = block
-        D = inp["D"][0]
+        D = inp["D"][0].reshape(shape[::-1])
         for iz in range(0, shape[2], bz):
             for iy in range(0, shape[1], by):
                 for ix in range(0, shape[0], bx):
@@ -212,3 +219,115 @@ def test_oracle_and_twin_share_the_tabulated_gauss_rule(rt, shape, block):
         assert du <= 1e-18 and max(ro, rt_) <= 2.0 ** -40
         if rt == 2:
             assert rot < min(ro, rt_)
+
+
+# ---- two CG steps and one outer iteration on the twin: the references of tests/test_gpu_orders_exact.py ------------------------------
+@pytest.mark.parametrize("name", ["1d", "2d-mixed", "3d", "3d-mixed"])
+def test_two_cg_steps_on_the_twin_agree_with_the_closed_forms(name):
+    """RT0-P0: exact_cg2_op on ExactTwin against exact_cg2 (the closed forms), b = |input vector| -- the bar of
+    test_exact_twin_agrees_with_the_closed_forms, per component of the two-step scale"""
+    from subcrit_exact import ref_from_inputs
+    c = _case(name)
+    ex = ExactTwin(ref_from_inputs(c["inp"]))
+    for g in range(c["ng"]):
+        b = np.abs(np.asarray(c["x"][g]))
+        x2, sc = exact_cg2(c["inp"], g, b)
+        dus = []
+        x2t, sct = exact_cg2_op(ex.operator(g, dus), b)
+        r = rho(x2t, x2, sc)
+        print(f"{name} g={g}: two CG steps, twin against the closed forms rho = {r:.2e} = {r / EPS:.2f} x 2^-53, last corrections {max(dus):.1e}")
+        assert len(dus) == 2 and max(dus) <= 1e-18 and r <= 4 * EPS
+        assert (np.abs(sct - sc) <= 1e-15 * sc).all()
+
+
+def test_one_outer_on_the_twin_agrees_with_the_closed_forms():
+    """RT0-P0 at the filler's contrast (shape R of tests/test_gpu_apply_exact.py): ExactTwin.outer -- right-hand sides from the twin's
+    diagonals -- against the same outer written with cell volumes and the closed-form apply"""
+    from subcrit_exact import ref_from_inputs
+    inp = f6_block_inputs((12, 11, 10), (4, 4, 5))
+    cells = inp["D"][0].size
+    out = ExactTwin(ref_from_inputs(inp)).outer()
+    V = np.full(cells, LD(1.25) ** 3)
+    F = (inp["NSF"].reshape(2, cells).astype(LD) * V).sum(axis=0)
+    b0 = inp["Chi"].reshape(2, cells)[0].astype(LD) * F
+    y0, s0 = exact_cg2(inp, 0, b0)
+    b1 = inp["Chi"].reshape(2, cells)[1].astype(LD) * F + inp["SigS"].reshape(2, 2, cells)[1, 0].astype(LD) * V * y0
+    y1, s1 = exact_cg2(inp, 1, b1)
+    assert len(out["du"]) == 4 and max(out["du"]) <= 1e-18
+    # b0 is the same arithmetic on either side; b1 carries the distance of the two y0 through the scattering block
+    slack = (LD(2) ** -60 * np.abs(b0), LD(2) ** -60 * np.abs(b1) + 4 * EPS * inp["SigS"].reshape(2, 2, cells)[1, 0].astype(LD) * V * s0)
+    for g, (b, y, s) in enumerate(((b0, y0, s0), (b1, y1, s1))):
+        r = rho(out["y"][g], y, s)
+        print(f"one outer g={g}: twin against the closed forms rho = {r:.2e} = {r / EPS:.2f} x 2^-53")
+        assert (np.abs(out["b"][g] - b) <= slack[g]).all() and r <= 4 * EPS
+
+
+def _lane_plans():
+    """lane_plan (neutfem_amd/csrc/nf_resident_lanes.h) of every case, two-sided and one-sided, at the 160 KiB of LDS the library plans
+    with (resident_lds_cap: bytes / 8 - 32 doubles)"""
+    import os, shutil, subprocess, tempfile
+    here = os.path.dirname(os.path.abspath(__file__))
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "the build needs a host C++ compiler anyway"
+    args = []
+    for rt, p, shape, _ in ORDER_CASES.values():
+        dim = len(shape)
+        args += [dim, *shape, *([1] * (3 - dim)), min(rt, p), (p + 1) ** dim, (p + 1) ** (dim - 1)]   # NB, moments per cell, transverse modes: as nf_create counts them
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "resident_lanes_cases")
+        subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-o", exe, os.path.join(here, "host", "resident_lanes_cases_main.cpp")])
+        lines = subprocess.run([exe, str(160 * 1024 // 8 - 32)] + [str(a) for a in args], capture_output=True, text=True, check=True).stdout.split("\n")
+    keys = ("fits", "tw0", "tw1", "tw2", "slots", "PC", "NPp", "need")
+    rows = [dict(zip(keys, map(int, l.split()))) for l in lines if l]
+    assert len(rows) == 2 * len(ORDER_CASES)
+    return {name: (rows[2 * i], rows[2 * i + 1]) for i, name in enumerate(ORDER_CASES)}
+
+
+def test_order_cases_cover_what_they_are_for():
+    """by lane_plan's arithmetic every case fits a line-per-lane variant, two-sided and one-sided -- the bubble variant where the flux has
+    bubble moments (NB = min(RT, P) > 0), the RT0-P0 one at its smaller pitch for the P0 cases; the set covers RT1 and RT2 in 2D and 3D with
+    P = RT and P < RT, both parities of nx at NB = 1 and at NB = 2 (the scan variants' VEC), RT2-P0, and lines shorter than 4 cells in some
+    directions beside two-sided ones"""
+    plans = _lane_plans()
+    for name, (two, one) in plans.items():
+        rt, p, shape, _ = ORDER_CASES[name]
+        print(name, ORDER_CASES[name], two, one)
+        assert two["fits"] == 1 and one["fits"] == 1 and one["tw0"] + one["tw1"] + one["tw2"] == 0, (name, two, one)
+        assert [two["tw0"], two["tw1"], two["tw2"]] == [int(n >= 4) for n in shape] + [0] * (3 - len(shape)), (name, two)
+        if min(rt, p) > 0: assert 0 < two["NPp"] <= 5120 and (p + 1) ** (len(shape) - 1) <= 9 and (p + 1) ** len(shape) <= 27
+        else: assert two["PC"] == 0 and (shape[0] | 1) * int(np.prod(shape[1:])) <= 1536      # nf_batch_result::variant 1
+    have = {(rt, len(shape), p == rt) for rt, p, shape, _ in ORDER_CASES.values()}
+    assert {(1, 2, True), (2, 2, True), (1, 3, True), (2, 3, True)} <= have and {rt for rt, _, eq in have if not eq} == {1, 2}
+    assert {(min(rt, p), shape[0] % 2) for rt, p, shape, _ in ORDER_CASES.values()} >= {(1, 0), (1, 1), (2, 0), (2, 1)}
+    assert {(2, 0), (2, 1), (1, 0)} <= {(rt, p) for rt, p, _, _ in ORDER_CASES.values()}
+    two = plans["h"][0]
+    assert (two["tw0"], two["tw1"], two["tw2"]) == (1, 0, 0)
+
+
+@pytest.mark.parametrize("name", list(ORDER_CASES))
+def test_order_cases_meet_their_conditions(name):
+    """what tests/test_gpu_orders_exact.py asserts of its references, with the oracle alone: the refinement has converged on every
+    reference apply, the oracle takes exactly 2 CG steps, the filler covers 20 - 40 % of the cells, b vanishes on every filler DOF and is
+    positive somewhere in each group -- for the two CG steps and for the one outer from either start flux.  Prints the bars' base: the
+    double oracle's own rho x 2^53"""
+    c = order_case(name)
+    rt, p, shape, _ = ORDER_CASES[name]
+    cg, ou, rough = order_ref_cg(name), order_ref_outer(name), order_ref_outer(name, "rough")
+    fill = float(f6_mask(c["inp"]).mean())
+    print(f"{name} RT{rt}-P{p} {shape}: {c['ex'].r.nPhi} unknowns per group, filler {100 * fill:.0f} %, oracle rho x 2^53: two CG steps "
+          f"{cg['rho_o'][0] / EPS:.0f} / {cg['rho_o'][1] / EPS:.0f}, one outer {ou['rho_o'][0] / EPS:.0f} / {ou['rho_o'][1] / EPS:.0f}, "
+          f"from the rough start {rough['rho_o'][0] / EPS:.0f} / {rough['rho_o'][1] / EPS:.0f}; last corrections up to {max(cg['du'] + ou['du'] + rough['du']):.1e}")
+    assert 0.2 <= fill <= 0.4 and c["filler"].size == c["ex"].r.nPhi and c["filler"].sum() == c["nloc"] * f6_mask(c["inp"]).sum()
+    phi0 = order_start_flux(name, "rough")
+    assert order_start_flux(name, "flat") is None and phi0.shape == (2, c["ex"].r.nPhi) and phi0.min() >= 0.5 and phi0.max() <= 1.5
+    for ref in (cg, ou, rough):
+        assert len(ref["du"]) == 4 and max(ref["du"]) <= 1e-18
+    for o_ in (ou, rough):
+        assert o_["n_outer_o"] == 1 and (o_["cg_o"] == 2).all()
+    for g in (0, 1):
+        assert cg["its_o"][g] == 2
+        for b in (cg["x"][g], ou["b"][g], rough["b"][g]):
+            b = np.asarray(b)
+            assert not b[c["filler"]].any() and b.max() > 0, (name, g)
+        for r in (cg["rho_o"][g], ou["rho_o"][g], rough["rho_o"][g]):
+            assert 0 < r <= 2.0 ** -36, (name, g, r / EPS)            # a sanity bound on the oracle (its largest, RT2-P1: 6069 x 2^-53)

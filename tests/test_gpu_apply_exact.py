@@ -46,6 +46,7 @@ oracle's own rho on the same input (a condition, not a measurement).  K = the ne
   cg2    line_dict 1 and 0 (bit-equal): B / D                                     184.9 610.3   1301.7 2348.5
   cg2    one-XCD kernel / k_apply3 (W)                                              39.8 40.5   187.1
   cg2    resident kernel, one outer: line-per-lane / scans / one-sided / no LDS (R)       7.9   66.1
+  cg2    k_keff_xcd, one outer (W)                                                       6.5   490.9
   K_APPLY = 64 (4 x 8.4 = 34), K_SOLVE = 8192 (4 x 1241 = 4964).  No case is above its oracle: the scan-based line solves lose nothing to
   the band LDL^T at a 1/D contrast of 2000.  The two-step solves sit at 1e3 x 2^-53 on either side because alpha_1 = |r1|^2 / p1.S p1 is
   dominated by the filler cells (C = 2e15 against p1 = -a0 (S b)_i) and inherits the error of (S b)_i where the face terms cancel.
@@ -384,6 +385,23 @@ def test_resident_kernel(variant):
         ro = ref["rho_o"][g]
         print(f"RHO cg2 R resident {variant} g={g}: gpu {r:.2e} = {r / EPS:.1f} x 2^-53 (bar {K_SOLVE}), oracle {ro:.2e} = {ro / EPS:.1f} x 2^-53, gpu / oracle {r / ro:.1f}")
         assert r <= K_SOLVE * EPS and r <= 100 * ro, (variant, g, r / EPS, ro / EPS)
+    s.close()
+
+
+def test_keff_one_xcd():
+    """k_keff_xcd: the whole power iteration as one launch on one XCD (last_path 3), one outer iteration on W like the resident kernel on R;
+    also held to 4 x the oracle's own rho, the bar of tests/test_gpu_orders_exact.py"""
+    ref = _ref_outer("W")
+    s = make_hip(ref["inp"]); _set(s, dict(resident=0, keff_xcd=1, cg_xcd=1)); s.set_tol(0.0, 0.0, 0.0, 1, 2)
+    assert s.apply_plan(True)["form"] == "xcd"
+    k, n = s.solve_keff()
+    assert n == 1 and s.info("last_path") == 3 and s.info("xcd_refused") == 0 and (s.history()["cg"] == 2).all(), (n, s.info("last_path"), s.history()["cg"])
+    phi = s.get_phi()
+    assert np.isfinite(phi).all()
+    for g, r in enumerate(_outer_rho(phi, ref)):
+        ro = ref["rho_o"][g]
+        print(f"RHO cg2 W k_keff_xcd g={g}: gpu {r:.2e} = {r / EPS:.1f} x 2^-53 (bar {K_SOLVE}), oracle {ro:.2e} = {ro / EPS:.1f} x 2^-53, gpu / oracle {r / ro:.1f}")
+        assert r <= K_SOLVE * EPS and r <= 4 * ro, (g, r / EPS, ro / EPS)
     s.close()
 
 
