@@ -112,6 +112,31 @@ class ExactApply:
             s += np.moveaxis(beta * (np.abs(u[1:]) + np.abs(u[:-1])), 0, ax)
         return y.ravel(), s.ravel()
 
+    def currents(self, x, diag=False):
+        """The face currents of the field x -> (J, s), np.longdouble in the reference DOF order (x faces, y faces, z faces; each block the
+        face array in C order with the line axis put back).  Full path: J = -u, A u = B^T x by the Thomas sweep, with the componentwise bound
+        of a solve as the scale, s = |A^-1| (|A| |u| + |B^T| |x|): a line's matrix is a symmetric positive definite tridiagonal, so
+        |A^-1| = M(A)^-1 with M(A) its comparison matrix (same diagonal, off-diagonals negated) -- one more Thomas sweep.  diag = True: the
+        diagonal path's J_f = +(B^T x)_f / A_ff (src/NeutFEM.cpp:620-633) with s_f = beta (|x_f-1| + |x_f|) / A_ff"""
+        x = np.asarray(x).astype(LD).reshape(self.shape)
+        beta = self.beta
+        Js, ss = [], []
+        for ax, dg, off in self.lines:
+            xm = np.moveaxis(x, ax, 0)
+            n = xm.shape[0]
+            t = np.zeros((n + 1,) + xm.shape[1:], dtype=LD); ta = np.zeros_like(t)
+            t[1:] += beta * xm; t[:-1] -= beta * xm               # B^T x: face f sees beta (x_{f-1} - x_f)
+            ta[1:] += beta * np.abs(xm); ta[:-1] += beta * np.abs(xm)
+            if diag:
+                J, s = t / dg, ta / dg
+            else:
+                u = thomas(dg, off, t)
+                au = dg * np.abs(u)
+                au[1:] += off * np.abs(u[:-1]); au[:-1] += off * np.abs(u[1:])
+                J, s = -u, thomas(dg, -off, au + ta)
+            Js.append(np.moveaxis(J, 0, ax).ravel()); ss.append(np.moveaxis(s, 0, ax).ravel())
+        return np.concatenate(Js), np.concatenate(ss)
+
 
 def exact_apply(inp, g, x):
     """(y, s) of group g: the apply and the per-component scale, np.longdouble"""
@@ -222,6 +247,9 @@ def gauss_legendre_ld(n):
     return x, LD(2) / ((LD(1) - x * x) * _legendre_ld(n, x)[1] ** 2)
 
 
+_ABS_INVERSE = {}                                                 # ExactTwin._abs_inverse: the block inverses of one twin at a time
+
+
 class ExactTwin:
     """RT_k-P_m of any order: the operator oracle/ref_scipy.RefScipy assembles, in extended precision.
 
@@ -296,6 +324,68 @@ class ExactTwin:
         y = cx + self._mv(br, bc, bv, u, r.nPhi)
         s = np.abs(cx) + self._mv(br, bc, np.abs(bv), np.abs(u), r.nPhi)
         return y, s, float(np.abs(du).max() / np.abs(u).max())
+
+    def currents(self, g, x, sweeps=5):
+        """The currents of the field x of group g (host DOF order) -> (J, s, last relative correction): J = -u with A_g u = B^T x, in the
+        twin's numbering (RefScipy._faces: x, y, z face DOFs, then x, y, z bubbles -- the reference's, and get_J's).
+
+        Structural zeros are exact zeros: the twin's own drop rules (RefScipy.build: B-hat entries <= 1e-14, element entries of A <= 1e-13 x
+        the largest) are applied to the extended-precision triplets.  Without them entries that vanish by orthogonality sit at 1e-17 ...
+        1e-20, the RT modes that see no flux moment at P < RT get a reference of 1e-25 on a scale of 1e-28, and the metric means nothing
+        there.  With them those DOFs have reference 0 and scale 0, and rho demands an exact match.
+
+        Scale: a solve is backward stable, not componentwise forward accurate -- a tiny u_f beside large ones carries its neighbours'
+        error -- so s = |A^-1| (|A| |u| + |B^T| |x|), the componentwise bound of the solve, in double.  A is block diagonal by line and
+        transverse mode: |A^-1| block by block (_abs_inverse), never of the whole matrix"""
+        r = self.r
+        D = np.asarray(r.D[g]).astype(LD)
+        x = np.asarray(x).astype(LD).ravel()
+        A = [(rows, cols, vals / D[cell]) for rows, cols, vals, cell in self.Apat]
+        vmax = max(float(np.abs(v).max()) for _, _, v in A)
+        kept = [np.abs(v) > 1e-13 * vmax for _, _, v in A]
+        A = [(rows[k], cols[k], v[k]) for (rows, cols, v), k in zip(A, kept)] + [(dof, dof, val * D[cell]) for dof, val, cell in self.dirichlet]
+        Au = lambda u: sum(self._mv(rows, cols, vals, u, r.nJ) for rows, cols, vals in A)
+        br, bc, bv = self.B
+        keep = np.abs(bv) > 1e-14
+        t = self._mv(bc[keep], br[keep], bv[keep], x, r.nJ)         # B^T x
+        u = r.lu[g].solve(np.asarray(t, dtype=np.float64)).astype(LD)
+        for _ in range(sweeps):
+            du = r.lu[g].solve(np.asarray(t - Au(u), dtype=np.float64)).astype(LD)
+            u = u + du
+        ua, xa = np.abs(np.asarray(u, dtype=np.float64)), np.abs(np.asarray(x, dtype=np.float64))
+        rhs = abs(r.A[g]) @ ua + abs(r.BT) @ xa
+        s = np.zeros(r.nJ)
+        for dofs, inv in self._abs_inverse(g):
+            s[dofs] = np.einsum("bij,bj->bi", inv, rhs[dofs])
+        umax = np.abs(u).max()
+        return -u, s.astype(LD), float(np.abs(du).max() / umax) if umax > 0 else 0.0
+
+    def _abs_inverse(self, g):
+        """|A_g^-1| as [(dofs (blocks, n), |inverse| (blocks, n, n)) for every block size n]: the connected components of the twin's A_g
+        (one per line and transverse mode), inverted densely in double.  One twin's inverses are kept at a time"""
+        if _ABS_INVERSE.get("owner") is not self:
+            _ABS_INVERSE.clear(); _ABS_INVERSE["owner"] = self
+        if g not in _ABS_INVERSE:
+            from scipy.sparse.csgraph import connected_components
+            A = self.r.A[g].tocoo()
+            nblk, lab = connected_components(self.r.A[g], directed=False)
+            sizes = np.bincount(lab, minlength=nblk)
+            assert sizes.max() <= 512, sizes.max()                    # a line's faces and bubbles; anything larger is not a line
+            order = np.argsort(lab, kind="stable")
+            pos = np.empty(lab.size, dtype=np.int64)
+            pos[order] = np.arange(lab.size) - np.repeat(np.cumsum(sizes) - sizes, sizes)
+            out = []
+            for n in np.unique(sizes):
+                which = np.full(nblk, -1); which[sizes == n] = np.arange((sizes == n).sum())
+                m = sizes[lab[A.row]] == n
+                M = np.zeros((int((sizes == n).sum()), n, n))
+                np.add.at(M, (which[lab[A.row[m]]], pos[A.row[m]], pos[A.col[m]]), A.data[m])
+                dofs = np.empty(M.shape[:2], dtype=np.int64)
+                sel = np.flatnonzero(sizes[lab] == n)
+                dofs[which[lab[sel]], pos[sel]] = sel
+                out.append((dofs, np.abs(np.linalg.inv(M))))
+            _ABS_INVERSE[g] = out
+        return _ABS_INVERSE[g]
 
     def operator(self, g, dus):
         """group g as apply(x) -> (y, s) for exact_cg2_op; the last relative correction of every apply is appended to dus"""
@@ -420,3 +510,176 @@ def order_ref_outer(name, start="flat"):
         out["rho_o"] = outer_rho(o.phi_dofs(), out)
         c[key] = out
     return c[key]
+
+
+# ---- the reconstructed currents: cases, DOF classes and the oracle's own figures for tests/test_gpu_currents_exact.py ------------------
+# RT0-P0 beside ORDER_CASES: R and T are shapes R and T of tests/test_gpu_apply_exact.py (the resident kernel's; the slab teams'), 2D is case a's mesh
+P0_CASES = {"R": ((12, 11, 10), (4, 4, 5)), "2D": ((20, 18), (4, 3)), "T": ((16, 8, 96), (4, 4, 8))}
+_p0_cache = {}
+
+
+def rough_start(ng, nphi):
+    """the rough start flux of order_start_flux for any input: uniform in 0.5 ... 1.5 per DOF, (ng, nphi), read-only"""
+    phi0 = np.random.default_rng(7).uniform(0.5, 1.5, (ng, nphi))
+    phi0.setflags(write=False)
+    return phi0
+
+
+def p0_case(name):
+    """inputs and the closed-form operators of both groups of a case of P0_CASES, computed once"""
+    if name not in _p0_cache:
+        inp = f6_block_inputs(*P0_CASES[name])
+        _p0_cache[name] = dict(name=name, rt=0, p=0, shape=P0_CASES[name][0], inp=inp, ea=[ExactApply(inp, g) for g in range(int(inp["ng"]))])
+    return _p0_cache[name]
+
+
+def current_classes(dims, rt, interfaces=()):
+    """DOF class -> indices into one group's J (reference numbering): "x", "y", "z" faces and "bubbles"; the z faces on the planes listed
+    in `interfaces` (the planes at which a slab team is cut) leave "z" for a class of their own, "z interface".  dims = (nx, ny[, nz])"""
+    d = len(dims)
+    nx, ny, nz = tuple(dims) + (1,) * (3 - d)
+    k = min(rt, 2)
+    nf, ni = (k + 1) ** (d - 1), k * (k + 1) ** (d - 1)
+    n = [(nx + 1) * ny * nz * nf, nx * (ny + 1) * nz * nf if d >= 2 else 0, nx * ny * (nz + 1) * nf if d == 3 else 0]
+    lo = np.concatenate([[0], np.cumsum(n)])
+    out = {"xyz"[a]: np.arange(lo[a], lo[a + 1]) for a in range(d)}
+    if interfaces:
+        plane = (out["z"] - lo[2]) // (nx * ny * nf)
+        cut = np.isin(plane, list(interfaces))
+        out["z interface"], out["z"] = out["z"][cut], out["z"][~cut]
+    if ni:
+        out["bubbles"] = np.arange(lo[3], lo[3] + d * nx * ny * nz * ni)
+    return out, int(lo[3] + d * nx * ny * nz * ni)
+
+
+def exact_outer_p0(inp, phi0, diag=False):
+    """RT0-P0: the raw iterate of one outer iteration of SolveKeff from phi0 (ng, cells) with k = 1, per group in extended precision, on the
+    closed forms: the right-hand sides of ExactTwin.outer written with cell volumes, then two CG steps (exact_cg2) -- or, diag = True, the
+    diagonal path's phi = rhs / (C + sum_faces beta^2 / A_ff) (src/NeutFEM.cpp:483-634)"""
+    ng, cells = int(inp["ng"]), inp["D"][0].size
+    V = np.einsum("k,j,i->kji", *(np.diff(inp[k]).astype(LD) if len(inp[k]) > 1 else np.ones(1, dtype=LD) for k in ("z_breaks", "y_breaks", "x_breaks"))).ravel()
+    flat = lambda a, *lead: np.asarray(a, dtype=np.float64).reshape(*lead, cells).astype(LD)
+    NSF, Chi, SigS = flat(inp["NSF"], ng), flat(inp["Chi"], ng), flat(inp["SigS"], ng, ng)
+    phi = [np.asarray(phi0[g]).astype(LD).ravel() for g in range(ng)]
+    tf = sum(NSF[g] * V * phi[g] for g in range(ng))
+    for g in range(ng):
+        rhs = Chi[g] * tf
+        for gp in range(ng):
+            if gp != g: rhs = rhs + SigS[g, gp] * V * phi[gp]
+        if diag:
+            ea = ExactApply(inp, g)
+            S = ea.C.copy()
+            for ax, dg, _ in ea.lines:
+                S += np.moveaxis(ea.beta * ea.beta * (1 / dg[1:] + 1 / dg[:-1]), 0, ax)
+            phi[g] = rhs / S.ravel()
+        else:
+            phi[g] = exact_cg2(inp, g, rhs)[0]
+    return phi
+
+
+def currents_reference(case, phi, diag=False):
+    """per group (J, s) of the field phi (ng, n_phi: a solver's returned flux, doubles) on a case of order_case / p0_case / a dict with "ex"
+    or "ea"; the refinement's last corrections are appended to case["du_J"]"""
+    out = []
+    for g in range(len(phi)):
+        if "ea" in case:
+            out.append(case["ea"][g].currents(phi[g], diag))
+        else:
+            J, s, du = case["ex"].currents(g, phi[g])
+            case.setdefault("du_J", []).append(du)
+            out.append((J, s))
+    return out
+
+
+def currents_fit(J, ref):
+    """the one scalar of a normalised solve, fitted on the currents of group 0 in extended precision: J_0 = c J_ref,0"""
+    J0 = np.asarray(J[0]).astype(LD)
+    return (J0 * ref[0][0]).sum() / (ref[0][0] * ref[0][0]).sum()
+
+
+def currents_rho(J, ref, classes, c=None):
+    """class -> [rho of every group], J / c judged per component against ref = currents_reference(...); c = None: no scalar (the field is
+    the one J was built from)"""
+    out = {}
+    for name, idx in classes.items():
+        out[name] = []
+        for g, (Jr, s) in enumerate(ref):
+            Jg = np.asarray(J[g]).astype(LD)[idx]
+            out[name].append(rho(Jg if c is None else Jg / c, Jr[idx], s[idx]))
+    return out
+
+
+def _case_of(family, name):
+    return order_case(name) if family == "higher" else p0_case(name)
+
+
+def currents_cg_oracle(family, name):
+    """fit-free: the oracle's solve_group(g, b, with_J = True) with two CG steps on order_ref_cg's b returns phi and J of the same
+    unnormalised field -- its J against the reference applied to its phi.  dict(J, ref, rho: class -> per group), computed once"""
+    c = _case_of(family, name)
+    if "J cg" not in c:
+        from helpers import make_oracle
+        o = make_oracle(c["inp"], c["rt"], c["p"]); o.set_tol(1e-5, 0.0, 0.0, 200, 2)
+        filler = np.repeat(f6_mask(c["inp"]), o.n_phi // o.ne)
+        phis, Js = [], []
+        for g in range(int(c["inp"]["ng"])):
+            b = np.abs(np.asarray(input_vector(o.n_phi, g))) * ~filler
+            phi, J, its = o.solve_group(g, b, with_J=True)
+            assert its == 2, (name, g, its)
+            phis.append(phi); Js.append(J)
+        ref = currents_reference(c, phis)
+        classes, nJ = current_classes(c["shape"], c["rt"])
+        assert nJ == o.n_J
+        c["J cg"] = dict(J=Js, ref=ref, classes=classes, rho=currents_rho(Js, ref, classes))
+    return c["J cg"]
+
+
+def currents_outer_oracle(family, name):
+    """the procedure of the GPU tests on the oracle: one outer iteration from the rough start with two CG steps per group (diagonal family: the
+    diagonal path), phi_dofs() and J_dofs(), the reference applied to that phi, the scalar fitted on the currents of group 0.
+    dict(rho: class -> per group, c, c_flux: the scalar of the flux against the exact outer, kappa, phi: the oracle's returned flux, y0: the exact raw iterate of group 0),
+    computed once"""
+    c = _case_of("higher" if family == "higher" else "p0", name)
+    key = "J outer " + family
+    if key not in c:
+        from helpers import make_oracle
+        diag = family == "diag"
+        o = make_oracle(c["inp"], c["rt"], c["p"]); o.set_tol(0.0, 0.0, 0.0, 1, 2)
+        phi0 = rough_start(o.ng, o.n_phi)
+        o.phi_dofs()[...] = phi0
+        o.SolveKeff(False, [], diag)
+        h = o.history()
+        assert int(h["n_outer"]) == 1 and (np.asarray(h["cg"]) == (0 if diag else 2)).all(), (name, h["n_outer"], h["cg"])
+        phi, J = o.phi_dofs().copy(), o.J_dofs().copy()
+        y0 = order_ref_outer(name, "rough")["y"][0] if family == "higher" else exact_outer_p0(c["inp"], phi0, diag)[0]
+        c[key] = dict(currents_judge(c, phi, J, y0, diag), phi=phi, y0=y0)
+    return c[key]
+
+
+def currents_judge(case, phi, J, y0, diag=False, interfaces=()):
+    """what every one-outer test of the currents does with a solver's (phi, J): the reference applied to phi, the scalar fitted on the currents
+    of group 0, rho per class and group; beside them c_flux = phi_0 . y0 / y0 . y0 against the exact raw iterate y0 of group 0 (c c_flux = 1 up to
+    rounding: a wrong global factor or sign is O(1)) and kappa = sum s |J_ref| / sum J_ref^2 on group 0, which bounds what the fit itself can add.
+    rho_flux is the same judgement with 1 / c_flux for the scalar: a wrong class drags the least-squares c with it and so shows in every class
+    of rho; rho_flux, whose scalar never saw J, says which class it was (printed by the tests, not asserted: its scalar carries the error of
+    the flux iterate)"""
+    ref = currents_reference(case, phi, diag)
+    classes, nJ = current_classes(case["shape"], case["rt"], interfaces)
+    assert np.asarray(J).shape == (len(ref), nJ), (np.asarray(J).shape, nJ)
+    cJ = currents_fit(J, ref)
+    p0 = np.asarray(phi[0]).astype(LD).ravel()
+    c_flux = (p0 * y0).sum() / (y0 * y0).sum()
+    kappa = float((ref[0][1] * np.abs(ref[0][0])).sum() / (ref[0][0] * ref[0][0]).sum())
+    return dict(rho=currents_rho(J, ref, classes, cJ), rho_flux=currents_rho(J, ref, classes, 1 / c_flux), c=cJ, c_flux=c_flux, kappa=kappa,
+                zero_scale=[int((s == 0).sum()) for _, s in ref], classes=classes)
+
+
+CURRENT_FAMILIES = {"higher": list(ORDER_CASES), "p0": list(P0_CASES), "diag": list(P0_CASES)}
+
+
+def currents_bar(family):
+    """the bar of a family of tests/test_gpu_currents_exact.py: ORDER_BAR x the oracle's largest rho over the family's case table, groups and
+    classes under the same procedure (currents_outer_oracle), floored at 2^-53.  Pooled over the table: the oracle's per-case figures
+    scatter by a factor of three for one and the same algorithm, and a per-case bar would judge luck.  Returns (bar, the pool's maximum)"""
+    worst = max(r for name in CURRENT_FAMILIES[family] for rs in currents_outer_oracle(family, name)["rho"].values() for r in rs)
+    return ORDER_BAR * max(worst, EPS), worst

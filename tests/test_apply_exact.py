@@ -13,9 +13,10 @@ import functools
 import numpy as np
 import pytest
 
-from apply_exact import (EPS, LD, ORDER_CASES, ExactApply, ExactTwin, exact_cg2, exact_cg2_op, f6_block_inputs, f6_mask, gauss_legendre_ld, input_vector,
-                         normwise, order_case, order_ref_cg, order_ref_outer, order_start_flux, rho)
-from helpers import load_inputs, make_oracle, synthetic_inputs
+from apply_exact import (CURRENT_FAMILIES, EPS, LD, ORDER_BAR, ORDER_CASES, P0_CASES, ExactApply, ExactTwin, current_classes, currents_bar, currents_cg_oracle,
+                         currents_outer_oracle, exact_cg2, exact_cg2_op, exact_outer_p0, f6_block_inputs, f6_mask, gauss_legendre_ld, input_vector,
+                         normwise, order_case, order_ref_cg, order_ref_outer, order_start_flux, p0_case, rho, rough_start)
+from helpers import load_inputs, make_oracle, rel_l2, synthetic_inputs
 
 BAR = 64 * EPS
 F6_SHAPES = {"A": ((130, 8, 16), (13, 4, 8)), "B": ((70, 24, 4), (10, 6, 2)), "C": ((130, 9, 7), (13, 3, 7))}
@@ -331,3 +332,139 @@ def test_order_cases_meet_their_conditions(name):
             assert not b[c["filler"]].any() and b.max() > 0, (name, g)
         for r in (cg["rho_o"][g], ou["rho_o"][g], rough["rho_o"][g]):
             assert 0 < r <= 2.0 ** -36, (name, g, r / EPS)            # a sanity bound on the oracle (its largest, RT2-P1: 6069 x 2^-53)
+
+
+# ---- the reconstructed currents J = -A^-1 B^T phi: the references of tests/test_gpu_currents_exact.py -----------------------------------
+CURRENT_CASES = [("p0", n) for n in P0_CASES] + [("higher", n) for n in ORDER_CASES]
+ZERO_SCALE = {"e": (1478, 2956), "f": (11390, 20502), "i": (18224, 20502)}      # P < RT: the RT modes that see no flux moment, of all current DOFs
+
+
+def test_the_two_current_references_agree():
+    """RT0-P0 on shape R: ExactApply.currents (closed-form tridiagonals, Thomas, M(A)^-1 for the scale) and ExactTwin.currents (the twin's
+    triplets, iterative refinement, dense block inverses) are two restatements with nothing in common but the input dict.  On what they are
+    used on -- a solver's returned flux, here the oracle's after one outer iteration from the rough start -- they agree to 1e-17 of the
+    scale per component (measured 7.5e-18 and 7.3e-18: a fifteenth of 2^-53); the two scales are the same bound computed twice, one of
+    them in double.  On the signed input vector of the apply tests (10 % of its entries x 1e-12) the distance is 1.10e-17 / 1.11e-17, the
+    same with more refinement sweeps: it is the twin's local tables, summed from a 7-point rule, against the closed forms 2/3 and 1/3 --
+    printed here, and the reason why the RT0-P0 tests judge with the closed forms"""
+    from subcrit_exact import ref_from_inputs
+    c = p0_case("R")
+    ex = ExactTwin(ref_from_inputs(c["inp"], 0, 0))
+    phi = currents_outer_oracle("p0", "R")["phi"]
+    for g in (0, 1):
+        x = input_vector(phi[g].size, g)
+        print(f"R g={g}: on the signed input vector rho = {rho(ex.currents(g, x)[0], *c['ea'][g].currents(x)):.2e}")
+        J, s = c["ea"][g].currents(phi[g])
+        J2, s2, du = ex.currents(g, phi[g])
+        r = rho(J2, J, s)
+        print(f"R g={g}: the two references rho = {r:.2e}, last correction {du:.1e}, scales apart {float((np.abs(s2 - s) / s).max()):.1e}")
+        assert J.shape == J2.shape == (ex.r.nJ,) and (s > 0).all()
+        assert du <= 1e-18 and r <= 1e-17, (g, du, r)
+        assert (np.abs(s2 - s) <= 1e-13 * s).all()
+        assert (np.abs(J) <= s * (1 + LD(2) ** -60)).all()             # |u| = |A^-1 t| <= |A^-1| |t| <= s
+
+
+@pytest.mark.parametrize("family,name", CURRENT_CASES)
+def test_oracle_currents_per_component(family, name):
+    """Fit-free: solve_group(g, b, with_J = True) with two CG steps returns phi and J of the same unnormalised field, so the oracle's J is
+    judged against the reference applied to its own phi with no scalar in between -- which also pins the references' DOF order and sign.
+    The cap of 64 x 2^-53 is a sanity bound on the yardstick (about 8 x the largest figure measured, 7.4): an oracle above it means the
+    reference or its scale is broken.  Conditions: refinement du <= 1e-18, filler in 20 - 40 % of the cells, no zero-scale DOF at P = RT
+    and exactly the modes without a flux moment at P < RT, where reference and oracle are exact zeros"""
+    r = currents_cg_oracle(family, name)
+    c = order_case(name) if family == "higher" else p0_case(name)
+    fill = float(f6_mask(c["inp"]).mean())
+    print(f"{family} {name}: oracle rho x 2^53 " + ", ".join(f"{k} {v[0] / EPS:.1f} / {v[1] / EPS:.1f}" for k, v in r["rho"].items()) + f"; filler {fill:.3f}")
+    assert 0.2 <= fill <= 0.4
+    for vs in r["rho"].values():
+        for v in vs:
+            assert np.isfinite(v) and v <= 64 * EPS, (family, name, r["rho"])
+    if family == "higher":
+        assert len(c["du_J"]) >= 2 and max(c["du_J"]) <= 1e-18, c["du_J"]
+    for g, (J, s) in enumerate(r["ref"]):
+        zero = s == 0
+        want = ZERO_SCALE.get(name, (0, zero.size)) if family == "higher" else (0, zero.size)
+        assert (int(zero.sum()), zero.size) == want, (name, g, int(zero.sum()), zero.size)
+        assert not J[zero].any() and not r["J"][g][zero].any() and np.abs(J[~zero]).min() >= 0
+
+
+@pytest.mark.parametrize("family,name", [(f, n) for f in CURRENT_FAMILIES for n in CURRENT_FAMILIES[f]])
+def test_fitted_scalar_on_the_oracle(family, name):
+    """The procedure of the GPU tests on the oracle: one outer iteration from the rough start, phi_dofs() and J_dofs(), one scalar fitted on
+    the currents of group 0.  SolveKeff returns phi = raw / |raw| and builds J from raw; after ONE outer iteration no Chebyshev step has
+    touched phi, so raw = c phi up to one rounding per entry, which moves the reference by at most 2^-53 s.  The fit adds at most
+    kappa x the fit-free rho, kappa = sum s |J| / sum J^2 on group 0 (|dc / c| <= rho sum s |J| / sum J^2), hence the cap (64 (1 + kappa) + 1) x 2^-53 --
+    a sanity bound again; the figures are 1 ... 14.  c agrees with the scalar of the flux against the exact outer to rounding (measured
+    3e-15 at most); a wrong sign or global factor is O(1)"""
+    r = currents_outer_oracle(family, name)
+    worst = max(v for vs in r["rho"].values() for v in vs)
+    print(f"{family} {name}: oracle rho x 2^53 " + ", ".join(f"{k} {v[0] / EPS:.1f} / {v[1] / EPS:.1f}" for k, v in r["rho"].items()) +
+          f"; c c_flux - 1 = {float(r['c'] * r['c_flux'] - 1):.1e}, kappa {r['kappa']:.1f}")
+    assert np.isfinite(worst) and worst <= (64 * (1 + r["kappa"]) + 1) * EPS, (family, name, worst / EPS)
+    assert abs(float(r["c"] * r["c_flux"] - 1)) <= 1e-12
+    if family == "higher":
+        assert max(order_case(name)["du_J"]) <= 1e-18 and r["zero_scale"] == [ZERO_SCALE.get(name, (0, 0))[0]] * 2
+
+
+def test_current_bars_are_pooled_over_their_family():
+    for family in CURRENT_FAMILIES:
+        bar, worst = currents_bar(family)
+        print(f"{family}: the oracle's largest rho {worst / EPS:.1f} x 2^-53 over {CURRENT_FAMILIES[family]}, bar {bar / EPS:.1f}")
+        assert bar == ORDER_BAR * max(worst, EPS) and EPS <= worst <= 64 * (1 + 64) * EPS
+
+
+def test_exact_outer_p0_is_the_twins_outer():
+    """the closed-form outer of the RT0-P0 cases against ExactTwin.outer from the same rough start (shape R)"""
+    from subcrit_exact import ref_from_inputs
+    c = p0_case("R")
+    phi0 = rough_start(2, c["inp"]["D"][0].size)
+    y = exact_outer_p0(c["inp"], phi0)
+    out = ExactTwin(ref_from_inputs(c["inp"], 0, 0)).outer(phi0)
+    for g in (0, 1):
+        assert rho(out["y"][g], y[g], out["s"][g]) <= 4 * EPS
+
+
+@pytest.mark.parametrize("name", list(ORDER_CASES))
+def test_currents_metric_sees_what_the_normwise_bars_cannot(name):
+    """the largest bubble current of the oracle's J times 1 + 1e-9 -- a wrong iM / eL / eR coefficient at that level: rel_l2 against the
+    unperturbed J, the measure of every older current test (bars 1e-7 ... 1e-9), moves by 1e-10; rho goes from a few 2^-53 to 1e5 x 2^-53"""
+    r = currents_cg_oracle("higher", name)
+    bub = r["classes"]["bubbles"]
+    for g, (Jr, s) in enumerate(r["ref"]):
+        J = r["J"][g]
+        i = bub[np.argmax(np.abs(J[bub]))]
+        bad = J.copy(); bad[i] *= 1.0 + 1e-9
+        new, clean, old = rho(bad[bub], Jr[bub], s[bub]), r["rho"]["bubbles"][g], rel_l2(bad, J)
+        print(f"{name} g={g}: bubble DOF {i}: rho {clean / EPS:.1f} -> {new / EPS:.3g} x 2^-53, rel_l2 {old:.1e}")
+        assert old < 1e-8 and new > 1e4 * EPS, (name, g, old, new / EPS)
+
+
+def test_currents_metric_sees_a_misplaced_small_bubble(name="c"):
+    """a bubble of one transverse mode stored in its neighbour's slot where both are small: the two bubble DOFs of neighbouring modes (slots
+    l + k a and l + k (a + 1) of one cell and direction) with the smallest larger-of-the-two magnitude, swapped.  rel_l2 does not move
+    (below 1e-8: on case c, whose filler blocks are 4 x 3 x 5 cells, they sit inside the filler at 1e-17 of the largest current -- asserted
+    as a condition; on the synthetic inputs of the older tests no pair is small, and those tests do see a swap); rho says the DOFs are
+    wrong by their own size"""
+    r = currents_cg_oracle("higher", name)
+    c = order_case(name)
+    k, bub = c["rt"], r["classes"]["bubbles"]
+    ni = k * (k + 1) ** (len(c["shape"]) - 1)
+    for g, (Jr, s) in enumerate(r["ref"]):
+        J = r["J"][g]
+        slots = bub.reshape(-1, ni)[:, :ni - k]                      # every (cell, direction) block: slot and its neighbour in the next mode
+        big = np.maximum(np.abs(J[slots]), np.abs(J[slots + k]))
+        big[(J[slots] == J[slots + k])] = np.inf
+        i = slots.ravel()[np.argmin(big)]
+        assert big.min() <= 1e-10 * np.abs(J).max(), (name, g, big.min())
+        bad = J.copy(); bad[i], bad[i + k] = J[i + k], J[i]
+        new, old = rho(bad[bub], Jr[bub], s[bub]), rel_l2(bad, J)
+        print(f"{name} g={g}: bubbles {i} and {i + k} ({J[i]:.2e}, {J[i + k]:.2e}) swapped: rho {new / EPS:.3g} x 2^-53, rel_l2 {old:.1e}")
+        assert old < 1e-8 and new > 1e4 * EPS, (name, g, old, new / EPS)
+
+
+def test_current_classes_partition_the_dofs():
+    for dims, rt, cut in (((5, 4, 20), 2, (9,)), ((20, 18), 1, ()), ((12, 11, 10), 0, ())):
+        classes, nJ = current_classes(dims, rt, cut)
+        allidx = np.sort(np.concatenate(list(classes.values())))
+        assert np.array_equal(allidx, np.arange(nJ))
+        if cut: assert classes["z interface"].size == len(cut) * dims[0] * dims[1] * (rt + 1) ** 2
